@@ -66,8 +66,33 @@ def parse():
                          "clocks (the first ~50 iterations after idle run 15 %% slower); the factors are reset "
                          "afterwards, so the W + K steps start from the same state as without it (0 = off)")
     ap.add_argument("--no-others", action="store_true", help="skip the other_configs legs (configs 3, 4, 5-on-1-GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what they computed (w, h, obj_history: what mur() hands its caller) "
+                         "as DIR/<name>.npy in float64, at most DUMP_LIMIT bytes in all (single-GPU runs)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("NMFX_BENCH_FORCE_SHARDED")):
+        ap.error("--dump-outputs reads the factors of the single-GPU loop: run it with --gpus 1")
+    return a
+
+
+DUMP_LIMIT = 64 * 10 ** 6         # bytes: --dump-outputs writes no more than this in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> array) as <path>/<name>.npy in float64.  When they would exceed DUMP_LIMIT
+    together, an array larger than its equal share keeps a fixed sample of its elements (flattened, in index order, drawn from
+    RandomState(0)): the same arguments give the same sample, so two builds can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    share = DUMP_LIMIT // 8 // len(arrays)
+    over = sum(a.size for a in arrays.values()) * 8 > DUMP_LIMIT
+    for name, a in arrays.items():
+        if over and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def hbm_traffic(kernel_prefix, m, n, k):
@@ -1029,6 +1054,9 @@ def main():
     obj = eng.objectives(0, n_obj)
     if not os.environ.get("NMFX_BENCH_NOASSERT"):      # (timing experiments with deliberately wrong kernels)
         assert np.all(np.isfinite(obj)) and obj[-1] < obj[0], "bench run produced a bad objective"
+    if args.dump_outputs:
+        w_t, h_t = eng.get_factors()          # the iterate the last timed step left (the passes below move on from it)
+        dump_outputs(args.dump_outputs, {"w": w_t, "h": h_t, "obj_history": obj})
 
     # profiled pass: per-kernel device time from HIP events on the engine's stream
     roof = None

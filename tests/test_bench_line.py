@@ -69,3 +69,42 @@ def test_this_rounds_record_and_line_agree():
     ao = legs["aoadmm_kl_on_cfg3_shape"]["dominant_kernel"]
     assert ao["name"] == "kl_vaux_fused" and ao["algorithmic_bytes_per_launch"] == 3 * 16384 * 8192 * 4.0
     assert 0.3 < ao["frac"] < 1.0
+
+
+def test_dump_outputs_writes_float64_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files, whole while they fit in DUMP_LIMIT; past it the large arrays keep the same seeded
+    sample of their elements on every run and the files stay inside the limit."""
+    import numpy as np
+
+    import bench
+    w = np.arange(3000, dtype=np.float32).reshape(300, 10)
+    h = np.arange(200, dtype=np.float32).reshape(10, 20)
+    obj = np.linspace(2.0, 1.0, 5)
+    bench.dump_outputs(str(tmp_path / "whole"), {"w": w, "h": h, "obj_history": obj})
+    for name, a in (("w", w), ("h", h), ("obj_history", obj)):
+        got = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 8 * 1200)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"w": w, "h": h, "obj_history": obj})
+    files = sorted((tmp_path / "a").iterdir())
+    assert sum(np.load(f).nbytes for f in files) <= bench.DUMP_LIMIT
+    wa, wb = np.load(tmp_path / "a" / "w.npy"), np.load(tmp_path / "b" / "w.npy")
+    assert wa.dtype == np.float64 and wa.size == 400 and np.array_equal(wa, wb)
+    assert np.all(np.diff(wa) > 0) and np.isin(wa, w).all()        # elements of w, in index order
+    assert np.array_equal(np.load(tmp_path / "a" / "h.npy"), h)      # within its share: whole
+
+
+def test_bench_arguments_refuse_what_cannot_be_honoured(monkeypatch, capsys):
+    import pytest
+
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.delenv("NMFX_BENCH_FORCE_SHARDED", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, "out")
+    for argv in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "out"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        with pytest.raises(SystemExit):
+            bench.parse()
