@@ -94,6 +94,19 @@ int nmfx_upload_v(nmfx_handle_t h, const void* host, int dtype, int64_t ld,
  * stream); the call returns when the copy is done, `dev` may then be freed.                 */
 int nmfx_upload_v_device(nmfx_handle_t h, const void* dev, int dtype, int64_t ld,
                          int64_t row0, int64_t rows);
+/* ---- sparse V (version 310) ----------------------------------------------
+ * A handle for a sparse m x n V with `nnz` stored entries, 1 <= k <= 256.  It runs MUR (both losses) without ever
+ * forming V densely: nmfx_upload_csr takes V as CSR -- row_ptr [m + 1] (int64: nnz may pass 2^31), col_idx [nnz]
+ * strictly increasing within each row (no duplicates), values [nnz] >= 0 in dtype NMFX_F32 / NMFX_F64, stored as f32 --
+ * and builds the transposed (CSC) index itself, deterministically.  The arrays are borrowed, never modified.
+ * On a sparse handle these entry points keep their meaning and the iteration contract of a dense handle, with the same
+ * layouts of W and H: nmfx_set_factors, nmfx_get_factors, nmfx_mur_run, nmfx_mur_finish, nmfx_get_state,
+ * nmfx_get_objectives, nmfx_objective_f64, nmfx_set_stop_guard, nmfx_resume, nmfx_synchronize, nmfx_set_stream
+ * (and nmfx_reset_stream, nmfx_destroy, nmfx_last_error, nmfx_get_note).  The objective is recorded in f64 from the
+ * non-zeros plus k x k terms ("Sparse V").  Every other entry point returns NMFX_E_ARG and launches nothing. */
+int nmfx_create_csr(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k, int64_t nnz);
+int nmfx_upload_csr(nmfx_handle_t h, const int64_t* row_ptr, const int32_t* col_idx, const void* values, int dtype);
+
 /* W (m x k) and H (k x n), float64 row-major; either may be NULL to skip.
  * set_factors also zeroes all dual/auxiliary state and the iteration state.   */
 int nmfx_set_factors(nmfx_handle_t h, const double* w, const double* hmat);

@@ -11,6 +11,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib as L
+from . import sparse
 from . import utils
 from ._driver import Referee, Results, drive
 from .engine import Engine
@@ -41,6 +42,7 @@ def admm(v, k, *, rho=1, distance_type='eu', reg_w=(0, 'nn'), reg_h=(0, 'l2n'), 
                             reg_w[0], reg_w[1], reg_h[0], reg_h[1])
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via admm.py:289
+    sparse.reject(v, 'admm')
     dist = L.EU if distance_type == 'eu' else L.KL
     init = utils.initial_factors(v, k, nndsvd_init, defer_device=True)
     prox_h = _prox_code(reg_h[1])

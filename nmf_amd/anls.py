@@ -13,6 +13,7 @@ import logging
 from collections import namedtuple
 
 from . import _lib as L
+from . import sparse
 from . import utils
 from ._driver import Referee, Results, drive
 from .engine import Engine
@@ -27,6 +28,7 @@ def anls(x, k, *, distance_type='eu', use_fcnnls=False, lambda_w=0, lambda_h=0, 
                             lambda_h, use_fcnnls)
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via anls.py:108
+    sparse.reject(x, 'anls')
     dist = L.EU if distance_type == 'eu' else L.KL
     init = utils.initial_factors(x, k, nndsvd_init, uniform=True, defer_device=True)
     with Engine.for_data(x, k, device=device, engine=engine) as eng:

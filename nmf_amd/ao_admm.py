@@ -21,6 +21,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib as L
+from . import sparse
 from . import utils
 from ._driver import Referee, Results, drive
 from .engine import Engine
@@ -51,6 +52,7 @@ def ao_admm(v, k, *, distance_type='eu', reg_w=(0, 'nn'), reg_h=(0, 'l2n'), min_
                             tol1, tol2, reg_w[0], reg_w[1], reg_h[0], reg_h[1])
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via ao_admm.py:256
+    sparse.reject(v, 'ao_admm')
     dist = L.EU if distance_type == 'eu' else L.KL
     init = utils.initial_factors(v, k, nndsvd_init, defer_device=True)
     # the reference meets the H regulariser first (ao_admm.py:261), then W's

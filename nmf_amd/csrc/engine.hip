@@ -45,7 +45,8 @@ static int preload_once(nmfx_engine* E) {
     std::lock_guard<std::mutex> lock(mu);
     if (done[E->device]) return NMFX_OK;
     if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_aoadmm() ||
-        nmfx_preload_anls() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic()) {
+        nmfx_preload_anls() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic() ||
+        nmfx_preload_sparse()) {
         E->err = "loading the kernels onto the device failed"; return NMFX_E_HIP; }
     hipLaunchKernelGGL(nmfx_startup_kernel, dim3(1), dim3(1), 0, 0, (int*)nullptr);
     NMFX_HIP(hipGetLastError());
@@ -124,7 +125,7 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
 
 extern "C" {
 
-int nmfx_version(void) { return 300; }      // round 3: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 310; }      // 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -216,10 +217,42 @@ int nmfx_create(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k) {
     return NMFX_OK;
 }
 
+int nmfx_create_csr(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k, int64_t nnz) {
+    if (!out) { g_err = "out is NULL"; return NMFX_E_ARG; }
+    *out = nullptr;
+    if (m <= 0 || n <= 0 || nnz < 0) { g_err = "create_csr: m, n must be positive and nnz >= 0"; return NMFX_E_ARG; }
+    if (k < 1 || k > 256) { g_err = "create_csr: sparse input supports 1 <= k <= 256 components"; return NMFX_E_ARG; }
+    if (m > INT32_MAX || n > INT32_MAX || nnz > m * n) { g_err = "create_csr: m, n < 2^31 and nnz <= m n"; return NMFX_E_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device"; return NMFX_E_HIP; }
+    if (device < 0 || device >= ndev) { g_err = "device index out of range"; return NMFX_E_ARG; }
+    nmfx_engine* E = new nmfx_engine();
+    E->device = device; E->m = m; E->n = n; E->k = k;
+    E->kp = k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : k <= 64 ? 64 : k <= 128 ? 128 : 256;
+    E->mp = m; E->np = n;
+    auto fail = [&](int rc) { g_err = E->err; nmfx_destroy(E); return rc; };
+    if (hipSetDevice(device) != hipSuccess) { E->err = "hipSetDevice failed"; return fail(NMFX_E_HIP); }
+    int rc;
+    if ((rc = preload_once(E))) return fail(rc);
+    if (hipStreamCreateWithFlags(&E->own_stream, hipStreamNonBlocking) != hipSuccess) { E->err = "hipStreamCreate failed"; return fail(NMFX_E_HIP); }
+    E->stream = E->own_stream;
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) E->ncu = prop.multiProcessorCount; }
+    E->precision = 0;
+    if ((rc = dev_alloc(E, &E->xf64, 8))) return fail(rc);
+    if ((rc = dev_alloc(E, &E->state, 1))) return fail(rc);
+    hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, E->stream, E->state);
+    if (hipGetLastError() != hipSuccess) { E->err = "init_state launch failed"; return fail(NMFX_E_HIP); }
+    if ((rc = nmfx_ensure_obj_capacity(E, 4096))) return fail(rc);
+    if ((rc = nmfx_sparse_init(E, nnz))) return fail(rc);
+    *out = E;
+    return NMFX_OK;
+}
+
 int nmfx_destroy(nmfx_handle_t E) {
     if (!E) return NMFX_OK;
     hipSetDevice(E->device);
     if (E->stream) hipStreamSynchronize(E->stream);
+    nmfx_sparse_free(E);
     nmfx_comm_free(E);
     for (auto& t : E->prof_pending) { hipEventDestroy(std::get<1>(t)); hipEventDestroy(std::get<2>(t)); }
     void* bufs[] = {E->V, E->W[0], E->W[1], E->H, E->HHt, E->HHt_part, E->G_part, E->A_part, E->B_part,
@@ -253,6 +286,7 @@ int nmfx_reset_stream(nmfx_handle_t E) {
 }
 
 int nmfx_set_precision(nmfx_handle_t E, int mode) {
+    NMFX_DENSE_ONLY(E);
     if (E) { E->himg_both = false; E->wimg_ok = false; E->gxb_img_ready = false; }
     if (!E || (mode != 0 && mode != 1)) { if (E) E->err = "precision must be 0 (f32) or 1 (split bf16)"; return NMFX_E_ARG; }
     if (E->precision != mode) nmfx_comm_invalidate(E);
@@ -263,6 +297,7 @@ int nmfx_set_precision(nmfx_handle_t E, int mode) {
 const char* nmfx_get_note(nmfx_handle_t E) { return E ? E->note.c_str() : ""; }
 
 int nmfx_get_precision(nmfx_handle_t E) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     return (E->precision == 1 && nmfx_bf16_supported(E)) ? 1 : 0;
 }
@@ -275,6 +310,7 @@ int nmfx_synchronize(nmfx_handle_t E) {
 }
 
 int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int64_t row0, int64_t rows) {
+    NMFX_DENSE_ONLY(E);
     if (E) E->anls_a_ready = false;
     if (!E) return NMFX_E_ARG;
     if (!host || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
@@ -313,6 +349,7 @@ int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int6
 }
 
 int nmfx_upload_v_device(nmfx_handle_t E, const void* dev, int dtype, int64_t ld, int64_t row0, int64_t rows) {
+    NMFX_DENSE_ONLY(E);
     if (E) E->anls_a_ready = false;
     if (!E) return NMFX_E_ARG;
     if (!dev || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
@@ -363,6 +400,12 @@ static int get_padded(nmfx_engine* E, const float* src, double* dst, int64_t row
 
 int nmfx_set_factors(nmfx_handle_t E, const double* w, const double* hmat) {
     if (!E) return NMFX_E_ARG;
+    if (E->sp) {                                       // (the same reset of the iteration state as below, then the sparse layouts)
+        NMFX_HIP(hipSetDevice(E->device));
+        hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, E->stream, E->state);
+        NMFX_HIP(hipGetLastError());
+        return nmfx_sparse_set_factors(E, w, hmat);
+    }
     NMFX_HIP(hipSetDevice(E->device));
     int rc;
     if (w) {
@@ -404,6 +447,7 @@ static int read_state(nmfx_engine* E, DevState* hs) {
 
 int nmfx_get_factors(nmfx_handle_t E, double* w, double* hmat) {
     if (!E) return NMFX_E_ARG;
+    if (E->sp) return nmfx_sparse_get_factors(E, w, hmat);
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
     if (hs.flag && !E->w_in_place) E->wsel = (int)((hs.stop_i + 1) & 1);
@@ -413,6 +457,7 @@ int nmfx_get_factors(nmfx_handle_t E, double* w, double* hmat) {
 }
 
 int nmfx_get_matrix(nmfx_handle_t E, const char* name, double* out) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !name || !out) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     const std::string s(name);
@@ -428,6 +473,7 @@ int nmfx_get_matrix(nmfx_handle_t E, const char* name, double* out) {
 }
 
 int nmfx_set_matrix(nmfx_handle_t E, const char* name, const double* in) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !name || !in) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     int rc;
@@ -456,6 +502,7 @@ int nmfx_get_state(nmfx_handle_t E, int* stop_rule, int64_t* stop_i, int64_t* n_
 }
 
 int nmfx_get_diagnostics(nmfx_handle_t E, int64_t* nnls_evicted, int64_t* nnls_capped) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
@@ -465,6 +512,7 @@ int nmfx_get_diagnostics(nmfx_handle_t E, int64_t* nnls_evicted, int64_t* nnls_c
 }
 
 int nmfx_get_nnls_fallbacks(nmfx_handle_t E, int64_t* problems, int64_t* half_steps) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
@@ -474,6 +522,7 @@ int nmfx_get_nnls_fallbacks(nmfx_handle_t E, int64_t* problems, int64_t* half_st
 }
 
 int nmfx_get_inner_paths(nmfx_handle_t E, int64_t out[4]) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !out) return NMFX_E_ARG;
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
@@ -492,6 +541,7 @@ int nmfx_get_objectives(nmfx_handle_t E, int64_t first, int64_t count, double* o
 }
 
 int nmfx_get_inner_counts(nmfx_handle_t E, int64_t first, int64_t count, int32_t* out) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !out || first < 0 || count < 0 || first + count > E->inner_cap) {
         if (E) E->err = "get_inner_counts: range"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
@@ -503,6 +553,7 @@ int nmfx_get_inner_counts(nmfx_handle_t E, int64_t first, int64_t count, int32_t
 
 // ---- exchange buffers ----------------------------------------------------
 int nmfx_exchange_sizes(nmfx_handle_t E, int64_t* n_f32, int64_t* n_f64) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (n_f32) *n_f32 = (int64_t)E->kp * E->np + (int64_t)E->kp * E->kp + E->kp + NMFX_XTAIL;
     if (n_f64) *n_f64 = 8 + 4 * NMFX_MAX_FUSED_ROUNDS;
@@ -510,6 +561,7 @@ int nmfx_exchange_sizes(nmfx_handle_t E, int64_t* n_f32, int64_t* n_f64) {
 }
 
 int nmfx_set_exchange_rank(nmfx_handle_t E, int rank, int world) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (world == 0) { E->xrank = -1; E->xworld = 0; return NMFX_OK; }           // back to the separate f64 exchange
     if (world < 1 || world > NMFX_XTAIL_RANKS || rank < 0 || rank >= world) { E->err = "set_exchange_rank: 1 <= world <= 64, 0 <= rank < world"; return NMFX_E_ARG; }
@@ -519,6 +571,7 @@ int nmfx_set_exchange_rank(nmfx_handle_t E, int rank, int world) {
 }
 
 int nmfx_set_exchange_buffers(nmfx_handle_t E, void* f32, int64_t n_f32, void* f64, int64_t n_f64) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !f32 || !f64) return NMFX_E_ARG;
     int64_t need32, need64;
     nmfx_exchange_sizes(E, &need32, &need64);
@@ -535,6 +588,7 @@ int nmfx_set_exchange_buffers(nmfx_handle_t E, void* f32, int64_t n_f32, void* f
 }
 
 int nmfx_get_exchange_buffers(nmfx_handle_t E, void** f32, void** f64) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (f32) *f32 = E->xf32;
     if (f64) *f64 = E->xf64;
@@ -560,12 +614,14 @@ int nmfx_resume(nmfx_handle_t E) {
 
 // ---- iteration base (hipGraph replay support) --------------------------------
 int nmfx_reserve_objectives(nmfx_handle_t E, int64_t count) {
+    NMFX_DENSE_ONLY(E);
     if (!E || count < 0) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     return nmfx_ensure_obj_capacity(E, count + 2);
 }
 
 int nmfx_shift_iteration_base(nmfx_handle_t E, int64_t delta) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     hipLaunchKernelGGL(shift_iteration_base_kernel, dim3(1), dim3(1), 0, E->stream, E->state, (long long)delta);
@@ -591,6 +647,7 @@ static int check_ready(nmfx_engine* E, int64_t first, int64_t count, bool mur_en
 // only good if NOTHING else has written H or those buffers in between -- every entry point of another solver, and the
 // Euclidean MUR phases, void them; ADVICE r2: only nmfx_set_factors did)
 int nmfx_mur_phase_a(nmfx_handle_t E, int distance, double lambda_w, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (E) E->himg_both = false;
     if (!E) return NMFX_E_ARG;
     if (distance != NMFX_KL) E->kl_h_iter = -2;
@@ -610,6 +667,7 @@ static bool mur_chunkable(nmfx_engine* E, int distance) {
     return distance == NMFX_EU && E->precision == 1 && nmfx_bf16_supported(E);
 }
 int nmfx_mur_chunk_info(nmfx_handle_t E, int distance, int64_t* unit, int64_t* n_padded, int64_t* k_padded) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     const bool ok = mur_chunkable(E, distance);
     if (unit) *unit = ok ? 128 : 0;
@@ -618,6 +676,7 @@ int nmfx_mur_chunk_info(nmfx_handle_t E, int distance, int64_t* unit, int64_t* n
     return NMFX_OK;
 }
 int nmfx_mur_phase_a_head(nmfx_handle_t E, int distance, double lambda_w, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     E->himg_both = false;
     E->kl_h_iter = -2;
@@ -626,6 +685,7 @@ int nmfx_mur_phase_a_head(nmfx_handle_t E, int distance, double lambda_w, int64_
     return nmfx_mur_eu_phase_a_head_bf16(E, lambda_w, j);
 }
 int nmfx_mur_phase_a_cols(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (!mur_chunkable(E, distance)) { E->err = "phase_a_cols: Euclidean loss on the split-bf16 path only (nmfx_mur_chunk_info)"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
@@ -634,6 +694,7 @@ int nmfx_mur_phase_a_cols(nmfx_handle_t E, int distance, int64_t c0, int64_t c1)
 
 int nmfx_mur_phase_b(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1,
                      double tol2, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (E) E->himg_both = false;
     if (!E) return NMFX_E_ARG;
     if (distance != NMFX_KL) E->kl_h_iter = -2;
@@ -654,6 +715,7 @@ int nmfx_mur_phase_b(nmfx_handle_t E, int distance, double lambda_h, int64_t min
 
 // Phase B by column slices (reduce-scatter / all-gather exchange, include/nmfx.h)
 int nmfx_mur_slice_info(nmfx_handle_t E, int distance, int world, int64_t* cols, int64_t* elems) {
+    NMFX_DENSE_ONLY(E);
     if (!E || world < 1) return NMFX_E_ARG;
     const bool ok = mur_chunkable(E, distance) && E->xworld == world && (E->np / 64) % world == 0;
     const int64_t c = ok ? E->np / world : 0;
@@ -668,6 +730,7 @@ static int slice_args(nmfx_engine* E, int distance, int64_t c0, int64_t c1, cons
 }
 int nmfx_mur_phase_b_slice(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j,
                            int64_t c0, int64_t c1) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     E->himg_both = false;
     E->kl_h_iter = -2;
@@ -678,6 +741,7 @@ int nmfx_mur_phase_b_slice(nmfx_handle_t E, int distance, double lambda_h, int64
     return nmfx_mur_eu_phase_b_slice_bf16(E, lambda_h, min_iter, tol1, tol2, j, (int)(c0 / 64), (int)((c1 - c0) / 64));
 }
 int nmfx_mur_phase_b_rest(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     int rc = slice_args(E, distance, c0, c1, "phase_b_rest"); if (rc) return rc;
     NMFX_HIP(hipSetDevice(E->device));
@@ -685,6 +749,7 @@ int nmfx_mur_phase_b_rest(nmfx_handle_t E, int distance, int64_t c0, int64_t c1)
 }
 
 int nmfx_mur_finish_a(nmfx_handle_t E, int distance, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     int rc = check_ready(E, j, 1); if (rc) return rc;
     if (E->kp > 128 && (distance == NMFX_EU || distance == NMFX_KL)) return nmfx_generic_mur_finish_a(E, distance, j);
@@ -694,6 +759,7 @@ int nmfx_mur_finish_a(nmfx_handle_t E, int distance, int64_t j) {
 }
 
 int nmfx_mur_finish_b(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     int rc = check_ready(E, j, 1, false); if (rc) return rc;       // (the closing step of EVERY row-sharded solver, not only MUR's)
     return nmfx_finish_b(E, min_iter, tol1, tol2, j);
@@ -702,6 +768,7 @@ int nmfx_mur_finish_b(nmfx_handle_t E, int64_t min_iter, double tol1, double tol
 int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h, int64_t min_iter,
                  double tol1, double tol2, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
+    if (E->sp) return nmfx_sparse_mur_run(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
     int rc = check_ready(E, first, count); if (rc) return rc;
     E->fused_pack = true;            // nothing is exchanged between the phases here
     for (int64_t j = first; j < first + count && !rc; ++j) {
@@ -714,6 +781,7 @@ int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h
 
 int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1, double tol2,
                     int64_t iters_done) {
+    if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
     int rc;
     if ((rc = nmfx_mur_finish_a(E, distance, iters_done))) return rc;
     return nmfx_mur_finish_b(E, min_iter, tol1, tol2, iters_done);
@@ -735,6 +803,7 @@ static void drain_profile(nmfx_engine* E) {
 }
 
 int nmfx_profile_enable(nmfx_handle_t E, int on) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     drain_profile(E);
     E->prof = on != 0;
@@ -742,6 +811,7 @@ int nmfx_profile_enable(nmfx_handle_t E, int on) {
 }
 
 int nmfx_profile_get(nmfx_handle_t E, const char* name, double* total_ms, int64_t* launches) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !name) return NMFX_E_ARG;
     drain_profile(E);
     auto it = E->prof_slots.find(name);
@@ -754,6 +824,7 @@ int nmfx_profile_get(nmfx_handle_t E, const char* name, double* total_ms, int64_
 // the per-launch time of the dominant kernel without an event (= a command-processor barrier) in front of
 // every launch, which costs the W phase ~10 us that no real iteration pays.
 int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int reps, double* ms_per_launch) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !which || reps <= 0 || !ms_per_launch) return NMFX_E_ARG;
     const std::string w(which);
     int rc = check_ready(E, 0, 0, !(w.rfind("ao_", 0) == 0 || w.rfind("sk_", 0) == 0)); if (rc) return rc;
@@ -807,6 +878,7 @@ int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int re
 }
 
 int nmfx_profile_reset(nmfx_handle_t E) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     drain_profile(E);
     E->prof_slots.clear();

@@ -248,6 +248,7 @@ static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double
 }
 
 extern "C" int nmfx_set_l2n_operator(nmfx_handle_t E, int which, const double* p) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !p || (which != 0 && which != 1)) { if (E) E->err = "set_l2n_operator: bad argument"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
     float** dst = which == 0 ? &E->Pw : &E->Ph;
@@ -264,6 +265,7 @@ extern "C" int nmfx_set_l2n_operator(nmfx_handle_t E, int which, const double* p
 // Function-level entry (tests, and callers that drive their own ADMM loop): X = prox(X_aux, dual) on one side of the
 // current ADMM state; update_dual != 0 also performs dual += X - X_aux (admm.py:321-322).
 extern "C" int nmfx_prox_apply(nmfx_handle_t E, int side, int prox, double rho, double lambda, int update_dual) {
+    NMFX_DENSE_ONLY(E);
     if (!E || (side != 0 && side != 1)) { if (E) E->err = "prox_apply: side must be 0 (W) or 1 (H)"; return NMFX_E_ARG; }
     if (prox != NMFX_PROX_L1INF && prox != NMFX_PROX_L1INF_T) { E->err = "prox_apply: only the l1inf operators have a launch of their own"; return NMFX_E_ARG; }
     if (!(rho != 0.0)) { E->err = "prox_apply: rho must not be zero"; return NMFX_E_ARG; }
@@ -314,6 +316,7 @@ static int admm_begin(nmfx_engine* E, int distance, double rho, int prox_w, int 
 // ---- row-sharded form: phase_products -> [all-reduce f32 + f64] -> phase_update (the H half is replicated work on the
 // all-reduced sums, the W half is local to the rank's rows; ADMM has no inner loop, so this is the only exchange) ----
 extern "C" int nmfx_admm_phase_products(nmfx_handle_t E, int distance, double rho, int prox_w, int prox_h, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = admm_begin(E, distance, rho, prox_w, prox_h, j, 1); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_admm_phase(E, 0, distance, rho, prox_w, 0.0, prox_h, 0.0, 0, 0.0, 0.0, j);      // (r4)
     return distance == NMFX_EU ? admm_eu_products(E) : admm_kl_products(E);
@@ -321,6 +324,7 @@ extern "C" int nmfx_admm_phase_products(nmfx_handle_t E, int distance, double rh
 
 extern "C" int nmfx_admm_phase_update(nmfx_handle_t E, int distance, double rho, int prox_w, double lambda_w, int prox_h,
                                       double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown loss type."; return NMFX_E_ARG; }
     if (!E->auxH || j < 0) { E->err = "admm_phase_update: call nmfx_admm_phase_products first"; return NMFX_E_STATE; }
@@ -333,6 +337,7 @@ extern "C" int nmfx_admm_phase_update(nmfx_handle_t E, int distance, double rho,
 extern "C" int nmfx_admm_run(nmfx_handle_t E, int distance, double rho, int prox_w, double lambda_w, int prox_h,
                              double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t first,
                              int64_t count) {
+    NMFX_DENSE_ONLY(E);
     int rc = admm_begin(E, distance, rho, prox_w, prox_h, first, count, true); if (rc) return rc;
     E->kl_bt_ready = false;    // (slabs a fused auxiliaries launch left for this iteration are not trusted across calls)
     if (E->kp > 128)           // composed from the generic product kernel (kernels_generic.hip)

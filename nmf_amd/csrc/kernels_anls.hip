@@ -884,6 +884,7 @@ static int anls_ready(nmfx_engine* E, int64_t j, double lam) {
 // ---- row-sharded form: objective partial -> [all-reduce f64] -> phase_w -> [all-reduce f32]
 // -> phase_h ----
 extern "C" int nmfx_anls_phase_objective(nmfx_handle_t E, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (E) { E->himg_both = false; E->kl_h_iter = -2; }
     int rc = anls_ready(E, j, 0.0); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_anls_phase(E, 0, 0.0, 0, 0.0, 0.0, j);
@@ -893,6 +894,7 @@ extern "C" int nmfx_anls_phase_objective(nmfx_handle_t E, int64_t j) {
 
 extern "C" int nmfx_anls_phase_w(nmfx_handle_t E, double lambda_w, int64_t min_iter, double tol1, double tol2,
                                  int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (E) { E->himg_both = false; E->kl_h_iter = -2; }
     int rc = anls_ready(E, j, lambda_w); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_anls_phase(E, 1, lambda_w, min_iter, tol1, tol2, j);
@@ -900,6 +902,7 @@ extern "C" int nmfx_anls_phase_w(nmfx_handle_t E, double lambda_w, int64_t min_i
 }
 
 extern "C" int nmfx_anls_phase_h(nmfx_handle_t E, double lambda_h, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     if (E) { E->himg_both = false; E->kl_h_iter = -2; }
     int rc = anls_ready(E, j, lambda_h); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_anls_phase(E, 2, lambda_h, 0, 0.0, 0.0, j);
@@ -907,6 +910,7 @@ extern "C" int nmfx_anls_phase_h(nmfx_handle_t E, double lambda_h, int64_t j) {
 }
 
 extern "C" int nmfx_anls_set_distance(nmfx_handle_t E, int distance) {
+    NMFX_DENSE_ONLY(E);
     if (!E || (distance != NMFX_EU && distance != NMFX_KL)) { if (E) E->err = "Unknown distance type."; return NMFX_E_ARG; }
     E->anls_dist = distance;
     E->anls_a_ready = false;
@@ -915,6 +919,7 @@ extern "C" int nmfx_anls_set_distance(nmfx_handle_t E, int distance) {
 
 extern "C" int nmfx_anls_run(nmfx_handle_t E, double lambda_w, double lambda_h, int64_t min_iter, double tol1,
                              double tol2, int64_t first, int64_t count) {
+    NMFX_DENSE_ONLY(E);
     if (E) { E->himg_both = false; E->kl_h_iter = -2; }
     if (!E) return NMFX_E_ARG;
     if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }

@@ -2049,6 +2049,7 @@ static int aoadmm_kl_iteration_bf16(nmfx_engine* E, int prox_w, double lam_w, in
 extern "C" int nmfx_aoadmm_run(nmfx_handle_t E, int distance, int prox_w, double lambda_w, int prox_h,
                                double lambda_h, int admm_iter, int64_t min_iter, double tol1, double tol2,
                                int64_t first, int64_t count) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
     if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown loss function type."; return NMFX_E_ARG; }
@@ -2118,6 +2119,7 @@ static int ao_sharded_ready(nmfx_engine* E, int64_t j, bool any_k = false) {
 }
 
 extern "C" int nmfx_aoadmm_phase_h_products(nmfx_handle_t E, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_sharded_ready(E, j, true); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_phase(E, 0, 0, 0.0, 0, 0, 0.0, 0.0, j, 0);
     if (j == 0 && (rc = ao_new_pair_objective(E))) return rc;                      // obj[0] partials (ao_admm.py:256)
@@ -2126,6 +2128,7 @@ extern "C" int nmfx_aoadmm_phase_h_products(nmfx_handle_t E, int64_t j) {
 
 extern "C" int nmfx_aoadmm_phase_h_solve(nmfx_handle_t E, int prox_h, double lambda_h, int admm_iter,
                                          int64_t min_iter, double tol1, double tol2, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_sharded_ready(E, j, true); if (rc) return rc;
     if (prox_h != NMFX_PROX_NN && prox_h != NMFX_PROX_L1N) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     if (E->kp > 128) return nmfx_generic_aoadmm_phase(E, 1, prox_h, lambda_h, admm_iter, min_iter, tol1, tol2, j, 0);
@@ -2133,6 +2136,7 @@ extern "C" int nmfx_aoadmm_phase_h_solve(nmfx_handle_t E, int prox_h, double lam
 }
 
 extern "C" int nmfx_aoadmm_phase_w_products(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_sharded_ready(E, j, true); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_phase(E, 2, 0, 0.0, 0, min_iter, tol1, tol2, j, 0);
     return ao_w_products(E, j, min_iter, tol1, tol2);
@@ -2141,6 +2145,7 @@ extern "C" int nmfx_aoadmm_phase_w_products(nmfx_handle_t E, int64_t min_iter, d
 // One inner round of the W sub-problem on this rank's rows; leaves this rank's norm sums of
 // the round in the f64 exchange buffer [1..4] for the caller to all-reduce.
 extern "C" int nmfx_aoadmm_phase_w_round(nmfx_handle_t E, int prox_w, double lambda_w, int round) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_sharded_ready(E, 0, true); if (rc) return rc;
     if (prox_w != NMFX_PROX_NN && prox_w != NMFX_PROX_L1N) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
@@ -2156,6 +2161,7 @@ extern "C" int nmfx_aoadmm_phase_w_round(nmfx_handle_t E, int prox_w, double lam
 // the new pair (summed into the exchange buffer by the next nmfx_aoadmm_phase_h_products or by
 // nmfx_objective_partial).
 extern "C" int nmfx_aoadmm_phase_w_close(nmfx_handle_t E, int admm_iter, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_sharded_ready(E, j, true); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_phase(E, 4, 0, 0.0, admm_iter, 0, 0.0, 0.0, j, 0);
     if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1, E->xf64 + 1))) return rc;
@@ -2197,6 +2203,7 @@ static int ao_kl_sharded_ready(nmfx_engine* E, int64_t j) {
 static bool kl_prox_ok(int p) { return p == NMFX_PROX_NN || p == NMFX_PROX_L1N; }
 
 extern "C" int nmfx_aoadmm_kl_phase_h_products(nmfx_handle_t E, int64_t j, int round) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_kl_sharded_ready(E, j); if (rc) return rc;
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 0, 0, 0.0, 0, 0, 0.0, 0.0, j, round);
@@ -2215,6 +2222,7 @@ extern "C" int nmfx_aoadmm_kl_phase_h_products(nmfx_handle_t E, int64_t j, int r
 
 extern "C" int nmfx_aoadmm_kl_phase_h_round(nmfx_handle_t E, int prox_h, double lambda_h, int round, int64_t min_iter,
                                             double tol1, double tol2, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_kl_sharded_ready(E, j); if (rc) return rc;
     if (!kl_prox_ok(prox_h)) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
@@ -2226,6 +2234,7 @@ extern "C" int nmfx_aoadmm_kl_phase_h_round(nmfx_handle_t E, int prox_h, double 
 
 extern "C" int nmfx_aoadmm_kl_phase_h_close(nmfx_handle_t E, int admm_iter, int64_t min_iter, double tol1, double tol2,
                                             int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_kl_sharded_ready(E, j); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 2, 0, 0.0, admm_iter, min_iter, tol1, tol2, j, 0);
     const int64_t kk = (int64_t)E->kp * E->kp;
@@ -2238,6 +2247,7 @@ extern "C" int nmfx_aoadmm_kl_phase_h_close(nmfx_handle_t E, int admm_iter, int6
 // One round of the W sub-problem on this rank's rows; leaves this rank's norm sums of the round in the f64 exchange
 // buffer [1..4] for the caller to all-reduce (round r + 1 takes the stop decision of round r from the reduced sums).
 extern "C" int nmfx_aoadmm_kl_phase_w_round(nmfx_handle_t E, int prox_w, double lambda_w, int round) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_kl_sharded_ready(E, 0); if (rc) return rc;
     if (!kl_prox_ok(prox_w)) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
@@ -2256,6 +2266,7 @@ extern "C" int nmfx_aoadmm_kl_phase_w_round(nmfx_handle_t E, int prox_w, double 
 }
 
 extern "C" int nmfx_aoadmm_kl_phase_w_close(nmfx_handle_t E, int admm_iter, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_kl_sharded_ready(E, j); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 4, 0, 0.0, admm_iter, 0, 0.0, 0.0, j, 0);
     if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1, E->xf64 + 1))) return rc;
@@ -2269,6 +2280,7 @@ extern "C" int nmfx_aoadmm_kl_phase_w_close(nmfx_handle_t E, int admm_iter, int6
 // before the last one, reruns exactly that many rounds from the saved start -- what the single-GPU path does with
 // its block partials.  admm_iter <= NMFX_MAX_FUSED_ROUNDS (64).
 extern "C" int nmfx_aoadmm_phase_w_fused(nmfx_handle_t E, int prox_w, double lambda_w, int admm_iter) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (prox_w != NMFX_PROX_NN && prox_w != NMFX_PROX_L1N) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     if (admm_iter < 1 || admm_iter > NMFX_MAX_FUSED_ROUNDS) { E->err = "phase_w_fused: admm_iter out of range"; return NMFX_E_ARG; }
@@ -2286,6 +2298,7 @@ extern "C" int nmfx_aoadmm_phase_w_fused(nmfx_handle_t E, int prox_w, double lam
 }
 
 extern "C" int nmfx_aoadmm_phase_w_repair(nmfx_handle_t E, int prox_w, double lambda_w, int admm_iter, int64_t j) {
+    NMFX_DENSE_ONLY(E);
     int rc = ao_sharded_ready(E, j); if (rc) return rc;
     if (admm_iter < 1 || admm_iter > NMFX_MAX_FUSED_ROUNDS) { E->err = "phase_w_repair: admm_iter out of range"; return NMFX_E_ARG; }
     { ProfScope ps(E, "inner_w");
@@ -2295,6 +2308,7 @@ extern "C" int nmfx_aoadmm_phase_w_repair(nmfx_handle_t E, int prox_w, double la
 
 // f64 exchange buffer [0] = this rank's objective partial of the current pair.
 extern "C" int nmfx_objective_partial(nmfx_handle_t E) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     if (E->kp > 128 && (E->family == 2 || E->family == 3)) return NMFX_OK;      // (the composed AO-ADMM / ADMM phases close every iteration with it: xf64[0] holds it)
@@ -2304,6 +2318,7 @@ extern "C" int nmfx_objective_partial(nmfx_handle_t E) {
 
 // bookkeeping of the last iteration's objective (obj_part is already filled)
 extern "C" int nmfx_aoadmm_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t done) {
+    NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     int rc;

@@ -3438,6 +3438,7 @@ static int pair_iteration(nmfx_engine* E, const double* lw, const double* lh, in
 
 extern "C" int nmfx_mur_pair_run(nmfx_handle_t E, const double* lambda_w, const double* lambda_h, int64_t min_iter, double tol1,
                                  double tol2, int64_t first, int64_t count) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !lambda_w || !lambda_h) { if (E) E->err = "mur_pair_run: lambda_w[2], lambda_h[2]"; return NMFX_E_ARG; }
     int rc = pair_ready(E, first, count); if (rc) return rc;
     for (int64_t j = first; j < first + count; ++j)
@@ -3447,6 +3448,7 @@ extern "C" int nmfx_mur_pair_run(nmfx_handle_t E, const double* lambda_w, const 
 
 // objective of the pair(s) the last iteration left, and the last evaluation of the stop rule (nmf/mur.py:127-131 for i = max_iter - 1)
 extern "C" int nmfx_mur_pair_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
+    NMFX_DENSE_ONLY(E);
     int rc = pair_ready(E, iters_done, 1); if (rc) return rc;
     if (!E->bf_ready) E->wsel = (int)(iters_done & 1);
     if ((rc = nmfx_bf16_prepare(E))) return rc;
@@ -3465,6 +3467,7 @@ static int pair_state(nmfx_engine* E, DevState* hs) {
 }
 
 extern "C" int nmfx_pair_get_state(nmfx_handle_t E, int p, int* stop_rule, int64_t* stop_i, int64_t* n_obj) {
+    NMFX_DENSE_ONLY(E);
     if (!E || (p != 0 && p != 1)) { if (E) E->err = "pair: problem index 0 or 1"; return NMFX_E_ARG; }
     DevState hs; int rc;
     if ((rc = pair_state(E, &hs))) return rc;
@@ -3475,6 +3478,7 @@ extern "C" int nmfx_pair_get_state(nmfx_handle_t E, int p, int* stop_rule, int64
 }
 
 extern "C" int nmfx_pair_get_objectives(nmfx_handle_t E, int p, int64_t first, int64_t count, double* out) {
+    NMFX_DENSE_ONLY(E);
     if (!E || !out || (p != 0 && p != 1) || first < 0 || count < 0 || 2 * (first + count) > E->obj_cap) {
         if (E) E->err = "pair_get_objectives: range"; return NMFX_E_ARG; }
     if (count == 0) return NMFX_OK;
@@ -3489,6 +3493,7 @@ extern "C" int nmfx_pair_get_objectives(nmfx_handle_t E, int p, int64_t first, i
 // factors of problem p (k_p <= 64 columns of W / rows of H from offset 64 p): the iterate the reference returns -- W_{stop_i + 1}
 // once the problem's stop rule has fired, else the latest one
 extern "C" int nmfx_pair_get_factors(nmfx_handle_t E, int p, int k_p, double* w, double* hmat) {
+    NMFX_DENSE_ONLY(E);
     if (!E || (p != 0 && p != 1) || k_p < 1 || k_p > 64) { if (E) E->err = "pair_get_factors: p in {0, 1}, 1 <= k_p <= 64"; return NMFX_E_ARG; }
     if (E->kp != 128) { E->err = "pair_get_factors: handle was not created with k = 128"; return NMFX_E_STATE; }
     DevState hs; int rc;

@@ -1,0 +1,660 @@
+// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.
+//
+// Layout.  Both factors are row-major along their long dimension: W [m][kp] (double buffered, E->W) and H^T [n][kp]
+// (nmfx_sparse::Ht), kp in {4, 8, 16, 32, 64, 128, 256}.  V is held twice: CSR (the W phase walks rows of V and gathers
+// rows of H^T) and CSC (the H phase walks columns of V and gathers rows of the new W).  Both phases are one kernel
+// template with the roles swapped (sp_phase_kernel).
+//
+// One wave owns one "unit": a whole row, or a piece of at most SP_CHUNK non-zeros of a longer one.  Inside the wave,
+// groups of G = kp / 4 lanes each take one non-zero at a time (float4 of the gathered row per lane), NG = 64 / G
+// non-zeros per step, four steps' gathers in flight.  Per non-zero: wh = <own row, gathered row> in f64 (products of f32
+// are exact in f64), then the objective term of the pair the W phase starts from, then Sum x h (Euclidean) or
+// Sum x / (wh + 1e-9) h (KL).  The groups' sums are combined by a fixed xor butterfly.  A whole row finishes with the
+// update epilogue of nmf/mur.py:20-49; a piece stores its sum into a slab, and a second launch (sp_fixup_kernel) adds a
+// long row's pieces in piece order and applies the same epilogue.
+//
+// No atomics: k x k Grams and column sums are per-slab f64 partials summed in slab order (sp_stats_kernel /
+// sp_stats_reduce_kernel), objective partials are one f64 per block summed in block order (sp_objective_kernel).
+// Unit -> wave assignment is a fixed stride over the unit list built at upload, so two runs are bit-identical.
+//
+// Objective (nmf/utils.py:18-33) over all m n entries, from the non-zeros plus k x k / k-sized terms:
+//   Euclidean  1/2 [ ||X||^2 - 2 Sum_nz x wh + <W^T W, H H^T> ]      (||X||^2 in f64 at upload, Grams in f64)
+//   KL         Sum_nz [x log(x / wh) - x] + Sum_c colsum(W)_c rowsum(H)_c     (inf / nan log terms -> 0, as the reference)
+#include "kernels_small.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#define SP_CHUNK 256          // non-zeros per unit: longer rows are split into pieces
+#define SP_WAVES 8            // waves per block of the phase kernels
+
+struct SpUnit { long long beg; int row; int len; int slot; int pad; };   // slot -1: a whole row; else the piece's slab row
+struct SpLong { int row; int slot0; int npieces; int pad; };            // a row split into pieces [slot0, slot0 + npieces)
+
+struct SpSide {               // one orientation of V: 0 = CSR (W phase), 1 = CSC (H phase)
+    int64_t rows = 0;
+    int32_t* idx = nullptr;   // [nnz] column (CSR) / row (CSC) of each non-zero
+    float* val = nullptr;     // [nnz]
+    SpUnit* units = nullptr; int64_t nunits = 0;
+    SpLong* longs = nullptr; int64_t nlong = 0;
+    float* slab = nullptr;    // [pieces][kp]
+    int nblk = 1;             // blocks of the phase kernel (a fixed stride over the units)
+};
+
+struct nmfx_sparse {
+    int64_t nnz = 0;
+    double x2 = 0.0;          // ||X||^2 of the stored (f32) values, in f64
+    SpSide side[2];
+    float* Ht = nullptr;      // H^T [n][kp]
+    double* g64[2] = {nullptr, nullptr};   // [0] W^T W, [1] H H^T  [kp][kp]
+    float* gf[2] = {nullptr, nullptr};     // ... in f32 (the Euclidean epilogues)
+    double* cs64[2] = {nullptr, nullptr};  // [0] column sums of W, [1] row sums of H  [kp]
+    float* csf[2] = {nullptr, nullptr};
+    double* stat_part = nullptr;           // [slabs][kp * kp + kp]
+    double* obj_part = nullptr;            // [blocks]
+    int obj_cap = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// device code
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float4 sp_xor4(float4 a, int off) {
+    return make_float4(__shfl_xor(a.x, off, 64), __shfl_xor(a.y, off, 64), __shfl_xor(a.z, off, 64), __shfl_xor(a.w, off, 64));
+}
+__device__ __forceinline__ float4 sp_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float sp_comp(float4 a, int c) { return c == 0 ? a.x : c == 1 ? a.y : c == 2 ? a.z : a.w; }
+
+// Sum over the NG groups of a wave (lanes with equal position in their group); every lane ends with the same bits.
+template <int G>
+__device__ __forceinline__ float4 sp_sum_groups(float4 a) {
+#pragma unroll
+    for (int off = G; off < 64; off <<= 1) a = sp_add4(a, sp_xor4(a, off));
+    return a;
+}
+
+// The update epilogue of one owned row (every lane of the wave takes part; group 0 writes).
+//   Euclidean  out = w a / (w G + lam w + 1e-9)                         (nmf/mur.py:30, 45: (WH)H^T = W (H H^T))
+//   KL         out = 2 w a / (s + sqrt(s^2 + 4 lam w a)),  s = sums     (nmf/mur.py:25-27, 40-42)
+// Components c >= k (the zero padding) are written as 0.
+template <int KP, bool KL>
+__device__ __forceinline__ void sp_epilogue(float4 w4, float4 a4, const float* __restrict__ Gsrc, const float* __restrict__ S,
+                                            float lam, int k, float* __restrict__ out_row, int lig, int grp)
+{
+    constexpr int G = KP / 4, NG = 64 / G;
+    float4 o;
+    if constexpr (KL) {
+        const float4 s4 = *reinterpret_cast<const float4*>(S + lig * 4);
+        float c;
+        c = w4.x * a4.x; o.x = 2.f * c / (s4.x + sqrtf(s4.x * s4.x + 4.f * lam * c));
+        c = w4.y * a4.y; o.y = 2.f * c / (s4.y + sqrtf(s4.y * s4.y + 4.f * lam * c));
+        c = w4.z * a4.z; o.z = 2.f * c / (s4.z + sqrtf(s4.z * s4.z + 4.f * lam * c));
+        c = w4.w * a4.w; o.w = 2.f * c / (s4.w + sqrtf(s4.w * s4.w + 4.f * lam * c));
+    } else {
+        // d = w G for this lane's four components; the groups split the rows of G (l4 = grp, grp + NG, ...), w_l comes
+        // from lane l / 4 (group 0; every group holds the same owned row)
+        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int l4 = grp; l4 < G; l4 += NG) {
+            const float wl[4] = {__shfl(w4.x, l4, 64), __shfl(w4.y, l4, 64), __shfl(w4.z, l4, 64), __shfl(w4.w, l4, 64)};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float4 g = *reinterpret_cast<const float4*>(Gsrc + (4 * l4 + t) * KP + lig * 4);
+                d.x = fmaf(wl[t], g.x, d.x); d.y = fmaf(wl[t], g.y, d.y);
+                d.z = fmaf(wl[t], g.z, d.z); d.w = fmaf(wl[t], g.w, d.w);
+            }
+        }
+        d = sp_sum_groups<G>(d);
+        o.x = w4.x * a4.x / (d.x + lam * w4.x + 1e-9f);
+        o.y = w4.y * a4.y / (d.y + lam * w4.y + 1e-9f);
+        o.z = w4.z * a4.z / (d.z + lam * w4.z + 1e-9f);
+        o.w = w4.w * a4.w / (d.w + lam * w4.w + 1e-9f);
+    }
+    const int c0 = lig * 4;
+    if (c0 + 0 >= k) o.x = 0.f;
+    if (c0 + 1 >= k) o.y = 0.f;
+    if (c0 + 2 >= k) o.z = 0.f;
+    if (c0 + 3 >= k) o.w = 0.f;
+    if (grp == 0) *reinterpret_cast<float4*>(out_row + lig * 4) = o;
+}
+
+// One phase over the units of one orientation.
+//   Own [rows][KP]: the factor being updated (read), Out: where its update goes (may be Own: rows are owned by one wave),
+//   Other [*][KP]: the factor gathered per non-zero, G (KP x KP f32) / S (KP f32): the other factor's Gram / sums.
+//   OBJ: objective partial of the pair (Own, Other) per block into obj_part (Euclidean: Sum x wh; KL: Sum x log(x/wh) - x).
+//   UPDATE: accumulate and run the epilogue (whole rows) or store the piece's sum (pieces).
+template <int KP, bool KL, bool OBJ, bool UPDATE>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
+    const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
+    const float* __restrict__ Other, const float* Own, float* Out, const float* __restrict__ Gf, const float* __restrict__ S,
+    float* __restrict__ slab, double* __restrict__ obj_part, float lam, int k, const int* flag)
+{
+    if (flag && *flag) return;
+    constexpr int G = KP / 4, NG = 64 / G;
+    constexpr bool GLDS = UPDATE && !KL && KP <= 128;
+    __shared__ __attribute__((aligned(16))) float gs[GLDS ? KP * KP : 4];
+    __shared__ double ob[SP_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
+    if constexpr (GLDS) {
+        for (int i = tid * 4; i < KP * KP; i += 64 * SP_WAVES * 4)
+            *reinterpret_cast<float4*>(gs + i) = *reinterpret_cast<const float4*>(Gf + i);
+        __syncthreads();
+    }
+    const float* Gsrc = GLDS ? gs : Gf;
+    double objacc = 0.0;
+    for (int64_t u = (int64_t)blockIdx.x * SP_WAVES + wave; u < nunits; u += (int64_t)gridDim.x * SP_WAVES) {
+        const SpUnit U = units[u];
+        const float4 w4 = *reinterpret_cast<const float4*>(Own + (int64_t)U.row * KP + lig * 4);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        const long long end = U.beg + U.len;
+        for (long long e0 = U.beg + grp; e0 < end; e0 += 4 * NG) {
+            int c[4]; float x[4]; bool ok[4]; float4 h[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const long long e = e0 + (long long)t * NG;
+                ok[t] = e < end;
+                c[t] = ok[t] ? idx[e] : 0;
+                x[t] = ok[t] ? val[e] : 0.f;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) h[t] = *reinterpret_cast<const float4*>(Other + (int64_t)c[t] * KP + lig * 4);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                double wh = (double)w4.x * h[t].x + (double)w4.y * h[t].y + (double)w4.z * h[t].z + (double)w4.w * h[t].w;
+#pragma unroll
+                for (int off = 1; off < G; off <<= 1) wh += __shfl_xor(wh, off, 64);
+                if constexpr (OBJ) {
+                    if (lig == 0 && ok[t]) {
+                        const double xv = x[t];
+                        if constexpr (KL) {
+                            double tl = xv * log(xv / wh);
+                            if (tl == INFINITY || tl != tl) tl = 0.0;      // np.where(t == inf, 0, t); np.where(isnan(t), 0, t)
+                            objacc += tl - xv;
+                        } else {
+                            objacc += xv * wh;
+                        }
+                    }
+                }
+                if constexpr (UPDATE) {
+                    const float q = KL ? (float)((double)x[t] / (wh + 1e-9)) : x[t];
+                    acc.x = fmaf(q, h[t].x, acc.x); acc.y = fmaf(q, h[t].y, acc.y);
+                    acc.z = fmaf(q, h[t].z, acc.z); acc.w = fmaf(q, h[t].w, acc.w);
+                }
+            }
+        }
+        if constexpr (UPDATE) {
+            acc = sp_sum_groups<G>(acc);
+            if (U.slot >= 0) {
+                if (grp == 0) *reinterpret_cast<float4*>(slab + (int64_t)U.slot * KP + lig * 4) = acc;
+            } else {
+                sp_epilogue<KP, KL>(w4, acc, Gsrc, S, lam, k, Out + (int64_t)U.row * KP, lig, grp);
+            }
+        }
+    }
+    if constexpr (OBJ) {
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) objacc += __shfl_xor(objacc, off, 64);
+        if (lane == 0) ob[wave] = objacc;
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0.0;
+            for (int w = 0; w < SP_WAVES; ++w) s += ob[w];
+            obj_part[blockIdx.x] = s;
+        }
+    }
+}
+
+// Rows split into pieces: the pieces' sums added in piece order (group g takes pieces g, g + NG, ..., then the groups'
+// butterfly), then the epilogue.
+template <int KP, bool KL>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_fixup_kernel(
+    const SpLong* __restrict__ longs, int64_t nlong, const float* __restrict__ slab, const float* Own, float* Out,
+    const float* __restrict__ Gf, const float* __restrict__ S, float lam, int k, const int* flag)
+{
+    if (flag && *flag) return;
+    constexpr int G = KP / 4, NG = 64 / G;
+    constexpr bool GLDS = !KL && KP <= 128;
+    __shared__ __attribute__((aligned(16))) float gs[GLDS ? KP * KP : 4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
+    if constexpr (GLDS) {
+        for (int i = tid * 4; i < KP * KP; i += 64 * SP_WAVES * 4)
+            *reinterpret_cast<float4*>(gs + i) = *reinterpret_cast<const float4*>(Gf + i);
+        __syncthreads();
+    }
+    const float* Gsrc = GLDS ? gs : Gf;
+    for (int64_t l = (int64_t)blockIdx.x * SP_WAVES + wave; l < nlong; l += (int64_t)gridDim.x * SP_WAVES) {
+        const SpLong L = longs[l];
+        const float4 w4 = *reinterpret_cast<const float4*>(Own + (int64_t)L.row * KP + lig * 4);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int p = grp; p < L.npieces; p += NG)
+            acc = sp_add4(acc, *reinterpret_cast<const float4*>(slab + (int64_t)(L.slot0 + p) * KP + lig * 4));
+        acc = sp_sum_groups<G>(acc);
+        sp_epilogue<KP, KL>(w4, acc, Gsrc, S, lam, k, Out + (int64_t)L.row * KP, lig, grp);
+    }
+}
+
+// Per-slab f64 partials of F^T F (KP x KP) and of the column sums of F [R][KP]: block (slab, tile) covers rows
+// [s * rps, (s + 1) * rps) and the TD x TD tile (ti, tj) of the Gram; tiles with tj = 0 also sum their columns.
+template <int KP>
+__global__ __launch_bounds__(256) void sp_stats_kernel(const float* __restrict__ F, int64_t R, int64_t rps,
+                                                       double* __restrict__ part, const int* flag)
+{
+    if (flag && *flag) return;
+    constexpr int TD = KP < 64 ? KP : 64, T = KP / TD, NO = TD * TD >= 256 ? TD * TD / 256 : 1;
+    __shared__ float a[16][TD], b[16][TD];
+    const int tid = threadIdx.x, s = blockIdx.x, ti = blockIdx.y / T, tj = blockIdx.y % T;
+    const int64_t r0 = (int64_t)s * rps, r1 = std::min<int64_t>(R, r0 + rps);
+    double acc[NO], cs = 0.0;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) acc[o] = 0.0;
+    for (int64_t rc = r0; rc < r1; rc += 16) {
+        for (int i = tid; i < 16 * TD; i += 256) {
+            const int rr = i / TD, cc = i % TD;
+            const int64_t r = rc + rr;
+            a[rr][cc] = r < r1 ? F[r * KP + ti * TD + cc] : 0.f;
+            b[rr][cc] = r < r1 ? F[r * KP + tj * TD + cc] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int o = 0; o < NO; ++o) {
+            const int e = tid + 256 * o;
+            if (e < TD * TD) {
+                const int p = e / TD, q = e % TD;
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) acc[o] = fma((double)a[rr][p], (double)b[rr][q], acc[o]);
+            }
+        }
+        if (tj == 0 && tid < TD)
+            for (int rr = 0; rr < 16; ++rr) cs += (double)a[rr][tid];
+        __syncthreads();
+    }
+    double* out = part + (int64_t)s * (KP * KP + KP);
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+        const int e = tid + 256 * o;
+        if (e < TD * TD) out[(ti * TD + e / TD) * KP + tj * TD + e % TD] = acc[o];
+    }
+    if (tj == 0 && tid < TD) out[KP * KP + ti * TD + tid] = cs;
+}
+
+// Slabs summed in slab order: [0, kp^2) the Gram, [kp^2, kp^2 + kp) the column sums; f64 and f32 copies.
+__global__ void sp_stats_reduce_kernel(const double* __restrict__ part, int slabs, int kp, double* __restrict__ g64, float* __restrict__ gf,
+                                       double* __restrict__ c64, float* __restrict__ cf, const int* flag)
+{
+    if (flag && *flag) return;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x, kk = kp * kp;
+    if (e >= kk + kp) return;
+    double s = 0.0;
+    for (int i = 0; i < slabs; ++i) s += part[(int64_t)i * (kk + kp) + e];
+    if (e < kk) { g64[e] = s; gf[e] = (float)s; }
+    else { c64[e - kk] = s; cf[e - kk] = (float)s; }
+}
+
+// The objective of the pair from the block partials (block order, then a fixed tree) and the small terms; recorded as
+// obj[j] with the reference's stop rule (record) or only stored to *out.
+template <bool KL>
+__global__ __launch_bounds__(256) void sp_objective_kernel(
+    const double* __restrict__ part, int nblk, const double* __restrict__ gw, const double* __restrict__ gh,
+    const double* __restrict__ cw, const double* __restrict__ ch, int kp, double x2, double* __restrict__ out, int record,
+    long long j, long long min_iter, double tol1, double tol2, DevState* __restrict__ st, double* __restrict__ obj_hist)
+{
+    if (record && st->flag) return;
+    __shared__ double r[2][256];
+    const int tid = threadIdx.x;
+    double s = 0.0, t = 0.0;
+    for (int i = tid; i < nblk; i += 256) s += part[i];
+    if (KL) { for (int c = tid; c < kp; c += 256) t += cw[c] * ch[c]; }
+    else { for (int e = tid; e < kp * kp; e += 256) t += gw[e] * gh[e]; }
+    r[0][tid] = s; r[1][tid] = t;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { r[0][tid] += r[0][tid + w]; r[1][tid] += r[1][tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double obj = KL ? r[0][0] + r[1][0] : 0.5 * (x2 - 2.0 * r[0][0] + r[1][0]);
+        *out = obj;
+        if (record) nmfx_record_objective(st, obj_hist, obj, j, min_iter, tol1, tol2, true);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+static int sp_alloc(nmfx_engine* E, T** p, int64_t count) {
+    NMFX_HIP(hipMalloc(reinterpret_cast<void**>(p), (size_t)std::max<int64_t>(count, 1) * sizeof(T)));
+    NMFX_HIP(hipMemsetAsync(*p, 0, (size_t)std::max<int64_t>(count, 1) * sizeof(T), E->stream));
+    return NMFX_OK;
+}
+
+static int stat_slabs(int kp, int64_t R) {
+    const int T = kp < 64 ? 1 : kp / 64;
+    const int64_t smax = std::max(16, 256 / (T * T));
+    return (int)std::min<int64_t>(smax, std::max<int64_t>(1, (R + 1023) / 1024));
+}
+
+int nmfx_sparse_init(nmfx_engine* E, int64_t nnz) {
+    nmfx_sparse* S = new nmfx_sparse();
+    E->sp = S;
+    S->nnz = nnz;
+    const int64_t kp = E->kp;
+    int rc;
+    if ((rc = sp_alloc(E, &E->W[0], E->m * kp))) return rc;
+    if ((rc = sp_alloc(E, &E->W[1], E->m * kp))) return rc;
+    if ((rc = sp_alloc(E, &S->Ht, E->n * kp))) return rc;
+    for (int f = 0; f < 2; ++f) {
+        if ((rc = sp_alloc(E, &S->g64[f], kp * kp))) return rc;
+        if ((rc = sp_alloc(E, &S->gf[f], kp * kp))) return rc;
+        if ((rc = sp_alloc(E, &S->cs64[f], kp))) return rc;
+        if ((rc = sp_alloc(E, &S->csf[f], kp))) return rc;
+        if ((rc = sp_alloc(E, &S->side[f].idx, nnz))) return rc;
+        if ((rc = sp_alloc(E, &S->side[f].val, nnz))) return rc;
+    }
+    S->side[0].rows = E->m; S->side[1].rows = E->n;
+    const int slabs = std::max(stat_slabs((int)kp, E->m), stat_slabs((int)kp, E->n));
+    if ((rc = sp_alloc(E, &S->stat_part, (int64_t)slabs * (kp * kp + kp)))) return rc;
+    S->obj_cap = 4 * E->ncu + 64;
+    if ((rc = sp_alloc(E, &S->obj_part, S->obj_cap))) return rc;
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
+void nmfx_sparse_free(nmfx_engine* E) {
+    nmfx_sparse* S = E->sp;
+    if (!S) return;
+    void* bufs[] = {S->Ht, S->g64[0], S->g64[1], S->gf[0], S->gf[1], S->cs64[0], S->cs64[1], S->csf[0], S->csf[1],
+                    S->stat_part, S->obj_part};
+    for (void* b : bufs) if (b) hipFree(b);
+    for (auto& sd : S->side) {
+        void* sb[] = {sd.idx, sd.val, sd.units, sd.longs, sd.slab};
+        for (void* b : sb) if (b) hipFree(b);
+    }
+    delete S;
+    E->sp = nullptr;
+}
+
+// Units of one orientation from its pointer array: whole rows, and rows longer than SP_CHUNK cut into pieces.
+static int build_side(nmfx_engine* E, SpSide& sd, const int64_t* ptr) {
+    std::vector<SpUnit> units;
+    std::vector<SpLong> longs;
+    units.reserve((size_t)sd.rows);
+    int slot = 0;
+    for (int64_t r = 0; r < sd.rows; ++r) {
+        const int64_t b = ptr[r], len = ptr[r + 1] - ptr[r];
+        if (len <= SP_CHUNK) { units.push_back({(long long)b, (int)r, (int)len, -1, 0}); continue; }
+        const int np = (int)((len + SP_CHUNK - 1) / SP_CHUNK);
+        longs.push_back({(int)r, slot, np, 0});
+        for (int p = 0; p < np; ++p)
+            units.push_back({(long long)(b + (int64_t)p * SP_CHUNK), (int)r, (int)std::min<int64_t>(SP_CHUNK, len - (int64_t)p * SP_CHUNK), slot + p, 0});
+        slot += np;
+    }
+    for (void* b : {(void*)sd.units, (void*)sd.longs, (void*)sd.slab}) if (b) hipFree(b);
+    sd.units = nullptr; sd.longs = nullptr; sd.slab = nullptr;
+    sd.nunits = (int64_t)units.size(); sd.nlong = (int64_t)longs.size();
+    int rc;
+    if ((rc = sp_alloc(E, &sd.units, sd.nunits))) return rc;
+    if ((rc = sp_alloc(E, &sd.longs, sd.nlong))) return rc;
+    if ((rc = sp_alloc(E, &sd.slab, (int64_t)slot * E->kp))) return rc;
+    if (sd.nunits) NMFX_HIP(hipMemcpyAsync(sd.units, units.data(), units.size() * sizeof(SpUnit), hipMemcpyHostToDevice, E->stream));
+    if (sd.nlong) NMFX_HIP(hipMemcpyAsync(sd.longs, longs.data(), longs.size() * sizeof(SpLong), hipMemcpyHostToDevice, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    sd.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(4 * E->ncu, (sd.nunits + SP_WAVES - 1) / SP_WAVES));
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_upload_csr(nmfx_handle_t E, const int64_t* row_ptr, const int32_t* col_idx, const void* values, int dtype) {
+    if (!E) return NMFX_E_ARG;
+    if (!E->sp) { E->err = "upload_csr: not a sparse handle (nmfx_create_csr)"; return NMFX_E_ARG; }
+    nmfx_sparse* S = E->sp;
+    const int64_t m = E->m, n = E->n, nnz = S->nnz;
+    if (!row_ptr || (nnz > 0 && (!col_idx || !values))) { E->err = "upload_csr: NULL array"; return NMFX_E_ARG; }
+    if (dtype != NMFX_F32 && dtype != NMFX_F64) { E->err = "upload_csr: dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
+    if (row_ptr[0] != 0 || row_ptr[m] != nnz) { E->err = "upload_csr: row_ptr[0] must be 0 and row_ptr[m] the nnz of nmfx_create_csr"; return NMFX_E_ARG; }
+    for (int64_t r = 0; r < m; ++r)          // (the whole row_ptr before any col_idx / values entry is read)
+        if (row_ptr[r + 1] < row_ptr[r] || row_ptr[r + 1] > nnz) { E->err = "upload_csr: row_ptr must not decrease nor exceed nnz"; return NMFX_E_ARG; }
+    std::vector<float> v((size_t)nnz);
+    double x2 = 0.0;
+    for (int64_t r = 0; r < m; ++r) {
+        for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+            const int32_t c = col_idx[e];
+            if (c < 0 || c >= n || (e > row_ptr[r] && c <= col_idx[e - 1])) {
+                E->err = "upload_csr: column indices must lie in [0, n) and increase strictly within a row (no duplicates)"; return NMFX_E_ARG; }
+            const float x = dtype == NMFX_F32 ? static_cast<const float*>(values)[e] : (float)static_cast<const double*>(values)[e];
+            if (!(x >= 0.f)) { E->err = "upload_csr: values must be non-negative (MUR)"; return NMFX_E_ARG; }
+            v[(size_t)e] = x;
+            x2 += (double)x * (double)x;
+        }
+    }
+    // CSC by a counting sort over the rows in order: rows ascend within every column (deterministic)
+    std::vector<int64_t> cptr((size_t)n + 1, 0);
+    for (int64_t e = 0; e < nnz; ++e) cptr[(size_t)col_idx[e] + 1]++;
+    for (int64_t c = 0; c < n; ++c) cptr[(size_t)c + 1] += cptr[(size_t)c];
+    std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
+    std::vector<int32_t> ridx((size_t)nnz);
+    std::vector<float> vt((size_t)nnz);
+    for (int64_t r = 0; r < m; ++r)
+        for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e) {
+            const int64_t d = fill[(size_t)col_idx[e]]++;
+            ridx[(size_t)d] = (int32_t)r; vt[(size_t)d] = v[(size_t)e];
+        }
+    NMFX_HIP(hipSetDevice(E->device));
+    if (nnz) {
+        NMFX_HIP(hipMemcpyAsync(S->side[0].idx, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, E->stream));
+        NMFX_HIP(hipMemcpyAsync(S->side[0].val, v.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, E->stream));
+        NMFX_HIP(hipMemcpyAsync(S->side[1].idx, ridx.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, E->stream));
+        NMFX_HIP(hipMemcpyAsync(S->side[1].val, vt.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, E->stream));
+    }
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    int rc;
+    if ((rc = build_side(E, S->side[0], row_ptr))) return rc;
+    if ((rc = build_side(E, S->side[1], cptr.data()))) return rc;
+    S->x2 = x2;
+    E->have_v = true;
+    return NMFX_OK;
+}
+
+// ---- launchers --------------------------------------------------------------------------------------------------------
+template <int KP>
+static int launch_stats(nmfx_engine* E, const float* F, int64_t R, int f, const int* flag) {
+    nmfx_sparse* S = E->sp;
+    const int slabs = stat_slabs(KP, R), T = KP < 64 ? 1 : KP / 64;
+    const int64_t rps = (R + slabs - 1) / slabs;
+    hipLaunchKernelGGL((sp_stats_kernel<KP>), dim3(slabs, T * T), dim3(256), 0, E->stream, F, R, rps, S->stat_part, flag);
+    const int tot = KP * KP + KP;
+    hipLaunchKernelGGL(sp_stats_reduce_kernel, dim3((tot + 255) / 256), dim3(256), 0, E->stream, (const double*)S->stat_part, slabs, KP,
+                       S->g64[f], S->gf[f], S->cs64[f], S->csf[f], flag);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+// side 0: own W (Wold -> Wnew), gather H^T, other factor's stats 1; side 1: own H^T (in place), gather W, stats 0
+template <int KP, bool KL>
+static int launch_phase(nmfx_engine* E, int side, const float* Own, float* Out, const float* Other, bool obj, bool update,
+                        float lam, const int* flag) {
+    nmfx_sparse* S = E->sp;
+    SpSide& sd = S->side[side];
+    const int o = 1 - side;
+    const dim3 grid(sd.nblk), blk(64 * SP_WAVES);
+#define SP_ARGS sd.units, sd.nunits, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, Out, (const float*)S->gf[o], \
+                (const float*)S->csf[o], sd.slab, S->obj_part, lam, E->k, flag
+    if (obj && update) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, true>), grid, blk, 0, E->stream, SP_ARGS);
+    else if (obj) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, false>), grid, blk, 0, E->stream, SP_ARGS);
+    else hipLaunchKernelGGL((sp_phase_kernel<KP, KL, false, true>), grid, blk, 0, E->stream, SP_ARGS);
+#undef SP_ARGS
+    NMFX_HIP(hipGetLastError());
+    if (update && sd.nlong) {
+        const int nb = (int)std::min<int64_t>(4 * E->ncu, (sd.nlong + SP_WAVES - 1) / SP_WAVES);
+        hipLaunchKernelGGL((sp_fixup_kernel<KP, KL>), dim3(nb), blk, 0, E->stream, (const SpLong*)sd.longs, sd.nlong,
+                           (const float*)sd.slab, Own, Out, (const float*)S->gf[o], (const float*)S->csf[o], lam, E->k, flag);
+        NMFX_HIP(hipGetLastError());
+    }
+    return NMFX_OK;
+}
+
+static int launch_objective(nmfx_engine* E, bool kl, double* out, bool record, int64_t j, int64_t min_iter, double tol1, double tol2) {
+    nmfx_sparse* S = E->sp;
+    auto kern = kl ? sp_objective_kernel<true> : sp_objective_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, E->stream, (const double*)S->obj_part, S->side[0].nblk,
+                       (const double*)S->g64[0], (const double*)S->g64[1], (const double*)S->cs64[0], (const double*)S->cs64[1],
+                       E->kp, S->x2, out, record ? 1 : 0, (long long)j, (long long)min_iter, tol1, tol2, E->state, E->obj_hist);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+template <int KP>
+static int sp_iteration(nmfx_engine* E, bool kl, double lw, double lh, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    nmfx_sparse* S = E->sp;
+    const int* flag = &E->state->flag;
+    const float* Wold = E->W[j & 1];
+    float* Wnew = E->W[(j + 1) & 1];
+    int rc;
+    { ProfScope ps(E, "sp_wphase");
+      rc = kl ? launch_phase<KP, true>(E, 0, Wold, Wnew, S->Ht, true, true, (float)lw, flag)
+              : launch_phase<KP, false>(E, 0, Wold, Wnew, S->Ht, true, true, (float)lw, flag);
+      if (rc) return rc; }
+    if ((rc = launch_objective(E, kl, E->xf64, true, j, min_iter, tol1, tol2))) return rc;
+    { ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<KP>(E, Wnew, E->m, 0, flag))) return rc; }
+    { ProfScope ps(E, "sp_hphase");
+      rc = kl ? launch_phase<KP, true>(E, 1, S->Ht, S->Ht, Wnew, false, true, (float)lh, flag)
+              : launch_phase<KP, false>(E, 1, S->Ht, S->Ht, Wnew, false, true, (float)lh, flag);
+      if (rc) return rc; }
+    { ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<KP>(E, S->Ht, E->n, 1, flag))) return rc; }
+    E->wsel = (int)((j + 1) & 1);
+    return NMFX_OK;
+}
+
+// objective pass of (W[wsel or j & 1], H) without an update
+template <int KP>
+static int sp_objective_pass(nmfx_engine* E, bool kl, const float* W, const int* flag) {
+    return kl ? launch_phase<KP, true>(E, 0, W, nullptr, E->sp->Ht, true, false, 0.f, flag)
+              : launch_phase<KP, false>(E, 0, W, nullptr, E->sp->Ht, true, false, 0.f, flag);
+}
+
+#define SP_DISPATCH(call) \
+    switch (E->kp) { case 4: rc = call<4>; break; case 8: rc = call<8>; break; case 16: rc = call<16>; break; \
+                     case 32: rc = call<32>; break; case 64: rc = call<64>; break; case 128: rc = call<128>; break; \
+                     default: rc = call<256>; break; }
+
+static int sp_ready(nmfx_engine* E, int distance, int64_t first, int64_t count) {
+    if (!E->have_v || !E->have_f) { E->err = "upload the CSR matrix and set factors first"; return NMFX_E_STATE; }
+    if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
+    if (first < 0 || count < 0) { E->err = "negative iteration range"; return NMFX_E_ARG; }
+    int rc = nmfx_enter_family(E, 1); if (rc) return rc;
+    NMFX_HIP(hipSetDevice(E->device));
+    return nmfx_ensure_obj_capacity(E, first + count + 2);
+}
+
+int nmfx_sparse_mur_run(nmfx_engine* E, int distance, double lw, double lh, int64_t min_iter, double tol1, double tol2,
+                        int64_t first, int64_t count) {
+    int rc = sp_ready(E, distance, first, count); if (rc) return rc;
+    const bool kl = distance == NMFX_KL;
+    for (int64_t j = first; j < first + count && !rc; ++j) {
+#define SP_IT(KP) sp_iteration<KP>(E, kl, lw, lh, min_iter, tol1, tol2, j)
+        switch (E->kp) { case 4: rc = SP_IT(4); break; case 8: rc = SP_IT(8); break; case 16: rc = SP_IT(16); break;
+                         case 32: rc = SP_IT(32); break; case 64: rc = SP_IT(64); break; case 128: rc = SP_IT(128); break;
+                         default: rc = SP_IT(256); break; }
+#undef SP_IT
+    }
+    return rc;
+}
+
+static int objective_pass(nmfx_engine* E, bool kl, const float* W, const int* flag) {
+    int rc;
+#define SP_OP(KP) sp_objective_pass<KP>(E, kl, W, flag)
+    switch (E->kp) { case 4: rc = SP_OP(4); break; case 8: rc = SP_OP(8); break; case 16: rc = SP_OP(16); break;
+                     case 32: rc = SP_OP(32); break; case 64: rc = SP_OP(64); break; case 128: rc = SP_OP(128); break;
+                     default: rc = SP_OP(256); break; }
+#undef SP_OP
+    return rc;
+}
+
+int nmfx_sparse_mur_finish(nmfx_engine* E, int distance, int64_t min_iter, double tol1, double tol2, int64_t done) {
+    int rc = sp_ready(E, distance, done, 0); if (rc) return rc;
+    const bool kl = distance == NMFX_KL;
+    if ((rc = objective_pass(E, kl, E->W[done & 1], &E->state->flag))) return rc;
+    return launch_objective(E, kl, E->xf64, true, done, min_iter, tol1, tol2);
+}
+
+// After the stop rule has fired, the launches behind it in the batch did nothing: the current W is the one of the pair at
+// the stop (W[(stop_i + 1) & 1]), whose Gram is still in g64[0].
+static int sync_wsel(nmfx_engine* E) {
+    NMFX_HIP(hipSetDevice(E->device));
+    DevState hs;
+    NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    if (hs.flag) E->wsel = (int)((hs.stop_i + 1) & 1);
+    return NMFX_OK;
+}
+
+int nmfx_sparse_objective_f64(nmfx_engine* E, double* out) {
+    if (!E->have_v || !E->have_f) { E->err = "upload the CSR matrix and set factors first"; return NMFX_E_STATE; }
+    int rc;
+    if ((rc = sync_wsel(E))) return rc;
+    if ((rc = objective_pass(E, false, E->W[E->wsel], nullptr))) return rc;
+    if ((rc = launch_objective(E, false, E->xf64 + 1, false, 0, 0, 0.0, 0.0))) return rc;
+    NMFX_HIP(hipMemcpyAsync(out, E->xf64 + 1, sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
+static int stats_both(nmfx_engine* E) {
+    int rc = NMFX_OK;
+#define SP_ST(KP) (launch_stats<KP>(E, E->W[0], E->m, 0, nullptr) ? NMFX_E_HIP : launch_stats<KP>(E, E->sp->Ht, E->n, 1, nullptr))
+    switch (E->kp) { case 4: rc = SP_ST(4); break; case 8: rc = SP_ST(8); break; case 16: rc = SP_ST(16); break;
+                     case 32: rc = SP_ST(32); break; case 64: rc = SP_ST(64); break; case 128: rc = SP_ST(128); break;
+                     default: rc = SP_ST(256); break; }
+#undef SP_ST
+    return rc;
+}
+
+int nmfx_sparse_set_factors(nmfx_engine* E, const double* w, const double* hmat) {
+    NMFX_HIP(hipSetDevice(E->device));
+    const int64_t m = E->m, n = E->n, k = E->k, kp = E->kp;
+    if (w) {
+        std::vector<float> t((size_t)(m * kp), 0.f);
+        for (int64_t r = 0; r < m; ++r)
+            for (int64_t c = 0; c < k; ++c) t[(size_t)(r * kp + c)] = (float)w[r * k + c];
+        NMFX_HIP(hipMemcpyAsync(E->W[0], t.data(), t.size() * 4, hipMemcpyHostToDevice, E->stream));
+        NMFX_HIP(hipMemsetAsync(E->W[1], 0, t.size() * 4, E->stream));
+        NMFX_HIP(hipStreamSynchronize(E->stream));
+    }
+    if (hmat) {
+        std::vector<float> t((size_t)(n * kp), 0.f);
+        for (int64_t c = 0; c < k; ++c)
+            for (int64_t j = 0; j < n; ++j) t[(size_t)(j * kp + c)] = (float)hmat[c * n + j];
+        NMFX_HIP(hipMemcpyAsync(E->sp->Ht, t.data(), t.size() * 4, hipMemcpyHostToDevice, E->stream));
+        NMFX_HIP(hipStreamSynchronize(E->stream));
+    }
+    E->wsel = 0;
+    E->have_f = true;
+    E->family = 0;
+    E->w_in_place = false;
+    int rc;
+    if ((rc = stats_both(E))) return rc;
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
+int nmfx_sparse_get_factors(nmfx_engine* E, double* w, double* hmat) {
+    int rc;
+    if ((rc = sync_wsel(E))) return rc;
+    const int64_t m = E->m, n = E->n, k = E->k, kp = E->kp;
+    if (w) {
+        std::vector<float> t((size_t)(m * kp));
+        NMFX_HIP(hipMemcpyAsync(t.data(), E->W[E->wsel], t.size() * 4, hipMemcpyDeviceToHost, E->stream));
+        NMFX_HIP(hipStreamSynchronize(E->stream));
+        for (int64_t r = 0; r < m; ++r)
+            for (int64_t c = 0; c < k; ++c) w[r * k + c] = (double)t[(size_t)(r * kp + c)];
+    }
+    if (hmat) {
+        std::vector<float> t((size_t)(n * kp));
+        NMFX_HIP(hipMemcpyAsync(t.data(), E->sp->Ht, t.size() * 4, hipMemcpyDeviceToHost, E->stream));
+        NMFX_HIP(hipStreamSynchronize(E->stream));
+        for (int64_t c = 0; c < k; ++c)
+            for (int64_t j = 0; j < n; ++j) hmat[c * n + j] = (double)t[(size_t)(j * kp + c)];
+    }
+    return NMFX_OK;
+}
+
+int nmfx_preload_sparse() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(sp_stats_reduce_kernel)) == hipSuccess ? 0 : -1; }

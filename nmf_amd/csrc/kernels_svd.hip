@@ -551,6 +551,7 @@ int topk_svd(nmfx_engine* E, int k, double tol, int max_sweeps, uint64_t seed, d
 extern "C" int nmfx_topk_svd(nmfx_handle_t E, int k, int block, double tol, int max_sweeps, uint64_t seed,
                              double* u, double* s, double* vt, int* sweeps, double* resid)
 {
+    NMFX_DENSE_ONLY(E);
     if (!E || !u || !s || !vt || k < 1) return NMFX_E_ARG;
     if (!E->have_v) { E->err = "upload V first"; return NMFX_E_STATE; }
     const int64_t lim = std::min(E->m, E->n);

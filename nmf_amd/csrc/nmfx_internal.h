@@ -175,6 +175,7 @@ struct nmfx_engine {
     bool pair = false;             // nmfx_mur_pair_*: factor columns [0, 64) and [64, 128) are two independent problems
     int family = 0;                // solver family that has run since nmfx_set_factors (0 none, 1 MUR eu/kl, 2 AO-ADMM, 3 ADMM, 4 ANLS): nmfx_enter_family
     bool w_in_place = false;       // solver updates W[0] in place (all but MUR, which ping-pongs)
+    struct nmfx_sparse* sp = nullptr;   // a sparse handle (nmfx_create_csr): CSR / CSC of V, H^T, Grams (kernels_sparse.hip); MUR only
     // profiling
     bool prof = false;
     std::map<std::string, ProfSlot> prof_slots;
@@ -322,6 +323,21 @@ int nmfx_allow_lds(nmfx_engine* E, const void* kernel, int bytes);
 // prox 'l1inf' / 'l1inf_transpose' of ADMM (kernels_prox.hip): X = prox(X_aux, dual) on the W or the H side
 int nmfx_launch_prox_l1inf(nmfx_engine* E, bool h_side, bool transpose, double rho, double lam, double ub, bool update_dual, bool ao = false);
 
+// Sparse handles (kernels_sparse.hip): W [m][kp] in W[0] / W[1], H^T [n][kp], kp in {4, 8, ..., 256}; V as CSR and CSC.
+int nmfx_sparse_init(nmfx_engine* E, int64_t nnz);
+void nmfx_sparse_free(nmfx_engine* E);
+int nmfx_sparse_set_factors(nmfx_engine* E, const double* w, const double* hmat);
+int nmfx_sparse_get_factors(nmfx_engine* E, double* w, double* hmat);
+int nmfx_sparse_mur_run(nmfx_engine* E, int distance, double lambda_w, double lambda_h, int64_t min_iter, double tol1, double tol2,
+                        int64_t first, int64_t count);
+int nmfx_sparse_mur_finish(nmfx_engine* E, int distance, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
+int nmfx_sparse_objective_f64(nmfx_engine* E, double* out);
+// First statement of every entry point a sparse handle does not support: NMFX_E_ARG with a message, nothing launched.
+#define NMFX_DENSE_ONLY(E) do { if ((E) && (E)->sp) { \
+    (E)->err = std::string(__func__) + ": not available on a sparse handle (nmfx_create_csr handles run MUR only)"; \
+    return NMFX_E_ARG; } } while (0)
+
+int nmfx_preload_sparse();
 int nmfx_preload_bf16();
 int nmfx_preload_products();
 int nmfx_preload_mur();

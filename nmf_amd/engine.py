@@ -47,6 +47,27 @@ class Engine:
     def __exit__(self, *exc):
         self.close()
 
+    @classmethod
+    def for_sparse(cls, x, k, device=0):
+        """A fresh engine on sparse `x` (canonical CSR from nmf_amd.sparse.normalise), uploaded through nmfx_create_csr /
+        nmfx_upload_csr.  Runs MUR only (include/nmfx.h); usable as a context manager like any Engine."""
+        from . import sparse
+        row_ptr, col_idx, values = sparse.arrays(x)
+        self = cls.__new__(cls)
+        self.lib = L.require_gpu()
+        self.m, self.n, self.k = int(x.shape[0]), int(x.shape[1]), int(k)
+        self.precision_epoch = 0
+        h = C.c_void_p()
+        L.check(self.lib.nmfx_create_csr(C.byref(h), int(device), self.m, self.n, self.k, int(values.size)))
+        self.h = h
+        try:
+            self._ck(self.lib.nmfx_upload_csr(self.h, _ptr(row_ptr), _ptr(col_idx), _ptr(values),
+                                              L.F32 if values.dtype == np.float32 else L.F64))
+        except Exception:
+            self.close()
+            raise
+        return self
+
     def _ck(self, rc):
         L.check(rc, self.h)
 

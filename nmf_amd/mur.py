@@ -9,6 +9,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib as L
+from . import sparse
 from . import utils
 from ._driver import Referee, Results, drive
 from .engine import Engine
@@ -18,7 +19,8 @@ Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_in
 
 def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5,
         lambda_w=0.0, lambda_h=0.0, nndsvd_init=(False, 'zero'), save_dir='./results/', device=0, engine=None):
-    """Lee-Seung NMF.  x: 2-D non-negative data, k: number of components.
+    """Lee-Seung NMF.  x: 2-D non-negative data (a numpy array, or any scipy.sparse matrix / array with 1 <= k <= 256:
+    never densified), k: number of components.
 
     distance_type 'eu' | 'kl' (default 'kl' as in the reference), min_iter,
     max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init=(bool, variant) and
@@ -29,6 +31,8 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31
     dist = L.EU if distance_type == 'eu' else L.KL
+    if sparse.is_sparse(x):
+        return _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine)
 
     # negative data is lifted IN PLACE on the caller's array (nmf/mur.py:99-101)
     lowest = np.min(x)
@@ -54,6 +58,27 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
             lambda done: eng.mur_finish(dist, NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
             max_iter, tol1, tol2, referee=referee)
         mur.last_referee = referee                  # diagnostic: guard in force, iterations walked with the float64 objective
+        w, h = eng.get_factors()
+    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine):
+    """MUR on scipy.sparse input (kernels_sparse.hip): the caller's matrix is copied into canonical CSR and never modified.
+    The recorded objective is evaluated in float64 from the non-zeros plus k x k terms, so the Euclidean stop rule needs
+    no float64 referee here ("Sparse V")."""
+    if engine is not None:
+        raise ValueError('sparse input: engine= is not supported (the engine is created for the sparse matrix)')
+    xs = sparse.normalise(x, k)
+    init = utils.initial_factors(xs, k, nndsvd_init)
+    with Engine.for_sparse(xs, k, device=device) as eng:
+        eng.set_factors(*init)
+        logging.info('Entering Main Loop.')
+        i, history = drive(
+            eng,
+            lambda first, count: eng.mur_run(dist, lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
+            lambda done: eng.mur_finish(dist, min_iter, tol1, tol2, done),
+            max_iter, tol1, tol2, referee=None)
+        mur.last_referee = None
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
 

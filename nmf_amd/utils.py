@@ -9,6 +9,7 @@ stdout line for a stop rule the device already decided.
 import os
 
 import numpy as np
+import scipy.sparse as sp
 
 QUIET = os.environ.get("NMF_AMD_QUIET", "0") == "1"
 
@@ -73,6 +74,20 @@ def nndsvd(x, rank=None, variant='zero'):
     return _nndsvd_from_triplets(x, u, s, vt, rank, variant)
 
 
+def nndsvd_sparse(x, rank, variant='zero', dense_below=1 << 22):
+    """NNDSVD of a scipy.sparse matrix on the host.  Below `dense_below` elements (the threshold of nndsvd_on_device)
+    the matrix is densified and the result is nndsvd's, bit for bit.  Above it the leading `rank` triplets come from
+    scipy.sparse.linalg.svds with a fixed start vector (deterministic); the construction is sign-invariant."""
+    m, n = x.shape
+    if m * n < dense_below or rank >= min(m, n):
+        return nndsvd(x.toarray(), rank, variant=variant)
+    from scipy.sparse.linalg import svds
+    v0 = np.full(min(m, n), 1.0 / np.sqrt(min(m, n)))
+    u, s, vt = svds(x.astype(np.float64), k=rank, v0=v0)
+    order = np.argsort(s)[::-1]
+    return _nndsvd_from_triplets(x, u[:, order], s[order], vt[order], rank, variant)
+
+
 def nndsvd_device(eng, x, rank, variant='zero'):
     """NNDSVD whose singular triplets come from the device (Engine.topk_svd on the uploaded V,
     f64 subspace iteration) instead of a full LAPACK SVD on the host: the only part of
@@ -116,6 +131,8 @@ def initial_factors(x, k, nndsvd_init, uniform=False, defer_device=False):
     With defer_device=True returns None when the NNDSVD is to be computed from the device
     SVD once V is uploaded (`device_initial_factors`)."""
     if nndsvd_init[0]:
+        if sp.issparse(x):
+            return nndsvd_sparse(x, k, variant=nndsvd_init[1])
         if defer_device and nndsvd_on_device(x, k):
             return None
         return nndsvd(x, k, variant=nndsvd_init[1])
