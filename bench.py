@@ -12,6 +12,17 @@ HBM before the timed region.  For N > 1 the SAME matrix is row-sharded over the
 ranks (strong scaling) with one RCCL all-reduce of [W^T V | W^T W | objective]
 per iteration.  Rank 0 prints one JSON line.
 
+A plain run does only what that line's headline figure needs: it sets up, preheats and warms up, times the steps, writes
+--dump-outputs and prints the line (`roofline`, `cpu_baseline` and `parity` null, no time-to-tol or per-config slots).
+Everything else is measured with --full:
+
+    python bench.py --gpus 1 --steps 50 --warmup 3 --full
+
+that is the per-kernel pass and `roofline` (with its rocprofv3 PMC passes), time-to-tol with the oracle's stop check,
+full-size parity and the CPU baseline, the other BASELINE configs and the scaling model (N = 1), and config 5 row-sharded
+over the ranks (N > 1).  --no-cpu, --no-traffic, --no-others, --tol-max-iter 0 and --profile-steps 0 leave legs out of a
+--full run.
+
 `roofline`: the dominant kernel (the W phase: A = V H^T with the fused residual
 objective), mean launch time from HIP events on the engine's stream in a
 separate pass of back-to-back launches.  In the default arithmetic (split bf16: each f32 operand
@@ -55,6 +66,9 @@ def parse():
     ap.add_argument("--m", type=int, default=dm)
     ap.add_argument("--n", type=int, default=dn)
     ap.add_argument("--k", type=int, default=dk)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: per-kernel pass and roofline, time-to-tol, parity and "
+                         "CPU baseline, other configs and scaling model (N = 1), config 5 sharded (N > 1)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-iters", type=int, default=10)     # ~12 s of host work at 0.9 iterations/s
     ap.add_argument("--profile-steps", type=int, default=20)
@@ -1061,7 +1075,7 @@ def main():
     # profiled pass: per-kernel device time from HIP events on the engine's stream
     roof = None
     prof = {}
-    if args.profile_steps > 0 and not args.pmc_child:
+    if args.full and args.profile_steps > 0 and not args.pmc_child:
         eng.profile_enable(True)
         eng.profile_reset()
         (run.eager if sharded else run)(done, args.profile_steps)   # per-kernel events need eager launches
@@ -1110,7 +1124,7 @@ def main():
     # min_iter=100, tol1=tol2=1e-5), or the cap.  Factors stay on the device; the stop rule is
     # evaluated on the device every iteration; the host looks at the flag once per 256 iterations.
     ttt = None
-    if rank == 0 and world == 1 and args.tol_max_iter > 0:
+    if args.full and rank == 0 and world == 1 and args.tol_max_iter > 0:
         ttt = []
         for tol in (1e-5, 1e-2, 1e-3):    # the reference's default (capped), and two looser absolute tolerances
             rule, stop_i, done_t, secs, ref = converge_on_device(eng, w0, h0, tol, args.tol_max_iter)
@@ -1135,7 +1149,7 @@ def main():
     # parity at the full size, GPU leg: the same cpu_iters + 1 iterations the cpu_baseline leg runs, from
     # the same start, in the arithmetic that was timed; compared with the oracle's factors further down
     par_gpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         p_it = args.cpu_iters + 1
         eng.set_factors(w0, h0)
         eng.mur_run(0, 0.0, 0.0, NEVER, 1e-5, 1e-5, 0, p_it)
@@ -1180,7 +1194,7 @@ def main():
         }
 
     others = None
-    if sharded and not args.no_others and ((m, n, k) == (M, N, K) or os.environ.get("NMFX_BENCH_CFG5_SHAPE")):
+    if args.full and sharded and not args.no_others and ((m, n, k) == (M, N, K) or os.environ.get("NMFX_BENCH_CFG5_SHAPE")):
         # config 5 proper (the 8-GPU config of BASELINE.json), sharded over this run's ranks: every rank takes part
         eng.close()
         progress = {}
@@ -1199,7 +1213,7 @@ def main():
             others = [{"config": "cfg5", "error": f"{type(e).__name__}: {e}"}]          # collectives -- the deadline above ends that)
         guard.cancel()
     smodel = None
-    if rank == 0 and world == 1 and not sharded and not args.no_others and (m, n, k) == (M, N, K):
+    if args.full and rank == 0 and world == 1 and not sharded and not args.no_others and (m, n, k) == (M, N, K):
         eng.close()               # free the HBM: config 5 on one GPU holds three 8 GiB copies of V
         others = other_configs(torch, torch.device(f"cuda:{local_rank}"))
         try:
@@ -1216,7 +1230,7 @@ def main():
                                 "FETCH_SIZE x2 (gfx950 correction)")
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         v_full = v_local if (r0, r1) == (0, m) else planted_matrix(m, n, k, seed=0, dtype=np.float32)
         val, w_r, h_r, obj_r = cpu_baseline(v_full, k, args.cpu_iters)
         parity = parity_block(v_full, par_gpu[0], par_gpu[1], par_gpu[2], w_r, h_r, obj_r)

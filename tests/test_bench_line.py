@@ -4,6 +4,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -108,3 +110,40 @@ def test_bench_arguments_refuse_what_cannot_be_honoured(monkeypatch, capsys):
         monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
         with pytest.raises(SystemExit):
             bench.parse()
+
+
+def test_full_is_off_by_default(monkeypatch):
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.delenv("NMFX_BENCH_FORCE_SHARDED", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert bench.parse().full is True
+
+
+def _run_bench(cwd, *extra):
+    import subprocess
+    cwd.mkdir()
+    env = dict(os.environ, NMFX_BENCH_SHAPE="1024x512x64", NMF_AMD_QUIET="1", NMFX_BENCH_DETAIL=str(cwd / "detail.json"))
+    for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NMFX_BENCH_FORCE_SHARDED"):
+        env.pop(key, None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", *extra],
+                       env=env, cwd=str(cwd), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0]), json.loads((cwd / "detail.json").read_text())
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_full_adds_the_legs(tmp_path):
+    """A plain run times the steps and prints the line with the other legs empty; --full runs the per-kernel pass and roofline
+    (the CPU, traffic and time-to-tol legs are left out here: the shrunken shape has no other configs either)."""
+    line, detail = _run_bench(tmp_path / "plain")
+    assert line["value"] > 0 and line["steps"] == 4 and line["warmup"] == 2 and line["higher_is_better"] is True
+    assert abs(line["ms_per_step"] * line["value"] - 1e3) < 1e-6
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["parity"] is None and "time_to_tol" not in line
+    assert not detail["kernels"] and detail["other_configs"] is None and detail["scaling_model"] is None
+    line, detail = _run_bench(tmp_path / "full", "--full", "--no-cpu", "--no-traffic", "--tol-max-iter", "0")
+    assert line["value"] > 0 and line["roofline"]["frac"] > 0 and "wphase" in detail["kernels"]

@@ -587,7 +587,7 @@ def test_bench_two_ranks_on_one_gpu_runs_both_sharded_legs(launch, tmp_path):
                NMF_AMD_QUIET="1", HSA_ENABLE_IPC_MODE_LEGACY="0", NMFX_BENCH_DETAIL=str(tmp_path / "detail.json"))
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NMFX_DIST_INIT_METHOD"):
         env.pop(key, None)
-    tail = ["--gpus", "2", "--steps", "4", "--warmup", "2", "--preheat", "0", "--profile-steps", "2", "--no-cpu", "--no-traffic",
+    tail = ["--gpus", "2", "--steps", "4", "--warmup", "2", "--preheat", "0", "--full", "--profile-steps", "2", "--no-cpu", "--no-traffic",
             "--tol-max-iter", "0"]
     if launch == "deadline":                             # (r5) the config-5 leg "never comes back": the line is printed without it, exit code 0
         env["NMFX_BENCH_CFG5_DEADLINE"] = "0.01"
