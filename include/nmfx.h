@@ -106,6 +106,14 @@ int nmfx_upload_v_device(nmfx_handle_t h, const void* dev, int dtype, int64_t ld
  * non-zeros plus k x k terms ("Sparse V").  Every other entry point returns NMFX_E_ARG and launches nothing. */
 int nmfx_create_csr(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k, int64_t nnz);
 int nmfx_upload_csr(nmfx_handle_t h, const int64_t* row_ptr, const int32_t* col_idx, const void* values, int dtype);
+/* Masked V (version 320).  on = 1: the stored entries are the OBSERVED set M -- stored zeros included -- and every other
+ * entry is unknown, not zero.  Legal only between nmfx_create_csr and nmfx_upload_csr (NMFX_E_ARG on a dense handle,
+ * NMFX_E_STATE after the upload; neither launches anything).  MUR then runs the weighted (0/1) Lee-Seung update
+ *   Euclidean  W <- W (M.X) H^T / ((M.(W H)) H^T + lambda_w W + 1e-9),  H likewise with the new W
+ *   KL         A = W ((M.X / (W H + 1e-9)) H^T),  B = M H^T,  W <- 2 A / (B + sqrt(B^2 + 4 lambda_w A)),  0 where B = 0
+ * and records Sum_M 1/2 (x - wh)^2 (Euclidean) / Sum_M [x log(x / wh) - x + wh] (KL) in f64 ("Masked V").
+ * The other entry points keep the sparse handle's contract; nmfx_objective_f64 gives the masked Euclidean objective. */
+int nmfx_set_masked(nmfx_handle_t h, int on);
 
 /* W (m x k) and H (k x n), float64 row-major; either may be NULL to skip.
  * set_factors also zeroes all dual/auxiliary state and the iteration state.   */

@@ -34,6 +34,7 @@ SIGNATURES = {
     "nmfx_get_note": (C.c_char_p, [_vp]),
     "nmfx_create_csr": (_i32, [C.POINTER(_vp), _i32, _i64, _i64, _i32, _i64]),
     "nmfx_upload_csr": (_i32, [_vp, _vp, _vp, _vp, _i32]),
+    "nmfx_set_masked": (_i32, [_vp, _i32]),
     "nmfx_upload_v": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
     "nmfx_upload_v_device": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
     "nmfx_set_factors": (_i32, [_vp, _vp, _vp]),

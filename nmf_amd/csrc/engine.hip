@@ -125,7 +125,7 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
 
 extern "C" {
 
-int nmfx_version(void) { return 310; }      // 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 320; }      // 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;

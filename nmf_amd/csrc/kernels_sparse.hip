@@ -20,6 +20,13 @@
 // Objective (nmf/utils.py:18-33) over all m n entries, from the non-zeros plus k x k / k-sized terms:
 //   Euclidean  1/2 [ ||X||^2 - 2 Sum_nz x wh + <W^T W, H H^T> ]      (||X||^2 in f64 at upload, Grams in f64)
 //   KL         Sum_nz [x log(x / wh) - x] + Sum_c colsum(W)_c rowsum(H)_c     (inf / nan log terms -> 0, as the reference)
+//
+// Masked handles (nmfx_set_masked): the stored entries are the observed set M and nothing else is part of the fit.  The
+// phase kernels (MASKED = true) sum a second float4 per lane in the same pass, the denominator of the masked update:
+//   Euclidean  a = Sum_M x h,  d = Sum_M (float) wh h      out = w a / (d + lam w + 1e-9)
+//   KL         a = Sum_M x / (wh + 1e-9) h,  d = Sum_M h   out = 2 w a / (d + sqrt(d^2 + 4 lam w a)),  d = 0 -> 0
+// Pieces store [a | d] (slab [pieces][2 kp]).  The objective is summed per observed entry in f64 (Euclidean 1/2 (x - wh)^2,
+// KL x log(x / wh) - x + wh); there are no Grams, column sums nor ||X||^2 terms, and no sp_stats_kernel passes.
 #include "kernels_small.h"
 #include <algorithm>
 #include <cmath>
@@ -37,7 +44,7 @@ struct SpSide {               // one orientation of V: 0 = CSR (W phase), 1 = CS
     float* val = nullptr;     // [nnz]
     SpUnit* units = nullptr; int64_t nunits = 0;
     SpLong* longs = nullptr; int64_t nlong = 0;
-    float* slab = nullptr;    // [pieces][kp]
+    float* slab = nullptr;    // [pieces][kp] ([pieces][2 kp] on a masked handle)
     int nblk = 1;             // blocks of the phase kernel (a fixed stride over the units)
 };
 
@@ -53,6 +60,7 @@ struct nmfx_sparse {
     double* stat_part = nullptr;           // [slabs][kp * kp + kp]
     double* obj_part = nullptr;            // [blocks]
     int obj_cap = 0;
+    bool masked = false;      // the stored entries are the observed set (nmfx_set_masked)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -116,12 +124,42 @@ __device__ __forceinline__ void sp_epilogue(float4 w4, float4 a4, const float* _
     if (grp == 0) *reinterpret_cast<float4*>(out_row + lig * 4) = o;
 }
 
+// The update epilogue of one owned row on a masked handle, with the denominator d summed by the pass (no Gram, no sums):
+//   Euclidean  out = w a / (d + lam w + 1e-9)
+//   KL         out = 2 w a / (d + sqrt(d^2 + 4 lam w a)), and 0 where d = 0 (no observed entry: 0 / 0 is defined as 0)
+template <bool KL>
+__device__ __forceinline__ void sp_epilogue_masked(float4 w4, float4 a4, float4 d4, float lam, int k, float* __restrict__ out_row,
+                                                   int lig, int grp)
+{
+    float4 o;
+    if constexpr (KL) {
+        float c;
+        c = w4.x * a4.x; o.x = d4.x > 0.f ? 2.f * c / (d4.x + sqrtf(d4.x * d4.x + 4.f * lam * c)) : 0.f;
+        c = w4.y * a4.y; o.y = d4.y > 0.f ? 2.f * c / (d4.y + sqrtf(d4.y * d4.y + 4.f * lam * c)) : 0.f;
+        c = w4.z * a4.z; o.z = d4.z > 0.f ? 2.f * c / (d4.z + sqrtf(d4.z * d4.z + 4.f * lam * c)) : 0.f;
+        c = w4.w * a4.w; o.w = d4.w > 0.f ? 2.f * c / (d4.w + sqrtf(d4.w * d4.w + 4.f * lam * c)) : 0.f;
+    } else {
+        o.x = w4.x * a4.x / (d4.x + lam * w4.x + 1e-9f);
+        o.y = w4.y * a4.y / (d4.y + lam * w4.y + 1e-9f);
+        o.z = w4.z * a4.z / (d4.z + lam * w4.z + 1e-9f);
+        o.w = w4.w * a4.w / (d4.w + lam * w4.w + 1e-9f);
+    }
+    const int c0 = lig * 4;
+    if (c0 + 0 >= k) o.x = 0.f;
+    if (c0 + 1 >= k) o.y = 0.f;
+    if (c0 + 2 >= k) o.z = 0.f;
+    if (c0 + 3 >= k) o.w = 0.f;
+    if (grp == 0) *reinterpret_cast<float4*>(out_row + lig * 4) = o;
+}
+
 // One phase over the units of one orientation.
 //   Own [rows][KP]: the factor being updated (read), Out: where its update goes (may be Own: rows are owned by one wave),
 //   Other [*][KP]: the factor gathered per non-zero, G (KP x KP f32) / S (KP f32): the other factor's Gram / sums.
-//   OBJ: objective partial of the pair (Own, Other) per block into obj_part (Euclidean: Sum x wh; KL: Sum x log(x/wh) - x).
+//   OBJ: objective partial of the pair (Own, Other) per block into obj_part (Euclidean: Sum x wh; KL: Sum x log(x/wh) - x;
+//   MASKED: Euclidean Sum (x - wh)^2, KL Sum x log(x/wh) - x + wh).
 //   UPDATE: accumulate and run the epilogue (whole rows) or store the piece's sum (pieces).
-template <int KP, bool KL, bool OBJ, bool UPDATE>
+//   MASKED: also accumulate the denominator (Sum wh h / Sum h) and run the masked epilogue; pieces store [sum | denominator].
+template <int KP, bool KL, bool OBJ, bool UPDATE, bool MASKED>
 __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
     const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
     const float* __restrict__ Other, const float* Own, float* Out, const float* __restrict__ Gf, const float* __restrict__ S,
@@ -129,7 +167,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
 {
     if (flag && *flag) return;
     constexpr int G = KP / 4, NG = 64 / G;
-    constexpr bool GLDS = UPDATE && !KL && KP <= 128;
+    constexpr bool GLDS = UPDATE && !KL && !MASKED && KP <= 128;
     __shared__ __attribute__((aligned(16))) float gs[GLDS ? KP * KP : 4];
     __shared__ double ob[SP_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
@@ -144,6 +182,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
         const SpUnit U = units[u];
         const float4 w4 = *reinterpret_cast<const float4*>(Own + (int64_t)U.row * KP + lig * 4);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 den = make_float4(0.f, 0.f, 0.f, 0.f);     // (MASKED only)
         const long long end = U.beg + U.len;
         for (long long e0 = U.beg + grp; e0 < end; e0 += 4 * NG) {
             int c[4]; float x[4]; bool ok[4]; float4 h[4];
@@ -167,7 +206,11 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
                         if constexpr (KL) {
                             double tl = xv * log(xv / wh);
                             if (tl == INFINITY || tl != tl) tl = 0.0;      // np.where(t == inf, 0, t); np.where(isnan(t), 0, t)
-                            objacc += tl - xv;
+                            if constexpr (MASKED) objacc += tl - xv + wh;
+                            else objacc += tl - xv;
+                        } else if constexpr (MASKED) {
+                            const double d = xv - wh;
+                            objacc += d * d;
                         } else {
                             objacc += xv * wh;
                         }
@@ -177,10 +220,27 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
                     const float q = KL ? (float)((double)x[t] / (wh + 1e-9)) : x[t];
                     acc.x = fmaf(q, h[t].x, acc.x); acc.y = fmaf(q, h[t].y, acc.y);
                     acc.z = fmaf(q, h[t].z, acc.z); acc.w = fmaf(q, h[t].w, acc.w);
+                    if constexpr (MASKED) {            // (a slot past the unit's end gathered row 0: weight 0)
+                        const float r = !ok[t] ? 0.f : KL ? 1.f : (float)wh;
+                        den.x = fmaf(r, h[t].x, den.x); den.y = fmaf(r, h[t].y, den.y);
+                        den.z = fmaf(r, h[t].z, den.z); den.w = fmaf(r, h[t].w, den.w);
+                    }
                 }
             }
         }
-        if constexpr (UPDATE) {
+        if constexpr (UPDATE && MASKED) {
+            acc = sp_sum_groups<G>(acc);
+            den = sp_sum_groups<G>(den);
+            if (U.slot >= 0) {
+                if (grp == 0) {
+                    float* p = slab + (int64_t)U.slot * (2 * KP) + lig * 4;
+                    *reinterpret_cast<float4*>(p) = acc;
+                    *reinterpret_cast<float4*>(p + KP) = den;
+                }
+            } else {
+                sp_epilogue_masked<KL>(w4, acc, den, lam, k, Out + (int64_t)U.row * KP, lig, grp);
+            }
+        } else if constexpr (UPDATE) {
             acc = sp_sum_groups<G>(acc);
             if (U.slot >= 0) {
                 if (grp == 0) *reinterpret_cast<float4*>(slab + (int64_t)U.slot * KP + lig * 4) = acc;
@@ -203,15 +263,32 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
 }
 
 // Rows split into pieces: the pieces' sums added in piece order (group g takes pieces g, g + NG, ..., then the groups'
-// butterfly), then the epilogue.
-template <int KP, bool KL>
+// butterfly), then the epilogue.  MASKED: the same for both halves of a piece's [sum | denominator], then the masked epilogue.
+template <int KP, bool KL, bool MASKED>
 __global__ __launch_bounds__(64 * SP_WAVES) void sp_fixup_kernel(
     const SpLong* __restrict__ longs, int64_t nlong, const float* __restrict__ slab, const float* Own, float* Out,
     const float* __restrict__ Gf, const float* __restrict__ S, float lam, int k, const int* flag)
 {
     if (flag && *flag) return;
     constexpr int G = KP / 4, NG = 64 / G;
-    constexpr bool GLDS = !KL && KP <= 128;
+    if constexpr (MASKED) {
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
+        for (int64_t l = (int64_t)blockIdx.x * SP_WAVES + wave; l < nlong; l += (int64_t)gridDim.x * SP_WAVES) {
+            const SpLong L = longs[l];
+            const float4 w4 = *reinterpret_cast<const float4*>(Own + (int64_t)L.row * KP + lig * 4);
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), den = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int p = grp; p < L.npieces; p += NG) {
+                const float* s = slab + (int64_t)(L.slot0 + p) * (2 * KP) + lig * 4;
+                acc = sp_add4(acc, *reinterpret_cast<const float4*>(s));
+                den = sp_add4(den, *reinterpret_cast<const float4*>(s + KP));
+            }
+            acc = sp_sum_groups<G>(acc);
+            den = sp_sum_groups<G>(den);
+            sp_epilogue_masked<KL>(w4, acc, den, lam, k, Out + (int64_t)L.row * KP, lig, grp);
+        }
+        return;
+    }
+    constexpr bool GLDS = !KL && !MASKED && KP <= 128;
     __shared__ __attribute__((aligned(16))) float gs[GLDS ? KP * KP : 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
     if constexpr (GLDS) {
@@ -289,8 +366,9 @@ __global__ void sp_stats_reduce_kernel(const double* __restrict__ part, int slab
 }
 
 // The objective of the pair from the block partials (block order, then a fixed tree) and the small terms; recorded as
-// obj[j] with the reference's stop rule (record) or only stored to *out.
-template <bool KL>
+// obj[j] with the reference's stop rule (record) or only stored to *out.  MASKED: the block partials alone (KL: their sum,
+// Euclidean: half of it).
+template <bool KL, bool MASKED>
 __global__ __launch_bounds__(256) void sp_objective_kernel(
     const double* __restrict__ part, int nblk, const double* __restrict__ gw, const double* __restrict__ gh,
     const double* __restrict__ cw, const double* __restrict__ ch, int kp, double x2, double* __restrict__ out, int record,
@@ -301,8 +379,10 @@ __global__ __launch_bounds__(256) void sp_objective_kernel(
     const int tid = threadIdx.x;
     double s = 0.0, t = 0.0;
     for (int i = tid; i < nblk; i += 256) s += part[i];
-    if (KL) { for (int c = tid; c < kp; c += 256) t += cw[c] * ch[c]; }
-    else { for (int e = tid; e < kp * kp; e += 256) t += gw[e] * gh[e]; }
+    if constexpr (!MASKED) {
+        if (KL) { for (int c = tid; c < kp; c += 256) t += cw[c] * ch[c]; }
+        else { for (int e = tid; e < kp * kp; e += 256) t += gw[e] * gh[e]; }
+    }
     r[0][tid] = s; r[1][tid] = t;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
@@ -310,7 +390,8 @@ __global__ __launch_bounds__(256) void sp_objective_kernel(
         __syncthreads();
     }
     if (tid == 0) {
-        const double obj = KL ? r[0][0] + r[1][0] : 0.5 * (x2 - 2.0 * r[0][0] + r[1][0]);
+        const double obj = MASKED ? (KL ? r[0][0] : 0.5 * r[0][0])
+                                  : KL ? r[0][0] + r[1][0] : 0.5 * (x2 - 2.0 * r[0][0] + r[1][0]);
         *out = obj;
         if (record) nmfx_record_objective(st, obj_hist, obj, j, min_iter, tol1, tol2, true);
     }
@@ -393,7 +474,7 @@ static int build_side(nmfx_engine* E, SpSide& sd, const int64_t* ptr) {
     int rc;
     if ((rc = sp_alloc(E, &sd.units, sd.nunits))) return rc;
     if ((rc = sp_alloc(E, &sd.longs, sd.nlong))) return rc;
-    if ((rc = sp_alloc(E, &sd.slab, (int64_t)slot * E->kp))) return rc;
+    if ((rc = sp_alloc(E, &sd.slab, (int64_t)slot * E->kp * (E->sp->masked ? 2 : 1)))) return rc;
     if (sd.nunits) NMFX_HIP(hipMemcpyAsync(sd.units, units.data(), units.size() * sizeof(SpUnit), hipMemcpyHostToDevice, E->stream));
     if (sd.nlong) NMFX_HIP(hipMemcpyAsync(sd.longs, longs.data(), longs.size() * sizeof(SpLong), hipMemcpyHostToDevice, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
@@ -452,6 +533,15 @@ extern "C" int nmfx_upload_csr(nmfx_handle_t E, const int64_t* row_ptr, const in
     return NMFX_OK;
 }
 
+// Between nmfx_create_csr and nmfx_upload_csr only: the stored entries become the observed set (the header's sparse block).
+extern "C" int nmfx_set_masked(nmfx_handle_t E, int on) {
+    if (!E) return NMFX_E_ARG;
+    if (!E->sp) { E->err = "set_masked: not a sparse handle (nmfx_create_csr)"; return NMFX_E_ARG; }
+    if (E->have_v) { E->err = "set_masked: call it before nmfx_upload_csr"; return NMFX_E_STATE; }
+    E->sp->masked = on != 0;
+    return NMFX_OK;
+}
+
 // ---- launchers --------------------------------------------------------------------------------------------------------
 template <int KP>
 static int launch_stats(nmfx_engine* E, const float* F, int64_t R, int f, const int* flag) {
@@ -476,14 +566,21 @@ static int launch_phase(nmfx_engine* E, int side, const float* Own, float* Out, 
     const dim3 grid(sd.nblk), blk(64 * SP_WAVES);
 #define SP_ARGS sd.units, sd.nunits, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, Out, (const float*)S->gf[o], \
                 (const float*)S->csf[o], sd.slab, S->obj_part, lam, E->k, flag
-    if (obj && update) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, true>), grid, blk, 0, E->stream, SP_ARGS);
-    else if (obj) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, false>), grid, blk, 0, E->stream, SP_ARGS);
-    else hipLaunchKernelGGL((sp_phase_kernel<KP, KL, false, true>), grid, blk, 0, E->stream, SP_ARGS);
+    if (S->masked) {
+        if (obj && update) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, true, true>), grid, blk, 0, E->stream, SP_ARGS);
+        else if (obj) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, false, true>), grid, blk, 0, E->stream, SP_ARGS);
+        else hipLaunchKernelGGL((sp_phase_kernel<KP, KL, false, true, true>), grid, blk, 0, E->stream, SP_ARGS);
+    } else {
+        if (obj && update) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, true, false>), grid, blk, 0, E->stream, SP_ARGS);
+        else if (obj) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, false, false>), grid, blk, 0, E->stream, SP_ARGS);
+        else hipLaunchKernelGGL((sp_phase_kernel<KP, KL, false, true, false>), grid, blk, 0, E->stream, SP_ARGS);
+    }
 #undef SP_ARGS
     NMFX_HIP(hipGetLastError());
     if (update && sd.nlong) {
         const int nb = (int)std::min<int64_t>(4 * E->ncu, (sd.nlong + SP_WAVES - 1) / SP_WAVES);
-        hipLaunchKernelGGL((sp_fixup_kernel<KP, KL>), dim3(nb), blk, 0, E->stream, (const SpLong*)sd.longs, sd.nlong,
+        auto fix = S->masked ? sp_fixup_kernel<KP, KL, true> : sp_fixup_kernel<KP, KL, false>;
+        hipLaunchKernelGGL(fix, dim3(nb), blk, 0, E->stream, (const SpLong*)sd.longs, sd.nlong,
                            (const float*)sd.slab, Own, Out, (const float*)S->gf[o], (const float*)S->csf[o], lam, E->k, flag);
         NMFX_HIP(hipGetLastError());
     }
@@ -492,7 +589,8 @@ static int launch_phase(nmfx_engine* E, int side, const float* Own, float* Out, 
 
 static int launch_objective(nmfx_engine* E, bool kl, double* out, bool record, int64_t j, int64_t min_iter, double tol1, double tol2) {
     nmfx_sparse* S = E->sp;
-    auto kern = kl ? sp_objective_kernel<true> : sp_objective_kernel<false>;
+    auto kern = S->masked ? (kl ? sp_objective_kernel<true, true> : sp_objective_kernel<false, true>)
+                          : (kl ? sp_objective_kernel<true, false> : sp_objective_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, E->stream, (const double*)S->obj_part, S->side[0].nblk,
                        (const double*)S->g64[0], (const double*)S->g64[1], (const double*)S->cs64[0], (const double*)S->cs64[1],
                        E->kp, S->x2, out, record ? 1 : 0, (long long)j, (long long)min_iter, tol1, tol2, E->state, E->obj_hist);
@@ -512,13 +610,15 @@ static int sp_iteration(nmfx_engine* E, bool kl, double lw, double lh, int64_t m
               : launch_phase<KP, false>(E, 0, Wold, Wnew, S->Ht, true, true, (float)lw, flag);
       if (rc) return rc; }
     if ((rc = launch_objective(E, kl, E->xf64, true, j, min_iter, tol1, tol2))) return rc;
-    { ProfScope ps(E, "sp_stats");
+    if (!S->masked) {                 // (a masked update takes its denominators from the phase itself)
+      ProfScope ps(E, "sp_stats");
       if ((rc = launch_stats<KP>(E, Wnew, E->m, 0, flag))) return rc; }
     { ProfScope ps(E, "sp_hphase");
       rc = kl ? launch_phase<KP, true>(E, 1, S->Ht, S->Ht, Wnew, false, true, (float)lh, flag)
               : launch_phase<KP, false>(E, 1, S->Ht, S->Ht, Wnew, false, true, (float)lh, flag);
       if (rc) return rc; }
-    { ProfScope ps(E, "sp_stats");
+    if (!S->masked) {
+      ProfScope ps(E, "sp_stats");
       if ((rc = launch_stats<KP>(E, S->Ht, E->n, 1, flag))) return rc; }
     E->wsel = (int)((j + 1) & 1);
     return NMFX_OK;
@@ -631,7 +731,7 @@ int nmfx_sparse_set_factors(nmfx_engine* E, const double* w, const double* hmat)
     E->family = 0;
     E->w_in_place = false;
     int rc;
-    if ((rc = stats_both(E))) return rc;
+    if (!E->sp->masked && (rc = stats_both(E))) return rc;
     NMFX_HIP(hipStreamSynchronize(E->stream));
     return NMFX_OK;
 }

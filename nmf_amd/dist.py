@@ -876,7 +876,7 @@ def _defaults(method):
     mod = import_module('.' + method, __package__)
     sig = inspect.signature(getattr(mod, method))
     kw = {name: p.default for name, p in sig.parameters.items()
-          if p.kind is p.KEYWORD_ONLY and name not in ('device', 'engine', 'save_dir')}
+          if p.kind is p.KEYWORD_ONLY and name not in ('device', 'engine', 'save_dir', 'mask')}     # (no masked sharded runs)
     return mod, kw
 
 

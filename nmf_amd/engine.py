@@ -48,9 +48,10 @@ class Engine:
         self.close()
 
     @classmethod
-    def for_sparse(cls, x, k, device=0):
+    def for_sparse(cls, x, k, device=0, masked=False):
         """A fresh engine on sparse `x` (canonical CSR from nmf_amd.sparse.normalise), uploaded through nmfx_create_csr /
-        nmfx_upload_csr.  Runs MUR only (include/nmfx.h); usable as a context manager like any Engine."""
+        nmfx_upload_csr.  Runs MUR only (include/nmfx.h); usable as a context manager like any Engine.  masked=True: `x`
+        holds the observed entries (nmf_amd.masked.observed) and nmfx_set_masked is called before the upload."""
         from . import sparse
         row_ptr, col_idx, values = sparse.arrays(x)
         self = cls.__new__(cls)
@@ -61,6 +62,8 @@ class Engine:
         L.check(self.lib.nmfx_create_csr(C.byref(h), int(device), self.m, self.n, self.k, int(values.size)))
         self.h = h
         try:
+            if masked:
+                self._ck(self.lib.nmfx_set_masked(self.h, 1))
             self._ck(self.lib.nmfx_upload_csr(self.h, _ptr(row_ptr), _ptr(col_idx), _ptr(values),
                                               L.F32 if values.dtype == np.float32 else L.F64))
         except Exception:

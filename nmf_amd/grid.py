@@ -39,6 +39,8 @@ def factorize_grid(data, method='mur', *, features, lambda_w=(0.0,), lambda_h=(0
     result is written like NMF.save_factorization would."""
     if method not in _METHODS:
         raise Exception('Method not known. Choose one from: mur anls admm ao_admm')
+    if 'mask' in common:
+        raise TypeError("factorize_grid: mask= is not supported (run mur(x, k, mask=...) per grid point)")
     solver = getattr(import_module('.' + method, __package__), method)
     if method == 'mur':                         # the lift of negative data happens once, in place (nmf/mur.py:99-101)
         lowest = np.min(data)

@@ -9,6 +9,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib as L
+from . import masked
 from . import sparse
 from . import utils
 from ._driver import Referee, Results, drive
@@ -18,19 +19,23 @@ Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_in
 
 
 def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5,
-        lambda_w=0.0, lambda_h=0.0, nndsvd_init=(False, 'zero'), save_dir='./results/', device=0, engine=None):
+        lambda_w=0.0, lambda_h=0.0, nndsvd_init=(False, 'zero'), save_dir='./results/', device=0, engine=None, mask=None):
     """Lee-Seung NMF.  x: 2-D non-negative data (a numpy array, or any scipy.sparse matrix / array with 1 <= k <= 256:
     never densified), k: number of components.
 
     distance_type 'eu' | 'kl' (default 'kl' as in the reference), min_iter,
     max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init=(bool, variant) and
-    save_dir have the reference's meaning.  Returns
-    Results(w, h, i, obj_history, experiment) with float64 w, h."""
+    save_dir have the reference's meaning.  mask: None, or a boolean / 0-1 array or scipy.sparse matrix of x's shape
+    whose non-zero entries are the observed set -- only x there is fitted and read (masked MUR, nmf_amd.masked;
+    1 <= k <= 256).  Returns Results(w, h, i, obj_history, experiment) with float64 w, h."""
     experiment = Experiment('mur', k, distance_type, nndsvd_init, max_iter, tol1, tol2,
                             lambda_w, lambda_h)
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31
     dist = L.EU if distance_type == 'eu' else L.KL
+    if mask is not None:
+        return _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init,
+                           device, engine)
     if sparse.is_sparse(x):
         return _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine)
 
@@ -71,6 +76,28 @@ def _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w
     xs = sparse.normalise(x, k)
     init = utils.initial_factors(xs, k, nndsvd_init)
     with Engine.for_sparse(xs, k, device=device) as eng:
+        eng.set_factors(*init)
+        logging.info('Entering Main Loop.')
+        i, history = drive(
+            eng,
+            lambda first, count: eng.mur_run(dist, lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
+            lambda done: eng.mur_finish(dist, min_iter, tol1, tol2, done),
+            max_iter, tol1, tol2, referee=None)
+        mur.last_referee = None
+        w, h = eng.get_factors()
+    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine):
+    """Masked MUR (kernels_sparse.hip on a masked handle): the observed entries of x, stored zeros included, are the data;
+    the rest is unknown.  Everything is validated before any device work; nothing of the caller's is modified.  Same start
+    (the global RNG's draws as in mur; NNDSVD of x with the unobserved entries set to 0), Results, printed lines and batching
+    as the sparse path; the recorded objective is the masked one, summed in float64 (nmf_amd.masked.objective)."""
+    if engine is not None:
+        raise ValueError('mask=: engine= is not supported (the engine is created for the observed entries)')
+    xs = masked.observed(x, mask, k)
+    init = utils.initial_factors(xs, k, nndsvd_init)
+    with Engine.for_sparse(xs, k, device=device, masked=True) as eng:
         eng.set_factors(*init)
         logging.info('Entering Main Loop.')
         i, history = drive(

@@ -2,12 +2,14 @@
 
     python tools/sparse_perf.py --m 16384 --n 8192 --density 0.01 --k 64 --dist eu
     python tools/sparse_perf.py --m 16384 --n 8192 --density 0.01 --k 64 --dist kl --powerlaw 1.1
+    python tools/sparse_perf.py --m 16384 --n 8192 --density 0.10 --k 64 --dist eu --masked
 
 Inputs are seeded random CSR (uniform column positions; --powerlaw a: row lengths proportional to rank^-a, shuffled).
 One JSON line per case: ms per iteration over a warmed batch, nnz, the bytes the algorithm must move per iteration
 (both index streams, the gathered factor rows, the factors and their Grams' reads), the GB/s that makes, and -- where
 V fits densely (--dense-max-gib) -- the dense path's ms per iteration on the same matrix, measured alternately with the
-sparse one in the same process."""
+sparse one in the same process.  --masked: a masked handle on the same stored pattern (the stored entries as the observed
+set, nmfx_set_masked) timed alternately with the unmasked one ("masked_ms_per_iter"; dense leg skipped)."""
 import argparse
 import json
 import os
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3, help="alternating sparse / dense timing rounds")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dense-max-gib", type=float, default=8.0)
+    ap.add_argument("--masked", action="store_true", help="time a masked handle on the same pattern instead of the dense path")
     a = ap.parse_args()
 
     import torch
@@ -73,7 +76,12 @@ def main():
     se.set_factors(w0, h0)
     engines["sparse"] = se
     dense_gib = a.m * a.n * 4 / 2 ** 30
-    if dense_gib <= a.dense_max_gib:
+    if a.masked:
+        me = Engine.for_sparse(x, a.k, masked=True)
+        me.set_stream(stream)
+        me.set_factors(w0, h0)
+        engines["masked"] = me
+    elif dense_gib <= a.dense_max_gib:
         de = Engine(a.m, a.n, a.k)
         de.set_stream(stream)
         de.upload_v(x.toarray())
@@ -104,7 +112,8 @@ def main():
            "sparse_ms_per_iter": round(sparse_ms, 4), "bytes_per_iter": int(total), "gathered_bytes": int(gathers),
            "gb_per_s": round(total / sparse_ms / 1e6, 1),
            "dense_ms_per_iter": round(min(ms["dense"]), 4) if "dense" in ms else None,
-           "dense_precision": engines["dense"].precision() if "dense" in engines else None}
+           "dense_precision": engines["dense"].precision() if "dense" in engines else None,
+           "masked_ms_per_iter": round(min(ms["masked"]), 4) if "masked" in ms else None}
     print(json.dumps(out), flush=True)
     for eng in engines.values():
         eng.reset_stream()
