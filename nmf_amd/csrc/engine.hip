@@ -847,15 +847,8 @@ int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int re
     E->prof = false;
     hipEvent_t a, b;
     NMFX_HIP(hipEventCreate(&a)); NMFX_HIP(hipEventCreate(&b));
-#ifdef NMFX_EXP_REVERSE
-    extern int nmfx_debug_set_reverse(void* stream, int v);
-    static const int altrev = getenv("NMFX_EXP_ALTREV") ? atoi(getenv("NMFX_EXP_ALTREV")) : 0;
-#endif
     for (int i = -2; i < reps && !rc; ++i) {                               // two untimed launches first
         if (i == 0) NMFX_HIP(hipEventRecord(a, E->stream));
-#ifdef NMFX_EXP_REVERSE
-        nmfx_debug_set_reverse(E->stream, altrev ? (i & 1) : 0);          // (the setter launch is there in both variants)
-#endif
         if (ao) {
             const bool side = w.find("_side") != std::string::npos, hside = w.find("hphase") != std::string::npos;
             if (w.rfind("ao_", 0) == 0) rc = hside ? nmfx_bf16_vtw(E, true, "hphase", false, 3) : nmfx_bf16_vht(E, false, 0, "wphase_noobj", false, 3);

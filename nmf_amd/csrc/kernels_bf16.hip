@@ -71,9 +71,6 @@ __device__ __forceinline__ void dma_run4(unsigned long long base, unsigned dst, 
 }
 __device__ __forceinline__ void dma_run4_nt(unsigned long long base, unsigned dst, unsigned o0, unsigned o1,
                                             unsigned o2, unsigned o3) {       // streaming (non-temporal) policy
-#ifdef NMFX_EXP_TEMPORAL      // experiment: the tile stream with the default cache policy (does a small V stay in the Infinity Cache?)
-    dma_run4(base, dst, o0, o1, o2, o3); return;
-#endif
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %1 nt\n\t"
                  "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %1 nt\n\t"
@@ -90,9 +87,6 @@ __device__ __forceinline__ void dma_run2(unsigned long long base, unsigned dst, 
                  : "=&s"(keep) : "s"(base), "s"(dst), "v"(o0), "v"(o1) : "memory", "scc");
 }
 __device__ __forceinline__ void dma_run2_nt(unsigned long long base, unsigned dst, unsigned o0, unsigned o1) {
-#ifdef NMFX_EXP_TEMPORAL
-    dma_run2(base, dst, o0, o1); return;
-#endif
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %1 nt\n\t"
                  "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %1 nt\n\t"
@@ -120,61 +114,10 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned&
     const float ah = __uint_as_float(hi << 16), bh = __uint_as_float(hi & 0xffff0000u);
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(a - ah), "v"(b - bh));    // (r5: the two subtractions as ONE v_pk_add_f32 -- 6 % fewer VALU
 }                                                                                  //  instructions in the KL loops -- measured no faster, k = 128 1 % slower: not kept)
-#ifdef NMFX_EXP_FP8D           // experiment (r5): the cross terms of the RESIDUAL product (k = 128 Euclidean form) on the block-scaled fp8 matrix pipe, operands
-                               // converted in registers from the bf16 fragments (fixed scales: hi x 1, lo x 2^9).  Measured: config 5 W phase 2740 -> 2719 us,
-                               // config 3 180.2 -> 178.8 (-0.8 %): the 64 conversions per group cost the issue port what the 12 saved MFMAs give back;
-                               // recorded objective +1e-6 .. +1.4e-5 off the f64 one.  The fp8 pipe pays only with operands that arrive converted (LAB_NOTES R5)
-typedef int fp8_i32x8 __attribute__((ext_vector_type(8)));
-typedef short fp8_s16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 fp8_bf16x2 __attribute__((ext_vector_type(2)));
-// eight bf16 (one 32x32x16 k-step's fragment) -> eight e4m3 bytes = registers 2 j, 2 j + 1 of a 32x32x64 operand; stored value = x / scale
-__device__ __forceinline__ void frag_to_fp8(const Frag8& f, float scale, int& r0, int& r1) {
-    union { unsigned u; fp8_bf16x2 v; } a, b, c, d;
-    a.u = f.u.x; b.u = f.u.y; c.u = f.u.z; d.u = f.u.w;
-    union { fp8_s16x2 v; int i; } o0, o1;
-    o0.i = 0; o1.i = 0;
-    o0.v = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o0.v, a.v, scale, false);
-    o0.v = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o0.v, b.v, scale, true);
-    o1.v = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o1.v, c.v, scale, false);
-    o1.v = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o1.v, d.v, scale, true);
-    r0 = o0.i; r1 = o1.i;
-}
-#endif
-__device__ __forceinline__ void hi8(const float4& p, const float4& q, Frag8& hi) {       // the bf16 image alone (round to nearest even)
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi.u.x) : "v"(p.x), "v"(p.y));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi.u.y) : "v"(p.z), "v"(p.w));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi.u.z) : "v"(q.x), "v"(q.y));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi.u.w) : "v"(q.z), "v"(q.w));
-}
 __device__ __forceinline__ void split8(const float4& p, const float4& q, Frag8& hi, Frag8& lo) {
     split2(p.x, p.y, hi.u.x, lo.u.x); split2(p.z, p.w, hi.u.y, lo.u.y);
     split2(q.x, q.y, hi.u.z, lo.u.z); split2(q.z, q.w, hi.u.w, lo.u.w);
 }
-
-// ---------------------------------------------------------------------------
-// A_part[sp] = X(rows of the block, columns of split sp) * Y^T, optional residual
-// objective 0.5 * sum (X - Z Y)^2.  Block = 128 rows (8 waves x 16 rows, two waves per
-// SIMD), 64-column groups.  LDS (all of the 160 KiB):
-//   Y side, double buffered: ONE image of the Y tile per group -- Yhi and Ylo, each 64 rows
-//     (factors) x 128 B of bf16; 16-byte chunk c of row r sits at position c ^ yswz(r).  The
-//     A-product takes its B operand from it by rows (ds_read_b128), the residual product takes
-//     its A operand from the SAME image by columns (ds_read_b64_tr_b16, the gfx950 transposing
-//     read): yswz is conflict free for both (searched exhaustively over XOR-linear maps against
-//     the lane groups of MI355X_MICROARCH.md, LDS table).  A second, transposed copy of the tile
-//     would double the L2 -> LDS traffic, which is what bounds the W phase.
-//   V side, a 4-deep ring per wave: [16][64] f32, chunk c of row r at position c ^ r;
-//     this is the HBM stream, requested four groups ahead (the slot of the tile being consumed is
-//     refilled as soon as every wave holds its tile in registers: 128 KiB in flight per CU; the
-//     stream rate follows the bytes in flight until HBM saturates).  X is either row-major (ldx) or
-//     tile-major ([128 rows][64 cols] tiles, one contiguous 32 KiB read per block and group).
-// Everything is filled by LDS-DMA and retired with a COUNTED s_waitcnt vmcnt.  The DMA work
-// is split by wave (4 "Y loaders", 4 "V loaders" that each fetch the tiles of two waves) so
-// that the deep V prefetch is not drained by the shallow Y prefetch.  One barrier per group
-// publishes Y(grp) / V(grp) and frees the buffers read one group earlier.  All LDS reads are
-// (loop-invariant lane offset) + immediate and conflict free.
-// ---------------------------------------------------------------------------
-#pragma clang fp contract(fast)
-__device__ __forceinline__ int yswz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 // ds_read_b64_tr_b16: within each group of 16 lanes, lane 4q+p supplies the address of 4
@@ -186,407 +129,22 @@ __device__ __forceinline__ uint2 lds_read_tr(const unsigned char* p) {
     return r.u;
 }
 
-// KP = 64 or 128 factors.  KP = 128: Y image 2 x 16 KiB per group (double buffered: 64 KiB), V ring
-// 3 deep, accumulators for 8 factor tiles, the Gram by-product is left to the Gram kernels.
-//
-// KL = true (MUR with the KL divergence, nmf/mur.py:24-27, 40-43): A_part = (X / (Z Y + 1e-9)) Y^T.
-// The product Z Y comes FIRST (same transposed reads), the quotient is formed in registers in the
-// D layout (lane = row x, columns 16 e + 4 g + r) and is used as the A operand as it stands: the
-// contraction index of the A-product is PERMUTED (k-step s runs over the columns of e = 2s and
-// 2s + 1), and the B operand follows with two 8-byte reads of the same Y image instead of one
-// 16-byte read.  With WITH_OBJ the objective term x log(x / zy) - x + zy (nmf/utils.py:23-26) is
-// accumulated from the same registers.
 #ifdef NMFX_EXP_BLOCKTIME      // experiment (tools/lab/block_times.py): start / end time of every block of the last product launches
 __device__ unsigned long long nmfx_dbg_times[2][2][1024];      // [with objective][start | end][block]
 extern "C" int nmfx_debug_block_times(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(nmfx_dbg_times), sizeof(nmfx_dbg_times)) == hipSuccess ? 0 : -1;
 }
 #endif
-// WITH_A = false (with WITH_OBJ, Euclidean): only the residual objective -- no A-product, no Gram by-product,
-// nothing written but objpart (the objective passes of ADMM and ANLS).
-template <int KP, bool WITH_OBJ, bool KL, int TERMS, bool WITH_A = true>
-__global__ __launch_bounds__(512) void xyt_bf16_kernel(
-    const float* __restrict__ X, int64_t ldx,
-    const unsigned short* __restrict__ Yhi, const unsigned short* __restrict__ Ylo, int64_t ldy,
-    const unsigned short* __restrict__ Zhi, const unsigned short* __restrict__ Zlo,
-    float* __restrict__ Apart, double* __restrict__ objpart, float* __restrict__ gram_part, int64_t R,
-    int ngroups, const int* __restrict__ flag, int tiled, int ng)
-{
-    if (*flag) return;
-#ifdef NMFX_EXP_BLOCKTIME
-    const int dbg_b = blockIdx.y * gridDim.x + blockIdx.x;
-    if (threadIdx.x == 0 && dbg_b < 1024) nmfx_dbg_times[WITH_OBJ][0][dbg_b] = wall_clock64();
-#endif
-    constexpr int NJT = KP / 16;                      // factor tiles of the A-product
-    constexpr int YT = KP * 128;                      // bytes of one Y tile (KP rows x 64 bf16)
-    constexpr int YBUF = 2 * YT;                      // Yhi tile, Ylo tile
-    constexpr int VOFF = 2 * YBUF;                    // start of the V rings
-    constexpr int VRING = (KP == 64) ? 4 : 3;         // V ring depth (LDS: 2*YBUF + 8*VRING*4 KiB = 160 KiB)
-    static_assert(WITH_A || (WITH_OBJ && !KL), "without the A-product the launch must at least compute the objective");
-    constexpr bool WITH_GRAM = (KP == 64) && !KL && WITH_A;
-    constexpr bool WITH_D = WITH_OBJ || KL;           // the product Z Y is formed
-    constexpr int YPW = 2 * (KP / 8) / 4;             // Y pieces (8 rows x 128 B) per loader wave and group
-    constexpr int NA = WITH_A ? 2 * (NJT / 4) : 0;    // pipeline stages of the A-product: (k-step, half of the tiles)
-    constexpr int ND = WITH_D ? KP / 32 : 0;          // stages of the product Z Y: k-steps over the factors
-    constexpr int NS = NA + ND;                       // order: A.. then D.. (Euclidean), D.. then A.. (KL)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    // the wave index as a PROVABLY uniform value: everything derived from it (DMA bases, LDS
-    // destinations) then stays in SGPRs, which the "s" operands of the DMA statements need
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int x = lane & 15, g = lane >> 4;
-    const int S = gridDim.y, sp = blockIdx.y;
-    const int g0 = (int)((int64_t)ngroups * sp / S);
-    const int g1 = (int)((int64_t)ngroups * (sp + 1) / S);
-    const int64_t r0 = (int64_t)blockIdx.x * 128 + wave * 16;
-
-    // ---- DMA plan: roles by wave, so that every wave's vmcnt queue is homogeneous ----
-    // (vmcnt retires in order: a shallow Y request behind deep V requests would force
-    // the V requests to complete too.)
-    //   waves 4..7 ("Y loaders"): YPW of the pieces (8 rows x 128 B) of the Y tiles of group grp+1
-    //   waves 0..3 ("V loaders"): the V tiles of TWO waves each (w and w+4), VRING-1 groups ahead
-    const bool yrole = wave >= 4;
-    const int lw = wave & 3;
-    const int ytile = (lw * YPW) / (KP / 8), p0 = (lw * YPW) % (KP / 8);
-    const unsigned short* ysrc = ytile == 0 ? Yhi : Ylo;
-    unsigned long long ybase = (unsigned long long)ysrc + (unsigned long long)g0 * 128ull;
-    unsigned yoffs[YPW];
-#pragma unroll
-    for (int i = 0; i < YPW; ++i) {
-        const int row = 8 * (p0 + i) + (lane >> 3), pos = lane & 7, chunk = pos ^ yswz(row);
-        yoffs[i] = (unsigned)(((int64_t)row * ldy + 8 * chunk) * 2);
-    }
-    const unsigned ydst = (unsigned)(ytile * YT + p0 * 1024);
-    // V: rows 4t + g of a wave's 16, position x holds chunk x ^ row
-    const int64_t rblk = (int64_t)blockIdx.x * 128;
-    unsigned long long vbaseA = (unsigned long long)(X + (rblk + lw * 16) * ldx) + (unsigned long long)g0 * 256ull;
-    unsigned long long vbaseB = (unsigned long long)(X + (rblk + (lw + 4) * 16) * ldx) + (unsigned long long)g0 * 256ull;
-    unsigned long long vstep = 256ull;
-    unsigned voffs[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int row = 4 * t + g;
-        voffs[t] = (unsigned)(((int64_t)row * ldx + 4 * (x ^ row)) * 4);
-    }
-    if (tiled) {       // X stored tile-major: [R/128][ldx/64] tiles of [128 rows][64 cols], 32 KiB contiguous each
-        const unsigned long long tile0 = (unsigned long long)X + ((unsigned long long)blockIdx.x * (ldx / 64) + g0) * 32768ull;
-        vbaseA = tile0 + lw * 16 * 256; vbaseB = tile0 + (lw + 4) * 16 * 256; vstep = 32768ull;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { const int row = 4 * t + g; voffs[t] = (unsigned)((row * 64 + 4 * (x ^ row)) * 4); }
-    }
-    const unsigned smem0 = __builtin_amdgcn_readfirstlane(lds_off(smem));
-    const unsigned vdstA = smem0 + VOFF + lw * (VRING * 4096);
-    const unsigned vdstB = smem0 + VOFF + (lw + 4) * (VRING * 4096);
-    int yq = 0, vq = 0;                               // next Y buffer / V ring slot to fill
-    auto issue_y = [&]() {                            // Y loaders only
-#pragma unroll
-        for (int i = 0; i < YPW; i += 4)
-            dma_run4(ybase, smem0 + yq * YBUF + ydst + i * 1024, yoffs[i], yoffs[i + 1], yoffs[i + 2], yoffs[i + 3]);
-        ybase += 128ull; yq ^= 1;
-    };
-    auto issue_v = [&]() {                            // V loaders only
-        dma_run4_nt(vbaseA, vdstA + vq * 4096, voffs[0], voffs[1], voffs[2], voffs[3]);
-        dma_run4_nt(vbaseB, vdstB + vq * 4096, voffs[0], voffs[1], voffs[2], voffs[3]);
-        vbaseA += vstep; vbaseB += vstep; vq = (vq == VRING - 1) ? 0 : vq + 1;
-    };
-
-    // ---- loop-invariant LDS read offsets ----
-    int ylane[2], ykl[2][2], vaoff[2][2], vroff[4], tro[4];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        ylane[s] = x * 128 + 16 * ((4 * s + g) ^ yswz(x));           // + 2048 * (factor tile) + YT * (lo image)
-        // KL: columns 32 s + 4 g .. + 3 and 32 s + 16 + 4 g .. + 3 of row x (8 bytes each)
-        ykl[s][0] = x * 128 + 16 * ((4 * s + (g >> 1)) ^ yswz(x)) + 8 * (g & 1);
-        ykl[s][1] = x * 128 + 16 * ((4 * s + 2 + (g >> 1)) ^ yswz(x)) + 8 * (g & 1);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) vaoff[s][h] = x * 256 + 16 * ((8 * s + 2 * g + h) ^ x);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) vroff[e] = x * 256 + 16 * ((4 * e + g) ^ x);
-    {   // transposed reads: lane (q = x >> 2, p = x & 3) of group g addresses row 8g + q (+ 32 s + 4 t),
-        // columns 16 e + 4 p .. + 3; yswz of that row = 2 (q >> 1 & 1) + 4 (g & 1) whatever s and t are
-        const int q = x >> 2, pp = x & 3;
-        const int fz = (((q >> 1) & 1) << 1) | ((g & 1) << 2);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tro[e] = 128 * (8 * g + q) + 8 * (pp & 1) + 16 * ((2 * e + (pp >> 1)) ^ fz);
-    }
-    const unsigned char* vring = smem + VOFF + wave * (VRING * 4096);
-
-    f32x4 acc[NJT];
-#pragma unroll
-    for (int j = 0; j < NJT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // Gram by-product (KP = 64): Y Y^T (H H^T in the W phase, W^T W in the H phase) from the Y tiles
-    // the blocks fetch anyway.  The work is SPREAD over the first `ng` row blocks -- row block b takes
-    // the groups with (grp - g0) % ng == b of every split -- because the 32 extra MFMAs per group made
-    // the single row block that used to do all of it the tail of the whole launch (W phase 150 us
-    // with it, 123 us without).  Slab (b, split) = gram_part[b * S + split].  Wave w owns tile row
-    // w>>1 and tile columns 2(w&1), 2(w&1)+1.
-    const bool do_gram = WITH_GRAM && ((int)blockIdx.x < ng);
-    const int git = wave >> 1, gj0 = 2 * (wave & 1);
-    f32x4 gacc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-    double osum = 0.0;
-    // Launches without the objective are bound by the bytes in flight: they refill a V slot as soon as every
-    // wave holds its tile in registers (VRING groups ahead, one more barrier per group).  The launches that also
-    // carry the objective are bound by instruction issue and the extra barrier costs more than the deeper
-    // prefetch brings (config 5 W phase 3014 -> 3168 us, MUR-KL W phase 748 -> 812): those keep VRING - 1.
-    constexpr bool EARLY = !WITH_OBJ || !WITH_A;       // (also the KL H phase: 730 -> 695 us with it, and the objective-only pass)
-    constexpr int VAHEAD = EARLY ? VRING : VRING - 1;  // groups requested ahead of the one being consumed
-    if (yrole) { if (g0 < g1) issue_y(); }
-    else {
-#pragma unroll
-        for (int a = 0; a < VAHEAD; ++a) if (g0 + a < g1) issue_v();
-    }
-    // The Z fragments (ordinary vector loads) go out BEHIND the first DMAs, so the block pays one memory round
-    // trip at its start instead of two.  vmcnt retires in order: the wait below also lands the DMAs issued
-    // above, which the first group needs anyway, and every later counted wait only sees DMAs again.
-    Frag8 zh[WITH_D ? KP / 32 : 1], zl[WITH_D ? KP / 32 : 1];
-    if (WITH_D) {
-#pragma unroll
-        for (int s = 0; s < KP / 32; ++s) {
-            zh[s].u = *reinterpret_cast<const uint4*>(Zhi + (r0 + x) * KP + 32 * s + 8 * g);
-            zl[s].u = *reinterpret_cast<const uint4*>(Zlo + (r0 + x) * KP + 32 * s + 8 * g);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < KP / 32; ++s) { pinu(zh[s].u); pinu(zl[s].u); }
-    }
-    int ycur = 0, vcur = 0;
-    for (int grp = g0; grp < g1; ++grp) {
-        // Y loaders: Y(grp) is their newest request.  V loaders: V(grp+1 .. grp+VRING-1) may
-        // stay in flight (8 DMAs per group), V(grp) must have landed.
-        if (yrole) dma_wait_le<0>();
-        else {
-            const int ahead = min(VAHEAD - 1, g1 - 1 - grp);
-            if (ahead >= 3) dma_wait_le<24>(); else if (ahead == 2) dma_wait_le<16>(); else if (ahead == 1) dma_wait_le<8>(); else dma_wait_le<0>();
-        }
-        __syncthreads();
-        if (yrole) { if (grp + 1 < g1) issue_y(); }
-        else if (!EARLY && grp + VRING - 1 < g1) issue_v();
-        const unsigned char* ybuf = smem + ycur * YBUF;
-        const unsigned char* vt = vring + vcur * 4096;
-
-        // Explicit software pipeline (hipcc otherwise pairs every ds_read with its own
-        // s_waitcnt right in front of the MFMA that uses it): stage st first ISSUES the fragment
-        // reads of stage st+1 into the other register set, then runs its own 16 MFMAs.
-        // Stages: A-product (k-step, half of the factor tiles) ..., then the residual product's
-        // k-steps over the factors.  sched_barrier(0) pins the stage boundaries.
-#define NMFX_FENCE() __builtin_amdgcn_sched_barrier(0)
-        float4 va[2][2], vr[4];
-        Frag8 fh[2][4], fl[2][4];                      // [register set][fragment]: hi and lo images
-        auto issue = [&](int st, int set) {
-            const bool a_stage = KL ? st >= ND : st < NA;
-            if (a_stage) {                             // Y tile rows 16 jt.., k-step ast / (NJT / 4)
-                const int ast = KL ? st - ND : st;
-                const int ks = ast / (NJT / 4), half = ast % (NJT / 4);
-                if (KL) {
-                    const unsigned char* y0 = ybuf + ykl[ks][0] + half * 4 * 2048;
-                    const unsigned char* y1 = ybuf + ykl[ks][1] + half * 4 * 2048;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint2 a0 = *reinterpret_cast<const uint2*>(y0 + j * 2048);
-                        const uint2 a1 = *reinterpret_cast<const uint2*>(y1 + j * 2048);
-                        const uint2 b0 = *reinterpret_cast<const uint2*>(y0 + j * 2048 + YT);
-                        const uint2 b1 = *reinterpret_cast<const uint2*>(y1 + j * 2048 + YT);
-                        fh[set][j].u = make_uint4(a0.x, a0.y, a1.x, a1.y);
-                        fl[set][j].u = make_uint4(b0.x, b0.y, b1.x, b1.y);
-                    }
-                } else {
-                    const unsigned char* ys = ybuf + ylane[ks] + half * 4 * 2048;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        fh[set][j].u = *reinterpret_cast<const uint4*>(ys + j * 2048);
-                        fl[set][j].u = *reinterpret_cast<const uint4*>(ys + j * 2048 + YT);
-                    }
-                }
-            } else {                                   // columns 16 e.. of factors 32 s.. 32 s + 31, transposed
-                const int s = KL ? st : st - NA;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned char* ts = ybuf + tro[e] + s * 4096;
-                    const uint2 h0 = lds_read_tr(ts), h1 = lds_read_tr(ts + 512);
-                    const uint2 l0 = lds_read_tr(ts + YT), l1 = lds_read_tr(ts + YT + 512);
-                    fh[set][e].u = make_uint4(h0.x, h0.y, h1.x, h1.y);
-                    fl[set][e].u = make_uint4(l0.x, l0.y, l1.x, l1.y);
-                }
-            }
-        };
-        if (!KL && WITH_A) {
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) va[s][h] = *reinterpret_cast<const float4*>(vt + vaoff[s][h]);
-        }
-        if (WITH_D) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vr[e] = *reinterpret_cast<const float4*>(vt + vroff[e]);
-        }
-        issue(0, 0);
-        NMFX_FENCE();
-        Frag8 vh[2], vl[2];
-        if (!KL && WITH_A) {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) split8(va[s][0], va[s][1], vh[s], vl[s]);
-        }
-        if (EARLY) {
-            // Every wave now has its V tile of this group in registers, so the slot is refilled HERE, VRING groups
-            // ahead, instead of at the next group boundary (VRING - 1 ahead): the stream rate follows the bytes in
-            // flight (H phase of config 2: 96 -> 128 KiB per CU, 96 -> 87 us = 6.2 TB/s).  Costs one more barrier
-            // per group: the V loader waves must know that the OTHER waves have read their tiles too.
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (!yrole && grp + VRING < g1) issue_v();
-        }
-        float klpart = 0.f;
-        f32x4 d[4];                                    // D tiles: d[e][reg] = (Z Y)[row x][16 e + 4 g + reg]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int st = 0; st < NS; ++st) {
-            const int set = st & 1;
-            if (st + 1 < NS) issue(st + 1, set ^ 1);
-            NMFX_FENCE();
-            const bool a_stage = KL ? st >= ND : st < NA;
-            if (a_stage) {
-                const int ast = KL ? st - ND : st;
-                const int ks = ast / (NJT / 4), j0 = 4 * (ast % (NJT / 4));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j0 + j] = MFMA_BF16(vh[ks], fh[set][j], acc[j0 + j]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j0 + j] = MFMA_BF16(vl[ks], fh[set][j], acc[j0 + j]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j0 + j] = MFMA_BF16(vh[ks], fl[set][j], acc[j0 + j]);
-                if (TERMS >= 4) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j0 + j] = MFMA_BF16(vl[ks], fl[set][j], acc[j0 + j]);
-                }
-            } else {
-                const int s = KL ? st : st - NA;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = MFMA_BF16(fh[set][e], zh[WITH_D ? s : 0], d[e]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = MFMA_BF16(fl[set][e], zh[WITH_D ? s : 0], d[e]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = MFMA_BF16(fh[set][e], zl[WITH_D ? s : 0], d[e]);
-                if (TERMS >= 4 && KL) {               // (the Euclidean residual is only summed into the objective, which
-#pragma unroll                                        //  nothing is computed from: three terms whatever TERMS is)
-                    for (int e = 0; e < 4; ++e) d[e] = MFMA_BF16(fl[set][e], zl[WITH_D ? s : 0], d[e]);
-                }
-            }
-            NMFX_FENCE();
-            if (KL && st == ND - 1) {
-                // quotient x / (zy + 1e-9) in the D layout = the A operand of the permuted k-steps;
-                // objective term x log(x / zy) [inf, nan -> 0] - x + zy
-                float qv[4][4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float vv[4] = {vr[e].x, vr[e].y, vr[e].z, vr[e].w};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        // v_rcp_f32 / v_log_f32 (1 ulp each) instead of IEEE division and logf: this
-                        // phase is VALU bound, and 0 * log(0 / p), x * log(x / 0) and 0 / 0 still come
-                        // out as nan / inf / nan and are zeroed exactly like utils.py:24 does
-                        const float pv = d[e][r];
-                        if (WITH_OBJ) {
-                            float t = vv[r] * (__builtin_amdgcn_logf(vv[r] * __builtin_amdgcn_rcpf(pv)) * 0.69314718055994531f);
-                            t = (t != t || t == __builtin_inff()) ? 0.f : t;
-                            klpart += (t - vv[r]) + pv;
-                        }
-                        qv[e][r] = vv[r] * __builtin_amdgcn_rcpf(pv + 1e-9f);
-                    }
-                }
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    split2(qv[2 * ks][0], qv[2 * ks][1], vh[ks].u.x, vl[ks].u.x);
-                    split2(qv[2 * ks][2], qv[2 * ks][3], vh[ks].u.y, vl[ks].u.y);
-                    split2(qv[2 * ks + 1][0], qv[2 * ks + 1][1], vh[ks].u.z, vl[ks].u.z);
-                    split2(qv[2 * ks + 1][2], qv[2 * ks + 1][3], vh[ks].u.w, vl[ks].u.w);
-                }
-                NMFX_FENCE();
-            }
-            if (WITH_GRAM && st == NA - 1 && do_gram && ((grp - g0) % ng) == (int)blockIdx.x) {
-                // Gram by-product: operands straight from the LDS tiles at wave-uniform tile rows
-                // (A = rows 16*git.., B = rows 16*(gj0+c)..); row block b < ng takes every ng-th group
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const unsigned char* ys = ybuf + ylane[s];
-                    Frag8 ah, al;
-                    ah.u = *reinterpret_cast<const uint4*>(ys + git * 2048);
-                    al.u = *reinterpret_cast<const uint4*>(ys + git * 2048 + YT);
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        Frag8 bh, bl;
-                        bh.u = *reinterpret_cast<const uint4*>(ys + (gj0 + c) * 2048);
-                        bl.u = *reinterpret_cast<const uint4*>(ys + (gj0 + c) * 2048 + YT);
-                        gacc[c] = MFMA_BF16(ah, bh, gacc[c]);
-                        gacc[c] = MFMA_BF16(al, bh, gacc[c]);
-                        gacc[c] = MFMA_BF16(ah, bl, gacc[c]);
-                        if (TERMS >= 4) gacc[c] = MFMA_BF16(al, bl, gacc[c]);
-                    }
-                }
-            }
-        }
-        if (WITH_OBJ && !KL) {
-            float part = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float rx = vr[e].x - d[e][0], ry = vr[e].y - d[e][1];
-                const float rz = vr[e].z - d[e][2], rw = vr[e].w - d[e][3];
-                part += rx * rx + ry * ry + rz * rz + rw * rw;
-            }
-            osum += (double)part;
-        }
-        if (WITH_OBJ && KL) osum += (double)klpart;
-#undef NMFX_FENCE
-        ycur ^= 1;
-        vcur = (vcur == VRING - 1) ? 0 : vcur + 1;
-    }
-
-    if (WITH_A) {
-        float* out = Apart + ((int64_t)sp * R + r0) * KP;
-#pragma unroll
-        for (int jt = 0; jt < NJT; ++jt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out[(int64_t)(4 * g + r) * KP + jt * 16 + x] = acc[jt][r];
-    }
-    if (do_gram) {
-        float* go = gram_part + ((int64_t)blockIdx.x * S + sp) * KP * KP;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                go[(int64_t)(16 * git + 4 * g + r) * KP + 16 * (gj0 + c) + x] = gacc[c][r];
-    }
-#ifdef NMFX_EXP_BLOCKTIME
-    __syncthreads();
-    if (threadIdx.x == 0 && dbg_b < 1024) nmfx_dbg_times[WITH_OBJ][1][dbg_b] = wall_clock64();
-#endif
-    if (WITH_OBJ) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) osum += __shfl_down(osum, off, 64);
-        __syncthreads();                                   // everybody is done with the LDS tiles
-        double* red = reinterpret_cast<double*>(smem);
-        if (lane == 0) red[wave] = osum;
-        __syncthreads();
-        if (tid == 0) {
-            double t = 0.0;
-            for (int w = 0; w < 8; ++w) t += red[w];
-            objpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = (KL ? 1.0 : 0.5) * t;
-        }
-    }
-}
-#pragma clang fp contract(off)
-
 // ---------------------------------------------------------------------------
-// The 32-row form of the Euclidean product launch for KP = 64 (W phase and H phase of MUR, the
-// products of AO-ADMM / ADMM / ANLS): same arguments, same LDS budget, same DMA plan and the same
-// results layout as xyt_bf16_kernel<64, WITH_OBJ, false, TERMS>, but on v_mfma_f32_32x32x16_bf16
-// with the block's 8 waves arranged as 4 row groups (32 rows) x 2 column halves (32 of the group's
-// 64 columns).  Why: the 16-row form reads every Y fragment for 16 rows of V and each wave reads its
-// V tile twice (operand layout + accumulator layout): 2176 LDS-array cycles per 64-column group and
-// CU against 1536 MFMA cycles per SIMD -- the LDS array, not the matrix pipe or HBM, was the W phase's
-// longest queue.  Here a Y fragment feeds 32 rows (half the fragment reads per flop), the MFMA holds
-// the vector issue port for 8 of 32 cycles instead of 8 of 16, and per wave and group there are
-// 28 LDS reads (4 V, 8 Y rows, 16 transposed) instead of 56.
+// The product launch (W phase and H phase of MUR, the products of AO-ADMM / ADMM / ANLS):
+// A_part[sp] = X(rows of the block, columns of split sp) * Y^T, optional residual objective 0.5 * sum (X - Z Y)^2,
+// on v_mfma_f32_32x32x16_bf16.  Block = 128 rows, 64-column groups; the block's 8 waves are arranged as 4 row groups
+// (32 rows) x 2 column halves (32 of the group's 64 columns).  Why 32 rows: a 16-row form (16x16x32 tiles, one wave per
+// 16 rows; the first version of this kernel) reads every Y fragment for 16 rows of V and each wave reads its V tile twice
+// (operand layout + accumulator layout): 2176 LDS-array cycles per 64-column group and CU against 1536 MFMA cycles per
+// SIMD -- the LDS array, not the matrix pipe or HBM, was the W phase's longest queue.  Here a Y fragment feeds 32 rows
+// (half the fragment reads per flop), the MFMA holds the vector issue port for 8 of 32 cycles instead of 8 of 16, and per
+// wave and group there are 28 LDS reads (4 V, 8 Y rows, 16 transposed) instead of 56.
 //   wave (rg = w & 3, hh = w >> 2): rows 32 rg .. + 31 of the block, columns 32 hh .. + 31 of each group
 //   A-product  A[32 rows][64 factors] += V[32][32 cols] Y^T : 2 k-steps (16 columns) x 2 factor tiles
 //   residual   D^T[32 cols][32 rows]  = Y^T[32 cols][64 factors] Z^T : 4 k-steps (16 factors); the rows of
@@ -595,10 +153,25 @@ __global__ __launch_bounds__(512) void xyt_bf16_kernel(
 //              V in the A-operand layout: one LDS read of V serves both products, residual = va - d
 //   the two column halves of a row group hold partial A tiles; they are exchanged through LDS once,
 //   after the last group (each wave finishes one factor tile).
-// LDS: Y images as before ([64 factors][128 B] hi, lo; double buffered) with the chunk swizzle yswz32
-// (tools/lab/swizzle_search.py: conflict free for the b128 row reads of the 32x32x16 B operand, its
-// transposed b64 reads AND the 16x16x32 row reads of the Gram by-product); V ring per row group,
-// [32 rows][64 cols] f32, chunk c of row r at c ^ (r & 15), 4 deep.
+// LDS (all of the 160 KiB):
+//   Y side, double buffered: ONE image of the Y tile per group -- Yhi and Ylo, each [64 factors][128 B] of bf16; 16-byte
+//     chunk c of row r sits at position c ^ yswz32(r).  The A-product takes its B operand from it by rows (ds_read_b128),
+//     the residual product takes its A operand from the SAME image by columns (ds_read_b64_tr_b16, the gfx950 transposing
+//     read), and the Gram by-product reads it by rows on 16x16x32 tiles: yswz32 is conflict free for all three
+//     (tools/lab/swizzle_search.py).  A second, transposed copy of the tile would double the L2 -> LDS traffic, which is
+//     what bounds the W phase.
+//   V side, a ring per row group: [32 rows][64 cols] f32, chunk c of row r at c ^ (r & 15), 4 deep; this is the HBM
+//     stream, requested several groups ahead.  X is tile-major: [R/128][ldx/64] tiles of [128 rows][64 cols], one
+//     contiguous 32 KiB read per block and group.
+// DMA plan: everything is filled by LDS-DMA and retired with a COUNTED s_waitcnt vmcnt.  The requests are split by wave --
+// waves 4..7 are the "Y loaders", waves 0..3 the "V loaders" (row group lw each) -- so that every wave's vmcnt queue is
+// homogeneous: vmcnt retires in order, and a shallow Y request behind deep V requests would force the V requests to
+// complete too.  All LDS reads are (loop-invariant lane offset) + immediate and conflict free.
+// Gram by-product (KP = 64, Euclidean): Y Y^T (H H^T in the W phase, W^T W in the H phase) from the Y tiles the blocks
+// fetch anyway.  The work is SPREAD over the first `ng` row blocks -- row block b takes the groups with (grp - g0) % ng == b
+// of every split -- because the 32 extra MFMAs per group made the single row block that used to do all of it the tail of
+// the whole launch (W phase 150 us with it, 123 us without).  Slab (b, split) = gram_part[b * S + split].  Wave w owns
+// tile row w >> 1 and tile columns 2 (w & 1), 2 (w & 1) + 1.
 // ---------------------------------------------------------------------------
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define MFMA32_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a).v, (b).v, (c), 0, 0, 0)
@@ -617,8 +190,6 @@ extern "C" int nmfx_debug_stamps(unsigned long long* out) {
 #define NMFX_STAMP(var) do { } while (0)
 #endif
 #pragma clang fp contract(fast)
-// ABL (experiments only, NMFX_EXP_ABLATE builds; results are then WRONG): bit 0 no DMA in the loop, bit 1 no bf16 split,
-// bit 2 no residual arithmetic, bit 3 no fragment reads after the first group, bit 4 no MFMAs
 // KL = true (MUR with the KL divergence, nmf/mur.py:24-27, 40-43; W phase: X = V, Y = H, Z = W; H phase: X = V^T, Y = W^T,
 // Z = H^T): A_part = (X / (Z Y + 1e-9)) Y^T.  The product Z Y comes first (the residual product's transposed reads), the
 // quotient is formed in registers -- accumulator register 4 a + c sits on the lane that holds the same element of X in the
@@ -632,17 +203,6 @@ extern "C" int nmfx_debug_stamps(unsigned long long* out) {
 // on the same X -- the A-product is the k = 128 product as it stands (A = [X Y_0^T | X Y_1^T]); the residual product is closed
 // after the first four k-steps (objective of problem 0), restarted, and closed again after the last four (problem 1):
 // objpart[p][split][block].
-#ifdef NMFX_EXP_REVERSE
-// Experiment (tools/lab/rev_probe.py): every other launch walks its groups backwards, so that what the previous launch streamed
-// LAST is read FIRST -- how much of a V-sized stream does the 256 MiB Infinity Cache serve on the turn-around?
-__device__ int nmfx_rev_flag = 0;
-__global__ void nmfx_set_rev_kernel(int v) { nmfx_rev_flag = v; }
-extern "C" int nmfx_debug_set_reverse(void* stream, int v) {
-    hipLaunchKernelGGL(nmfx_set_rev_kernel, dim3(1), dim3(1), 0, reinterpret_cast<hipStream_t>(stream), v);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-#endif
-
 // TEMPORAL (r3): the V tiles with the default cache policy instead of non-temporal.  A V-sized stream goes 6 % faster
 // non-temporal (config 2: 212.8 vs 225.9 us per iteration) and leaves nothing in the 256 MiB Infinity Cache; but when V and V^T
 // TOGETHER fit there -- a rank's shard of a strongly scaled problem: 2 x 64 MiB at config 2 over 8 GPUs -- the default policy keeps
@@ -671,9 +231,9 @@ struct XytSide {                 // the side job: Minv = (sum of gslabs slabs of
 // the stores of group g behind the barrier of group g + 1 (stores count in vmcnt as well: issued at the END of a group they would
 // sit in front of the next group's counted waits).  The counted waits of the V loaders hold for the steady state only (groups
 // with three predecessors and three successors: 24 / 20 younger loads); the first and last groups of a block drain the queue.
-template <bool WITH_OBJ, int TERMS, int ABL = 0, bool KL = false, int KP = 64, int NPROB = 1, bool TEMPORAL = false, bool WITH_A = true, int NW = 8, bool SK = false,
+template <bool WITH_OBJ, int TERMS, bool KL = false, int KP = 64, int NPROB = 1, bool TEMPORAL = false, bool WITH_A = true, bool SK = false,
           int VMODE = 0>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
+__global__ __launch_bounds__(512, 1) void xyt32_bf16_kernel(
     const float* __restrict__ X, int64_t ldx,
     const unsigned short* __restrict__ Yhi, const unsigned short* __restrict__ Ylo, int64_t ldy,
     const unsigned short* __restrict__ Zhi, const unsigned short* __restrict__ Zlo,
@@ -683,7 +243,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     float* __restrict__ vaux_dv = nullptr, float* __restrict__ vaux_s = nullptr, const int* __restrict__ flag2 = nullptr,
     int xpriv = 0)               // r5: X (the S of the KL-loss ADMM variants) lies in the auxiliaries kernel's register order inside its tiles (kl_dv_pos)
 {
-#define MFMA32X(a, b, c) ((ABL & 16) ? (c) : MFMA32_BF16(a, b, c))
     if (*flag) return;
     if (flag2 && *flag2) return;                       // (the inner stop of a KL-ADMM sub-problem has fired: a no-op like every later round)
     // VMODE 1 = VAUX (above); VMODE 2 = the KL objective of (Z, Y) alone -- sum x log(x / zy) [inf, nan -> 0] - x + zy, nmf/utils.py:21-26 --
@@ -698,19 +257,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     // an argument: as a run-time branch in read_va and in the group step it cost EVERY instantiation 5-13 % (config 2 W phase 117 -> 128 us, H phase
     // 88 -> 100, config 5 H phase 1745 -> 1900: profiles/r05_gather_as_runtime_branch_regression.txt)
     constexpr bool VAUX = VMODE == 1, KLOBJ = VMODE == 2, VAUXF = VMODE == 3, XGATHER = VMODE == 4;
-    static_assert(VMODE != 4 || (!WITH_OBJ && WITH_A && !KL && NPROB == 1 && NW == 8 && !SK && ABL == 0), "XGATHER: the objective-free Euclidean product form");
-    static_assert(VMODE == 0 || VMODE == 3 || VMODE == 4 || (WITH_OBJ && !WITH_A && !KL && NPROB == 1 && NW == 8 && !SK && ABL == 0), "VMODE: the objective-only form of the kernel");
-    static_assert(VMODE != 3 || (!WITH_OBJ && WITH_A && KL && NPROB == 1 && NW == 8 && !SK && ABL == 0), "VAUXF: the one-register-set KL form (kl128_group, at either KP)");
-    static_assert(!SK || (KP == 128 && !KL && NPROB == 1 && NW == 8 && WITH_A && ABL == 0), "stream-K: the Euclidean k = 128 products");
-    static_assert(KP == 64 || (KP == 128 && ABL == 0), "KP = 64 or 128");
+    static_assert(VMODE != 4 || (!WITH_OBJ && WITH_A && !KL && NPROB == 1 && !SK), "XGATHER: the objective-free Euclidean product form");
+    static_assert(VMODE == 0 || VMODE == 3 || VMODE == 4 || (WITH_OBJ && !WITH_A && !KL && NPROB == 1 && !SK), "VMODE: the objective-only form of the kernel");
+    static_assert(VMODE != 3 || (!WITH_OBJ && WITH_A && KL && NPROB == 1 && !SK), "VAUXF: the one-register-set KL form (kl128_group, at either KP)");
+    static_assert(!SK || (KP == 128 && !KL && NPROB == 1 && WITH_A), "stream-K: the Euclidean k = 128 products");
+    static_assert(KP == 64 || KP == 128, "KP = 64 or 128");
     static_assert(NPROB == 1 || (NPROB == 2 && KP == 128 && WITH_OBJ && !KL), "pair mode: the k = 128 W phase with its objective");
-    static_assert(WITH_A || (WITH_OBJ && !KL && NPROB == 1 && ABL == 0), "without the A-product the launch must at least compute the Euclidean objective");
-    static_assert(NW == 8 || (NW == 4 && KP == 64 && NPROB == 1 && WITH_A && VMODE == 0), "four-wave blocks: the k = 64 products");
-    // KL in its one-register-set form (kl128_group): KP = 128, the fused auxiliaries (VAUXF), and -- experiment NMFX_EXP_KLNW4 -- KP = 64 in four-wave blocks
-    constexpr bool KLONE = KL && (KP == 128 || VMODE == 3 || NW == 4);
-    constexpr int NRG = NW / 2;                        // row groups of 32 rows per block (NW = 4: 64-row blocks, two of them per CU)
+    static_assert(WITH_A || (WITH_OBJ && !KL && NPROB == 1), "without the A-product the launch must at least compute the Euclidean objective");
+    // KL in its one-register-set form (kl128_group): KP = 128 and the fused auxiliaries (VAUXF)
+    constexpr bool KLONE = KL && (KP == 128 || VMODE == 3);
+    constexpr int NRG = 4;                             // row groups of 32 rows per block
     constexpr int YR = (KL && !KLONE) ? 3 : 2;       // Y ring (KL, KP = 64: the second product runs one group behind the first)
-    constexpr int YT = KP * 128, YBUF = 2 * YT, VOFF = YR * YBUF, VRING = (KP == 64 && !KL && NW == 8) ? 4 : 3, VSLOT = 8192;
+    constexpr int YT = KP * 128, YBUF = 2 * YT, VOFF = YR * YBUF, VRING = (KP == 64 && !KL) ? 4 : 3, VSLOT = 8192;
     constexpr int NT = KP / 32, NTP = NT / 2;          // factor tiles of 32, pairs of them (one A stage each per k-step)
     constexpr int NK = KP / 16;                        // k-steps of the product Z Y
     constexpr int YPW = 2 * (KP / 8) / NRG;            // Y pieces (8 rows x 128 B) per loader wave and group
@@ -764,25 +322,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     if constexpr (SK) sp_ &= 255;
     const int bx = bx_, sp = sp_, g0 = g0_, g1 = g1_;
     const int64_t oidx = SK ? (int64_t)seg : (int64_t)blockIdx.y * gridDim.x + blockIdx.x;     // objective partial of this segment
-    const int64_t r0 = (int64_t)bx * (32 * NRG) + rg * 32;
+    const int64_t r0 = (int64_t)bx * 128 + rg * 32;
 
-    // ---- DMA plan (roles by wave as in xyt_bf16_kernel: homogeneous vmcnt queues) ----
+    // ---- DMA plan (roles by wave: homogeneous vmcnt queues, see the kernel's header) ----
     //   waves 4..7: 4 of the 16 pieces (8 rows x 128 B) of the Y tiles of group grp + 1
     //   waves 0..3: the V tile [32][64] of row group lw (8 pieces of 4 rows x 256 B), VRING (- 1) groups ahead
     const bool yrole = wave >= NRG;
     const int lw = wave & (NRG - 1);
     const int ytile = (lw * YPW) / (KP / 8), p0 = (lw * YPW) % (KP / 8);
     const unsigned short* ysrc = ytile == 0 ? Yhi : Ylo;
-#ifdef NMFX_EXP_REVERSE
-    const bool rev = __builtin_amdgcn_readfirstlane(nmfx_rev_flag) != 0;
-#else
-    constexpr bool rev = false;
-#endif
-    const int gfirst = SK ? sk_start : rev ? g1 - 1 : g0;
+    const int gfirst = SK ? sk_start : g0;
     int y_left = g1 - gfirst, v_left = g1 - gfirst;     // (SK) requests until the wrap back to group g0
     const long long span_y = (long long)(g1 - g0) * 128ll, span_v = (long long)(g1 - g0) * 32768ll;
-    const long long ystep = rev ? -128ll : 128ll;
-    long long vstep = rev ? -32768ll : 32768ll, vstep2 = vstep;      // (XGATHER: the steps alternate; they are swapped after every group's requests)
+    long long vstep = 32768ll, vstep2 = vstep;      // (XGATHER: the steps alternate; they are swapped after every group's requests)
     unsigned long long ybase = (unsigned long long)ysrc + (unsigned long long)gfirst * 128ull;
     unsigned yoffs[YPW];
 #pragma unroll
@@ -792,8 +344,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     }
     const unsigned ydst = (unsigned)(ytile * YT + p0 * 1024);
     // X is tile-major: [R/128][ldx/64] tiles of [128 rows][64 cols], 32 KiB contiguous each
-    const unsigned long long tile0 = (unsigned long long)X + ((unsigned long long)(bx / (4 / NRG)) * (ldx / 64) + gfirst) * 32768ull;
-    unsigned long long vbaseA = tile0 + (unsigned long long)((bx % (4 / NRG)) * NRG + lw) * 32 * 256, vbaseB = vbaseA + 16 * 256;
+    const unsigned long long tile0 = (unsigned long long)X + ((unsigned long long)bx * (ldx / 64) + gfirst) * 32768ull;
+    unsigned long long vbaseA = tile0 + (unsigned long long)lw * 32 * 256, vbaseB = vbaseA + 16 * 256;
     unsigned voffs[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) { const int row = 4 * t + g; voffs[t] = (unsigned)((row * 64 + 4 * (x ^ row)) * 4); }   // rows 4t+g (< 16): row & 15 = row
@@ -801,7 +353,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
         // X in the auxiliaries kernel's register order (kl_dv_pos): the KiB of piece j of wave w = row group + 4 hh is what wave (row group, hh)
         // of THIS kernel wants in its va[j >> 1][j & 1], lane for lane.  So the pieces travel whole (a contiguous KiB per request instead of
         // 4 rows x 256 B) and stay in that order in the LDS slot: [hh][j][lane] float4s, read back with one conflict-free ds_read_b128 each
-        vbaseA = tile0 + (unsigned long long)((bx % (4 / NRG)) * NRG + lw) * 4096; vbaseB = vbaseA + 16384;
+        vbaseA = tile0 + (unsigned long long)lw * 4096; vbaseB = vbaseA + 16384;
 #pragma unroll
         for (int t = 0; t < 4; ++t) voffs[t] = (unsigned)(t * 1024 + lane * 16);
     }
@@ -828,29 +380,24 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
 #pragma unroll
         for (int i = 0; i < YPW; i += 4)
             dma_run4(ybase, smem0 + yq * YBUF + ydst + i * 1024, yoffs[i], yoffs[i + 1], yoffs[i + 2], yoffs[i + 3]);
-        ybase += ystep; yq = (yq == YR - 1) ? 0 : yq + 1;
+        ybase += 128ll; yq = (yq == YR - 1) ? 0 : yq + 1;
         if (SK && --y_left == 0) ybase -= span_y;
     };
     auto dma_step = [&](int st) {                      // a quarter (V loaders) / half (Y loaders, stages 0 and 1) of a group's requests
         if (yrole) {
             if (st < YPW / 2) dma_run2(ybase, smem0 + yq * YBUF + ydst + st * 2048, yoffs[2 * (st < YPW / 2 ? st : 0)], yoffs[2 * (st < YPW / 2 ? st : 0) + 1]);
-            if (st == YPW / 2 - 1) { ybase += ystep; yq = (yq == YR - 1) ? 0 : yq + 1; }
+            if (st == YPW / 2 - 1) { ybase += 128ll; yq = (yq == YR - 1) ? 0 : yq + 1; }
         } else {
-#ifdef NMFX_EXP_VFRONT         // experiment (r4): the V requests of a group in its first two stages (four pieces each) instead of two per stage
-            if (st == 0) (TEMPORAL ? dma_run4 : dma_run4_nt)(vbaseA, vdstA + vq * VSLOT, voffs[0], voffs[1], voffs[2], voffs[3]);
-            if (st == 1) (TEMPORAL ? dma_run4 : dma_run4_nt)(vbaseB, vdstB + vq * VSLOT, voffs[0], voffs[1], voffs[2], voffs[3]);
-#else
             (TEMPORAL ? dma_run2 : dma_run2_nt)(st < 2 ? vbaseA : vbaseB, (st < 2 ? vdstA : vdstB) + vq * VSLOT + (st & 1) * 2048, voffs[2 * (st & 1)], voffs[2 * (st & 1) + 1]);
-#endif
             if (st == 3) { vbaseA += vstep; vbaseB += vstep; if constexpr (XGATHER) { const long long t_ = vstep; vstep = vstep2; vstep2 = t_; }
-                           vq = (NW == 4) ? vq + 1 - 3 * (vq >> 1) : ((vq == VRING - 1) ? 0 : vq + 1); }
+                           vq = (vq == VRING - 1) ? 0 : vq + 1; }
         }
     };
     auto issue_v = [&]() {      // rows 16..31 of the tile: same lane offsets (row & 15 repeats), base + 16 rows
         (TEMPORAL ? dma_run4 : dma_run4_nt)(vbaseA, vdstA + vq * VSLOT, voffs[0], voffs[1], voffs[2], voffs[3]);
         (TEMPORAL ? dma_run4 : dma_run4_nt)(vbaseB, vdstB + vq * VSLOT, voffs[0], voffs[1], voffs[2], voffs[3]);
         vbaseA += vstep; vbaseB += vstep; if constexpr (XGATHER) { const long long t_ = vstep; vstep = vstep2; vstep2 = t_; }
-        vq = (NW == 4) ? vq + 1 - 3 * (vq >> 1) : ((vq == VRING - 1) ? 0 : vq + 1);
+        vq = (vq == VRING - 1) ? 0 : vq + 1;
         if (SK && --v_left == 0) { vbaseA -= span_v; vbaseB -= span_v; }
     };
 
@@ -884,9 +431,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) accA[t][r] = 0.f;
-    const bool do_gram = KP == 64 && !KL && WITH_A && bx < ng;  // Gram by-product: as in xyt_bf16_kernel (16x16x32 tiles)
-    constexpr int NGT = 16 / NW;                       // Gram tiles (16 x 16) per wave: tile row git, tile columns gj0 .. gj0 + NGT - 1
-    const int git = wave / (4 / NGT), gj0 = NGT * (wave % (4 / NGT));
+    const bool do_gram = KP == 64 && !KL && WITH_A && bx < ng;  // Gram by-product (see the kernel's header)
+    constexpr int NGT = 2;                             // Gram tiles (16 x 16) per wave: tile row git, tile columns gj0 .. gj0 + NGT - 1
+    const int git = wave / 2, gj0 = NGT * (wave % 2);
     f32x4 gacc[NGT];
 #pragma unroll
     for (int c = 0; c < NGT; ++c) gacc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -922,20 +469,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
 #pragma unroll
         for (int s = 0; s < NK; ++s) { pinu(zh[s].u); pinu(zl[s].u); }
     }
-#ifdef NMFX_EXP_FP8D
-    constexpr bool FP8D = WITH_D && !KL && KP == 128 && NPROB == 1 && VMODE == 0 && !(WITH_OBJ && !KL && KP == 64 && WITH_A);
-    fp8_i32x8 z8h[FP8D ? NK / 4 : 1], z8l[FP8D ? NK / 4 : 1], y8h, y8l;
-    if constexpr (FP8D) {
-#pragma unroll
-        for (int q8 = 0; q8 < NK / 4; ++q8)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int a0, a1;
-                frag_to_fp8(zh[4 * q8 + j], 1.f, a0, a1); z8h[q8][2 * j] = a0; z8h[q8][2 * j + 1] = a1;
-                frag_to_fp8(zl[4 * q8 + j], 0.001953125f, a0, a1); z8l[q8][2 * j] = a0; z8l[q8][2 * j + 1] = a1;
-            }
-    }
-#endif
     int ycur = 0, vcur = 0;
 #ifdef NMFX_EXP_STAMPS
     unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, acc_wait = 0, acc_head = 0, acc_early = 0, acc_mfma = 0;
@@ -950,7 +483,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     // the end of its own group it was a serial tail of ~250 cycles -- MFMA result, 16 dependent adds, an f64 add -- with
     // the matrix pipe idle in front of the barrier)
     auto residual = [&](const VRegs& v, double& osum) {
-        if (ABL & 4) { osum += (double)(v.d[0] + v.d[5] + v.va[0][0].x + v.va[1][1].y); return; }
         float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;  // four chains instead of one
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -977,7 +509,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     // requests in its own vmcnt bookkeeping and would put its waits where it believes the loads are the only ones in flight.
     f32x4 vx_cur[2][2], vx_next[2][2];
     float4 vx_s[2][2], vx_d[2][2];
-    auto vaux_tile = [&](int grp) { return ((int64_t)bx * (ldx / 64) + grp) * 8192; };           // floats (NW = 8: one tile per block and group)
+    auto vaux_tile = [&](int grp) { return ((int64_t)bx * (ldx / 64) + grp) * 8192; };           // floats (one tile per block and group)
     // r5: dual_v is only ever touched here and by the transposes between the sub-problems, so inside its 128 x 64 tiles it lives in THIS
     // kernel's register order -- piece j = 2 s + e of wave w, lane l at float4 index (4 w + j) 64 + l (kl_dv_pos below): every load /
     // store instruction of a wave is one contiguous KiB instead of 64 pieces of 16 bytes at a 256-byte stride.  S lies the same way: the
@@ -1029,19 +561,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     auto carried_stage = [&](f32x16& d, bool dma_on) {
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss) {
-            d = MFMA32X(fh[1][ss], zh[WITH_D ? 2 + ss : 0], d);
-#ifndef NMFX_EXP_R2
-            d = MFMA32X(fl[1][ss], zh[WITH_D ? 2 + ss : 0], d);
-#endif
+            d = MFMA32_BF16(fh[1][ss], zh[WITH_D ? 2 + ss : 0], d);
+            d = MFMA32_BF16(fl[1][ss], zh[WITH_D ? 2 + ss : 0], d);
             if (ss == 0) { NMFX_FENCE(); if (dma_on) dma_step(0); NMFX_FENCE(); }
-            d = MFMA32X(fh[1][ss], zl[WITH_D ? 2 + ss : 0], d);
+            d = MFMA32_BF16(fh[1][ss], zl[WITH_D ? 2 + ss : 0], d);
         }
     };
     // one group: `cur` holds V(grp) (PIPE: filled during the previous group), `nxt` receives V(grp + 1) (PIPE)
     auto group = [&](int grp, VRegs& cur, VRegs& nxt) {
         NMFX_STAMP(ts0);
-        if (ABL & 1) { }
-        else if (yrole) dma_wait_le<0>();
+        if (yrole) dma_wait_le<0>();
         else if (VAUX) {                               // steady state: 12 (VRING - 1) loads are younger than V(grp) (see the kernel's VAUX note)
             if (grp >= g0 + VRING && grp + VRING - 1 < g1) dma_wait_le<12 * (VRING - 1)>(); else dma_wait_le<0>();
         }
@@ -1057,7 +586,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
         // PIPE: the next requests -- Y(grp + 1) into the other Y buffer, V(grp + VRING) into the slot of V(grp), which every
         // wave read before this barrier -- go out in pairs BETWEEN the MFMAs of the stages below (dma_step): issued in one
         // burst at the top of the group they cost 500-800 cycles per loader wave with the matrix pipe idle (stamps)
-        const bool dma_on = PIPE && !(ABL & 1) && (yrole ? grp + 1 < g1 : grp + VRING < g1);
+        const bool dma_on = PIPE && (yrole ? grp + 1 < g1 : grp + VRING < g1);
         if (!PIPE && yrole) { if (grp + 1 < g1) issue_y(); }
         if constexpr (VAUX) {
             vaux_load(grp + 1 < g1 ? grp + 1 : grp, vx_next);       // (behind the last group: a harmless reload, so that every group issues the same)
@@ -1067,7 +596,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
         const unsigned char* vt = vring + vcur * VSLOT;
         const unsigned char* vtn = vring + (vcur == VRING - 1 ? 0 : vcur + 1) * VSLOT;
         auto issue = [&](int st, int set) {
-            if ((ABL & 8) && grp > g0 + 1) { pinu(fh[set][0].u); pinu(fh[set][1].u); pinu(fl[set][0].u); pinu(fl[set][1].u); return; }
             if (st < NA) {                             // Y rows (factors) 32 (2 tp + t) + n31, columns of k-step st / NTP
                 const unsigned char* ys = ybuf + yrow[st / NTP] + (st % NTP) * 8192;
 #pragma unroll
@@ -1122,40 +650,24 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
             if (st < NA) {
                 const int ks = st / NTP, t0 = 2 * (st % NTP);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vh[ks], fh[set][t], accA[t0 + t]);
+                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vh[ks], fh[set][t], accA[t0 + t]);
                 if (PIPE) { NMFX_FENCE(); if (dma_on) dma_step(st + 1); NMFX_FENCE(); }
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vl[ks], fh[set][t], accA[t0 + t]);
+                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vl[ks], fh[set][t], accA[t0 + t]);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vh[ks], fl[set][t], accA[t0 + t]);
+                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vh[ks], fl[set][t], accA[t0 + t]);
                 if (TERMS >= 4) {
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vl[ks], fl[set][t], accA[t0 + t]);
+                    for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vl[ks], fl[set][t], accA[t0 + t]);
                 }
             } else if (!(PIPE && st == NS - 1)) {      // (PIPE: the last stage is carried over the barrier)
 #pragma unroll
                 for (int ss = 0; ss < 2; ++ss) {
                     const int s = WITH_D ? 2 * (st - NA) + ss : 0;
-#ifdef NMFX_EXP_FP8D
-                    if constexpr (FP8D) {              // hi hi in bf16; the fragments of four k-steps make one K = 64 operand of each image
-                        d = MFMA32X(fh[set][ss], zh[s], d);
-                        int a0, a1;
-                        frag_to_fp8(fh[set][ss], 1.f, a0, a1); y8h[2 * (s & 3)] = a0; y8h[2 * (s & 3) + 1] = a1;
-                        frag_to_fp8(fl[set][ss], 0.001953125f, a0, a1); y8l[2 * (s & 3)] = a0; y8l[2 * (s & 3) + 1] = a1;
-                        if ((s & 3) == 3) {            // (lo images are stored x 2^9: scale byte 127 - 9)
-                            d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(y8l, z8h[s >> 2], d, 0, 0, 0, 118, 0, 127);
-                            d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(y8h, z8l[s >> 2], d, 0, 0, 0, 127, 0, 118);
-                        }
-                        continue;
-                    }
-#endif
-                    d = MFMA32X(fh[set][ss], zh[s], d);
-#ifndef NMFX_EXP_R2            // experiment (r5): the residual product with TWO terms (Y_lo Z_hi dropped): W phase -11 % (k = 128), -8 % (k = 64);
-                               // recorded objective +1.2e-5 .. +4.3e-4 off nmfx_objective_f64 (three terms: 1.6e-8), jitter 1.5e-6 (7e-9): not shipped, LAB_NOTES R5
-                    d = MFMA32X(fl[set][ss], zh[s], d);
-#endif
+                    d = MFMA32_BF16(fh[set][ss], zh[s], d);
+                    d = MFMA32_BF16(fl[set][ss], zh[s], d);
                     if (PIPE && ss == 0) { NMFX_FENCE(); if (dma_on) dma_step(st + 1); NMFX_FENCE(); }
-                    d = MFMA32X(fh[set][ss], zl[s], d);
+                    d = MFMA32_BF16(fh[set][ss], zl[s], d);
                 }
                 if (NPROB == 2 && st == NA + ND / 2 - 1) {     // factors 0 .. 63 are done: the first problem's residual, then start over
                     residual(cur, osum);
@@ -1173,15 +685,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
                 read_va(vtn, nxt.va);
             }
             if (PIPE) {                                // the bf16 split of V(grp + 1) rides between the MFMAs of stages 1 and 2
-                if (ABL & 2) {
-                    if (st == 1) { nxt.vh[0].u = make_uint4(__float_as_uint(nxt.va[0][0].x), __float_as_uint(nxt.va[0][0].y), __float_as_uint(nxt.va[0][0].z), __float_as_uint(nxt.va[0][0].w));
-                                   nxt.vl[0].u = make_uint4(__float_as_uint(nxt.va[0][1].x), __float_as_uint(nxt.va[0][1].y), __float_as_uint(nxt.va[0][1].z), __float_as_uint(nxt.va[0][1].w)); }
-                    if (st == 2) { nxt.vh[1].u = make_uint4(__float_as_uint(nxt.va[1][0].x), __float_as_uint(nxt.va[1][0].y), __float_as_uint(nxt.va[1][0].z), __float_as_uint(nxt.va[1][0].w));
-                                   nxt.vl[1].u = make_uint4(__float_as_uint(nxt.va[1][1].x), __float_as_uint(nxt.va[1][1].y), __float_as_uint(nxt.va[1][1].z), __float_as_uint(nxt.va[1][1].w)); }
-                } else {
                 if (st == 1) split8(nxt.va[0][0], nxt.va[0][1], nxt.vh[0], nxt.vl[0]);
                 if (st == 2) split8(nxt.va[1][0], nxt.va[1][1], nxt.vh[1], nxt.vl[1]);
-                }
             }
             NMFX_FENCE();
             if (st == NA - 1 && do_gram && ((grp - g0) % ng) == bx) {
@@ -1244,7 +749,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
         acc_wait += ts1 - ts0; acc_head += ts2 - ts1; acc_early += ts3 - ts2; acc_mfma += ts4 - ts3;
 #endif
         ycur ^= 1;
-        vcur = (NW == 4) ? vcur + 1 - 3 * (vcur >> 1) : ((vcur == VRING - 1) ? 0 : vcur + 1);
+        vcur = (vcur == VRING - 1) ? 0 : vcur + 1;
     };
     // ---- KL: product, quotient, product -- software-pipelined across groups ----
     // In its first form (one register set: product Z Y, quotient + split with the matrix pipe idle, second product with the
@@ -1257,13 +762,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
     // per group, the DMA requests in pairs between the MFMAs as in the Euclidean pipeline.  (A second barrier per group that
     // frees the slot of V(g) as soon as every wave holds the tile, with V(g + 3) requested behind it -- three groups in
     // flight instead of two -- measured no faster: W phase 537 vs 524 us, H phase 448 vs 450, tools/lab/ab_phase.py.)
-#ifdef NMFX_EXP_Q1             // experiment (r5): the quotient enters the second product as ONE bf16 image (q_hi Y_hi + q_hi Y_lo):
-                               // config 4 W phase 550 -> 495 us, H phase 466 -> 441 -- and WH against the oracle 5e-7 -> 3.4e-5 .. 6e-5 at contractions of
-                               // 4096 .. 16384, 1.3e-4 at 384 (tools/lab/kl_q1_check.py): half a digit inside north_star's 1e-4.  Not the default, not shipped.
-    constexpr bool Q1 = KL && KP == 64;
-#else
-    constexpr bool Q1 = false;
-#endif
     auto kl_iter = [&](int grp, VRegs& cur, VRegs& prv, auto do_d_t, auto do_a_t) {
         constexpr bool DO_D = decltype(do_d_t)::value, DO_A = decltype(do_a_t)::value;
         const unsigned char* ybuf = smem + ycur * YBUF;                              // Y(grp)
@@ -1346,7 +844,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
             else dma_wait_le<0>();
             __syncthreads();
             NMFX_STAMP(ts1);
-            dma_on = !(ABL & 1) && (yrole ? grp + 1 < g1 : grp + 2 < g1);
+            dma_on = yrole ? grp + 1 < g1 : grp + 2 < g1;
             f32x16& d = cur.d;
             cur.slow = 0u;
             read_va(vring + vcur * VSLOT, cur.va);
@@ -1360,14 +858,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
 #pragma unroll
                 for (int ss = 0; ss < 2; ++ss) {
                     const int s = 2 * half + ss;
-                    d = MFMA32X(fh[half][ss], zh[WITH_D ? s : 0], d);
-                    d = MFMA32X(fl[half][ss], zh[WITH_D ? s : 0], d);
+                    d = MFMA32_BF16(fh[half][ss], zh[WITH_D ? s : 0], d);
+                    d = MFMA32_BF16(fl[half][ss], zh[WITH_D ? s : 0], d);
                     NMFX_FENCE();
                     if (dma_on) dma_step(s);
                     if (DO_A && WITH_OBJ) kl_chunk(s);
                     NMFX_FENCE();
-                    d = MFMA32X(fh[half][ss], zl[WITH_D ? s : 0], d);
-                    if (TERMS >= 4) d = MFMA32X(fl[half][ss], zl[WITH_D ? s : 0], d);
+                    d = MFMA32_BF16(fh[half][ss], zl[WITH_D ? s : 0], d);
+                    if (TERMS >= 4) d = MFMA32_BF16(fl[half][ss], zl[WITH_D ? s : 0], d);
                 }
                 NMFX_FENCE();
                 if (DO_A) issue_a(half, half);         // (behind the MFMAs that read this register set)
@@ -1383,32 +881,30 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t] = MFMA32X(prv.vh[ks], fh[ks][t], accA[t]);
+                for (int t = 0; t < 2; ++t) accA[t] = MFMA32_BF16(prv.vh[ks], fh[ks][t], accA[t]);
                 NMFX_FENCE();
                 if (DO_D) quot(2 * ks); else if (WITH_OBJ) kl_chunk(2 * ks);
                 NMFX_FENCE();
-                if (!Q1) {
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) accA[t] = MFMA32X(prv.vl[ks], fh[ks][t], accA[t]);
-                }
+                for (int t = 0; t < 2; ++t) accA[t] = MFMA32_BF16(prv.vl[ks], fh[ks][t], accA[t]);
                 NMFX_FENCE();
                 if (DO_D) quot(2 * ks + 1); else if (WITH_OBJ) kl_chunk(2 * ks + 1);
                 NMFX_FENCE();
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t] = MFMA32X(prv.vh[ks], fl[ks][t], accA[t]);
+                for (int t = 0; t < 2; ++t) accA[t] = MFMA32_BF16(prv.vh[ks], fl[ks][t], accA[t]);
                 if (TERMS >= 4) {
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) accA[t] = MFMA32X(prv.vl[ks], fl[ks][t], accA[t]);
+                    for (int t = 0; t < 2; ++t) accA[t] = MFMA32_BF16(prv.vl[ks], fl[ks][t], accA[t]);
                 }
                 NMFX_FENCE();
-                if (DO_D) { if (Q1) hi8(qa[ks][0], qa[ks][1], cur.vh[ks]); else split8(qa[ks][0], qa[ks][1], cur.vh[ks], cur.vl[ks]); }
+                if (DO_D) split8(qa[ks][0], qa[ks][1], cur.vh[ks], cur.vl[ks]);
                 NMFX_FENCE();
             }
         } else {
 #pragma unroll
             for (int a = 0; a < 4; ++a) quot(a);
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) { if (Q1) hi8(qa[s2][0], qa[s2][1], cur.vh[s2]); else split8(qa[s2][0], qa[s2][1], cur.vh[s2], cur.vl[s2]); }
+            for (int s2 = 0; s2 < 2; ++s2) split8(qa[s2][0], qa[s2][1], cur.vh[s2], cur.vl[s2]);
         }
         if (WITH_OBJ) {
             if (DO_A) olog += (double)klog;
@@ -1421,7 +917,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
 #endif
         if (DO_D) {
             ycur = (ycur == YR - 1) ? 0 : ycur + 1;
-            vcur = (NW == 4) ? vcur + 1 - 3 * (vcur >> 1) : ((vcur == VRING - 1) ? 0 : vcur + 1);
+            vcur = (vcur == VRING - 1) ? 0 : vcur + 1;
         }
     };
     // ---- KL with KP = 128 (r3; MUR-KL at k = 128 ran the 16-row kernel before): one register set, no cross-group pipeline -- as for the
@@ -1492,10 +988,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
 #pragma unroll
                 for (int ss = 0; ss < 2; ++ss) {
                     const int s = 2 * u + ss;
-                    d = MFMA32X(fh[set][ss], zh[WITH_D ? s : 0], d);
-                    d = MFMA32X(fl[set][ss], zh[WITH_D ? s : 0], d);
-                    d = MFMA32X(fh[set][ss], zl[WITH_D ? s : 0], d);
-                    if (TERMS >= 4 && !VAUXF) d = MFMA32X(fl[set][ss], zl[WITH_D ? s : 0], d);   // (VAUXF: P = Z Y with three terms, as the separate auxiliaries launch forms it)
+                    d = MFMA32_BF16(fh[set][ss], zh[WITH_D ? s : 0], d);
+                    d = MFMA32_BF16(fl[set][ss], zh[WITH_D ? s : 0], d);
+                    d = MFMA32_BF16(fh[set][ss], zl[WITH_D ? s : 0], d);
+                    if (TERMS >= 4 && !VAUXF) d = MFMA32_BF16(fl[set][ss], zl[WITH_D ? s : 0], d);   // (VAUXF: P = Z Y with three terms, as the separate auxiliaries launch forms it)
                 }
                 if (VAUXF && u == NDK - 1) {           // v_aux, dual_v, S where the accumulator stands; S split as the second product's A operand
                     NMFX_FENCE();
@@ -1563,21 +1059,21 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
             } else {
                 const int st = u - NDK, ks = st / NTP, t0 = 2 * (st % NTP);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vh[ks], fh[set][t], accA[t0 + t]);
+                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vh[ks], fh[set][t], accA[t0 + t]);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vl[ks], fh[set][t], accA[t0 + t]);
+                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vl[ks], fh[set][t], accA[t0 + t]);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vh[ks], fl[set][t], accA[t0 + t]);
+                for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vh[ks], fl[set][t], accA[t0 + t]);
                 if (TERMS >= 4) {
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32X(cur.vl[ks], fl[set][t], accA[t0 + t]);
+                    for (int t = 0; t < 2; ++t) accA[t0 + t] = MFMA32_BF16(cur.vl[ks], fl[set][t], accA[t0 + t]);
                 }
             }
             NMFX_FENCE();
         }
         if (WITH_OBJ) { olog += (double)klog; osum += (double)(klin2.x + klin2.y); }
         ycur ^= 1;
-        vcur = (NW == 4) ? vcur + 1 - 3 * (vcur >> 1) : ((vcur == VRING - 1) ? 0 : vcur + 1);
+        vcur = (vcur == VRING - 1) ? 0 : vcur + 1;
     };
     VRegs P, Q;
     if (PIPE) {
@@ -1677,7 +1173,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xyt32_bf16_kernel(
         __syncthreads();
         if (tid == 0) {
             double t = 0.0;
-            for (int w = 0; w < NW; ++w) t += red[w];
+            for (int w = 0; w < 8; ++w) t += red[w];
             objpart[oidx] = ((KL || KLOBJ) ? 1.0 : 0.5) * t;
         }
         if (NPROB == 2) {
@@ -2333,100 +1829,22 @@ static int lazy_alloc(nmfx_engine* E, T** p, int64_t count) {
 
 bool nmfx_bf16_supported(const nmfx_engine* E) { return (E->kp == 64 || E->kp == 128) && E->mp % 128 == 0 && E->np % 128 == 0; }
 
-template <int KP, bool OBJ, bool KL, int TERMS, bool WITH_A = true>
-static int launch_xyt_t(nmfx_engine* E, const float* X, bool tiled, int64_t ldx, int64_t R, int ngroups, int splits,
-                        const unsigned short* Yhi, const unsigned short* Ylo, int64_t ldy, const unsigned short* Zhi,
-                        const unsigned short* Zlo, float* Apart, float* gram_part, int ng) {
-    dim3 grid((unsigned)(R / 128), (unsigned)splits), block(512);
-    const size_t shm = 160 * 1024;                                       // Y double buffer + V rings
-    auto kern = xyt_bf16_kernel<KP, OBJ, KL, TERMS, WITH_A>;
-    { int rc_ = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc_) return rc_; }
-    hipLaunchKernelGGL(kern, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldy, Zhi, Zlo, Apart, E->obj_part,
-                       gram_part, R, ngroups, &E->state->flag, tiled ? 1 : 0, ng);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-
-static bool nmfx_kl_nw4() {
-#ifdef NMFX_EXP_KLNW4
-    static const bool on = getenv("NMFX_KL_NW4") && atoi(getenv("NMFX_KL_NW4")) == 1;
-    return on;
-#else
-    return false;
-#endif
-}
 template <bool OBJ, int TERMS, bool KL = false, int KP = 64, bool WITH_A = true>
 static int launch_xyt32_t(nmfx_engine* E, const float* X, int64_t ldx, int64_t R, int ngroups, int splits,
                           const unsigned short* Yhi, const unsigned short* Ylo, int64_t ldy, const unsigned short* Zhi,
                           const unsigned short* Zlo, float* Apart, float* gram_part, int ng) {
-    dim3 grid((unsigned)(R / 128), (unsigned)splits), block(512);
-    size_t shm = 160 * 1024;
-    auto kern = xyt32_bf16_kernel<OBJ, TERMS, 0, KL, KP, 1, false, WITH_A>;
-    if constexpr (!KL && KP == 64 && TERMS == 3 && WITH_A) {
-        if (E->xyt_nw == 4) {      // four-wave blocks of 64 rows, two resident per CU (see the kernel's NW note)
-            grid = dim3((unsigned)(R / 64), (unsigned)splits); block = dim3(256); shm = 80 * 1024;
-            static const int forced = getenv("NMFX_TEMPORAL") ? atoi(getenv("NMFX_TEMPORAL")) : -1;
-            const bool small = 2.0 * (double)E->mp * (double)E->np * 4.0 <= 192.0 * 1024 * 1024;
-            auto k4 = (forced == 1 || (forced < 0 && small)) ? xyt32_bf16_kernel<OBJ, TERMS, 0, KL, KP, 1, true, WITH_A, 4>
-                                                             : xyt32_bf16_kernel<OBJ, TERMS, 0, KL, KP, 1, false, WITH_A, 4>;
-            int rc4 = nmfx_allow_lds(E, reinterpret_cast<const void*>(k4), (int)shm); if (rc4) return rc4;
-            hipLaunchKernelGGL(k4, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldy, Zhi, Zlo, Apart, E->obj_part,
-                               gram_part, R, ngroups, &E->state->flag, ng, (const int4*)nullptr, (const int*)nullptr, 0, XytSide(), (float*)nullptr, (float*)nullptr, E->xyt_flag2, E->xyt_xpriv);
-            NMFX_HIP(hipGetLastError());
-            return NMFX_OK;
-        }
-    }
-#ifdef NMFX_EXP_KLNW4          // experiment (r5): MUR-KL at k padded to 64 in FOUR-wave blocks of 64 rows, two per CU, in the one-register-set
-                               // form (80 KiB of LDS each: Y double buffer + V ring of 3) -- the two waves of a SIMD then belong to different workgroups, no
-                               // barrier ties them, one's VALU sections can meet the other's MFMAs.  Correct (the KL tests pass with NMFX_KL_NW4=1) and
-                               // SLOWER than the eight-wave cross-group pipeline: config 4 W phase 538 -> 588 us, H phase 414-430 -> 474-479
-                               // (profiles/r05_kl_four_wave_blocks_experiment.txt).  Not built by default.
-    if constexpr (KL && KP == 64 && TERMS == 3 && WITH_A) {
-        if (nmfx_kl_nw4()) {
-            grid = dim3((unsigned)(R / 64), (unsigned)splits); block = dim3(256); shm = 80 * 1024;
-            auto k4 = xyt32_bf16_kernel<OBJ, TERMS, 0, KL, KP, 1, false, WITH_A, 4>;
-            int rc4 = nmfx_allow_lds(E, reinterpret_cast<const void*>(k4), (int)shm); if (rc4) return rc4;
-            hipLaunchKernelGGL(k4, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldy, Zhi, Zlo, Apart, E->obj_part,
-                               gram_part, R, ngroups, &E->state->flag, ng, (const int4*)nullptr, (const int*)nullptr, 0, XytSide(), (float*)nullptr, (float*)nullptr, E->xyt_flag2, 0);
-            NMFX_HIP(hipGetLastError());
-            return NMFX_OK;
-        }
-    }
-#endif
+    const dim3 grid((unsigned)(R / 128), (unsigned)splits), block(512);
+    const size_t shm = 160 * 1024;
+    auto kern = xyt32_bf16_kernel<OBJ, TERMS, KL, KP, 1, false, WITH_A>;
     if constexpr (!KL && KP == 64 && TERMS == 3) {
         // V and V^T together small enough to live in the Infinity Cache (see the kernel's TEMPORAL note; NMFX_TEMPORAL=0/1 overrides)
         static const int forced = getenv("NMFX_TEMPORAL") ? atoi(getenv("NMFX_TEMPORAL")) : -1;
         const bool small = 2.0 * (double)E->mp * (double)E->np * 4.0 <= 192.0 * 1024 * 1024;
-        if (forced == 1 || (forced < 0 && small)) kern = xyt32_bf16_kernel<OBJ, TERMS, 0, KL, KP, 1, true, WITH_A>;
+        if (forced == 1 || (forced < 0 && small)) kern = xyt32_bf16_kernel<OBJ, TERMS, KL, KP, 1, true, WITH_A>;
     }
     if constexpr (OBJ && !KL && KP == 128 && TERMS == 3 && WITH_A) {
-        if (E->pair) kern = xyt32_bf16_kernel<OBJ, TERMS, 0, KL, KP, 2>;     // two stacked problems: one objective each
+        if (E->pair) kern = xyt32_bf16_kernel<OBJ, TERMS, KL, KP, 2>;     // two stacked problems: one objective each
     }
-#ifdef NMFX_EXP_ABLATE
-    if constexpr (TERMS == 3 && KL && KP == 64) {
-        static const int abl = getenv("NMFX_ABLATE") ? atoi(getenv("NMFX_ABLATE")) : 0;
-        switch (abl) {
-            case 1: kern = xyt32_bf16_kernel<OBJ, TERMS, 1, KL, KP>; break;
-            case 16: kern = xyt32_bf16_kernel<OBJ, TERMS, 16, KL, KP>; break;
-            case 17: kern = xyt32_bf16_kernel<OBJ, TERMS, 17, KL, KP>; break;
-            default: break;
-        }
-    }
-    if (OBJ && TERMS == 3 && !KL && KP == 64) {
-        static const int abl = getenv("NMFX_ABLATE") ? atoi(getenv("NMFX_ABLATE")) : 0;
-        switch (abl) {
-            case 1: kern = xyt32_bf16_kernel<OBJ, TERMS, 1>; break;
-            case 2: kern = xyt32_bf16_kernel<OBJ, TERMS, 2>; break;
-            case 4: kern = xyt32_bf16_kernel<OBJ, TERMS, 4>; break;
-            case 8: kern = xyt32_bf16_kernel<OBJ, TERMS, 8>; break;
-            case 16: kern = xyt32_bf16_kernel<OBJ, TERMS, 16>; break;
-            case 6: kern = xyt32_bf16_kernel<OBJ, TERMS, 6>; break;
-            case 17: kern = xyt32_bf16_kernel<OBJ, TERMS, 17>; break;
-            case 30: kern = xyt32_bf16_kernel<OBJ, TERMS, 30>; break;
-            default: break;
-        }
-    }
-#endif
     int rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc) return rc;
     hipLaunchKernelGGL(kern, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldy, Zhi, Zlo, Apart, E->obj_part,
                        gram_part, R, ngroups, &E->state->flag, ng, (const int4*)nullptr, (const int*)nullptr, 0, XytSide(), (float*)nullptr, (float*)nullptr, E->xyt_flag2, E->xyt_xpriv);
@@ -2434,74 +1852,37 @@ static int launch_xyt32_t(nmfx_engine* E, const float* X, int64_t ldx, int64_t R
     return NMFX_OK;
 }
 
-static int launch_xyt(nmfx_engine* E, bool obj, const float* X, bool tiled, int64_t ldx, int64_t R, int ngroups, int splits,
+// the product launch at E->kp = 64 or 128 with `terms` (3 or 4) terms, with or without the objective; X tile-major
+static int launch_xyt(nmfx_engine* E, bool obj, const float* X, int64_t ldx, int64_t R, int ngroups, int splits,
                       const unsigned short* Yhi, const unsigned short* Ylo, int64_t ldy, const unsigned short* Zhi,
                       const unsigned short* Zlo, float* Apart, float* gram_part, const char* name, bool kl = false,
                       int ng = 1, int terms = 4) {
     static const bool force4 = getenv("NMFX_BF16_TERMS") && atoi(getenv("NMFX_BF16_TERMS")) == 4;
     if (force4) terms = 4;
     ProfScope ps(E, name);
-    const bool nw4 = E->xyt_nw == 4 && E->kp == 64 && !kl && tiled && gram_part && Apart && terms == 3 &&
-                     !(getenv("NMFX_XYT16") && atoi(getenv("NMFX_XYT16")) == 1);
-    if (!nw4) E->xyt_nw = 8;
-    const bool klnw4 = kl && tiled && E->kp == 64 && terms == 3 && nmfx_kl_nw4() && !(getenv("NMFX_XYT16") && atoi(getenv("NMFX_XYT16")) == 1);
-    if (obj) E->obj_count = (R / ((nw4 || klnw4) ? 64 : 128)) * splits;
-#define NMFX_XYT2(KP_, OBJ_, KL_, T_) \
-    launch_xyt_t<KP_, OBJ_, KL_, T_>(E, X, tiled, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, gram_part, ng)
-#define NMFX_XYT(KP_, OBJ_, KL_) (terms == 3 ? NMFX_XYT2(KP_, OBJ_, KL_, 3) : NMFX_XYT2(KP_, OBJ_, KL_, 4))
+    if (obj) E->obj_count = (R / 128) * splits;
+    auto run = [&](auto kl_t, auto kp_t, float* gram) {
+        constexpr bool KL = decltype(kl_t)::value;
+        constexpr int KP = decltype(kp_t)::value;
+        if (terms == 3)
+            return obj ? launch_xyt32_t<true, 3, KL, KP>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, gram, ng)
+                       : launch_xyt32_t<false, 3, KL, KP>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, gram, ng);
+        return obj ? launch_xyt32_t<true, 4, KL, KP>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, gram, ng)
+                   : launch_xyt32_t<false, 4, KL, KP>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, gram, ng);
+    };
+    using K64 = std::integral_constant<int, 64>;
+    using K128 = std::integral_constant<int, 128>;
     if (!Apart) {                                      // objective only (Euclidean; three terms: nothing is fed back from it)
         if (!obj || kl) { E->err = "xyt: a launch without the A-product must compute the Euclidean objective"; return NMFX_E_ARG; }
-        static const bool rows16o = getenv("NMFX_XYT16") && atoi(getenv("NMFX_XYT16")) == 1;
-        if (tiled && !rows16o) {                       // the 32-row kernel without its A stages (r3)
-            if (E->kp == 64) return launch_xyt32_t<true, 3, false, 64, false>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, nullptr, nullptr, ng);
-            return launch_xyt32_t<true, 3, false, 128, false>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, nullptr, nullptr, ng);
-        }
-        if (E->kp == 64)
-            return launch_xyt_t<64, true, false, 3, false>(E, X, tiled, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, nullptr, nullptr, ng);
-        return launch_xyt_t<128, true, false, 3, false>(E, X, tiled, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, nullptr, nullptr, ng);
+        if (E->kp == 64) return launch_xyt32_t<true, 3, false, 64, false>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, nullptr, nullptr, ng);
+        return launch_xyt32_t<true, 3, false, 128, false>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, nullptr, nullptr, ng);
     }
-    if (E->kp == 64) {
-        // k padded to 64: the 32-row kernel (NMFX_XYT16=1 keeps the 16-row form, for A/B runs)
-        static const bool rows16_env = getenv("NMFX_XYT16") && atoi(getenv("NMFX_XYT16")) == 1;
-        const bool rows16 = rows16_env && !E->xyt_xpriv;      // (an X in the auxiliaries' register order is only read by the 32-row kernel)
-        if (kl && tiled && !rows16) {
-#define NMFX_X32K(OBJ_, T_) launch_xyt32_t<OBJ_, T_, true>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, nullptr, ng)
-            if (terms == 3) return obj ? NMFX_X32K(true, 3) : NMFX_X32K(false, 3);
-            return obj ? NMFX_X32K(true, 4) : NMFX_X32K(false, 4);
-#undef NMFX_X32K
-        }
-        if (kl) return obj ? NMFX_XYT(64, true, true) : NMFX_XYT(64, false, true);
-        if (tiled && gram_part && !rows16) {
-#define NMFX_X32(OBJ_, T_) launch_xyt32_t<OBJ_, T_>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, gram_part, ng)
-            if (terms == 3) return obj ? NMFX_X32(true, 3) : NMFX_X32(false, 3);
-            return obj ? NMFX_X32(true, 4) : NMFX_X32(false, 4);
-#undef NMFX_X32
-        }
-        return obj ? NMFX_XYT(64, true, false) : NMFX_XYT(64, false, false);
+    if (kl) return E->kp == 64 ? run(std::true_type(), K64(), nullptr) : run(std::true_type(), K128(), nullptr);
+    if (E->kp == 64) {                                 // (the Gram by-product is part of the k = 64 Euclidean products)
+        if (!gram_part) { E->err = "xyt: the k = 64 Euclidean products need a Gram buffer"; return NMFX_E_ARG; }
+        return run(std::false_type(), K64(), gram_part);
     }
-    if (kl) {      // MUR-KL at k padded to 128: the 32-row kernel as well (r3; NMFX_XYT16=1: the 16-row form)
-        static const bool rows16k = getenv("NMFX_XYT16") && atoi(getenv("NMFX_XYT16")) == 1;
-        if (tiled && !rows16k) {
-#define NMFX_X32KB(OBJ_, T_) launch_xyt32_t<OBJ_, T_, true, 128>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, nullptr, ng)
-            if (terms == 3) return obj ? NMFX_X32KB(true, 3) : NMFX_X32KB(false, 3);
-            return obj ? NMFX_X32KB(true, 4) : NMFX_X32KB(false, 4);
-#undef NMFX_X32KB
-        }
-        return obj ? NMFX_XYT(128, true, true) : NMFX_XYT(128, false, true);
-    }
-    {   // Euclidean products with k padded to 128: the 32-row kernel as well (NMFX_XYT16=1: the 16-row form)
-        static const bool rows16_env = getenv("NMFX_XYT16") && atoi(getenv("NMFX_XYT16")) == 1;
-        const bool rows16 = rows16_env && !E->xyt_xpriv;
-        if (tiled && !rows16) {
-#define NMFX_X32B(OBJ_, T_) launch_xyt32_t<OBJ_, T_, false, 128>(E, X, ldx, R, ngroups, splits, Yhi, Ylo, ldy, Zhi, Zlo, Apart, nullptr, ng)
-            if (terms == 3) return obj ? NMFX_X32B(true, 3) : NMFX_X32B(false, 3);
-            return obj ? NMFX_X32B(true, 4) : NMFX_X32B(false, 4);
-#undef NMFX_X32B
-        }
-    }
-    return obj ? NMFX_XYT(128, true, false) : NMFX_XYT(128, false, false);
-#undef NMFX_XYT2
-#undef NMFX_XYT
+    return run(std::false_type(), K128(), nullptr);
 }
 
 static int kl_part_alloc(nmfx_engine* E) {
@@ -2610,7 +1991,7 @@ int nmfx_bf16_images_h(nmfx_engine* E, bool transposed, const float* src) {   //
 // kl: A_part = (V / (W H + 1e-9)) H^T and the KL objective (the W images `zbuf` are then always read)
 int nmfx_bf16_vht(nmfx_engine* E, bool obj, int zbuf, const char* name, bool kl, int terms) {
     const bool z = obj || kl;
-    return launch_xyt(E, obj, E->Vtile, true, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
+    return launch_xyt(E, obj, E->Vtile, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
                       z ? E->Whi[zbuf] : nullptr, z ? E->Wlo[zbuf] : nullptr, E->A_part,
                       E->kp == 64 ? E->HHt_part : nullptr, name, kl, E->gram_ng_w, terms);
 }
@@ -2619,13 +2000,13 @@ int nmfx_bf16_vht(nmfx_engine* E, bool obj, int zbuf, const char* name, bool kl,
 // kl: Bt_part = (V / (W H + 1e-9))^T W
 // obj_part[(mp/128) * bf_wsplit] = residual objective of (W images `zbuf`, H images): one pass over V, no product output
 int nmfx_bf16_objective(nmfx_engine* E, int zbuf, const char* name) {
-    return launch_xyt(E, true, E->Vtile, true, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
+    return launch_xyt(E, true, E->Vtile, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
                       E->Whi[zbuf], E->Wlo[zbuf], nullptr, nullptr, name);
 }
 
 int nmfx_bf16_vtw(nmfx_engine* E, bool obj, const char* name, bool kl, int terms) {
     const bool z = obj || kl;
-    return launch_xyt(E, obj, E->Vt, true, E->mp, E->np, (int)(E->mp / 64), E->bt_split, E->WThi, E->WTlo, E->mp,
+    return launch_xyt(E, obj, E->Vt, E->mp, E->np, (int)(E->mp / 64), E->bt_split, E->WThi, E->WTlo, E->mp,
                       z ? E->HThi : nullptr, z ? E->HTlo : nullptr, E->Bt_part,
                       E->kp == 64 ? E->G_part : nullptr, name, kl, E->gram_ng_h, terms);
 }
@@ -2684,8 +2065,8 @@ int nmfx_bf16_vaux(nmfx_engine* E, int side, const int* flag2) {
     if (!E->kl_S[side] || !Zhi) { E->err = "vaux: state or images missing"; return NMFX_E_STATE; }
     const dim3 grid((unsigned)(R / 128), (unsigned)splits), block(512);
     const size_t shm = 160 * 1024;
-    auto k64 = xyt32_bf16_kernel<true, 3, 0, false, 64, 1, false, false, 8, false, 1>;
-    auto k128 = xyt32_bf16_kernel<true, 3, 0, false, 128, 1, false, false, 8, false, 1>;
+    auto k64 = xyt32_bf16_kernel<true, 3, false, 64, 1, false, false, false, 1>;
+    auto k128 = xyt32_bf16_kernel<true, 3, false, 128, 1, false, false, false, 1>;
     auto kern = E->kp == 64 ? k64 : k128;
     int rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc) return rc;
     hipLaunchKernelGGL(kern, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldx, Zhi, Zlo, (float*)nullptr, E->obj_part, (float*)nullptr, R,
@@ -2710,8 +2091,8 @@ int nmfx_bf16_vaux_fused(nmfx_engine* E, int side, const int* flag2, const doubl
     if (!E->kl_S[side] || !Zhi || !Apart) { E->err = "vaux_fused: state, images or slabs missing"; return NMFX_E_STATE; }
     const dim3 grid((unsigned)(R / 128), (unsigned)splits), block(512);
     const size_t shm = 160 * 1024;
-    auto k64 = xyt32_bf16_kernel<false, 4, 0, true, 64, 1, false, true, 8, false, 3>;
-    auto k128 = xyt32_bf16_kernel<false, 4, 0, true, 128, 1, false, true, 8, false, 3>;
+    auto k64 = xyt32_bf16_kernel<false, 4, true, 64, 1, false, true, false, 3>;
+    auto k128 = xyt32_bf16_kernel<false, 4, true, 128, 1, false, true, false, 3>;
     auto kern = E->kp == 64 ? k64 : k128;
     int rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc) return rc;
     hipLaunchKernelGGL(kern, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldx, Zhi, Zlo, Apart, const_cast<double*>(nrm), (float*)nullptr, R,
@@ -2725,8 +2106,8 @@ int nmfx_bf16_kl_objective(nmfx_engine* E) {
     ProfScope ps(E, "objective");
     const dim3 grid((unsigned)(E->mp / 128), (unsigned)E->bf_wsplit), block(512);
     const size_t shm = 160 * 1024;
-    auto k64 = xyt32_bf16_kernel<true, 3, 0, false, 64, 1, false, false, 8, false, 2>;
-    auto k128 = xyt32_bf16_kernel<true, 3, 0, false, 128, 1, false, false, 8, false, 2>;
+    auto k64 = xyt32_bf16_kernel<true, 3, false, 64, 1, false, false, false, 2>;
+    auto k128 = xyt32_bf16_kernel<true, 3, false, 128, 1, false, false, false, 2>;
     auto kern = E->kp == 64 ? k64 : k128;
     int rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc) return rc;
     E->obj_count = (E->mp / 128) * E->bf_wsplit;
@@ -2754,11 +2135,10 @@ int nmfx_bf16_kl_product(nmfx_engine* E, int side, int terms, const int* flag2, 
     const char* name = side == 0 ? "hphase" : "wphase_noobj";
     if (gather && terms == 4) {                        // the launch launch_xyt would make for these arguments, in the XGATHER form of the kernel
         ProfScope ps(E, name);
-        E->xyt_nw = 8;
         const dim3 grid((unsigned)(R / 128), (unsigned)splits), block(512);
         const size_t shm = 160 * 1024;
-        auto k64 = xyt32_bf16_kernel<false, 4, 0, false, 64, 1, false, true, 8, false, 4>;
-        auto k128 = xyt32_bf16_kernel<false, 4, 0, false, 128, 1, false, true, 8, false, 4>;
+        auto k64 = xyt32_bf16_kernel<false, 4, false, 64, 1, false, true, false, 4>;
+        auto k128 = xyt32_bf16_kernel<false, 4, false, 128, 1, false, true, false, 4>;
         auto kern = E->kp == 64 ? k64 : k128;
         int rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc) return rc;
         hipLaunchKernelGGL(kern, grid, block, shm, E->stream, S, ldx, Yhi, Ylo, ldx, (const unsigned short*)nullptr, (const unsigned short*)nullptr, Apart, E->obj_part,
@@ -2769,7 +2149,7 @@ int nmfx_bf16_kl_product(nmfx_engine* E, int side, int terms, const int* flag2, 
     }
     if (gather) { E->err = "kl_product: the gathered form is built for four terms"; return NMFX_E_ARG; }
     E->xyt_xpriv = 1;                                  // S lies in the auxiliaries kernel's register order (r5)
-    const int rc = launch_xyt(E, false, S, true, ldx, R, (int)(ldx / 64), splits, Yhi, Ylo, ldx, nullptr, nullptr, Apart, gram, name, false, ng, terms);
+    const int rc = launch_xyt(E, false, S, ldx, R, (int)(ldx / 64), splits, Yhi, Ylo, ldx, nullptr, nullptr, Apart, gram, name, false, ng, terms);
     E->xyt_xpriv = 0;
     return rc;
 }
@@ -2951,8 +2331,8 @@ int nmfx_bf16_sk_product(nmfx_engine* E, int side, bool obj, const float* gsrc, 
     job.defer = side == 0 ? 1 : 0;
     const dim3 grid((unsigned)(P.workers + (gsrc ? 1 : 0))), block(512);
     const size_t shm = 160 * 1024;
-    auto kern = obj ? xyt32_bf16_kernel<true, 3, 0, false, 128, 1, false, true, 8, true>
-                    : xyt32_bf16_kernel<false, 3, 0, false, 128, 1, false, true, 8, true>;
+    auto kern = obj ? xyt32_bf16_kernel<true, 3, false, 128, 1, false, true, true>
+                    : xyt32_bf16_kernel<false, 3, false, 128, 1, false, true, true>;
     if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm))) return rc;
     if (obj) E->obj_count = P.nseg;
     hipLaunchKernelGGL(kern, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldx, Zhi, Zlo, P.slabs, E->obj_part,
@@ -3205,18 +2585,13 @@ int nmfx_mur_eu_phase_a_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
     const float* Wold = E->W[cur];
     float* Wnew = E->W[nxt];
     // W phase: A = V H^T, residual objective of (W_j, H_j), and H H^T as a by-product
-    static const int nw4 = getenv("NMFX_NW4") ? atoi(getenv("NMFX_NW4")) : 0;      // bit 0: W phase, bit 1: H phase on four-wave blocks
-    E->xyt_nw = (nw4 & 1) ? 4 : 8;
-    rc = launch_xyt(E, true, E->Vtile, true, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
+    rc = launch_xyt(E, true, E->Vtile, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
                     E->Whi[cur], E->Wlo[cur], E->A_part, E->HHt_part, "wphase", false, E->gram_ng_w, 3);
-    E->xyt_nw = 8;
     if (rc) return rc;
     if ((rc = launch_w_update_bf16<64>(E, Wold, Wnew, nxt, E->HHt_part, nmfx_bf16_hht_slabs(E), (float)lambda_w))) return rc;
     // H phase: B^T = V^T W_new, and W_new^T W_new as a by-product
-    E->xyt_nw = (nw4 & 2) ? 4 : 8;
-    rc = launch_xyt(E, false, E->Vt, true, E->mp, E->np, (int)(E->mp / 64), E->bt_split, E->WThi, E->WTlo, E->mp,
+    rc = launch_xyt(E, false, E->Vt, E->mp, E->np, (int)(E->mp / 64), E->bt_split, E->WThi, E->WTlo, E->mp,
                     nullptr, nullptr, E->Bt_part, E->G_part, "hphase", false, E->gram_ng_h, 3);
-    E->xyt_nw = 8;
     if (rc) return rc;
     if (E->fused_pack) return NMFX_OK;          // single GPU: h_update reads the slabs itself
     return nmfx_launch_pack_from(E, E->Bt_part, E->bt_split, E->G_part, nmfx_bf16_g_slabs(E), E->obj_count);
@@ -3313,7 +2688,7 @@ int nmfx_mur_eu_phase_a_head_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
         E->chunk_gslabs = E->gsplit;
         return nmfx_bf16_gram_tn(E, &E->chunk_gslabs);
     }
-    if ((rc = launch_xyt(E, true, E->Vtile, true, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
+    if ((rc = launch_xyt(E, true, E->Vtile, E->np, E->mp, (int)(E->np / 64), E->bf_wsplit, E->Hhi, E->Hlo, E->np,
                          E->Whi[cur], E->Wlo[cur], E->A_part, E->HHt_part, "wphase", false, E->gram_ng_w, 3))) return rc;
     return launch_w_update_bf16<64>(E, E->W[cur], E->W[nxt], nxt, E->HHt_part, nmfx_bf16_hht_slabs(E), (float)lambda_w);
 }
@@ -3335,7 +2710,7 @@ int nmfx_mur_eu_phase_a_cols_bf16(nmfx_engine* E, int64_t c0, int64_t c1) {
     }
     const float* X = E->Vt + (c0 / 128) * mgroups * 8192;             // tile-major V^T: row block c0 / 128
     const int ng = (E->kp == 64 && c0 == 0) ? (int)std::min<int64_t>(E->gram_ng_h, rblocks) : 0;
-    if ((rc = launch_xyt(E, false, X, true, E->mp, R, (int)mgroups, (int)S, E->WThi, E->WTlo, E->mp, nullptr, nullptr,
+    if ((rc = launch_xyt(E, false, X, E->mp, R, (int)mgroups, (int)S, E->WThi, E->WTlo, E->mp, nullptr, nullptr,
                          E->Bt_chunk, E->kp == 64 ? E->G_part : nullptr, "hphase", false, ng, 3))) return rc;
     if (E->kp == 64 && c0 == 0) E->chunk_gslabs = ng * (int)S;
     ProfScope ps(E, "pack");

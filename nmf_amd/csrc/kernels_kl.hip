@@ -295,7 +295,7 @@ int nmfx_mur_kl_phase_b(nmfx_engine* E, double lambda_h, int64_t min_iter, doubl
 }
 
 // ---- split-bf16 products (kp = 64 / 128): the two quotient products of an iteration on the bf16
-// MFMA (xyt_bf16_kernel<.., KL = true>), everything else as above ----
+// MFMA (xyt32_bf16_kernel<.., KL = true>), everything else as above ----
 // part[blk][j] = sum over the block's 128 rows of W[r][j]   (coalesced along j)
 __global__ __launch_bounds__(256) void col_sums_part_kernel(const float* __restrict__ W, int kp, float* __restrict__ part,
                                                             const int* __restrict__ flag)
@@ -390,7 +390,7 @@ int nmfx_mur_kl_phase_a_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
       hipLaunchKernelGGL(col_sums_final_kernel, dim3((unsigned)((E->kp + 3) / 4)), dim3(256), 0, E->stream,
                          E->kl_part + (int64_t)(E->np / 64) * E->kp, (int)(E->mp / 64), E->kp, E->G_part, &E->state->flag);
       NMFX_HIP(hipGetLastError()); }
-    return nmfx_bf16_pack_t(E, E->G_part, 1, E->obj_count);            // (the W phase's launch has set it: (mp / 128) * bf_wsplit, or mp / 64 row blocks with NMFX_KL_NW4)
+    return nmfx_bf16_pack_t(E, E->G_part, 1, E->obj_count);            // (the W phase's launch has set it: (mp / 128) * bf_wsplit)
 }
 
 int nmfx_mur_kl_phase_b_bf16(nmfx_engine* E, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j) {

@@ -131,7 +131,6 @@ struct nmfx_engine {
     int64_t obj_count = 0;         // entries of obj_part the last objective-producing launch wrote
     const int* xyt_flag2 = nullptr;  // a second skip flag for the next 32-row product launches (the inner stop of a KL-ADMM sub-problem)
     int xyt_xpriv = 0;                // the next 32-row product launches read an X that lies in the KL auxiliaries' register order (kl_dv_pos)
-    int xyt_nw = 8;                // waves per block of the next 32-row product launch (4: 64-row blocks, two per CU; set and reset by the caller)
     int ao_a_slabs = 0;            // AO-ADMM W side: slabs of A_part the fused inner kernel adds itself (0: auxW holds the sum)
     const float* ao_b_src = nullptr; const int* ao_b_cnt = nullptr;   // AO-ADMM H side, behind a stream-K product: B^T slabs the fused rounds sum themselves (+ what their first launch records)
     int ao_rec_nobj = 0; int64_t ao_rec_j = 0, ao_rec_min_iter = 0; double ao_rec_tol1 = 0.0, ao_rec_tol2 = 0.0;

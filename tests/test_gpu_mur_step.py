@@ -166,11 +166,6 @@ KNOBS = [
     # (environment, shape, kind, (lambda_w, lambda_h)) -- one small shape per knob where it changes the path
     ({"NMFX_BF16_TERMS": "4"}, (384, 256, 40), "eu", (0.1, 0.0)),          # four split terms
     ({"NMFX_BF16_TERMS": "4"}, (384, 256, 100), "kl", (0.0, 0.1)),
-    ({"NMFX_XYT16": "1"}, (384, 256, 40), "eu", (0.0, 0.0)),               # the 16-row form of the k = 64 / 128 product kernel
-    ({"NMFX_XYT16": "1"}, (384, 256, 100), "kl", (0.0, 0.0)),
-    ({"NMFX_NW4": "1"}, (640, 384, 64), "eu", (0.1, 0.0)),                 # four-wave blocks: W phase, H phase, both
-    ({"NMFX_NW4": "2"}, (640, 384, 64), "eu", (0.0, 0.1)),
-    ({"NMFX_NW4": "3"}, (640, 385, 40), "eu", (0.0, 0.0)),
     ({"NMFX_TEMPORAL": "0"}, (640, 384, 64), "eu", (0.0, 0.0)),            # small V is temporal by default
     ({"NMFX_TEMPORAL": "1"}, (5120, 5121, 64), "eu", (0.0, 0.0)),          # V + V^T > 192 MiB: non-temporal by default
     ({"NMFX_GXR": "0"}, (384, 256, 160), "eu", (0.1, 0.0)),                # composed path: 256 x 128 tiles, short contractions

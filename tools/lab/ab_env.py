@@ -1,6 +1,6 @@
 """Same-box A/B of whole MUR iterations between ENVIRONMENT settings of one library build (children interleaved), with a
 checksum of the factors after a fixed number of iterations so that a knob that must not change results is seen not to:
-    python tools/lab/ab_env.py cfg2 base: nw4w:NMFX_NW4=1 nw4h:NMFX_NW4=2 nw4:NMFX_NW4=3 [--rounds 3]"""
+    python tools/lab/ab_env.py cfg2 base: nt:NMFX_TEMPORAL=0 t:NMFX_TEMPORAL=1 [--rounds 3]"""
 import json
 import os
 import subprocess

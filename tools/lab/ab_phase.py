@@ -1,7 +1,7 @@
 """Same-box A/B of the two product kernels: per-launch time over back-to-back launches (nmfx_profile_repeat), one child
 process per library build, the builds interleaved and repeated so that clock drift shows up as spread, not as a difference.
 
-    python tools/lab/ab_phase.py cfg4 nmf_amd/lib/libnmfx.so tools/lab/libnmfx_base.so [--rounds 3] [--env NMFX_ABLATE=1]
+    python tools/lab/ab_phase.py cfg4 nmf_amd/lib/libnmfx.so tools/lab/libnmfx_base.so [--rounds 3] [--env NMFX_TEMPORAL=1]
 """
 import json
 import os

@@ -1,4 +1,4 @@
-"""MUR-KL at k = 128 (16-row kernel today) against k = 64 (32-row KL kernel) on the config-2 matrix: per-phase times."""
+"""MUR-KL at k = 128 against k = 64 on the config-2 matrix (both on the 32-row product kernel): per-phase times."""
 import sys
 import numpy as np
 sys.path.insert(0, ".")
