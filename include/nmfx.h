@@ -46,7 +46,7 @@ enum {
 };
 
 enum { NMFX_F32 = 0, NMFX_F64 = 1 };                 /* host dtype of V          */
-enum { NMFX_EU = 0, NMFX_KL = 1 };                   /* distance_type            */
+enum { NMFX_EU = 0, NMFX_KL = 1, NMFX_IS = 2 };      /* distance_type (IS: nmfx_mur_run / nmfx_mur_finish only) */
 enum { NMFX_PROX_NN = 0, NMFX_PROX_L1N = 1, NMFX_PROX_L2N = 2,      /* reg type   */
        NMFX_PROX_L1INF = 3, NMFX_PROX_L1INF_T = 4 };                /* ADMM only (nmf/admm.py:158-210) */
 
@@ -152,7 +152,15 @@ int nmfx_get_inner_paths(nmfx_handle_t h, int64_t out[4]);
  * mur.py:122-127: W <- w_update (mur.py:20-33), H <- h_update with the new W
  * (mur.py:36-49), objective of the result (utils.py:18-33), and the
  * convergence check for `i = j` when j > min_iter (mur.py:131).  Asynchronous;
- * read results with nmfx_get_state / nmfx_get_objectives (they synchronise).  */
+ * read results with nmfx_get_state / nmfx_get_objectives (they synchronise).
+ * distance = NMFX_IS (version 330; the reference has no such loss): the Itakura-Saito divergence, with q = W H + 1e-9,
+ *   W <- W sqrt( ((V / q^2) H^T) / ((1 / q) H^T + lambda_w) ),  H likewise with the new W,  0 where the denominator is 0,
+ *   objective Sum [v / q - log(v / q) - 1] in f64 ("Itakura-Saito").  V must be strictly positive where it is
+ *   part of the fit.  Accepted by nmfx_mur_run and nmfx_mur_finish alone, on a dense handle with k <= 128 (exact-f32
+ *   kernels whatever the precision mode; nmfx_get_note says so) and on a masked sparse handle (sums over the observed
+ *   set).  An unmasked sparse handle (its zeros have infinite IS divergence), k > 128 on a dense handle, the phase /
+ *   chunk / slice / sharded entry points and nmfx_profile_repeat return NMFX_E_ARG with a message naming IS and launch
+ *   nothing, as does nmfx_objective_f64 (a Euclidean objective) on a handle whose current run is an IS run.            */
 int nmfx_mur_run(nmfx_handle_t h, int distance, double lambda_w, double lambda_h,
                  int64_t min_iter, double tol1, double tol2,
                  int64_t first, int64_t count);

@@ -381,6 +381,7 @@ static int capture_pair(nmfx_engine* E, int distance, double lw, double lh, int6
 extern "C" int nmfx_mur_run_sharded(nmfx_handle_t E, int distance, double lambda_w, double lambda_h, int64_t min_iter, double tol1,
                                     double tol2, int64_t first, int64_t count) {
     NMFX_DENSE_ONLY(E);
+    if (E && distance == NMFX_IS) { E->err = "mur_run_sharded: the Itakura-Saito divergence (IS) is not available row-sharded"; return NMFX_E_ARG; }
     int rc = have_comm(E); if (rc) return rc;
     if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
     if (first < 0 || count < 0) { E->err = "negative iteration range"; return NMFX_E_ARG; }
@@ -437,6 +438,7 @@ extern "C" int nmfx_mur_run_sharded(nmfx_handle_t E, int distance, double lambda
 // objective of the last pair and the final stop-rule evaluation (nmf/mur.py:127-131 for i = max_iter - 1)
 extern "C" int nmfx_mur_finish_sharded(nmfx_handle_t E, int distance, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
     NMFX_DENSE_ONLY(E);
+    if (E && distance == NMFX_IS) { E->err = "mur_finish_sharded: the Itakura-Saito divergence (IS) is not available row-sharded"; return NMFX_E_ARG; }
     int rc = have_comm(E); if (rc) return rc;
     NMFX_HIP(hipSetDevice(E->device));
     if ((rc = nmfx_mur_finish_a(E, distance, iters_done))) return rc;

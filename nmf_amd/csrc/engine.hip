@@ -44,7 +44,7 @@ static int preload_once(nmfx_engine* E) {
     static std::map<int, bool> done;
     std::lock_guard<std::mutex> lock(mu);
     if (done[E->device]) return NMFX_OK;
-    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_aoadmm() ||
+    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_is() || nmfx_preload_aoadmm() ||
         nmfx_preload_anls() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic() ||
         nmfx_preload_sparse()) {
         E->err = "loading the kernels onto the device failed"; return NMFX_E_HIP; }
@@ -125,7 +125,7 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
 
 extern "C" {
 
-int nmfx_version(void) { return 320; }      // 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 330; }      // 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -256,7 +256,7 @@ int nmfx_destroy(nmfx_handle_t E) {
     nmfx_comm_free(E);
     for (auto& t : E->prof_pending) { hipEventDestroy(std::get<1>(t)); hipEventDestroy(std::get<2>(t)); }
     void* bufs[] = {E->V, E->W[0], E->W[1], E->H, E->HHt, E->HHt_part, E->G_part, E->A_part, E->B_part,
-                    E->obj_part, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
+                    E->obj_part, E->is_part, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
                     E->obj_hist, E->state, E->dualW, E->dualH, E->auxW, E->auxH, E->Minv, E->nrm_part,
                     E->inner_hist, E->Pw, E->Ph, E->Asum, E->S, E->DV, E->Vt, E->Vtile, E->Bt_part, E->Whi[0], E->Whi[1],
                     E->Wlo[0], E->Wlo[1], E->WThi, E->WTlo, E->Hhi, E->Hlo, E->HThi, E->HTlo, E->nrm_rounds, E->bkX, E->bkU,
@@ -428,6 +428,7 @@ int nmfx_set_factors(nmfx_handle_t E, const double* w, const double* hmat) {
     E->kl_h_iter = -2;
     E->wimg_ok = false;
     E->family = 0;
+    E->is_run = false;
     E->pair = false;
     E->family_started = false;
     E->himg_both = false;
@@ -646,11 +647,20 @@ static int check_ready(nmfx_engine* E, int64_t first, int64_t count, bool mur_en
 // (kl_h_iter: the H images and row-sum partials the KL H epilogue of iteration j leaves for the KL W phase of iteration j + 1 are
 // only good if NOTHING else has written H or those buffers in between -- every entry point of another solver, and the
 // Euclidean MUR phases, void them; ADVICE r2: only nmfx_set_factors did)
+// The Itakura-Saito divergence (NMFX_IS) runs through nmfx_mur_run / nmfx_mur_finish only (dense k <= 128, masked sparse)
+static int refuse_is(nmfx_engine* E, const char* who) {
+    E->err = std::string(who) + ": the Itakura-Saito divergence (IS) is available through nmfx_mur_run / nmfx_mur_finish only";
+    return NMFX_E_ARG;
+}
+#define NMFX_NO_IS(E, distance) do { if ((E) && (distance) == NMFX_IS) return refuse_is((E), __func__); } while (0)
+
 int nmfx_mur_phase_a(nmfx_handle_t E, int distance, double lambda_w, int64_t j) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (E) E->himg_both = false;
     if (!E) return NMFX_E_ARG;
     if (distance != NMFX_KL) E->kl_h_iter = -2;
+    E->is_run = false;                                 // (a Euclidean / KL phase: the f64 referee applies again)
     int rc = check_ready(E, j, 1); if (rc) return rc;
     if (E->kp > 128 && (distance == NMFX_EU || distance == NMFX_KL)) return nmfx_generic_mur_phase_a(E, distance, lambda_w, j);
     if (distance == NMFX_EU)
@@ -668,6 +678,7 @@ static bool mur_chunkable(nmfx_engine* E, int distance) {
 }
 int nmfx_mur_chunk_info(nmfx_handle_t E, int distance, int64_t* unit, int64_t* n_padded, int64_t* k_padded) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E) return NMFX_E_ARG;
     const bool ok = mur_chunkable(E, distance);
     if (unit) *unit = ok ? 128 : 0;
@@ -677,15 +688,18 @@ int nmfx_mur_chunk_info(nmfx_handle_t E, int distance, int64_t* unit, int64_t* n
 }
 int nmfx_mur_phase_a_head(nmfx_handle_t E, int distance, double lambda_w, int64_t j) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E) return NMFX_E_ARG;
     E->himg_both = false;
     E->kl_h_iter = -2;
+    E->is_run = false;
     int rc = check_ready(E, j, 1); if (rc) return rc;
     if (!mur_chunkable(E, distance)) { E->err = "phase_a_head: Euclidean loss on the split-bf16 path only (nmfx_mur_chunk_info)"; return NMFX_E_ARG; }
     return nmfx_mur_eu_phase_a_head_bf16(E, lambda_w, j);
 }
 int nmfx_mur_phase_a_cols(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E) return NMFX_E_ARG;
     if (!mur_chunkable(E, distance)) { E->err = "phase_a_cols: Euclidean loss on the split-bf16 path only (nmfx_mur_chunk_info)"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
@@ -695,9 +709,11 @@ int nmfx_mur_phase_a_cols(nmfx_handle_t E, int distance, int64_t c0, int64_t c1)
 int nmfx_mur_phase_b(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1,
                      double tol2, int64_t j) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (E) E->himg_both = false;
     if (!E) return NMFX_E_ARG;
     if (distance != NMFX_KL) E->kl_h_iter = -2;
+    E->is_run = false;                                 // (a Euclidean / KL phase: the f64 referee applies again)
     int rc = check_ready(E, j, 1); if (rc) return rc;
     E->wsel = (int)((j + 1) & 1);
     E->w_in_place = false;
@@ -716,6 +732,7 @@ int nmfx_mur_phase_b(nmfx_handle_t E, int distance, double lambda_h, int64_t min
 // Phase B by column slices (reduce-scatter / all-gather exchange, include/nmfx.h)
 int nmfx_mur_slice_info(nmfx_handle_t E, int distance, int world, int64_t* cols, int64_t* elems) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E || world < 1) return NMFX_E_ARG;
     const bool ok = mur_chunkable(E, distance) && E->xworld == world && (E->np / 64) % world == 0;
     const int64_t c = ok ? E->np / world : 0;
@@ -731,9 +748,11 @@ static int slice_args(nmfx_engine* E, int distance, int64_t c0, int64_t c1, cons
 int nmfx_mur_phase_b_slice(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j,
                            int64_t c0, int64_t c1) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E) return NMFX_E_ARG;
     E->himg_both = false;
     E->kl_h_iter = -2;
+    E->is_run = false;
     int rc = check_ready(E, j, 1); if (rc) return rc;
     if ((rc = slice_args(E, distance, c0, c1, "phase_b_slice"))) return rc;
     E->wsel = (int)((j + 1) & 1);
@@ -742,6 +761,7 @@ int nmfx_mur_phase_b_slice(nmfx_handle_t E, int distance, double lambda_h, int64
 }
 int nmfx_mur_phase_b_rest(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E) return NMFX_E_ARG;
     int rc = slice_args(E, distance, c0, c1, "phase_b_rest"); if (rc) return rc;
     NMFX_HIP(hipSetDevice(E->device));
@@ -750,6 +770,7 @@ int nmfx_mur_phase_b_rest(nmfx_handle_t E, int distance, int64_t c0, int64_t c1)
 
 int nmfx_mur_finish_a(nmfx_handle_t E, int distance, int64_t j) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E) return NMFX_E_ARG;
     int rc = check_ready(E, j, 1); if (rc) return rc;
     if (E->kp > 128 && (distance == NMFX_EU || distance == NMFX_KL)) return nmfx_generic_mur_finish_a(E, distance, j);
@@ -765,11 +786,32 @@ int nmfx_mur_finish_b(nmfx_handle_t E, int64_t min_iter, double tol1, double tol
     return nmfx_finish_b(E, min_iter, tol1, tol2, j);
 }
 
+// IS on a dense handle: the tuned exact-f32 kernels of kernels_is.hip, k <= 128, whatever the precision mode says
+static int is_dense_ok(nmfx_engine* E, const char* who) {
+    if (E->kp > 128) { E->err = std::string(who) + ": the Itakura-Saito divergence (IS) needs k <= 128 on a dense handle"; return NMFX_E_ARG; }
+    if (E->precision == 1 && nmfx_bf16_supported(E) && E->note.find("Itakura-Saito") == std::string::npos)
+        E->note += (E->note.empty() ? "" : "; ") + std::string("the Itakura-Saito divergence (IS) runs the exact-f32 kernels; the split-bf16 mode does not apply to it");
+    return NMFX_OK;
+}
+
 int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h, int64_t min_iter,
                  double tol1, double tol2, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
     if (E->sp) return nmfx_sparse_mur_run(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
+    if (distance == NMFX_IS) {
+        { int rc_is = is_dense_ok(E, "mur_run"); if (rc_is) return rc_is; }
+        int rc = check_ready(E, first, count); if (rc) return rc;
+        E->himg_both = false; E->kl_h_iter = -2; E->is_run = true;
+        for (int64_t j = first; j < first + count && !rc; ++j) {
+            if ((rc = nmfx_mur_is_phase_a(E, lambda_w, j))) break;
+            E->wsel = (int)((j + 1) & 1);
+            E->w_in_place = false;
+            rc = nmfx_mur_is_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
+        }
+        return rc;
+    }
     int rc = check_ready(E, first, count); if (rc) return rc;
+    E->is_run = false;
     E->fused_pack = true;            // nothing is exchanged between the phases here
     for (int64_t j = first; j < first + count && !rc; ++j) {
         if ((rc = nmfx_mur_phase_a(E, distance, lambda_w, j))) break;
@@ -783,6 +825,13 @@ int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1
                     int64_t iters_done) {
     if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
     int rc;
+    if (E && distance == NMFX_IS) {
+        if ((rc = is_dense_ok(E, "mur_finish"))) return rc;
+        if ((rc = check_ready(E, iters_done, 1))) return rc;
+        E->is_run = true;
+        if ((rc = nmfx_mur_is_finish_a(E, iters_done))) return rc;
+        return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
+    }
     if ((rc = nmfx_mur_finish_a(E, distance, iters_done))) return rc;
     return nmfx_mur_finish_b(E, min_iter, tol1, tol2, iters_done);
 }
@@ -825,6 +874,7 @@ int nmfx_profile_get(nmfx_handle_t E, const char* name, double* total_ms, int64_
 // every launch, which costs the W phase ~10 us that no real iteration pays.
 int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int reps, double* ms_per_launch) {
     NMFX_DENSE_ONLY(E);
+    NMFX_NO_IS(E, distance);
     if (!E || !which || reps <= 0 || !ms_per_launch) return NMFX_E_ARG;
     const std::string w(which);
     int rc = check_ready(E, 0, 0, !(w.rfind("ao_", 0) == 0 || w.rfind("sk_", 0) == 0)); if (rc) return rc;

@@ -27,6 +27,11 @@
 //   KL         a = Sum_M x / (wh + 1e-9) h,  d = Sum_M h   out = 2 w a / (d + sqrt(d^2 + 4 lam w a)),  d = 0 -> 0
 // Pieces store [a | d] (slab [pieces][2 kp]).  The objective is summed per observed entry in f64 (Euclidean 1/2 (x - wh)^2,
 // KL x log(x / wh) - x + wh); there are no Grams, column sums nor ||X||^2 terms, and no sp_stats_kernel passes.
+//
+// Itakura-Saito on masked handles (template parameter IS, masked instantiations only; q = wh + 1e-9 in f64):
+//   a = Sum_M x / q^2 h,  d = Sum_M (1 / q) h     out = w sqrt(a / (d + lam)),  d + lam = 0 -> 0
+// and the objective Sum_M [x / q - log(x / q) - 1] per observed entry in f64.  The Euclidean and KL instantiations are the
+// ones they were: IS is a trailing parameter that defaults to false and only adds `if constexpr` branches.
 #include "kernels_small.h"
 #include <algorithm>
 #include <cmath>
@@ -127,12 +132,18 @@ __device__ __forceinline__ void sp_epilogue(float4 w4, float4 a4, const float* _
 // The update epilogue of one owned row on a masked handle, with the denominator d summed by the pass (no Gram, no sums):
 //   Euclidean  out = w a / (d + lam w + 1e-9)
 //   KL         out = 2 w a / (d + sqrt(d^2 + 4 lam w a)), and 0 where d = 0 (no observed entry: 0 / 0 is defined as 0)
-template <bool KL>
+template <bool KL, bool IS = false>
 __device__ __forceinline__ void sp_epilogue_masked(float4 w4, float4 a4, float4 d4, float lam, int k, float* __restrict__ out_row,
                                                    int lig, int grp)
 {
     float4 o;
-    if constexpr (KL) {
+    if constexpr (IS) {
+        float d;
+        d = d4.x + lam; o.x = d > 0.f ? w4.x * sqrtf(a4.x / d) : 0.f;
+        d = d4.y + lam; o.y = d > 0.f ? w4.y * sqrtf(a4.y / d) : 0.f;
+        d = d4.z + lam; o.z = d > 0.f ? w4.z * sqrtf(a4.z / d) : 0.f;
+        d = d4.w + lam; o.w = d > 0.f ? w4.w * sqrtf(a4.w / d) : 0.f;
+    } else if constexpr (KL) {
         float c;
         c = w4.x * a4.x; o.x = d4.x > 0.f ? 2.f * c / (d4.x + sqrtf(d4.x * d4.x + 4.f * lam * c)) : 0.f;
         c = w4.y * a4.y; o.y = d4.y > 0.f ? 2.f * c / (d4.y + sqrtf(d4.y * d4.y + 4.f * lam * c)) : 0.f;
@@ -159,7 +170,7 @@ __device__ __forceinline__ void sp_epilogue_masked(float4 w4, float4 a4, float4 
 //   MASKED: Euclidean Sum (x - wh)^2, KL Sum x log(x/wh) - x + wh).
 //   UPDATE: accumulate and run the epilogue (whole rows) or store the piece's sum (pieces).
 //   MASKED: also accumulate the denominator (Sum wh h / Sum h) and run the masked epilogue; pieces store [sum | denominator].
-template <int KP, bool KL, bool OBJ, bool UPDATE, bool MASKED>
+template <int KP, bool KL, bool OBJ, bool UPDATE, bool MASKED, bool IS = false>
 __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
     const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
     const float* __restrict__ Other, const float* Own, float* Out, const float* __restrict__ Gf, const float* __restrict__ S,
@@ -203,7 +214,10 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
                 if constexpr (OBJ) {
                     if (lig == 0 && ok[t]) {
                         const double xv = x[t];
-                        if constexpr (KL) {
+                        if constexpr (IS) {
+                            const double r = xv / (wh + 1e-9);
+                            objacc += r - log(r) - 1.0;
+                        } else if constexpr (KL) {
                             double tl = xv * log(xv / wh);
                             if (tl == INFINITY || tl != tl) tl = 0.0;      // np.where(t == inf, 0, t); np.where(isnan(t), 0, t)
                             if constexpr (MASKED) objacc += tl - xv + wh;
@@ -216,7 +230,14 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
                         }
                     }
                 }
-                if constexpr (UPDATE) {
+                if constexpr (UPDATE && IS) {          // (a slot past the unit's end: x = 0 and weight 0)
+                    const double iq = 1.0 / (wh + 1e-9);
+                    const float q = (float)((double)x[t] * iq * iq), r = ok[t] ? (float)iq : 0.f;
+                    acc.x = fmaf(q, h[t].x, acc.x); acc.y = fmaf(q, h[t].y, acc.y);
+                    acc.z = fmaf(q, h[t].z, acc.z); acc.w = fmaf(q, h[t].w, acc.w);
+                    den.x = fmaf(r, h[t].x, den.x); den.y = fmaf(r, h[t].y, den.y);
+                    den.z = fmaf(r, h[t].z, den.z); den.w = fmaf(r, h[t].w, den.w);
+                } else if constexpr (UPDATE) {
                     const float q = KL ? (float)((double)x[t] / (wh + 1e-9)) : x[t];
                     acc.x = fmaf(q, h[t].x, acc.x); acc.y = fmaf(q, h[t].y, acc.y);
                     acc.z = fmaf(q, h[t].z, acc.z); acc.w = fmaf(q, h[t].w, acc.w);
@@ -238,7 +259,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
                     *reinterpret_cast<float4*>(p + KP) = den;
                 }
             } else {
-                sp_epilogue_masked<KL>(w4, acc, den, lam, k, Out + (int64_t)U.row * KP, lig, grp);
+                sp_epilogue_masked<KL, IS>(w4, acc, den, lam, k, Out + (int64_t)U.row * KP, lig, grp);
             }
         } else if constexpr (UPDATE) {
             acc = sp_sum_groups<G>(acc);
@@ -264,7 +285,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_phase_kernel(
 
 // Rows split into pieces: the pieces' sums added in piece order (group g takes pieces g, g + NG, ..., then the groups'
 // butterfly), then the epilogue.  MASKED: the same for both halves of a piece's [sum | denominator], then the masked epilogue.
-template <int KP, bool KL, bool MASKED>
+template <int KP, bool KL, bool MASKED, bool IS = false>
 __global__ __launch_bounds__(64 * SP_WAVES) void sp_fixup_kernel(
     const SpLong* __restrict__ longs, int64_t nlong, const float* __restrict__ slab, const float* Own, float* Out,
     const float* __restrict__ Gf, const float* __restrict__ S, float lam, int k, const int* flag)
@@ -284,7 +305,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_fixup_kernel(
             }
             acc = sp_sum_groups<G>(acc);
             den = sp_sum_groups<G>(den);
-            sp_epilogue_masked<KL>(w4, acc, den, lam, k, Out + (int64_t)L.row * KP, lig, grp);
+            sp_epilogue_masked<KL, IS>(w4, acc, den, lam, k, Out + (int64_t)L.row * KP, lig, grp);
         }
         return;
     }
@@ -368,7 +389,7 @@ __global__ void sp_stats_reduce_kernel(const double* __restrict__ part, int slab
 // The objective of the pair from the block partials (block order, then a fixed tree) and the small terms; recorded as
 // obj[j] with the reference's stop rule (record) or only stored to *out.  MASKED: the block partials alone (KL: their sum,
 // Euclidean: half of it).
-template <bool KL, bool MASKED>
+template <bool KL, bool MASKED, bool IS = false>
 __global__ __launch_bounds__(256) void sp_objective_kernel(
     const double* __restrict__ part, int nblk, const double* __restrict__ gw, const double* __restrict__ gh,
     const double* __restrict__ cw, const double* __restrict__ ch, int kp, double x2, double* __restrict__ out, int record,
@@ -390,7 +411,7 @@ __global__ __launch_bounds__(256) void sp_objective_kernel(
         __syncthreads();
     }
     if (tid == 0) {
-        const double obj = MASKED ? (KL ? r[0][0] : 0.5 * r[0][0])
+        const double obj = MASKED ? (KL || IS ? r[0][0] : 0.5 * r[0][0])
                                   : KL ? r[0][0] + r[1][0] : 0.5 * (x2 - 2.0 * r[0][0] + r[1][0]);
         *out = obj;
         if (record) nmfx_record_objective(st, obj_hist, obj, j, min_iter, tol1, tol2, true);
@@ -557,16 +578,22 @@ static int launch_stats(nmfx_engine* E, const float* F, int64_t R, int f, const 
 }
 
 // side 0: own W (Wold -> Wnew), gather H^T, other factor's stats 1; side 1: own H^T (in place), gather W, stats 0
-template <int KP, bool KL>
+// LOSS: NMFX_EU / NMFX_KL / NMFX_IS (the last on masked handles only: sp_ready)
+template <int KP, int LOSS>
 static int launch_phase(nmfx_engine* E, int side, const float* Own, float* Out, const float* Other, bool obj, bool update,
                         float lam, const int* flag) {
+    constexpr bool KL = LOSS == NMFX_KL, IS = LOSS == NMFX_IS;
     nmfx_sparse* S = E->sp;
     SpSide& sd = S->side[side];
     const int o = 1 - side;
     const dim3 grid(sd.nblk), blk(64 * SP_WAVES);
 #define SP_ARGS sd.units, sd.nunits, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, Out, (const float*)S->gf[o], \
                 (const float*)S->csf[o], sd.slab, S->obj_part, lam, E->k, flag
-    if (S->masked) {
+    if constexpr (IS) {
+        if (obj && update) hipLaunchKernelGGL((sp_phase_kernel<KP, false, true, true, true, true>), grid, blk, 0, E->stream, SP_ARGS);
+        else if (obj) hipLaunchKernelGGL((sp_phase_kernel<KP, false, true, false, true, true>), grid, blk, 0, E->stream, SP_ARGS);
+        else hipLaunchKernelGGL((sp_phase_kernel<KP, false, false, true, true, true>), grid, blk, 0, E->stream, SP_ARGS);
+    } else if (S->masked) {
         if (obj && update) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, true, true>), grid, blk, 0, E->stream, SP_ARGS);
         else if (obj) hipLaunchKernelGGL((sp_phase_kernel<KP, KL, true, false, true>), grid, blk, 0, E->stream, SP_ARGS);
         else hipLaunchKernelGGL((sp_phase_kernel<KP, KL, false, true, true>), grid, blk, 0, E->stream, SP_ARGS);
@@ -579,7 +606,7 @@ static int launch_phase(nmfx_engine* E, int side, const float* Own, float* Out, 
     NMFX_HIP(hipGetLastError());
     if (update && sd.nlong) {
         const int nb = (int)std::min<int64_t>(4 * E->ncu, (sd.nlong + SP_WAVES - 1) / SP_WAVES);
-        auto fix = S->masked ? sp_fixup_kernel<KP, KL, true> : sp_fixup_kernel<KP, KL, false>;
+        auto fix = IS ? sp_fixup_kernel<KP, false, true, IS> : S->masked ? sp_fixup_kernel<KP, KL, true> : sp_fixup_kernel<KP, KL, false>;
         hipLaunchKernelGGL(fix, dim3(nb), blk, 0, E->stream, (const SpLong*)sd.longs, sd.nlong,
                            (const float*)sd.slab, Own, Out, (const float*)S->gf[o], (const float*)S->csf[o], lam, E->k, flag);
         NMFX_HIP(hipGetLastError());
@@ -587,9 +614,10 @@ static int launch_phase(nmfx_engine* E, int side, const float* Own, float* Out, 
     return NMFX_OK;
 }
 
-static int launch_objective(nmfx_engine* E, bool kl, double* out, bool record, int64_t j, int64_t min_iter, double tol1, double tol2) {
+static int launch_objective(nmfx_engine* E, int loss, double* out, bool record, int64_t j, int64_t min_iter, double tol1, double tol2) {
     nmfx_sparse* S = E->sp;
-    auto kern = S->masked ? (kl ? sp_objective_kernel<true, true> : sp_objective_kernel<false, true>)
+    const bool kl = loss == NMFX_KL;
+    auto kern = loss == NMFX_IS ? sp_objective_kernel<false, true, true> : S->masked ? (kl ? sp_objective_kernel<true, true> : sp_objective_kernel<false, true>)
                           : (kl ? sp_objective_kernel<true, false> : sp_objective_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, E->stream, (const double*)S->obj_part, S->side[0].nblk,
                        (const double*)S->g64[0], (const double*)S->g64[1], (const double*)S->cs64[0], (const double*)S->cs64[1],
@@ -598,24 +626,33 @@ static int launch_objective(nmfx_engine* E, bool kl, double* out, bool record, i
     return NMFX_OK;
 }
 
+// one phase launch for a run-time loss
 template <int KP>
-static int sp_iteration(nmfx_engine* E, bool kl, double lw, double lh, int64_t min_iter, double tol1, double tol2, int64_t j) {
+static int phase_for(nmfx_engine* E, int loss, int side, const float* Own, float* Out, const float* Other, bool obj, bool update,
+                     float lam, const int* flag) {
+    switch (loss) {
+        case NMFX_IS: return launch_phase<KP, NMFX_IS>(E, side, Own, Out, Other, obj, update, lam, flag);
+        case NMFX_KL: return launch_phase<KP, NMFX_KL>(E, side, Own, Out, Other, obj, update, lam, flag);
+        default: return launch_phase<KP, NMFX_EU>(E, side, Own, Out, Other, obj, update, lam, flag);
+    }
+}
+
+template <int KP>
+static int sp_iteration(nmfx_engine* E, int loss, double lw, double lh, int64_t min_iter, double tol1, double tol2, int64_t j) {
     nmfx_sparse* S = E->sp;
     const int* flag = &E->state->flag;
     const float* Wold = E->W[j & 1];
     float* Wnew = E->W[(j + 1) & 1];
     int rc;
     { ProfScope ps(E, "sp_wphase");
-      rc = kl ? launch_phase<KP, true>(E, 0, Wold, Wnew, S->Ht, true, true, (float)lw, flag)
-              : launch_phase<KP, false>(E, 0, Wold, Wnew, S->Ht, true, true, (float)lw, flag);
+      rc = phase_for<KP>(E, loss, 0, Wold, Wnew, S->Ht, true, true, (float)lw, flag);
       if (rc) return rc; }
-    if ((rc = launch_objective(E, kl, E->xf64, true, j, min_iter, tol1, tol2))) return rc;
+    if ((rc = launch_objective(E, loss, E->xf64, true, j, min_iter, tol1, tol2))) return rc;
     if (!S->masked) {                 // (a masked update takes its denominators from the phase itself)
       ProfScope ps(E, "sp_stats");
       if ((rc = launch_stats<KP>(E, Wnew, E->m, 0, flag))) return rc; }
     { ProfScope ps(E, "sp_hphase");
-      rc = kl ? launch_phase<KP, true>(E, 1, S->Ht, S->Ht, Wnew, false, true, (float)lh, flag)
-              : launch_phase<KP, false>(E, 1, S->Ht, S->Ht, Wnew, false, true, (float)lh, flag);
+      rc = phase_for<KP>(E, loss, 1, S->Ht, S->Ht, Wnew, false, true, (float)lh, flag);
       if (rc) return rc; }
     if (!S->masked) {
       ProfScope ps(E, "sp_stats");
@@ -626,9 +663,8 @@ static int sp_iteration(nmfx_engine* E, bool kl, double lw, double lh, int64_t m
 
 // objective pass of (W[wsel or j & 1], H) without an update
 template <int KP>
-static int sp_objective_pass(nmfx_engine* E, bool kl, const float* W, const int* flag) {
-    return kl ? launch_phase<KP, true>(E, 0, W, nullptr, E->sp->Ht, true, false, 0.f, flag)
-              : launch_phase<KP, false>(E, 0, W, nullptr, E->sp->Ht, true, false, 0.f, flag);
+static int sp_objective_pass(nmfx_engine* E, int loss, const float* W, const int* flag) {
+    return phase_for<KP>(E, loss, 0, W, nullptr, E->sp->Ht, true, false, 0.f, flag);
 }
 
 #define SP_DISPATCH(call) \
@@ -638,9 +674,14 @@ static int sp_objective_pass(nmfx_engine* E, bool kl, const float* W, const int*
 
 static int sp_ready(nmfx_engine* E, int distance, int64_t first, int64_t count) {
     if (!E->have_v || !E->have_f) { E->err = "upload the CSR matrix and set factors first"; return NMFX_E_STATE; }
-    if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
+    if (distance == NMFX_IS && !E->sp->masked) {
+        E->err = "the Itakura-Saito divergence (IS) is infinite at the zeros of an unmasked sparse V: make the handle masked (nmfx_set_masked)";
+        return NMFX_E_ARG;
+    }
+    if (distance != NMFX_EU && distance != NMFX_KL && distance != NMFX_IS) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
     if (first < 0 || count < 0) { E->err = "negative iteration range"; return NMFX_E_ARG; }
     int rc = nmfx_enter_family(E, 1); if (rc) return rc;
+    E->is_run = distance == NMFX_IS;
     NMFX_HIP(hipSetDevice(E->device));
     return nmfx_ensure_obj_capacity(E, first + count + 2);
 }
@@ -648,9 +689,8 @@ static int sp_ready(nmfx_engine* E, int distance, int64_t first, int64_t count) 
 int nmfx_sparse_mur_run(nmfx_engine* E, int distance, double lw, double lh, int64_t min_iter, double tol1, double tol2,
                         int64_t first, int64_t count) {
     int rc = sp_ready(E, distance, first, count); if (rc) return rc;
-    const bool kl = distance == NMFX_KL;
     for (int64_t j = first; j < first + count && !rc; ++j) {
-#define SP_IT(KP) sp_iteration<KP>(E, kl, lw, lh, min_iter, tol1, tol2, j)
+#define SP_IT(KP) sp_iteration<KP>(E, distance, lw, lh, min_iter, tol1, tol2, j)
         switch (E->kp) { case 4: rc = SP_IT(4); break; case 8: rc = SP_IT(8); break; case 16: rc = SP_IT(16); break;
                          case 32: rc = SP_IT(32); break; case 64: rc = SP_IT(64); break; case 128: rc = SP_IT(128); break;
                          default: rc = SP_IT(256); break; }
@@ -659,9 +699,9 @@ int nmfx_sparse_mur_run(nmfx_engine* E, int distance, double lw, double lh, int6
     return rc;
 }
 
-static int objective_pass(nmfx_engine* E, bool kl, const float* W, const int* flag) {
+static int objective_pass(nmfx_engine* E, int loss, const float* W, const int* flag) {
     int rc;
-#define SP_OP(KP) sp_objective_pass<KP>(E, kl, W, flag)
+#define SP_OP(KP) sp_objective_pass<KP>(E, loss, W, flag)
     switch (E->kp) { case 4: rc = SP_OP(4); break; case 8: rc = SP_OP(8); break; case 16: rc = SP_OP(16); break;
                      case 32: rc = SP_OP(32); break; case 64: rc = SP_OP(64); break; case 128: rc = SP_OP(128); break;
                      default: rc = SP_OP(256); break; }
@@ -671,9 +711,8 @@ static int objective_pass(nmfx_engine* E, bool kl, const float* W, const int* fl
 
 int nmfx_sparse_mur_finish(nmfx_engine* E, int distance, int64_t min_iter, double tol1, double tol2, int64_t done) {
     int rc = sp_ready(E, distance, done, 0); if (rc) return rc;
-    const bool kl = distance == NMFX_KL;
-    if ((rc = objective_pass(E, kl, E->W[done & 1], &E->state->flag))) return rc;
-    return launch_objective(E, kl, E->xf64, true, done, min_iter, tol1, tol2);
+    if ((rc = objective_pass(E, distance, E->W[done & 1], &E->state->flag))) return rc;
+    return launch_objective(E, distance, E->xf64, true, done, min_iter, tol1, tol2);
 }
 
 // After the stop rule has fired, the launches behind it in the batch did nothing: the current W is the one of the pair at
@@ -691,8 +730,8 @@ int nmfx_sparse_objective_f64(nmfx_engine* E, double* out) {
     if (!E->have_v || !E->have_f) { E->err = "upload the CSR matrix and set factors first"; return NMFX_E_STATE; }
     int rc;
     if ((rc = sync_wsel(E))) return rc;
-    if ((rc = objective_pass(E, false, E->W[E->wsel], nullptr))) return rc;
-    if ((rc = launch_objective(E, false, E->xf64 + 1, false, 0, 0, 0.0, 0.0))) return rc;
+    if ((rc = objective_pass(E, NMFX_EU, E->W[E->wsel], nullptr))) return rc;
+    if ((rc = launch_objective(E, NMFX_EU, E->xf64 + 1, false, 0, 0, 0.0, 0.0))) return rc;
     NMFX_HIP(hipMemcpyAsync(out, E->xf64 + 1, sizeof(double), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
     return NMFX_OK;
@@ -729,6 +768,7 @@ int nmfx_sparse_set_factors(nmfx_engine* E, const double* w, const double* hmat)
     E->wsel = 0;
     E->have_f = true;
     E->family = 0;
+    E->is_run = false;
     E->w_in_place = false;
     int rc;
     if (!E->sp->masked && (rc = stats_both(E))) return rc;

@@ -944,6 +944,8 @@ def factorize(data, k, method='mur', *, gather=True, device=None, backend=None, 
     import torch.distributed as tdist
     if method not in _SOLVERS:
         raise Exception('Method not known. Choose one from: mur anls admm ao_admm')      # nmf/nmf.py:76
+    if method_params.get('distance_type') == 'is':            # (no sharded Itakura-Saito runs)
+        raise TypeError("dist.factorize: distance_type='is' is not supported (the Itakura-Saito divergence runs on one GPU: mur(x, k, distance_type='is'))")
     rank, world, local = init_process_group(backend)
     mod, kw = _defaults(method)
     unknown = set(method_params) - set(kw)

@@ -42,7 +42,12 @@ def factorize_grid(data, method='mur', *, features, lambda_w=(0.0,), lambda_h=(0
     if 'mask' in common:
         raise TypeError("factorize_grid: mask= is not supported (run mur(x, k, mask=...) per grid point)")
     solver = getattr(import_module('.' + method, __package__), method)
-    if method == 'mur':                         # the lift of negative data happens once, in place (nmf/mur.py:99-101)
+    if method != 'mur' and common.get('distance_type') == 'is':
+        raise ValueError(f"{method}: distance_type='is' (Itakura-Saito) is a loss of mur only")
+    if method == 'mur' and common.get('distance_type') == 'is':     # checked once, before any engine exists; 'is' never lifts
+        from .mur import _check_is_input
+        _check_is_input(data, max(features))
+    elif method == 'mur':                       # the lift of negative data happens once, in place (nmf/mur.py:99-101)
         lowest = np.min(data)
         if lowest < 0:
             data += abs(lowest)
@@ -76,7 +81,7 @@ def factorize_grid(data, method='mur', *, features, lambda_w=(0.0,), lambda_h=(0
 
 
 def _pairable(method, common):
-    return method == 'mur' and common.get('distance_type', 'kl') == 'eu'
+    return method == 'mur' and common.get('distance_type', 'kl') == 'eu'      # ('is' and 'kl' take the sequential path)
 
 
 def _save(data, k, res, save_dir):

@@ -104,15 +104,31 @@ def observed(x, mask, k=None):
     return c
 
 
+def check_positive(c):
+    """The Itakura-Saito divergence is undefined at 0: every observed value of the canonical CSR `c` must be > 0."""
+    if not c.nnz:
+        return
+    with np.errstate(over='ignore', under='ignore'):            # (the device holds float32: judge that image)
+        lowest, highest = np.float32(np.min(c.data)), np.float32(np.max(c.data))
+    if not lowest > 0:
+        raise ValueError("distance_type='is': an observed value is 0, or underflows to 0 in float32 (the Itakura-Saito "
+                         "divergence needs strictly positive data; leave such entries out of the mask)")
+    if not np.isfinite(highest):
+        raise ValueError("distance_type='is': an observed value is beyond the float32 range")
+
+
 def objective(x, w, h, mask, distance_type='eu', chunk=1 << 20):
     """nmf/utils.py:18-33 restricted to the observed entries, in float64 on the host, `chunk` entries at a time:
         eu  1/2 Sum_M (x - wh)^2
         kl  Sum_M [x log(x / wh) - x + wh]       (inf / nan log terms -> 0)
+        is  Sum_M [x / q - log(x / q) - 1],  q = wh + 1e-9       (every observed x must be > 0)
     With the training mask it is the objective `mur(x, k, mask=...)` records; with a held-out mask it scores the fit
     there."""
-    if distance_type not in ('eu', 'kl'):
+    if distance_type not in ('eu', 'kl', 'is'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')
     c = observed(x, mask)
+    if distance_type == 'is':
+        check_positive(c)
     w = np.asarray(w, dtype=np.float64)
     h = np.asarray(h, dtype=np.float64)
     rows = np.repeat(np.arange(c.shape[0]), np.diff(c.indptr))
@@ -124,6 +140,9 @@ def objective(x, w, h, mask, distance_type='eu', chunk=1 << 20):
         xa = xv[a:b]
         if distance_type == 'eu':
             s += 0.5 * float(np.sum((xa - wh) ** 2))
+        elif distance_type == 'is':
+            r = xa / (wh + 1e-9)
+            s += float(np.sum(r - np.log(r) - 1.0))
         else:
             with np.errstate(divide='ignore', invalid='ignore'):
                 t = xa * np.log(xa / wh)

@@ -23,16 +23,19 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
     """Lee-Seung NMF.  x: 2-D non-negative data (a numpy array, or any scipy.sparse matrix / array with 1 <= k <= 256:
     never densified), k: number of components.
 
-    distance_type 'eu' | 'kl' (default 'kl' as in the reference), min_iter,
-    max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init=(bool, variant) and
+    distance_type 'eu' | 'kl' (default 'kl' as in the reference) | 'is' (Itakura-Saito, beyond the reference: dense
+    strictly positive x with k <= 128, or any x with mask= whose observed entries are strictly positive; x is never
+    lifted), min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init=(bool, variant) and
     save_dir have the reference's meaning.  mask: None, or a boolean / 0-1 array or scipy.sparse matrix of x's shape
     whose non-zero entries are the observed set -- only x there is fitted and read (masked MUR, nmf_amd.masked;
     1 <= k <= 256).  Returns Results(w, h, i, obj_history, experiment) with float64 w, h."""
     experiment = Experiment('mur', k, distance_type, nndsvd_init, max_iter, tol1, tol2,
                             lambda_w, lambda_h)
-    if distance_type not in ('eu', 'kl'):
+    if distance_type not in ('eu', 'kl', 'is'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31
-    dist = L.EU if distance_type == 'eu' else L.KL
+    dist = {'eu': L.EU, 'kl': L.KL, 'is': L.IS}[distance_type]
+    if dist == L.IS and mask is None:
+        _check_is_input(x, k)
     if mask is not None:
         return _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init,
                            device, engine)
@@ -67,6 +70,24 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
 
 
+def _check_is_input(x, k):
+    """Itakura-Saito without a mask, checked before any device work: dense, strictly positive, k <= 128.  The data is
+    not lifted by its minimum (the loss is scale-invariant, not shift-invariant) and never modified."""
+    if sparse.is_sparse(x):
+        raise ValueError("distance_type='is': the zeros of a sparse matrix have infinite Itakura-Saito divergence; "
+                         "pass mask= (for instance the matrix's own pattern) to fit the stored entries only")
+    if int(k) > 128:
+        raise ValueError(f"distance_type='is' supports k <= 128 components on dense input (got k = {k})")
+    # the device holds float32: a positive value that underflows to 0 there (or overflows to inf) is refused, not dropped
+    with np.errstate(over='ignore', under='ignore'):
+        lowest, highest = np.float32(np.min(x)), np.float32(np.max(x))
+    if not lowest > 0:                                          # (NaN included)
+        raise ValueError("distance_type='is': the data must be strictly positive in float32 (an entry is <= 0, NaN or "
+                         "below the float32 range); it is not lifted by its minimum")
+    if not np.isfinite(highest):
+        raise ValueError("distance_type='is': an entry is infinite or beyond the float32 range")
+
+
 def _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine):
     """MUR on scipy.sparse input (kernels_sparse.hip): the caller's matrix is copied into canonical CSR and never modified.
     The recorded objective is evaluated in float64 from the non-zeros plus k x k terms, so the Euclidean stop rule needs
@@ -96,6 +117,8 @@ def _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, la
     if engine is not None:
         raise ValueError('mask=: engine= is not supported (the engine is created for the observed entries)')
     xs = masked.observed(x, mask, k)
+    if dist == L.IS:
+        masked.check_positive(xs)
     init = utils.initial_factors(xs, k, nndsvd_init)
     with Engine.for_sparse(xs, k, device=device, masked=True) as eng:
         eng.set_factors(*init)
