@@ -94,6 +94,27 @@ int nmfx_upload_v(nmfx_handle_t h, const void* host, int dtype, int64_t ld,
  * stream); the call returns when the copy is done, `dev` may then be freed.                 */
 int nmfx_upload_v_device(nmfx_handle_t h, const void* dev, int dtype, int64_t ld,
                          int64_t row0, int64_t rows);
+/* ---- per-entry weights (version 340) ---------------------------------------
+ * Omega >= 0 with the shape of the local V, conventions of nmfx_upload_v (rows [row0, row0 + rows), row stride `ld`, dtype
+ * NMFX_F32 / F64, stored as f32).  A cell with weight 0 is unknown, not zero: V is not part of any sum there.  The buffer
+ * (the size of V) is allocated zeroed by the first call, so rows never uploaded carry zero weight; NMFX_E_NOMEM with a
+ * message when it does not fit.  Legal on a dense handle with k <= 128: NMFX_E_ARG on a sparse handle and for k > 128,
+ * nothing launched.  The entries must be finite and >= 0 (not checked here).
+ * While weights are present nmfx_mur_run / nmfx_mur_finish with NMFX_EU, NMFX_KL or NMFX_IS run the weighted update
+ * (kernels_weighted.hip, exact f32 whatever the precision mode; nmfx_get_note says so), with T = W H and W' the new W:
+ *   Euclidean  W <- W ((Om.V) H^T) / ((Om.T) H^T + lambda_w W + 1e-9)                          1/2 Sum om (v - T)^2
+ *   KL         A = W ((Om.V / (T + 1e-9)) H^T),  B = Om H^T,  W <- 2 A / (B + sqrt(B^2 + 4 lambda_w A)),  0 where B = 0
+ *                                                                                              Sum om [v log(v / T) - v + T]
+ *   IS         q = T + 1e-9,  W <- W sqrt( ((Om.V / q^2) H^T) / ((Om / q) H^T + lambda_w) ),  0 where the denominator is 0
+ *                                                                                              Sum om [v / q - log(v / q) - 1]
+ *   H likewise with W' and lambda_h; the objective is recorded in f64 with the iteration contract of nmfx_mur_run.
+ * nmfx_set_factors, nmfx_get_factors, nmfx_get_state, nmfx_get_objectives, nmfx_set_stop_guard, nmfx_resume,
+ * nmfx_set_stream, nmfx_reset_stream, nmfx_synchronize and nmfx_destroy keep their meaning, as do the entry points that
+ * only move data or read settings.  Every other compute entry point -- the MUR phase / chunk / slice / sharded forms,
+ * pair mode, nmfx_objective_f64, nmfx_profile_repeat, AO-ADMM, ADMM, ANLS, nmfx_topk_svd -- returns NMFX_E_ARG with a
+ * message naming the weights and launches nothing.  nmfx_clear_weights frees the buffer: the handle behaves as before. */
+int nmfx_upload_weights(nmfx_handle_t h, const void* host, int dtype, int64_t ld, int64_t row0, int64_t rows);
+int nmfx_clear_weights(nmfx_handle_t h);
 /* ---- sparse V (version 310) ----------------------------------------------
  * A handle for a sparse m x n V with `nnz` stored entries, 1 <= k <= 256.  It runs MUR (both losses) without ever
  * forming V densely: nmfx_upload_csr takes V as CSR -- row_ptr [m + 1] (int64: nnz may pass 2^31), col_idx [nnz]

@@ -37,6 +37,8 @@ SIGNATURES = {
     "nmfx_set_masked": (_i32, [_vp, _i32]),
     "nmfx_upload_v": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
     "nmfx_upload_v_device": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
+    "nmfx_upload_weights": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
+    "nmfx_clear_weights": (_i32, [_vp]),
     "nmfx_set_factors": (_i32, [_vp, _vp, _vp]),
     "nmfx_get_factors": (_i32, [_vp, _vp, _vp]),
     "nmfx_get_matrix": (_i32, [_vp, C.c_char_p, _vp]),

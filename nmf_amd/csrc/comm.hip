@@ -136,7 +136,7 @@ extern "C" int nmfx_comm_unique_id(void* id128) {
 }
 
 extern "C" int nmfx_comm_init_rank(nmfx_handle_t E, const void* id128, int rank, int world) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     if (!id128 || world < 1 || rank < 0 || rank >= world) { E->err = "comm_init_rank: 0 <= rank < world, id from nmfx_comm_unique_id of rank 0"; return NMFX_E_ARG; }
     int rc = need_rccl(E); if (rc) return rc;
@@ -164,7 +164,7 @@ extern "C" int nmfx_comm_init_rank(nmfx_handle_t E, const void* id128, int rank,
 }
 
 extern "C" int nmfx_comm_destroy(nmfx_handle_t E) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     nmfx_comm_free(E);
     nmfx_set_exchange_rank(E, 0, 0);
@@ -172,7 +172,7 @@ extern "C" int nmfx_comm_destroy(nmfx_handle_t E) {
 }
 
 extern "C" int nmfx_comm_info(nmfx_handle_t E, int* rank, int* world, int* merged, int* rccl_version) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     if (rank) *rank = E->comm ? E->comm->rank : 0;
     if (world) *world = E->comm ? E->comm->world : 1;
@@ -200,7 +200,7 @@ static int reduce_range(nmfx_engine* E, int which, int64_t first, int64_t count,
 }
 
 extern "C" int nmfx_comm_all_reduce(nmfx_handle_t E, int which, int64_t first, int64_t count) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     int rc = have_comm(E); if (rc) return rc;
     NMFX_HIP(hipSetDevice(E->device));
     return reduce_range(E, which, first, count, E->stream);
@@ -208,7 +208,7 @@ extern "C" int nmfx_comm_all_reduce(nmfx_handle_t E, int which, int64_t first, i
 
 // MIN over the ranks of a few host integers (mode negotiation, test rigs); blocking
 extern "C" int nmfx_comm_all_min(nmfx_handle_t E, int64_t* vals, int n) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     int rc = have_comm(E); if (rc) return rc;
     if (!vals || n < 1 || n > 64) { E->err = "comm_all_min: 1 .. 64 values"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
@@ -228,7 +228,7 @@ extern "C" int nmfx_comm_all_min(nmfx_handle_t E, int64_t* vals, int n) {
 // communicator the data path uses (a barrier through ANOTHER communicator -- torch.distributed's -- wakes that one up from idle:
 // ~0.5 ms at the end of a timed region), then a stream synchronisation.
 extern "C" int nmfx_comm_barrier(nmfx_handle_t E) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     int rc = have_comm(E); if (rc) return rc;
     NMFX_HIP(hipSetDevice(E->device));
     NMFX_RCCL(rccl().AllReduce(E->comm->bar, E->comm->bar, 1, ncclInt64, ncclSum, E->comm->comm, E->stream));
@@ -239,7 +239,7 @@ extern "C" int nmfx_comm_barrier(nmfx_handle_t E) {
 // Agree on what fixes the SEQUENCE of collectives (see nmf_amd/dist.py: DeviceShard.negotiate): merged objective exchange, chunk
 // unit, arithmetic mode.  NMFX_E_STATE when the ranks' arithmetic modes differ.
 extern "C" int nmfx_comm_negotiate(nmfx_handle_t E) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     int rc = have_comm(E); if (rc) return rc;
     nmfx_comm* c = E->comm;
     const int64_t bf16 = nmfx_get_precision(E) == 1 ? 1 : 0;
@@ -261,7 +261,7 @@ extern "C" int nmfx_comm_negotiate(nmfx_handle_t E) {
 }
 
 extern "C" int nmfx_comm_set_graph(nmfx_handle_t E, int enable) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     int rc = have_comm(E); if (rc) return rc;
     E->comm->want_graph = enable != 0;
     if (!enable) drop_graph(E->comm);
@@ -274,7 +274,7 @@ extern "C" int nmfx_comm_set_graph(nmfx_handle_t E, int enable) {
 // for which the sliced update is not available (nmfx_mur_slice_info: KL loss, exact-f32 epilogues, separate objective exchange,
 // n not a multiple of 64 * world) take the all-reduce.  Must be the same on every rank (as NMFX_DIST_EXCHANGE is).
 extern "C" int nmfx_comm_set_exchange(nmfx_handle_t E, int mode) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     int rc = have_comm(E); if (rc) return rc;
     if (mode != 0 && mode != 1) { E->err = "comm_set_exchange: 0 (all-reduce) or 1 (reduce-scatter + all-gather)"; return NMFX_E_ARG; }
     if (E->comm->exchange != mode) drop_graph(E->comm);
@@ -283,7 +283,7 @@ extern "C" int nmfx_comm_set_exchange(nmfx_handle_t E, int mode) {
 }
 
 extern "C" int nmfx_comm_get_exchange(nmfx_handle_t E, int* mode) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !mode) return NMFX_E_ARG;
     *mode = E->comm ? E->comm->exchange : 0;
     return NMFX_OK;
@@ -447,7 +447,7 @@ extern "C" int nmfx_mur_finish_sharded(nmfx_handle_t E, int distance, int64_t mi
 }
 
 extern "C" int nmfx_comm_graph_replays(nmfx_handle_t E, int64_t* replays) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !replays) return NMFX_E_ARG;
     *replays = E->comm ? E->comm->replays : 0;
     return NMFX_OK;

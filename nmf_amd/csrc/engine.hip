@@ -44,7 +44,7 @@ static int preload_once(nmfx_engine* E) {
     static std::map<int, bool> done;
     std::lock_guard<std::mutex> lock(mu);
     if (done[E->device]) return NMFX_OK;
-    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_is() || nmfx_preload_aoadmm() ||
+    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_is() || nmfx_preload_weighted() || nmfx_preload_aoadmm() ||
         nmfx_preload_anls() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic() ||
         nmfx_preload_sparse()) {
         E->err = "loading the kernels onto the device failed"; return NMFX_E_HIP; }
@@ -125,7 +125,7 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
 
 extern "C" {
 
-int nmfx_version(void) { return 330; }      // 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 340; }      // 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -256,7 +256,7 @@ int nmfx_destroy(nmfx_handle_t E) {
     nmfx_comm_free(E);
     for (auto& t : E->prof_pending) { hipEventDestroy(std::get<1>(t)); hipEventDestroy(std::get<2>(t)); }
     void* bufs[] = {E->V, E->W[0], E->W[1], E->H, E->HHt, E->HHt_part, E->G_part, E->A_part, E->B_part,
-                    E->obj_part, E->is_part, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
+                    E->obj_part, E->is_part, E->Om, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
                     E->obj_hist, E->state, E->dualW, E->dualH, E->auxW, E->auxH, E->Minv, E->nrm_part,
                     E->inner_hist, E->Pw, E->Ph, E->Asum, E->S, E->DV, E->Vt, E->Vtile, E->Bt_part, E->Whi[0], E->Whi[1],
                     E->Wlo[0], E->Wlo[1], E->WThi, E->WTlo, E->Hhi, E->Hlo, E->HThi, E->HTlo, E->nrm_rounds, E->bkX, E->bkU,
@@ -286,7 +286,7 @@ int nmfx_reset_stream(nmfx_handle_t E) {
 }
 
 int nmfx_set_precision(nmfx_handle_t E, int mode) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (E) { E->himg_both = false; E->wimg_ok = false; E->gxb_img_ready = false; }
     if (!E || (mode != 0 && mode != 1)) { if (E) E->err = "precision must be 0 (f32) or 1 (split bf16)"; return NMFX_E_ARG; }
     if (E->precision != mode) nmfx_comm_invalidate(E);
@@ -297,7 +297,7 @@ int nmfx_set_precision(nmfx_handle_t E, int mode) {
 const char* nmfx_get_note(nmfx_handle_t E) { return E ? E->note.c_str() : ""; }
 
 int nmfx_get_precision(nmfx_handle_t E) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     return (E->precision == 1 && nmfx_bf16_supported(E)) ? 1 : 0;
 }
@@ -309,16 +309,8 @@ int nmfx_synchronize(nmfx_handle_t E) {
     return NMFX_OK;
 }
 
-int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int64_t row0, int64_t rows) {
-    NMFX_DENSE_ONLY(E);
-    if (E) E->anls_a_ready = false;
-    if (!E) return NMFX_E_ARG;
-    if (!host || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
-        E->err = "upload_v: bad row range or leading dimension"; return NMFX_E_ARG; }
-    NMFX_HIP(hipSetDevice(E->device));
-    if (rows == 0) return NMFX_OK;
-    if (E->have_v) { int rc_ = nmfx_need_v(E); if (rc_) return rc_; }       // (rows of a V whose row-major copy was dropped)
-    float* dst = E->V + row0 * E->np;
+// rows of a host matrix (row stride ld, dtype NMFX_F32 / NMFX_F64) into rows of a padded [..][np] f32 device matrix
+static int copy_rows_in(nmfx_engine* E, float* dst, const void* host, int dtype, int64_t ld, int64_t rows, const char* who) {
     if (dtype == NMFX_F32) {
         NMFX_HIP(hipMemcpy2DAsync(dst, (size_t)E->np * 4, host, (size_t)ld * 4, (size_t)E->n * 4,
                                   (size_t)rows, hipMemcpyHostToDevice, E->stream));
@@ -340,7 +332,20 @@ int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int6
             if (e != hipSuccess) { hipFree(stage); E->err = hipGetErrorString(e); return NMFX_E_HIP; }
         }
         hipFree(stage);
-    } else { E->err = "upload_v: dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
+    } else { E->err = std::string(who) + ": dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
+    return NMFX_OK;
+}
+
+int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int64_t row0, int64_t rows) {
+    NMFX_NOT_SPARSE(E);
+    if (E) E->anls_a_ready = false;
+    if (!E) return NMFX_E_ARG;
+    if (!host || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
+        E->err = "upload_v: bad row range or leading dimension"; return NMFX_E_ARG; }
+    NMFX_HIP(hipSetDevice(E->device));
+    if (rows == 0) return NMFX_OK;
+    if (E->have_v) { int rc_ = nmfx_need_v(E); if (rc_) return rc_; }       // (rows of a V whose row-major copy was dropped)
+    { int rc_ = copy_rows_in(E, E->V + row0 * E->np, host, dtype, ld, rows, "upload_v"); if (rc_) return rc_; }
     E->have_v = true;
     E->bf_ready = false;
     E->gxb_v_ready = false;
@@ -348,8 +353,55 @@ int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int6
     return NMFX_OK;
 }
 
+// Per-entry weights (version 340): a second [mp][np] f32 matrix beside V, zero where nothing was uploaded (padding included).
+static const char* const WEIGHTS_NOTE = "per-entry weights are present: MUR runs the weighted exact-f32 kernels whatever the precision mode";
+int nmfx_upload_weights(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int64_t row0, int64_t rows) {
+    if (!E) return NMFX_E_ARG;
+    if (E->sp) { E->err = "upload_weights: not available on a sparse handle (its stored entries are its 0 / 1 weights: nmfx_set_masked)"; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = "upload_weights: per-entry weights need k <= 128"; return NMFX_E_ARG; }
+    if (!host || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
+        E->err = "upload_weights: bad row range or leading dimension"; return NMFX_E_ARG; }
+    if (dtype != NMFX_F32 && dtype != NMFX_F64) { E->err = "upload_weights: dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
+    NMFX_HIP(hipSetDevice(E->device));
+    if (!E->Om) {
+        const size_t bytes = (size_t)E->mp * E->np * sizeof(float);
+        float* buf = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&buf), bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            E->err = "upload_weights: the weights (" + std::to_string(bytes >> 20) + " MiB, the size of V) do not fit into the free device memory";
+            return NMFX_E_NOMEM;
+        }
+        hipError_t e = hipMemsetAsync(buf, 0, bytes, E->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
+        if (e != hipSuccess) { hipFree(buf); E->err = hipGetErrorString(e); return NMFX_E_HIP; }
+        E->Om = buf;
+        if (E->note.find(WEIGHTS_NOTE) == std::string::npos) E->note += (E->note.empty() ? "" : "; ") + std::string(WEIGHTS_NOTE);
+    }
+    E->anls_a_ready = false;
+    if (rows == 0) return NMFX_OK;
+    return copy_rows_in(E, E->Om + row0 * E->np, host, dtype, ld, rows, "upload_weights");
+}
+
+int nmfx_clear_weights(nmfx_handle_t E) {
+    if (!E) return NMFX_E_ARG;
+    if (!E->Om) return NMFX_OK;
+    NMFX_HIP(hipSetDevice(E->device));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    NMFX_HIP(hipFree(E->Om));
+    E->Om = nullptr;
+    const std::string w(WEIGHTS_NOTE);
+    size_t at = E->note.find(w);
+    if (at != std::string::npos) {
+        size_t len = w.size();
+        if (at >= 2 && E->note.compare(at - 2, 2, "; ") == 0) { at -= 2; len += 2; }
+        else if (E->note.compare(at + len, 2, "; ") == 0) len += 2;
+        E->note.erase(at, len);
+    }
+    return NMFX_OK;
+}
+
 int nmfx_upload_v_device(nmfx_handle_t E, const void* dev, int dtype, int64_t ld, int64_t row0, int64_t rows) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (E) E->anls_a_ready = false;
     if (!E) return NMFX_E_ARG;
     if (!dev || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
@@ -458,7 +510,7 @@ int nmfx_get_factors(nmfx_handle_t E, double* w, double* hmat) {
 }
 
 int nmfx_get_matrix(nmfx_handle_t E, const char* name, double* out) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !name || !out) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     const std::string s(name);
@@ -474,7 +526,7 @@ int nmfx_get_matrix(nmfx_handle_t E, const char* name, double* out) {
 }
 
 int nmfx_set_matrix(nmfx_handle_t E, const char* name, const double* in) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !name || !in) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     int rc;
@@ -503,7 +555,7 @@ int nmfx_get_state(nmfx_handle_t E, int* stop_rule, int64_t* stop_i, int64_t* n_
 }
 
 int nmfx_get_diagnostics(nmfx_handle_t E, int64_t* nnls_evicted, int64_t* nnls_capped) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
@@ -513,7 +565,7 @@ int nmfx_get_diagnostics(nmfx_handle_t E, int64_t* nnls_evicted, int64_t* nnls_c
 }
 
 int nmfx_get_nnls_fallbacks(nmfx_handle_t E, int64_t* problems, int64_t* half_steps) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
@@ -523,7 +575,7 @@ int nmfx_get_nnls_fallbacks(nmfx_handle_t E, int64_t* problems, int64_t* half_st
 }
 
 int nmfx_get_inner_paths(nmfx_handle_t E, int64_t out[4]) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !out) return NMFX_E_ARG;
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
@@ -542,7 +594,7 @@ int nmfx_get_objectives(nmfx_handle_t E, int64_t first, int64_t count, double* o
 }
 
 int nmfx_get_inner_counts(nmfx_handle_t E, int64_t first, int64_t count, int32_t* out) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !out || first < 0 || count < 0 || first + count > E->inner_cap) {
         if (E) E->err = "get_inner_counts: range"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
@@ -554,7 +606,7 @@ int nmfx_get_inner_counts(nmfx_handle_t E, int64_t first, int64_t count, int32_t
 
 // ---- exchange buffers ----------------------------------------------------
 int nmfx_exchange_sizes(nmfx_handle_t E, int64_t* n_f32, int64_t* n_f64) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     if (n_f32) *n_f32 = (int64_t)E->kp * E->np + (int64_t)E->kp * E->kp + E->kp + NMFX_XTAIL;
     if (n_f64) *n_f64 = 8 + 4 * NMFX_MAX_FUSED_ROUNDS;
@@ -562,7 +614,7 @@ int nmfx_exchange_sizes(nmfx_handle_t E, int64_t* n_f32, int64_t* n_f64) {
 }
 
 int nmfx_set_exchange_rank(nmfx_handle_t E, int rank, int world) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     if (world == 0) { E->xrank = -1; E->xworld = 0; return NMFX_OK; }           // back to the separate f64 exchange
     if (world < 1 || world > NMFX_XTAIL_RANKS || rank < 0 || rank >= world) { E->err = "set_exchange_rank: 1 <= world <= 64, 0 <= rank < world"; return NMFX_E_ARG; }
@@ -572,7 +624,7 @@ int nmfx_set_exchange_rank(nmfx_handle_t E, int rank, int world) {
 }
 
 int nmfx_set_exchange_buffers(nmfx_handle_t E, void* f32, int64_t n_f32, void* f64, int64_t n_f64) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !f32 || !f64) return NMFX_E_ARG;
     int64_t need32, need64;
     nmfx_exchange_sizes(E, &need32, &need64);
@@ -589,7 +641,7 @@ int nmfx_set_exchange_buffers(nmfx_handle_t E, void* f32, int64_t n_f32, void* f
 }
 
 int nmfx_get_exchange_buffers(nmfx_handle_t E, void** f32, void** f64) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     if (f32) *f32 = E->xf32;
     if (f64) *f64 = E->xf64;
@@ -615,14 +667,14 @@ int nmfx_resume(nmfx_handle_t E) {
 
 // ---- iteration base (hipGraph replay support) --------------------------------
 int nmfx_reserve_objectives(nmfx_handle_t E, int64_t count) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || count < 0) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     return nmfx_ensure_obj_capacity(E, count + 2);
 }
 
 int nmfx_shift_iteration_base(nmfx_handle_t E, int64_t delta) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
     hipLaunchKernelGGL(shift_iteration_base_kernel, dim3(1), dim3(1), 0, E->stream, E->state, (long long)delta);
@@ -794,10 +846,29 @@ static int is_dense_ok(nmfx_engine* E, const char* who) {
     return NMFX_OK;
 }
 
+// With per-entry weights (nmfx_upload_weights; dense, k <= 128 by construction) every loss runs kernels_weighted.hip
+static int weights_ok(nmfx_engine* E, int distance, const char* who) {
+    if (distance != NMFX_EU && distance != NMFX_KL && distance != NMFX_IS) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = std::string(who) + ": per-entry weights need k <= 128"; return NMFX_E_ARG; }
+    return NMFX_OK;
+}
+
 int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h, int64_t min_iter,
                  double tol1, double tol2, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
     if (E->sp) return nmfx_sparse_mur_run(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
+    if (E->Om) {                                       // per-entry weights: kernels_weighted.hip, all three losses
+        { int rc_wt = weights_ok(E, distance, "mur_run"); if (rc_wt) return rc_wt; }
+        int rc = check_ready(E, first, count); if (rc) return rc;
+        E->himg_both = false; E->kl_h_iter = -2; E->is_run = distance == NMFX_IS;
+        for (int64_t j = first; j < first + count && !rc; ++j) {
+            if ((rc = nmfx_mur_wt_phase_a(E, distance, lambda_w, j))) break;
+            E->wsel = (int)((j + 1) & 1);
+            E->w_in_place = false;
+            rc = nmfx_mur_wt_phase_b(E, distance, lambda_h, min_iter, tol1, tol2, j);
+        }
+        return rc;
+    }
     if (distance == NMFX_IS) {
         { int rc_is = is_dense_ok(E, "mur_run"); if (rc_is) return rc_is; }
         int rc = check_ready(E, first, count); if (rc) return rc;
@@ -825,6 +896,13 @@ int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1
                     int64_t iters_done) {
     if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
     int rc;
+    if (E && E->Om) {
+        if ((rc = weights_ok(E, distance, "mur_finish"))) return rc;
+        if ((rc = check_ready(E, iters_done, 1))) return rc;
+        E->is_run = distance == NMFX_IS;
+        if ((rc = nmfx_mur_wt_finish_a(E, distance, iters_done))) return rc;
+        return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
+    }
     if (E && distance == NMFX_IS) {
         if ((rc = is_dense_ok(E, "mur_finish"))) return rc;
         if ((rc = check_ready(E, iters_done, 1))) return rc;
@@ -852,7 +930,7 @@ static void drain_profile(nmfx_engine* E) {
 }
 
 int nmfx_profile_enable(nmfx_handle_t E, int on) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     drain_profile(E);
     E->prof = on != 0;
@@ -860,7 +938,7 @@ int nmfx_profile_enable(nmfx_handle_t E, int on) {
 }
 
 int nmfx_profile_get(nmfx_handle_t E, const char* name, double* total_ms, int64_t* launches) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !name) return NMFX_E_ARG;
     drain_profile(E);
     auto it = E->prof_slots.find(name);
@@ -921,7 +999,7 @@ int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int re
 }
 
 int nmfx_profile_reset(nmfx_handle_t E) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     drain_profile(E);
     E->prof_slots.clear();

@@ -248,7 +248,7 @@ static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double
 }
 
 extern "C" int nmfx_set_l2n_operator(nmfx_handle_t E, int which, const double* p) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || !p || (which != 0 && which != 1)) { if (E) E->err = "set_l2n_operator: bad argument"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
     float** dst = which == 0 ? &E->Pw : &E->Ph;

@@ -910,7 +910,7 @@ extern "C" int nmfx_anls_phase_h(nmfx_handle_t E, double lambda_h, int64_t j) {
 }
 
 extern "C" int nmfx_anls_set_distance(nmfx_handle_t E, int distance) {
-    NMFX_DENSE_ONLY(E);
+    NMFX_NOT_SPARSE(E);
     if (!E || (distance != NMFX_EU && distance != NMFX_KL)) { if (E) E->err = "Unknown distance type."; return NMFX_E_ARG; }
     E->anls_dist = distance;
     E->anls_a_ready = false;

@@ -82,8 +82,9 @@ struct nmfx_engine {
     int64_t kl_h_iter = -2;        // outer iteration whose H epilogue wrote the H partials and the H / H^T images (valid for iteration + 1 only)
     float* A_part = nullptr;       // [wsplit][mp][kp]
     float* B_part = nullptr;       // [hsplit][kp][np]
-    float* is_part = nullptr;      // MUR-IS (kernels_is.hip): [splits][numerator | denominator] slabs of the phase in flight, allocated on first use
+    float* is_part = nullptr;      // MUR-IS (kernels_is.hip) and weighted MUR (kernels_weighted.hip): [splits][numerator | denominator] slabs of the phase in flight, allocated on first use
     int64_t is_part_cap = 0;
+    float* Om = nullptr;           // per-entry weights (nmfx_upload_weights): [mp][np] like V, zero where nothing was uploaded; nullptr = none
     double* obj_part = nullptr;    // [max blocks]
     int64_t obj_part_cap = 0;
     float* xf32 = nullptr;         // exchange: [kp*np | kp*kp | kp]
@@ -259,6 +260,10 @@ int nmfx_finish_b(nmfx_engine* E, int64_t min_iter, double tol1, double tol2, in
 int nmfx_mur_is_phase_a(nmfx_engine* E, double lambda_w, int64_t j);
 int nmfx_mur_is_phase_b(nmfx_engine* E, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
 int nmfx_mur_is_finish_a(nmfx_engine* E, int64_t j);
+// kernels_weighted.hip: MUR with per-entry weights E->Om (dense, k <= 128, exact f32), distance NMFX_EU / NMFX_KL / NMFX_IS
+int nmfx_mur_wt_phase_a(nmfx_engine* E, int distance, double lambda_w, int64_t j);
+int nmfx_mur_wt_phase_b(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
+int nmfx_mur_wt_finish_a(nmfx_engine* E, int distance, int64_t j);
 // One solver family per set of factors: the families keep different device state next to W and H (MUR: W ping-pong and bf16 images of
 // both factors; AO-ADMM / ADMM: duals and auxiliaries; ANLS: warm-start supports), and a family that starts in the middle of another's
 // run would read leftovers.  A second family on the same handle needs nmfx_get_factors -> nmfx_set_factors first (NMFX_E_STATE otherwise).
@@ -339,8 +344,14 @@ int nmfx_sparse_mur_run(nmfx_engine* E, int distance, double lambda_w, double la
 int nmfx_sparse_mur_finish(nmfx_engine* E, int distance, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
 int nmfx_sparse_objective_f64(nmfx_engine* E, double* out);
 // First statement of every entry point a sparse handle does not support: NMFX_E_ARG with a message, nothing launched.
-#define NMFX_DENSE_ONLY(E) do { if ((E) && (E)->sp) { \
+#define NMFX_NOT_SPARSE(E) do { if ((E) && (E)->sp) { \
     (E)->err = std::string(__func__) + ": not available on a sparse handle (nmfx_create_csr handles run MUR only)"; \
+    return NMFX_E_ARG; } } while (0)
+// ... and of every COMPUTE entry point but nmfx_mur_run / nmfx_mur_finish: those two alone know the per-entry weights of
+// nmfx_upload_weights, so everything else that would compute from V refuses while weights are present.
+#define NMFX_DENSE_ONLY(E) do { NMFX_NOT_SPARSE(E); if ((E) && (E)->Om) { \
+    (E)->err = std::string(__func__) + ": not available while per-entry weights are present (nmfx_upload_weights): " \
+               "only nmfx_mur_run / nmfx_mur_finish compute with weights; nmfx_clear_weights removes them"; \
     return NMFX_E_ARG; } } while (0)
 
 int nmfx_preload_sparse();
@@ -349,6 +360,7 @@ int nmfx_preload_products();
 int nmfx_preload_mur();
 int nmfx_preload_kl();
 int nmfx_preload_is();
+int nmfx_preload_weighted();
 int nmfx_preload_aoadmm();
 int nmfx_preload_anls();
 int nmfx_preload_svd();

@@ -118,6 +118,23 @@ class Engine:
         self._ck(self.lib.nmfx_upload_v_device(self.h, C.c_void_p(int(ptr)), code, int(ld or self.n),
                                                int(row0), int(rows)))
 
+    def upload_weights(self, weights, row0=0):
+        """Per-entry weights for rows [row0, row0 + rows) of V (dense handle, k <= 128; rows never uploaded weigh 0).
+        While present, mur_run / mur_finish run the weighted update and the other solvers refuse (include/nmfx.h)."""
+        v = np.asarray(weights)
+        if v.dtype not in (np.float32, np.float64):
+            v = v.astype(np.float64)
+        if v.ndim != 2 or v.shape[1] != self.n:
+            raise ValueError("weights block has the wrong shape")
+        if not (v.strides[1] == v.itemsize and v.strides[0] % v.itemsize == 0 and v.strides[0] > 0):
+            v = np.ascontiguousarray(v)
+        ld = v.strides[0] // v.itemsize
+        self._ck(self.lib.nmfx_upload_weights(self.h, _ptr(v), L.F32 if v.dtype == np.float32 else L.F64,
+                                              ld, int(row0), v.shape[0]))
+
+    def clear_weights(self):
+        self._ck(self.lib.nmfx_clear_weights(self.h))
+
     def set_factors(self, w, h):
         w = np.ascontiguousarray(w, dtype=np.float64)
         h = np.ascontiguousarray(h, dtype=np.float64)

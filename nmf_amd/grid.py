@@ -41,6 +41,8 @@ def factorize_grid(data, method='mur', *, features, lambda_w=(0.0,), lambda_h=(0
         raise Exception('Method not known. Choose one from: mur anls admm ao_admm')
     if 'mask' in common:
         raise TypeError("factorize_grid: mask= is not supported (run mur(x, k, mask=...) per grid point)")
+    if 'weights' in common:
+        raise TypeError("factorize_grid: weights= is not supported (run mur(x, k, weights=...) per grid point)")
     solver = getattr(import_module('.' + method, __package__), method)
     if method != 'mur' and common.get('distance_type') == 'is':
         raise ValueError(f"{method}: distance_type='is' (Itakura-Saito) is a loss of mur only")

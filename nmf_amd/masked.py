@@ -70,6 +70,15 @@ def _values(x, row_ptr, col_idx, dtype):
     return out
 
 
+def check_values(vals):
+    """The observed values (a non-empty 1-D array) must be finite and non-negative."""
+    if not np.all(np.isfinite(vals)):
+        raise ValueError('masked input: an observed value is NaN or infinite')
+    if np.min(vals) < 0:
+        raise ValueError('masked input: an observed value is negative (MUR needs non-negative data; '
+                         'masked input is not lifted by its minimum)')
+
+
 def observed(x, mask, k=None):
     """Canonical CSR (float32 values if `x` is float32, else float64) of `x` at the positions where `mask` is non-zero.
     `x`: a 2-D numpy array or any scipy.sparse matrix (an observed position it does not store is 0); `mask`: a boolean
@@ -94,11 +103,7 @@ def observed(x, mask, k=None):
     if col_idx.size == 0:
         raise ValueError('mask observes no entry')
     vals = _values(x, row_ptr, col_idx, dtype)
-    if not np.all(np.isfinite(vals)):
-        raise ValueError('masked input: an observed value is NaN or infinite')
-    if np.min(vals) < 0:
-        raise ValueError('masked input: an observed value is negative (MUR needs non-negative data; '
-                         'masked input is not lifted by its minimum)')
+    check_values(vals)
     c = sp.csr_matrix((vals, col_idx, row_ptr), shape=x.shape)
     c.has_sorted_indices = True
     return c
@@ -106,10 +111,15 @@ def observed(x, mask, k=None):
 
 def check_positive(c):
     """The Itakura-Saito divergence is undefined at 0: every observed value of the canonical CSR `c` must be > 0."""
-    if not c.nnz:
+    check_positive_values(c.data)
+
+
+def check_positive_values(vals):
+    """check_positive on the observed values themselves (a 1-D array)."""
+    if not vals.size:
         return
     with np.errstate(over='ignore', under='ignore'):            # (the device holds float32: judge that image)
-        lowest, highest = np.float32(np.min(c.data)), np.float32(np.max(c.data))
+        lowest, highest = np.float32(np.min(vals)), np.float32(np.max(vals))
     if not lowest > 0:
         raise ValueError("distance_type='is': an observed value is 0, or underflows to 0 in float32 (the Itakura-Saito "
                          "divergence needs strictly positive data; leave such entries out of the mask)")

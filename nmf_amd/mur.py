@@ -7,11 +7,13 @@ import logging
 from collections import namedtuple
 
 import numpy as np
+import scipy.sparse as sp
 
 from . import _lib as L
 from . import masked
 from . import sparse
 from . import utils
+from . import weighted
 from ._driver import Referee, Results, drive
 from .engine import Engine
 
@@ -19,7 +21,7 @@ Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_in
 
 
 def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5,
-        lambda_w=0.0, lambda_h=0.0, nndsvd_init=(False, 'zero'), save_dir='./results/', device=0, engine=None, mask=None):
+        lambda_w=0.0, lambda_h=0.0, nndsvd_init=(False, 'zero'), save_dir='./results/', device=0, engine=None, mask=None, weights=None):
     """Lee-Seung NMF.  x: 2-D non-negative data (a numpy array, or any scipy.sparse matrix / array with 1 <= k <= 256:
     never densified), k: number of components.
 
@@ -28,12 +30,17 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
     lifted), min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init=(bool, variant) and
     save_dir have the reference's meaning.  mask: None, or a boolean / 0-1 array or scipy.sparse matrix of x's shape
     whose non-zero entries are the observed set -- only x there is fitted and read (masked MUR, nmf_amd.masked;
-    1 <= k <= 256).  Returns Results(w, h, i, obj_history, experiment) with float64 w, h."""
+    1 <= k <= 256).  weights: None, or a dense real array Omega >= 0 of x's shape (boolean counts as 0 / 1): the fit is
+    Sum omega * loss(x, wh) on the dense kernels with k <= 128; a cell with weight 0 is unknown and x is not read there
+    (nmf_amd.weighted; not together with mask= or engine=).  Returns Results(w, h, i, obj_history, experiment) with float64 w, h."""
     experiment = Experiment('mur', k, distance_type, nndsvd_init, max_iter, tol1, tol2,
                             lambda_w, lambda_h)
     if distance_type not in ('eu', 'kl', 'is'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31
     dist = {'eu': L.EU, 'kl': L.KL, 'is': L.IS}[distance_type]
+    if weights is not None:
+        return _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h,
+                             nndsvd_init, device, engine)
     if dist == L.IS and mask is None:
         _check_is_input(x, k)
     if mask is not None:
@@ -121,6 +128,40 @@ def _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, la
         masked.check_positive(xs)
     init = utils.initial_factors(xs, k, nndsvd_init)
     with Engine.for_sparse(xs, k, device=device, masked=True) as eng:
+        eng.set_factors(*init)
+        logging.info('Entering Main Loop.')
+        i, history = drive(
+            eng,
+            lambda first, count: eng.mur_run(dist, lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
+            lambda done: eng.mur_finish(dist, min_iter, tol1, tol2, done),
+            max_iter, tol1, tol2, referee=None)
+        mur.last_referee = None
+        w, h = eng.get_factors()
+    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init,
+                  device, engine):
+    """MUR with per-entry weights (kernels_weighted.hip on a dense handle, exact f32): Sum omega * loss(x, wh).  Everything
+    is validated before any device work; nothing of the caller's is modified or lifted.  Same start as the masked path
+    (the global RNG's draws as in mur; NNDSVD, unweighted and on the host, of x with the zero-weight cells set to 0),
+    same Results, printed lines and batching; the recorded objective is the weighted one (nmf_amd.weighted.objective),
+    summed per entry, so no float64 referee is needed."""
+    if mask is not None:
+        raise ValueError('weights= and mask= exclude each other (a mask is the 0 / 1 case of weights)')
+    if engine is not None:
+        raise ValueError('weights=: engine= is not supported (the engine is created for the weighted data)')
+    x32, w32 = weighted.prepare(x, weights, k, experiment.distance_type)
+    if nndsvd_init[0]:
+        with np.errstate(invalid='ignore'):
+            start = np.where(w32 > 0, np.asarray(x), 0)
+        init = utils.initial_factors(sp.csr_matrix(start), k, nndsvd_init)      # (the masked path's NNDSVD)
+        del start
+    else:
+        init = utils.initial_factors(x32, k, nndsvd_init)
+    with Engine(x32.shape[0], x32.shape[1], k, device=device) as eng:
+        eng.upload_v(x32)
+        eng.upload_weights(w32)
         eng.set_factors(*init)
         logging.info('Entering Main Loop.')
         i, history = drive(
