@@ -46,7 +46,7 @@ enum {
 };
 
 enum { NMFX_F32 = 0, NMFX_F64 = 1 };                 /* host dtype of V          */
-enum { NMFX_EU = 0, NMFX_KL = 1, NMFX_IS = 2 };      /* distance_type (IS: nmfx_mur_run / nmfx_mur_finish only) */
+enum { NMFX_EU = 0, NMFX_KL = 1, NMFX_IS = 2, NMFX_BETA = 3 };      /* distance_type (IS, BETA: nmfx_mur_run / nmfx_mur_finish only) */
 enum { NMFX_PROX_NN = 0, NMFX_PROX_L1N = 1, NMFX_PROX_L2N = 2,      /* reg type   */
        NMFX_PROX_L1INF = 3, NMFX_PROX_L1INF_T = 4 };                /* ADMM only (nmf/admm.py:158-210) */
 
@@ -115,6 +115,26 @@ int nmfx_upload_v_device(nmfx_handle_t h, const void* dev, int dtype, int64_t ld
  * message naming the weights and launches nothing.  nmfx_clear_weights frees the buffer: the handle behaves as before. */
 int nmfx_upload_weights(nmfx_handle_t h, const void* host, int dtype, int64_t ld, int64_t row0, int64_t rows);
 int nmfx_clear_weights(nmfx_handle_t h);
+/* ---- the beta-divergence (version 350) -------------------------------------
+ * nmfx_set_beta stores beta on the handle for runs with distance = NMFX_BETA (the reference has no such loss).  Legal on a
+ * dense handle with k <= 128 and -1 <= beta <= 3: NMFX_E_ARG for a beta outside that range (NaN included), on a sparse
+ * handle and for k > 128; nothing is launched and a beta stored before stays.  The range is what f32 carries: a cell can
+ * have q = 1e-9, and q^(beta - 2) times v has to stay finite.
+ * nmfx_mur_run / nmfx_mur_finish then accept NMFX_BETA (NMFX_E_STATE if beta was never set), with or without the weights
+ * of nmfx_upload_weights (Om = 1 without).  q = W H + 1e-9, W' the new W:
+ *   gamma = 1 / (2 - beta) for beta < 1,  1 for 1 <= beta <= 2,  1 / (beta - 1) for beta > 2
+ *   W <- W ( ((Om.V.q^(beta-2)) H^T) / ((Om.q^(beta-1)) H^T + lambda_w) )^gamma,  H likewise with W' and lambda_h,
+ *   0 where the denominator is 0  (the MM rule of Fevotte & Idier 2011)
+ *   objective  Sum om d_beta(v | q),  d_beta = (v^beta + (beta-1) q^beta - beta v q^(beta-1)) / (beta (beta-1)),
+ *              v log(v / q) - v + q at beta = 1 (log term 0 at v = 0),  v / q - log(v / q) - 1 at beta = 0,
+ *   recorded in f64 with the iteration contract of nmfx_mur_run.  For beta <= 0 V must be strictly positive
+ *   wherever it is part of the fit; for beta > 0 a zero is data (not checked here).  beta = 0, 1, 2 run this general rule:
+ *   NMFX_IS, NMFX_KL and NMFX_EU keep their own kernels and results.
+ * The kernels (kernels_beta.hip) are exact f32 whatever the precision mode; nmfx_get_note says so once a beta is set.
+ * Every entry point that refuses NMFX_IS -- the MUR phase / chunk / slice / sharded forms, nmfx_profile_repeat -- refuses
+ * NMFX_BETA the same way: NMFX_E_ARG, a message naming beta, nothing launched; so does nmfx_objective_f64 (a Euclidean
+ * objective) on a handle whose current run is a beta run. */
+int nmfx_set_beta(nmfx_handle_t h, double beta);
 /* ---- sparse V (version 310) ----------------------------------------------
  * A handle for a sparse m x n V with `nnz` stored entries, 1 <= k <= 256.  It runs MUR (both losses) without ever
  * forming V densely: nmfx_upload_csr takes V as CSR -- row_ptr [m + 1] (int64: nnz may pass 2^31), col_idx [nnz]

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("NMFX_LIB") or os.path.join(_HERE, "lib", "libnmfx.so"
 
 NMFX_OK, NMFX_E_ARG, NMFX_E_HIP, NMFX_E_NOTPD, NMFX_E_STATE, NMFX_E_NOMEM, NMFX_E_RCCL = 0, -1, -2, -3, -4, -5, -6
 F32, F64 = 0, 1
-EU, KL, IS = 0, 1, 2
+EU, KL, IS, BETA = 0, 1, 2, 3
 PROX = {"nn": 0, "l1n": 1, "l2n": 2, "l1inf": 3, "l1inf_transpose": 4}
 
 _i64, _i32, _dbl, _vp = C.c_int64, C.c_int, C.c_double, C.c_void_p
@@ -39,6 +39,7 @@ SIGNATURES = {
     "nmfx_upload_v_device": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
     "nmfx_upload_weights": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
     "nmfx_clear_weights": (_i32, [_vp]),
+    "nmfx_set_beta": (_i32, [_vp, _dbl]),
     "nmfx_set_factors": (_i32, [_vp, _vp, _vp]),
     "nmfx_get_factors": (_i32, [_vp, _vp, _vp]),
     "nmfx_get_matrix": (_i32, [_vp, C.c_char_p, _vp]),

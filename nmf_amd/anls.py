@@ -28,6 +28,8 @@ def anls(x, k, *, distance_type='eu', use_fcnnls=False, lambda_w=0, lambda_h=0, 
                             lambda_h, use_fcnnls)
     if distance_type == 'is':
         raise ValueError("anls: distance_type='is' (Itakura-Saito) is a loss of mur only")
+    if distance_type == 'beta':
+        raise ValueError("anls: distance_type='beta' (the beta-divergence) is a loss of mur only")
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via anls.py:108
     sparse.reject(x, 'anls')

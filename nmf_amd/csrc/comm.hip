@@ -382,6 +382,7 @@ extern "C" int nmfx_mur_run_sharded(nmfx_handle_t E, int distance, double lambda
                                     double tol2, int64_t first, int64_t count) {
     NMFX_DENSE_ONLY(E);
     if (E && distance == NMFX_IS) { E->err = "mur_run_sharded: the Itakura-Saito divergence (IS) is not available row-sharded"; return NMFX_E_ARG; }
+    if (E && distance == NMFX_BETA) { E->err = "mur_run_sharded: the beta-divergence (NMFX_BETA) is not available row-sharded"; return NMFX_E_ARG; }
     int rc = have_comm(E); if (rc) return rc;
     if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
     if (first < 0 || count < 0) { E->err = "negative iteration range"; return NMFX_E_ARG; }
@@ -439,6 +440,7 @@ extern "C" int nmfx_mur_run_sharded(nmfx_handle_t E, int distance, double lambda
 extern "C" int nmfx_mur_finish_sharded(nmfx_handle_t E, int distance, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
     NMFX_DENSE_ONLY(E);
     if (E && distance == NMFX_IS) { E->err = "mur_finish_sharded: the Itakura-Saito divergence (IS) is not available row-sharded"; return NMFX_E_ARG; }
+    if (E && distance == NMFX_BETA) { E->err = "mur_finish_sharded: the beta-divergence (NMFX_BETA) is not available row-sharded"; return NMFX_E_ARG; }
     int rc = have_comm(E); if (rc) return rc;
     NMFX_HIP(hipSetDevice(E->device));
     if ((rc = nmfx_mur_finish_a(E, distance, iters_done))) return rc;

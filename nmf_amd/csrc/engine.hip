@@ -44,7 +44,7 @@ static int preload_once(nmfx_engine* E) {
     static std::map<int, bool> done;
     std::lock_guard<std::mutex> lock(mu);
     if (done[E->device]) return NMFX_OK;
-    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_is() || nmfx_preload_weighted() || nmfx_preload_aoadmm() ||
+    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_is() || nmfx_preload_weighted() || nmfx_preload_beta() || nmfx_preload_aoadmm() ||
         nmfx_preload_anls() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic() ||
         nmfx_preload_sparse()) {
         E->err = "loading the kernels onto the device failed"; return NMFX_E_HIP; }
@@ -125,7 +125,7 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
 
 extern "C" {
 
-int nmfx_version(void) { return 340; }      // 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 350; }      // 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -397,6 +397,19 @@ int nmfx_clear_weights(nmfx_handle_t E) {
         else if (E->note.compare(at + len, 2, "; ") == 0) len += 2;
         E->note.erase(at, len);
     }
+    return NMFX_OK;
+}
+
+// The beta of NMFX_BETA runs (version 350).  The range is what f32 carries: q = 1e-9 in a real cell, q^(beta - 2) v finite.
+int nmfx_set_beta(nmfx_handle_t E, double beta) {
+    if (!E) return NMFX_E_ARG;
+    if (E->sp) { E->err = "set_beta: the beta-divergence is not available on a sparse handle (dense V, k <= 128)"; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = "set_beta: the beta-divergence needs k <= 128"; return NMFX_E_ARG; }
+    if (!(beta >= -1.0 && beta <= 3.0)) { E->err = "set_beta: beta must lie in [-1, 3] (what f32 carries at q = 1e-9)"; return NMFX_E_ARG; }
+    E->beta = beta;
+    E->beta_set = true;
+    static const char* const BETA_NOTE = "the beta-divergence (NMFX_BETA) runs the exact-f32 kernels; the split-bf16 mode does not apply to it";
+    if (E->note.find(BETA_NOTE) == std::string::npos) E->note += (E->note.empty() ? "" : "; ") + std::string(BETA_NOTE);
     return NMFX_OK;
 }
 
@@ -704,7 +717,13 @@ static int refuse_is(nmfx_engine* E, const char* who) {
     E->err = std::string(who) + ": the Itakura-Saito divergence (IS) is available through nmfx_mur_run / nmfx_mur_finish only";
     return NMFX_E_ARG;
 }
-#define NMFX_NO_IS(E, distance) do { if ((E) && (distance) == NMFX_IS) return refuse_is((E), __func__); } while (0)
+// ... and so does the beta-divergence (NMFX_BETA, nmfx_set_beta; dense k <= 128)
+static int refuse_beta(nmfx_engine* E, const char* who) {
+    E->err = std::string(who) + ": the beta-divergence (NMFX_BETA) is available through nmfx_mur_run / nmfx_mur_finish only";
+    return NMFX_E_ARG;
+}
+#define NMFX_NO_IS(E, distance) do { if ((E) && (distance) == NMFX_IS) return refuse_is((E), __func__); \
+                                     if ((E) && (distance) == NMFX_BETA) return refuse_beta((E), __func__); } while (0)
 
 int nmfx_mur_phase_a(nmfx_handle_t E, int distance, double lambda_w, int64_t j) {
     NMFX_DENSE_ONLY(E);
@@ -853,14 +872,34 @@ static int weights_ok(nmfx_engine* E, int distance, const char* who) {
     return NMFX_OK;
 }
 
+// NMFX_BETA: kernels_beta.hip on a dense handle with k <= 128 (what nmfx_set_beta accepted), with or without weights
+static int beta_ok(nmfx_engine* E, const char* who) {
+    if (E->sp) { E->err = std::string(who) + ": the beta-divergence (NMFX_BETA) is not available on a sparse handle"; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = std::string(who) + ": the beta-divergence (NMFX_BETA) needs k <= 128"; return NMFX_E_ARG; }
+    if (!E->beta_set) { E->err = std::string(who) + ": NMFX_BETA without a beta (nmfx_set_beta)"; return NMFX_E_STATE; }
+    return NMFX_OK;
+}
+
 int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h, int64_t min_iter,
                  double tol1, double tol2, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
+    if (distance == NMFX_BETA) {
+        { int rc_b = beta_ok(E, "mur_run"); if (rc_b) return rc_b; }
+        int rc = check_ready(E, first, count); if (rc) return rc;
+        E->himg_both = false; E->kl_h_iter = -2; E->is_run = true; E->beta_run = true;
+        for (int64_t j = first; j < first + count && !rc; ++j) {
+            if ((rc = nmfx_mur_beta_phase_a(E, lambda_w, j))) break;
+            E->wsel = (int)((j + 1) & 1);
+            E->w_in_place = false;
+            rc = nmfx_mur_beta_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
+        }
+        return rc;
+    }
     if (E->sp) return nmfx_sparse_mur_run(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
     if (E->Om) {                                       // per-entry weights: kernels_weighted.hip, all three losses
         { int rc_wt = weights_ok(E, distance, "mur_run"); if (rc_wt) return rc_wt; }
         int rc = check_ready(E, first, count); if (rc) return rc;
-        E->himg_both = false; E->kl_h_iter = -2; E->is_run = distance == NMFX_IS;
+        E->himg_both = false; E->kl_h_iter = -2; E->is_run = distance == NMFX_IS; E->beta_run = false;
         for (int64_t j = first; j < first + count && !rc; ++j) {
             if ((rc = nmfx_mur_wt_phase_a(E, distance, lambda_w, j))) break;
             E->wsel = (int)((j + 1) & 1);
@@ -872,7 +911,7 @@ int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h
     if (distance == NMFX_IS) {
         { int rc_is = is_dense_ok(E, "mur_run"); if (rc_is) return rc_is; }
         int rc = check_ready(E, first, count); if (rc) return rc;
-        E->himg_both = false; E->kl_h_iter = -2; E->is_run = true;
+        E->himg_both = false; E->kl_h_iter = -2; E->is_run = true; E->beta_run = false;
         for (int64_t j = first; j < first + count && !rc; ++j) {
             if ((rc = nmfx_mur_is_phase_a(E, lambda_w, j))) break;
             E->wsel = (int)((j + 1) & 1);
@@ -894,19 +933,26 @@ int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h
 
 int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1, double tol2,
                     int64_t iters_done) {
-    if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
     int rc;
+    if (E && distance == NMFX_BETA) {
+        if ((rc = beta_ok(E, "mur_finish"))) return rc;
+        if ((rc = check_ready(E, iters_done, 1))) return rc;
+        E->is_run = true; E->beta_run = true;
+        if ((rc = nmfx_mur_beta_finish_a(E, iters_done))) return rc;
+        return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
+    }
+    if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
     if (E && E->Om) {
         if ((rc = weights_ok(E, distance, "mur_finish"))) return rc;
         if ((rc = check_ready(E, iters_done, 1))) return rc;
-        E->is_run = distance == NMFX_IS;
+        E->is_run = distance == NMFX_IS; E->beta_run = false;
         if ((rc = nmfx_mur_wt_finish_a(E, distance, iters_done))) return rc;
         return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
     }
     if (E && distance == NMFX_IS) {
         if ((rc = is_dense_ok(E, "mur_finish"))) return rc;
         if ((rc = check_ready(E, iters_done, 1))) return rc;
-        E->is_run = true;
+        E->is_run = true; E->beta_run = false;
         if ((rc = nmfx_mur_is_finish_a(E, iters_done))) return rc;
         return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
     }

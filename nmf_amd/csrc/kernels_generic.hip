@@ -2666,6 +2666,7 @@ int nmfx_generic_anls_phase(nmfx_engine* E, int phase, double lam, int64_t min_i
 extern "C" int nmfx_objective_f64(nmfx_handle_t E, double* out) {
     if (!E || !out) { if (E) E->err = "objective_f64: out is NULL"; return NMFX_E_ARG; }
     if (E->Om) { E->err = "objective_f64: evaluates the unweighted Euclidean objective; not available while per-entry weights are present (nmfx_upload_weights; nmfx_clear_weights removes them)"; return NMFX_E_ARG; }
+    if (E->is_run && E->beta_run) { E->err = "objective_f64: evaluates the Euclidean objective; not available while the handle runs the beta-divergence (NMFX_BETA)"; return NMFX_E_ARG; }
     if (E->is_run) { E->err = "objective_f64: evaluates the Euclidean objective; not available while the handle runs the Itakura-Saito divergence (IS)"; return NMFX_E_ARG; }
     if (E->sp) return nmfx_sparse_objective_f64(E, out);
     if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }

@@ -876,7 +876,7 @@ def _defaults(method):
     mod = import_module('.' + method, __package__)
     sig = inspect.signature(getattr(mod, method))
     kw = {name: p.default for name, p in sig.parameters.items()
-          if p.kind is p.KEYWORD_ONLY and name not in ('device', 'engine', 'save_dir', 'mask', 'weights')}     # (no masked or weighted sharded runs)
+          if p.kind is p.KEYWORD_ONLY and name not in ('device', 'engine', 'save_dir', 'mask', 'weights', 'beta')}     # (no masked, weighted or beta-divergence sharded runs)
     return mod, kw
 
 
@@ -946,6 +946,9 @@ def factorize(data, k, method='mur', *, gather=True, device=None, backend=None, 
         raise Exception('Method not known. Choose one from: mur anls admm ao_admm')      # nmf/nmf.py:76
     if method_params.get('distance_type') == 'is':            # (no sharded Itakura-Saito runs)
         raise TypeError("dist.factorize: distance_type='is' is not supported (the Itakura-Saito divergence runs on one GPU: mur(x, k, distance_type='is'))")
+    if method_params.get('distance_type') == 'beta' or 'beta' in method_params:      # (no sharded beta-divergence runs)
+        raise TypeError("dist.factorize: distance_type='beta' / beta= is not supported (the beta-divergence runs on one GPU: "
+                        "mur(x, k, distance_type='beta', beta=b))")
     if 'weights' in method_params:                             # (no sharded weighted runs; refused before anything touches a GPU)
         raise TypeError("dist.factorize: weights= is not supported (per-entry weights run on one GPU: mur(x, k, weights=...))")
     rank, world, local = init_process_group(backend)

@@ -135,6 +135,10 @@ class Engine:
     def clear_weights(self):
         self._ck(self.lib.nmfx_clear_weights(self.h))
 
+    def set_beta(self, beta):
+        """The beta of mur_run / mur_finish with L.BETA (dense handle, k <= 128, -1 <= beta <= 3; include/nmfx.h)."""
+        self._ck(self.lib.nmfx_set_beta(self.h, float(beta)))
+
     def set_factors(self, w, h):
         w = np.ascontiguousarray(w, dtype=np.float64)
         h = np.ascontiguousarray(h, dtype=np.float64)

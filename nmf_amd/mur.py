@@ -18,16 +18,21 @@ from ._driver import Referee, Results, drive
 from .engine import Engine
 
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h')
+BetaExperiment = namedtuple('Experiment', Experiment._fields + ('beta',))      # distance_type='beta' alone: one trailing field
+BETA_RANGE = (-1.0, 3.0)          # what float32 carries: q^(beta - 2) x at q = 1e-9
 
 
 def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5,
-        lambda_w=0.0, lambda_h=0.0, nndsvd_init=(False, 'zero'), save_dir='./results/', device=0, engine=None, mask=None, weights=None):
+        lambda_w=0.0, lambda_h=0.0, nndsvd_init=(False, 'zero'), save_dir='./results/', device=0, engine=None, mask=None, weights=None,
+        beta=None):
     """Lee-Seung NMF.  x: 2-D non-negative data (a numpy array, or any scipy.sparse matrix / array with 1 <= k <= 256:
     never densified), k: number of components.
 
     distance_type 'eu' | 'kl' (default 'kl' as in the reference) | 'is' (Itakura-Saito, beyond the reference: dense
     strictly positive x with k <= 128, or any x with mask= whose observed entries are strictly positive; x is never
-    lifted), min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init=(bool, variant) and
+    lifted) | 'beta' (the beta-divergence with beta=b, -1 <= b <= 3, beyond the reference: dense x with k <= 128, with or
+    without weights=; x >= 0 for b > 0, strictly positive for b <= 0; never lifted; b = 0, 1, 2 are the IS, KL and Euclidean
+    losses under the general rule), min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init=(bool, variant) and
     save_dir have the reference's meaning.  mask: None, or a boolean / 0-1 array or scipy.sparse matrix of x's shape
     whose non-zero entries are the observed set -- only x there is fitted and read (masked MUR, nmf_amd.masked;
     1 <= k <= 256).  weights: None, or a dense real array Omega >= 0 of x's shape (boolean counts as 0 / 1): the fit is
@@ -35,12 +40,18 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
     (nmf_amd.weighted; not together with mask= or engine=).  Returns Results(w, h, i, obj_history, experiment) with float64 w, h."""
     experiment = Experiment('mur', k, distance_type, nndsvd_init, max_iter, tol1, tol2,
                             lambda_w, lambda_h)
-    if distance_type not in ('eu', 'kl', 'is'):
+    if distance_type not in ('eu', 'kl', 'is', 'beta'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31
-    dist = {'eu': L.EU, 'kl': L.KL, 'is': L.IS}[distance_type]
+    dist = {'eu': L.EU, 'kl': L.KL, 'is': L.IS, 'beta': L.BETA}[distance_type]
+    beta = check_beta(distance_type, beta)
+    if dist == L.BETA:
+        experiment = BetaExperiment(*experiment, beta)
+        _check_beta_request(x, k, mask, beta)
     if weights is not None:
         return _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h,
-                             nndsvd_init, device, engine)
+                             nndsvd_init, device, engine, beta)
+    if dist == L.BETA:
+        _check_beta_input(x, beta)
     if dist == L.IS and mask is None:
         _check_is_input(x, k)
     if mask is not None:
@@ -62,6 +73,8 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
             eng.upload_v(x)             # a resident engine still holds the data as it was before the lift
         w0, h0 = utils.device_initial_factors(eng, x, k, nndsvd_init, init)
         eng.set_factors(w0, h0)
+        if dist == L.BETA:
+            eng.set_beta(beta)
         logging.info('Entering Main Loop.')
         NEVER = 10 ** 15
         referee = None
@@ -93,6 +106,58 @@ def _check_is_input(x, k):
                          "below the float32 range); it is not lifted by its minimum")
     if not np.isfinite(highest):
         raise ValueError("distance_type='is': an entry is infinite or beyond the float32 range")
+
+
+def check_beta(distance_type, beta):
+    """beta= belongs to distance_type='beta' and to nothing else; returns it as a float (None for the other losses)."""
+    if distance_type != 'beta':
+        if beta is not None:
+            raise ValueError(f"beta= is the parameter of distance_type='beta' (got beta={beta!r} with distance_type={distance_type!r})")
+        return None
+    if beta is None:
+        raise ValueError("distance_type='beta' needs beta= (a number in [-1, 3]; 0, 1 and 2 are the IS, KL and Euclidean losses)")
+    try:
+        b = float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"distance_type='beta': beta must be a real number (got beta={beta!r})") from None
+    if not np.isfinite(b) or not BETA_RANGE[0] <= b <= BETA_RANGE[1]:
+        raise ValueError(f"distance_type='beta': beta must be finite and lie in [-1, 3], the range float32 carries (got beta={beta!r})")
+    return b
+
+
+def _check_beta_request(x, k, mask, beta):
+    """What distance_type='beta' runs on, checked before any device work: dense x, no mask=, k <= 128."""
+    if mask is not None:
+        raise ValueError(f"distance_type='beta' (beta={beta}): mask= is not supported; pass the 0 / 1 pattern as weights= "
+                         "(a dense 0 / 1 array is a mask on the dense kernels)")
+    if sparse.is_sparse(x):
+        raise ValueError(f"distance_type='beta' (beta={beta}): scipy.sparse input is not supported (the k x k shortcut of the "
+                         "sparse path exists only for beta = 1 and beta = 2: distance_type='kl' / 'eu'); pass a dense array")
+    if int(k) > 128:
+        raise ValueError(f"distance_type='beta' (beta={beta}) supports k <= 128 components (got k = {k})")
+
+
+def _check_beta_input(x, beta):
+    """The beta-divergence without weights: _check_is_input's value checks, with "> 0" relaxed to ">= 0" for beta > 0 (a
+    zero is data there: d_beta(0 | q) = q^beta / beta).  Not lifted by its minimum, never modified."""
+    with np.errstate(over='ignore', under='ignore'):            # (the device holds float32: judge that image)
+        lowest, highest = np.float32(np.min(x)), np.float32(np.max(x))
+    if beta > 0:
+        if not lowest >= 0:                                     # (NaN included)
+            raise ValueError(f"distance_type='beta' (beta={beta}): the data must be non-negative (an entry is negative or NaN); "
+                             "it is not lifted by its minimum")
+        xa = np.asarray(x)
+        if xa.dtype != np.float32:                              # a zero is data, so a positive value must not underflow to one
+            for a in range(0, xa.shape[0], 1024):
+                blk = xa[a:a + 1024]
+                with np.errstate(under='ignore', over='ignore'):
+                    if np.any((blk > 0) & (blk.astype(np.float32) == 0)):
+                        raise ValueError(f"distance_type='beta' (beta={beta}): a positive entry is below the float32 range")
+    elif not lowest > 0:
+        raise ValueError(f"distance_type='beta' (beta={beta}): for beta <= 0 the data must be strictly positive in float32 (an "
+                         "entry is <= 0, NaN or below the float32 range); it is not lifted by its minimum")
+    if not np.isfinite(highest):
+        raise ValueError(f"distance_type='beta' (beta={beta}): an entry is infinite or beyond the float32 range")
 
 
 def _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine):
@@ -141,7 +206,7 @@ def _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, la
 
 
 def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init,
-                  device, engine):
+                  device, engine, beta=None):
     """MUR with per-entry weights (kernels_weighted.hip on a dense handle, exact f32): Sum omega * loss(x, wh).  Everything
     is validated before any device work; nothing of the caller's is modified or lifted.  Same start as the masked path
     (the global RNG's draws as in mur; NNDSVD, unweighted and on the host, of x with the zero-weight cells set to 0),
@@ -151,7 +216,7 @@ def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol
         raise ValueError('weights= and mask= exclude each other (a mask is the 0 / 1 case of weights)')
     if engine is not None:
         raise ValueError('weights=: engine= is not supported (the engine is created for the weighted data)')
-    x32, w32 = weighted.prepare(x, weights, k, experiment.distance_type)
+    x32, w32 = weighted.prepare(x, weights, k, experiment.distance_type, beta=beta)
     if nndsvd_init[0]:
         with np.errstate(invalid='ignore'):
             start = np.where(w32 > 0, np.asarray(x), 0)
@@ -163,6 +228,8 @@ def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol
         eng.upload_v(x32)
         eng.upload_weights(w32)
         eng.set_factors(*init)
+        if dist == L.BETA:
+            eng.set_beta(beta)
         logging.info('Entering Main Loop.')
         i, history = drive(
             eng,

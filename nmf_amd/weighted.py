@@ -40,13 +40,32 @@ def _check_weights(weights, shape):
     return weights, w32
 
 
-def prepare(x, weights, k, distance='eu'):
-    """Validate (x, weights, k) for the loss `distance` ('eu' | 'kl' | 'is') and return the two float32 arrays the device
+def _beta(distance, beta):
+    from .mur import check_beta                                 # (one statement of beta's rules)
+    return check_beta(distance, beta)
+
+
+def beta_cells(x, q, beta):
+    """d_beta(x | q) per cell in float64: the three-term form, its limits at beta = 0 and 1."""
+    if beta == 0:
+        r = x / q
+        return r - np.log(r) - 1.0
+    if beta == 1:
+        with np.errstate(divide='ignore', invalid='ignore'):
+            t = np.where(x > 0, x * np.log(x / q), 0.0)
+        return t - x + q
+    return (x ** beta + (beta - 1.0) * q ** beta - beta * x * q ** (beta - 1.0)) / (beta * (beta - 1.0))
+
+
+def prepare(x, weights, k, distance='eu', beta=None):
+    """Validate (x, weights, k) for the loss `distance` ('eu' | 'kl' | 'is' | 'beta' with beta=) and return the two float32 arrays the device
     takes: x with the zero-weight cells set to 0, and the weights.  Where the weight is positive x is held to what `mask=`
-    asks of observed entries (nmf_amd.masked): finite and non-negative, with 'is' strictly positive in float32.  Raises
+    asks of observed entries (nmf_amd.masked): finite and non-negative, with 'is' and 'beta' at beta <= 0 strictly positive
+    in float32.  Raises
     ValueError for a bad entry, shape or k (1 <= k <= 128), TypeError for sparse or complex input."""
-    if distance not in ('eu', 'kl', 'is'):
+    if distance not in ('eu', 'kl', 'is', 'beta'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')
+    beta = _beta(distance, beta)
     if sp.issparse(x):
         raise TypeError('weights= needs dense data; for a sparse matrix use mask= (0 / 1 weights on the stored pattern)')
     x = np.asarray(x)
@@ -63,6 +82,8 @@ def prepare(x, weights, k, distance='eu'):
     masked.check_values(vals)
     if distance == 'is':
         masked.check_positive_values(vals)
+    if distance == 'beta':
+        _check_beta_values(vals, beta)
     with np.errstate(over='ignore', under='ignore', invalid='ignore'):
         x32 = np.where(live, x, 0).astype(np.float32)
     if not np.all(np.isfinite(x32)):
@@ -70,15 +91,31 @@ def prepare(x, weights, k, distance='eu'):
     return x32, w32
 
 
-def objective(x, w, h, weights, distance_type='eu'):
+def _check_beta_values(vals, beta):
+    """The cells under positive weight for the beta-divergence: strictly positive in float32 for beta <= 0; for beta > 0 a
+    zero is data, but a positive value must not underflow to one."""
+    with np.errstate(over='ignore', under='ignore'):
+        v32 = vals.astype(np.float32)
+    if beta <= 0 and not np.min(v32) > 0:
+        raise ValueError(f"distance_type='beta' (beta={beta}): a value under positive weight is 0, or underflows to 0 in float32 "
+                         "(beta <= 0 needs strictly positive data; give such cells weight 0)")
+    if np.any((v32 == 0) & (vals > 0)):
+        raise ValueError(f"distance_type='beta' (beta={beta}): a positive value under positive weight is below the float32 range")
+    if not np.all(np.isfinite(v32)):
+        raise ValueError(f"distance_type='beta' (beta={beta}): a value under positive weight is beyond the float32 range")
+
+
+def objective(x, w, h, weights, distance_type='eu', beta=None):
     """The weighted objective in float64 on the host, a block of rows at a time:
         eu  1/2 Sum om (x - wh)^2
         kl  Sum om [x log(x / wh) - x + wh]       (inf / nan log terms -> 0)
         is  Sum om [x / q - log(x / q) - 1],  q = wh + 1e-9       (x > 0 wherever om > 0)
+        beta (with beta=b)  Sum om d_b(x | q),  q = wh + 1e-9      (x > 0 wherever om > 0 if b <= 0)
     Cells with weight 0 contribute nothing and x is not read there.  With the training weights it is the objective
     `mur(x, k, weights=...)` records; with other weights (for instance 1 on held-out cells) it scores the fit there."""
-    if distance_type not in ('eu', 'kl', 'is'):
+    if distance_type not in ('eu', 'kl', 'is', 'beta'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')
+    beta = _beta(distance_type, beta)
     if sp.issparse(x):
         raise TypeError('weights= needs dense data; for a sparse matrix use nmf_amd.masked.objective')
     x = np.asarray(x)
@@ -97,6 +134,10 @@ def objective(x, w, h, weights, distance_type='eu'):
         wh = (w[a:a + ROWS] @ h)[live]
         if distance_type == 'eu':
             s += 0.5 * float(np.sum(oa * (xa - wh) ** 2))
+        elif distance_type == 'beta':
+            if beta <= 0 and not np.min(xa) > 0:
+                raise ValueError(f"distance_type='beta' (beta={beta}): a scored value is 0 (beta <= 0 needs strictly positive data)")
+            s += float(np.sum(oa * beta_cells(xa, wh + 1e-9, beta)))
         elif distance_type == 'is':
             masked.check_positive_values(xa)
             r = xa / (wh + 1e-9)
