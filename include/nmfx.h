@@ -101,7 +101,7 @@ int nmfx_upload_v_device(nmfx_handle_t h, const void* dev, int dtype, int64_t ld
  * message when it does not fit.  Legal on a dense handle with k <= 128: NMFX_E_ARG on a sparse handle and for k > 128,
  * nothing launched.  The entries must be finite and >= 0 (not checked here).
  * While weights are present nmfx_mur_run / nmfx_mur_finish with NMFX_EU, NMFX_KL or NMFX_IS run the weighted update
- * (kernels_weighted.hip, exact f32 whatever the precision mode; nmfx_get_note says so), with T = W H and W' the new W:
+ * (kernels_phase.hip, exact f32 whatever the precision mode; nmfx_get_note says so), with T = W H and W' the new W:
  *   Euclidean  W <- W ((Om.V) H^T) / ((Om.T) H^T + lambda_w W + 1e-9)                          1/2 Sum om (v - T)^2
  *   KL         A = W ((Om.V / (T + 1e-9)) H^T),  B = Om H^T,  W <- 2 A / (B + sqrt(B^2 + 4 lambda_w A)),  0 where B = 0
  *                                                                                              Sum om [v log(v / T) - v + T]
@@ -130,7 +130,7 @@ int nmfx_clear_weights(nmfx_handle_t h);
  *   recorded in f64 with the iteration contract of nmfx_mur_run.  For beta <= 0 V must be strictly positive
  *   wherever it is part of the fit; for beta > 0 a zero is data (not checked here).  beta = 0, 1, 2 run this general rule:
  *   NMFX_IS, NMFX_KL and NMFX_EU keep their own kernels and results.
- * The kernels (kernels_beta.hip) are exact f32 whatever the precision mode; nmfx_get_note says so once a beta is set.
+ * The kernels (kernels_phase.hip) are exact f32 whatever the precision mode; nmfx_get_note says so once a beta is set.
  * Every entry point that refuses NMFX_IS -- the MUR phase / chunk / slice / sharded forms, nmfx_profile_repeat -- refuses
  * NMFX_BETA the same way: NMFX_E_ARG, a message naming beta, nothing launched; so does nmfx_objective_f64 (a Euclidean
  * objective) on a handle whose current run is a beta run. */

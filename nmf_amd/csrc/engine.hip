@@ -44,7 +44,7 @@ static int preload_once(nmfx_engine* E) {
     static std::map<int, bool> done;
     std::lock_guard<std::mutex> lock(mu);
     if (done[E->device]) return NMFX_OK;
-    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_is() || nmfx_preload_weighted() || nmfx_preload_beta() || nmfx_preload_aoadmm() ||
+    if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_phase() || nmfx_preload_aoadmm() ||
         nmfx_preload_anls() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic() ||
         nmfx_preload_sparse()) {
         E->err = "loading the kernels onto the device failed"; return NMFX_E_HIP; }
@@ -256,7 +256,7 @@ int nmfx_destroy(nmfx_handle_t E) {
     nmfx_comm_free(E);
     for (auto& t : E->prof_pending) { hipEventDestroy(std::get<1>(t)); hipEventDestroy(std::get<2>(t)); }
     void* bufs[] = {E->V, E->W[0], E->W[1], E->H, E->HHt, E->HHt_part, E->G_part, E->A_part, E->B_part,
-                    E->obj_part, E->is_part, E->Om, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
+                    E->obj_part, E->phase_part, E->Om, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
                     E->obj_hist, E->state, E->dualW, E->dualH, E->auxW, E->auxH, E->Minv, E->nrm_part,
                     E->inner_hist, E->Pw, E->Ph, E->Asum, E->S, E->DV, E->Vt, E->Vtile, E->Bt_part, E->Whi[0], E->Whi[1],
                     E->Wlo[0], E->Wlo[1], E->WThi, E->WTlo, E->Hhi, E->Hlo, E->HThi, E->HTlo, E->nrm_rounds, E->bkX, E->bkU,
@@ -857,7 +857,7 @@ int nmfx_mur_finish_b(nmfx_handle_t E, int64_t min_iter, double tol1, double tol
     return nmfx_finish_b(E, min_iter, tol1, tol2, j);
 }
 
-// IS on a dense handle: the tuned exact-f32 kernels of kernels_is.hip, k <= 128, whatever the precision mode says
+// IS on a dense handle: the tuned exact-f32 kernels of kernels_phase.hip, k <= 128, whatever the precision mode says
 static int is_dense_ok(nmfx_engine* E, const char* who) {
     if (E->kp > 128) { E->err = std::string(who) + ": the Itakura-Saito divergence (IS) needs k <= 128 on a dense handle"; return NMFX_E_ARG; }
     if (E->precision == 1 && nmfx_bf16_supported(E) && E->note.find("Itakura-Saito") == std::string::npos)
@@ -865,14 +865,14 @@ static int is_dense_ok(nmfx_engine* E, const char* who) {
     return NMFX_OK;
 }
 
-// With per-entry weights (nmfx_upload_weights; dense, k <= 128 by construction) every loss runs kernels_weighted.hip
+// With per-entry weights (nmfx_upload_weights; dense, k <= 128 by construction) every loss runs kernels_phase.hip
 static int weights_ok(nmfx_engine* E, int distance, const char* who) {
     if (distance != NMFX_EU && distance != NMFX_KL && distance != NMFX_IS) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
     if (E->kp > 128) { E->err = std::string(who) + ": per-entry weights need k <= 128"; return NMFX_E_ARG; }
     return NMFX_OK;
 }
 
-// NMFX_BETA: kernels_beta.hip on a dense handle with k <= 128 (what nmfx_set_beta accepted), with or without weights
+// NMFX_BETA: kernels_phase.hip on a dense handle with k <= 128 (what nmfx_set_beta accepted), with or without weights
 static int beta_ok(nmfx_engine* E, const char* who) {
     if (E->sp) { E->err = std::string(who) + ": the beta-divergence (NMFX_BETA) is not available on a sparse handle"; return NMFX_E_ARG; }
     if (E->kp > 128) { E->err = std::string(who) + ": the beta-divergence (NMFX_BETA) needs k <= 128"; return NMFX_E_ARG; }
@@ -880,46 +880,35 @@ static int beta_ok(nmfx_engine* E, const char* who) {
     return NMFX_OK;
 }
 
+// The dense exact-f32 phase path (kernels_phase.hip) takes a call with NMFX_BETA, a dense handle with weights whatever the
+// loss, and NMFX_IS on a dense handle -- asked in that order, each with its own guard.  *takes says whether it does.
+static int dense_phase_path(nmfx_engine* E, int distance, const char* who, bool* takes) {
+    *takes = true;
+    if (distance == NMFX_BETA) return beta_ok(E, who);
+    if (!E->sp && E->Om) return weights_ok(E, distance, who);
+    if (!E->sp && distance == NMFX_IS) return is_dense_ok(E, who);
+    *takes = false;
+    return NMFX_OK;
+}
+
 int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h, int64_t min_iter,
                  double tol1, double tol2, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
-    if (distance == NMFX_BETA) {
-        { int rc_b = beta_ok(E, "mur_run"); if (rc_b) return rc_b; }
+    bool dense_phase;
+    { int rc_p = dense_phase_path(E, distance, "mur_run", &dense_phase); if (rc_p) return rc_p; }
+    if (dense_phase) {
         int rc = check_ready(E, first, count); if (rc) return rc;
-        E->himg_both = false; E->kl_h_iter = -2; E->is_run = true; E->beta_run = true;
+        E->himg_both = false; E->kl_h_iter = -2;
+        E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
         for (int64_t j = first; j < first + count && !rc; ++j) {
-            if ((rc = nmfx_mur_beta_phase_a(E, lambda_w, j))) break;
+            if ((rc = nmfx_mur_dense_phase_a(E, distance, lambda_w, j))) break;
             E->wsel = (int)((j + 1) & 1);
             E->w_in_place = false;
-            rc = nmfx_mur_beta_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
+            rc = nmfx_mur_dense_phase_b(E, distance, lambda_h, min_iter, tol1, tol2, j);
         }
         return rc;
     }
     if (E->sp) return nmfx_sparse_mur_run(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
-    if (E->Om) {                                       // per-entry weights: kernels_weighted.hip, all three losses
-        { int rc_wt = weights_ok(E, distance, "mur_run"); if (rc_wt) return rc_wt; }
-        int rc = check_ready(E, first, count); if (rc) return rc;
-        E->himg_both = false; E->kl_h_iter = -2; E->is_run = distance == NMFX_IS; E->beta_run = false;
-        for (int64_t j = first; j < first + count && !rc; ++j) {
-            if ((rc = nmfx_mur_wt_phase_a(E, distance, lambda_w, j))) break;
-            E->wsel = (int)((j + 1) & 1);
-            E->w_in_place = false;
-            rc = nmfx_mur_wt_phase_b(E, distance, lambda_h, min_iter, tol1, tol2, j);
-        }
-        return rc;
-    }
-    if (distance == NMFX_IS) {
-        { int rc_is = is_dense_ok(E, "mur_run"); if (rc_is) return rc_is; }
-        int rc = check_ready(E, first, count); if (rc) return rc;
-        E->himg_both = false; E->kl_h_iter = -2; E->is_run = true; E->beta_run = false;
-        for (int64_t j = first; j < first + count && !rc; ++j) {
-            if ((rc = nmfx_mur_is_phase_a(E, lambda_w, j))) break;
-            E->wsel = (int)((j + 1) & 1);
-            E->w_in_place = false;
-            rc = nmfx_mur_is_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
-        }
-        return rc;
-    }
     int rc = check_ready(E, first, count); if (rc) return rc;
     E->is_run = false;
     E->fused_pack = true;            // nothing is exchanged between the phases here
@@ -934,28 +923,15 @@ int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h
 int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1, double tol2,
                     int64_t iters_done) {
     int rc;
-    if (E && distance == NMFX_BETA) {
-        if ((rc = beta_ok(E, "mur_finish"))) return rc;
+    bool dense_phase = false;
+    if (E && (rc = dense_phase_path(E, distance, "mur_finish", &dense_phase))) return rc;
+    if (dense_phase) {
         if ((rc = check_ready(E, iters_done, 1))) return rc;
-        E->is_run = true; E->beta_run = true;
-        if ((rc = nmfx_mur_beta_finish_a(E, iters_done))) return rc;
+        E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
+        if ((rc = nmfx_mur_dense_finish_a(E, distance, iters_done))) return rc;
         return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
     }
     if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
-    if (E && E->Om) {
-        if ((rc = weights_ok(E, distance, "mur_finish"))) return rc;
-        if ((rc = check_ready(E, iters_done, 1))) return rc;
-        E->is_run = distance == NMFX_IS; E->beta_run = false;
-        if ((rc = nmfx_mur_wt_finish_a(E, distance, iters_done))) return rc;
-        return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
-    }
-    if (E && distance == NMFX_IS) {
-        if ((rc = is_dense_ok(E, "mur_finish"))) return rc;
-        if ((rc = check_ready(E, iters_done, 1))) return rc;
-        E->is_run = true; E->beta_run = false;
-        if ((rc = nmfx_mur_is_finish_a(E, iters_done))) return rc;
-        return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
-    }
     if ((rc = nmfx_mur_finish_a(E, distance, iters_done))) return rc;
     return nmfx_mur_finish_b(E, min_iter, tol1, tol2, iters_done);
 }

@@ -82,8 +82,8 @@ struct nmfx_engine {
     int64_t kl_h_iter = -2;        // outer iteration whose H epilogue wrote the H partials and the H / H^T images (valid for iteration + 1 only)
     float* A_part = nullptr;       // [wsplit][mp][kp]
     float* B_part = nullptr;       // [hsplit][kp][np]
-    float* is_part = nullptr;      // MUR-IS (kernels_is.hip), weighted MUR (kernels_weighted.hip) and MUR-beta (kernels_beta.hip): [splits][numerator | denominator] slabs of the phase in flight, allocated on first use
-    int64_t is_part_cap = 0;
+    float* phase_part = nullptr;   // MUR-IS, weighted MUR and MUR-beta (kernels_phase.hip): [splits][numerator | denominator] slabs of the phase in flight, allocated on first use
+    int64_t phase_part_cap = 0;
     float* Om = nullptr;           // per-entry weights (nmfx_upload_weights): [mp][np] like V, zero where nothing was uploaded; nullptr = none
     double* obj_part = nullptr;    // [max blocks]
     int64_t obj_part_cap = 0;
@@ -176,7 +176,7 @@ struct nmfx_engine {
     bool family_started = false;   // a MUR run has begun since nmfx_set_factors (pair mode must be chosen at its start)
     bool is_run = false;           // the MUR run since nmfx_set_factors uses the Itakura-Saito divergence (nmfx_objective_f64 is Euclidean: refused)
     bool beta_run = false;         // ... or, with is_run set as well, the beta-divergence (dense handles only; it only words that refusal)
-    double beta = 0.0;             // nmfx_set_beta: the beta of NMFX_BETA runs (kernels_beta.hip)
+    double beta = 0.0;             // nmfx_set_beta: the beta of NMFX_BETA runs (kernels_phase.hip)
     bool beta_set = false;
     bool pair = false;             // nmfx_mur_pair_*: factor columns [0, 64) and [64, 128) are two independent problems
     int family = 0;                // solver family that has run since nmfx_set_factors (0 none, 1 MUR eu/kl, 2 AO-ADMM, 3 ADMM, 4 ANLS): nmfx_enter_family
@@ -259,18 +259,11 @@ int nmfx_mur_eu_phase_b_bf16(nmfx_engine* E, double lambda_h, int64_t min_iter, 
 int nmfx_mur_eu_phase_b_slice_bf16(nmfx_engine* E, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j, int cb0, int nblk);
 int nmfx_mur_eu_phase_b_rest_bf16(nmfx_engine* E, int cb0, int nblk);
 int nmfx_finish_b(nmfx_engine* E, int64_t min_iter, double tol1, double tol2, int64_t j);
-// kernels_is.hip: MUR with the Itakura-Saito divergence (dense, k <= 128, exact f32), same phase protocol as MUR-KL
-int nmfx_mur_is_phase_a(nmfx_engine* E, double lambda_w, int64_t j);
-int nmfx_mur_is_phase_b(nmfx_engine* E, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
-int nmfx_mur_is_finish_a(nmfx_engine* E, int64_t j);
-// kernels_weighted.hip: MUR with per-entry weights E->Om (dense, k <= 128, exact f32), distance NMFX_EU / NMFX_KL / NMFX_IS
-int nmfx_mur_wt_phase_a(nmfx_engine* E, int distance, double lambda_w, int64_t j);
-int nmfx_mur_wt_phase_b(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
-int nmfx_mur_wt_finish_a(nmfx_engine* E, int distance, int64_t j);
-// kernels_beta.hip: MUR with the beta-divergence E->beta (dense, k <= 128, exact f32), with E->Om as weights where present
-int nmfx_mur_beta_phase_a(nmfx_engine* E, double lambda_w, int64_t j);
-int nmfx_mur_beta_phase_b(nmfx_engine* E, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
-int nmfx_mur_beta_finish_a(nmfx_engine* E, int64_t j);
+// kernels_phase.hip: the dense exact-f32 phase path of MUR (k <= 128), same phase protocol as MUR-KL.  The policy follows from the
+// call: NMFX_BETA (E->beta, with E->Om as weights where present), any of NMFX_EU / NMFX_KL / NMFX_IS with weights E->Om, NMFX_IS without
+int nmfx_mur_dense_phase_a(nmfx_engine* E, int distance, double lambda_w, int64_t j);
+int nmfx_mur_dense_phase_b(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
+int nmfx_mur_dense_finish_a(nmfx_engine* E, int distance, int64_t j);
 // One solver family per set of factors: the families keep different device state next to W and H (MUR: W ping-pong and bf16 images of
 // both factors; AO-ADMM / ADMM: duals and auxiliaries; ANLS: warm-start supports), and a family that starts in the middle of another's
 // run would read leftovers.  A second family on the same handle needs nmfx_get_factors -> nmfx_set_factors first (NMFX_E_STATE otherwise).
@@ -366,9 +359,7 @@ int nmfx_preload_bf16();
 int nmfx_preload_products();
 int nmfx_preload_mur();
 int nmfx_preload_kl();
-int nmfx_preload_is();
-int nmfx_preload_weighted();
-int nmfx_preload_beta();
+int nmfx_preload_phase();
 int nmfx_preload_aoadmm();
 int nmfx_preload_anls();
 int nmfx_preload_svd();

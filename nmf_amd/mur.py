@@ -207,7 +207,7 @@ def _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, la
 
 def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init,
                   device, engine, beta=None):
-    """MUR with per-entry weights (kernels_weighted.hip on a dense handle, exact f32): Sum omega * loss(x, wh).  Everything
+    """MUR with per-entry weights (kernels_phase.hip on a dense handle, exact f32): Sum omega * loss(x, wh).  Everything
     is validated before any device work; nothing of the caller's is modified or lifted.  Same start as the masked path
     (the global RNG's draws as in mur; NNDSVD, unweighted and on the host, of x with the zero-weight cells set to 0),
     same Results, printed lines and batching; the recorded objective is the weighted one (nmf_amd.weighted.objective),

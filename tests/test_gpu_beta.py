@@ -1,4 +1,4 @@
-"""MUR with the beta-divergence on the device (kernels_beta.hip) against the float64 statement of tests/beta_ref.py.
+"""MUR with the beta-divergence on the device (kernels_phase.hip) against the float64 statement of tests/beta_ref.py.
 Runs only on a real MI355X (`-m gpu`).
 
 Bars.  Half-steps: mur_step.BARS[("f32", "kl")] = 2e-5, the project's bar for exact-f32 kernels: gamma <= 1 never amplifies
@@ -96,10 +96,10 @@ def check(tag, x, om, beta, w0, h0, lw, lh, runs):
 
 # ---- 1. half-steps element by element ------------------------------------------------------------------------------------
 # (m, n, k, lambda_w, lambda_h, betas): the shapes of tests/test_gpu_is.py / test_gpu_weighted.py -- padded ranks 16, 64, 128,
-# ragged edges, n = 1, splits -- plus one that pads to 32; every padded rank sees a beta of each gamma branch
+# ragged edges, n = 1, splits -- plus two that pad to 32; every padded rank sees a beta of each gamma branch
 # (beta < 1, 1 <= beta <= 2, beta > 2) and every beta of the grid appears.
 SHAPES = [(127, 1, 3, 0.0, 0.0, (-1.0, 1.0, 2.5)), (700, 600, 16, 0.05, 0.0, (0.5, 1.5, 3.0)),
-          (130, 70, 20, 0.0, 0.02, (0.9, 2.0, 2.5)), (300, 200, 33, 0.0, 0.1, (-0.5, 2.0, 2.5)),
+          (130, 70, 20, 0.0, 0.02, (0.9, 2.0, 2.5)), (300, 200, 20, 0.0, 0.1, (0.5,)), (300, 200, 33, 0.0, 0.1, (-0.5, 2.0, 2.5)),
           (257, 130, 64, 0.1, 0.05, (0.9, 1.0, 3.0)), (700, 600, 100, 0.0, 0.0, (0.0, 1.5, 2.5)),
           (640, 384, 128, 0.02, 0.3, (0.5, 2.0, 3.0))]
 CASES = [(m, n, k, lw, lh, b) for m, n, k, lw, lh, bs in SHAPES for b in bs]
@@ -127,8 +127,12 @@ def test_half_steps_element_by_element(m, n, k, lw, lh, beta):
 
 
 # ---- 2. the same with weights= ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("beta", [0.5, 1.5, -1.0])
-@pytest.mark.parametrize("m,n,k,lw,lh", [(300, 200, 33, 0.0, 0.1), (257, 130, 64, 0.1, 0.05), (640, 384, 128, 0.02, 0.3)])
+WEIGHTED_CASES = [(m, n, k, lw, lh, b) for b in (0.5, 1.5, -1.0)
+                  for m, n, k, lw, lh in [(300, 200, 33, 0.0, 0.1), (257, 130, 64, 0.1, 0.05), (640, 384, 128, 0.02, 0.3)]]
+WEIGHTED_CASES.append((300, 200, 20, 0.0, 0.1, 0.5))              # padded rank 32
+
+
+@pytest.mark.parametrize("m,n,k,lw,lh,beta", WEIGHTED_CASES)
 def test_weighted_half_steps_element_by_element(m, n, k, lw, lh, beta):
     from nmf_amd import _lib as L
     from nmf_amd import weighted

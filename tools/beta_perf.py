@@ -1,11 +1,11 @@
-"""Time one MUR iteration with the beta-divergence (kernels_beta.hip) beside the two kernels it generalises.
+"""Time one MUR iteration with the beta-divergence (kernels_phase.hip, BetaEntry) beside the two kernels it generalises.
 
     python tools/beta_perf.py                       # 16384 x 8192, k = 64
     python tools/beta_perf.py --m 2048 --n 1024
 
 On one seeded strictly positive matrix, ms per iteration of
-    (a) 'beta' at beta = 0.5 and 1.5     kernels_beta.hip
-    (b) 'is'                             kernels_is.hip: the same structure without the power
+    (a) 'beta' at beta = 0.5 and 1.5     the BetaEntry policy of kernels_phase.hip
+    (b) 'is'                             its IsEntry policy: the same kernel without the power
     (c) 'kl' under NMFX_PRECISION=f32    the exact-f32 KL path
 All four run in one process on one stream, alternated: a warm-up batch each, then --reps rounds of one batch of --iters
 iterations each between device events; the best round counts.  One JSON line."""

@@ -1,4 +1,4 @@
-"""Time one MUR iteration with the Itakura-Saito divergence (kernels_is.hip) beside exact-f32 MUR-KL on the same matrix.
+"""Time one MUR iteration with the Itakura-Saito divergence (kernels_phase.hip, IsEntry) beside exact-f32 MUR-KL on the same matrix.
 
     python tools/is_perf.py --m 16384 --n 8192 --k 64 128
     python tools/is_perf.py --k 64 --kl-lib /path/to/another/libnmfx.so       # KL from another build (e.g. the parent commit's)

@@ -1,4 +1,4 @@
-"""Time one MUR iteration with per-entry weights (kernels_weighted.hip) beside the two paths it sits between.
+"""Time one MUR iteration with per-entry weights (kernels_phase.hip, WtEntry) beside the two paths it sits between.
 
     python tools/weighted_perf.py                       # 16384 x 8192, k = 64, 10 % / 50 % / 90 % observed, eu and kl
     python tools/weighted_perf.py --m 2048 --n 1024 --fractions 0.5
