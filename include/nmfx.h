@@ -135,6 +135,27 @@ int nmfx_clear_weights(nmfx_handle_t h);
  * NMFX_BETA the same way: NMFX_E_ARG, a message naming beta, nothing launched; so does nmfx_objective_f64 (a Euclidean
  * objective) on a handle whose current run is a beta run. */
 int nmfx_set_beta(nmfx_handle_t h, double beta);
+/* ---- automatic relevance determination (version 360) -----------------------
+ * The l1 form of Tan & Fevotte (TPAMI 2013) on top of the beta-divergence: component c < k of a run with k chosen too large
+ * carries a relevance lambda_c shared by column c of W and row c of H, and the superfluous components are driven to zero
+ * during the run.  With F x N the shape of the local V, phi > 0 the dispersion, a > 0, b > 0 and c = F + N + a + 1:
+ *   C(W, H, lambda) = Sum om d_beta(v | q)  +  phi Sum_{c<k} [ (|w_c|_1 + |h_c|_1 + b) / lambda_c + c log lambda_c ]
+ *   lambda_c = (|w_c|_1 + |h_c|_1 + b) / c          (the closed-form minimiser; its floor is b / c)
+ *   W <- W ( ((Om.V.q^(beta-2)) H^T) / ((Om.q^(beta-1)) H^T + phi / lambda_c) )^gamma       column c uses phi / lambda_c
+ *   H likewise with W' and the same lambda (row c uses phi / lambda_c); then lambda is recomputed from the new pair.
+ * nmfx_set_ard turns it on: a dense handle with k <= 128 on which a beta is set.  NMFX_E_ARG for a parameter that is not
+ * finite or not > 0, on a sparse handle and for k > 128; NMFX_E_STATE when no beta is set; nothing is launched.  While it is
+ * set, nmfx_mur_run / nmfx_mur_finish accept only NMFX_BETA with lambda_w = lambda_h = 0 (NMFX_E_ARG otherwise) and record
+ * obj[j] = C(W_j, H_j, lambda_j) = Sum om d_beta + phi c Sum_{c<k} (1 + log lambda_c), both parts and their sum in f64, under
+ * the usual stop rule; lambda_0 is computed from the start factors at the first run after nmfx_set_factors.  Every other
+ * compute entry point -- the MUR phase / chunk / slice / sharded forms, pair mode, nmfx_profile_repeat, AO-ADMM, ADMM, ANLS,
+ * nmfx_topk_svd -- returns NMFX_E_STATE and launches nothing.  nmfx_set_beta keeps ARD set (the relevances are recomputed
+ * before the next run).  nmfx_clear_ard turns it off: a run then equals a fresh handle's bit for bit.
+ * nmfx_get_relevance copies lambda_c, c < k, of the current iterate -- the one nmfx_get_factors returns -- to lambda_out
+ * (NMFX_E_STATE without nmfx_set_ard or factors).  The sums are f64 over the f32 factors in a fixed order. */
+int nmfx_set_ard(nmfx_handle_t h, double phi, double a, double b);
+int nmfx_clear_ard(nmfx_handle_t h);
+int nmfx_get_relevance(nmfx_handle_t h, double* lambda_out /* k */);
 /* ---- sparse V (version 310) ----------------------------------------------
  * A handle for a sparse m x n V with `nnz` stored entries, 1 <= k <= 256.  It runs MUR (both losses) without ever
  * forming V densely: nmfx_upload_csr takes V as CSR -- row_ptr [m + 1] (int64: nnz may pass 2^31), col_idx [nnz]

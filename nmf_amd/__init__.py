@@ -7,6 +7,7 @@
 The solver loops run as hand-written gfx950 HIP kernels behind the C ABI of
 include/nmfx.h (libnmfx.so, built in-tree by `python -m nmf_amd.build`).
 """
+from . import ard  # noqa: F401
 from .nmf import NMF  # noqa: F401
 
-__all__ = ['NMF']
+__all__ = ['NMF', 'ard']

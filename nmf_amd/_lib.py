@@ -40,6 +40,9 @@ SIGNATURES = {
     "nmfx_upload_weights": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64]),
     "nmfx_clear_weights": (_i32, [_vp]),
     "nmfx_set_beta": (_i32, [_vp, _dbl]),
+    "nmfx_set_ard": (_i32, [_vp, _dbl, _dbl, _dbl]),
+    "nmfx_clear_ard": (_i32, [_vp]),
+    "nmfx_get_relevance": (_i32, [_vp, _vp]),
     "nmfx_set_factors": (_i32, [_vp, _vp, _vp]),
     "nmfx_get_factors": (_i32, [_vp, _vp, _vp]),
     "nmfx_get_matrix": (_i32, [_vp, C.c_char_p, _vp]),

@@ -125,7 +125,7 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
 
 extern "C" {
 
-int nmfx_version(void) { return 350; }      // 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 360; }      // 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -256,7 +256,7 @@ int nmfx_destroy(nmfx_handle_t E) {
     nmfx_comm_free(E);
     for (auto& t : E->prof_pending) { hipEventDestroy(std::get<1>(t)); hipEventDestroy(std::get<2>(t)); }
     void* bufs[] = {E->V, E->W[0], E->W[1], E->H, E->HHt, E->HHt_part, E->G_part, E->A_part, E->B_part,
-                    E->obj_part, E->phase_part, E->Om, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
+                    E->obj_part, E->phase_part, E->Om, E->ard_sums, E->ard_lam, E->ard_pen, E->own_x ? (void*)E->xf32 : nullptr, E->own_x ? (void*)E->xf64 : nullptr,
                     E->obj_hist, E->state, E->dualW, E->dualH, E->auxW, E->auxH, E->Minv, E->nrm_part,
                     E->inner_hist, E->Pw, E->Ph, E->Asum, E->S, E->DV, E->Vt, E->Vtile, E->Bt_part, E->Whi[0], E->Whi[1],
                     E->Wlo[0], E->Wlo[1], E->WThi, E->WTlo, E->Hhi, E->Hlo, E->HThi, E->HTlo, E->nrm_rounds, E->bkX, E->bkU,
@@ -408,8 +408,54 @@ int nmfx_set_beta(nmfx_handle_t E, double beta) {
     if (!(beta >= -1.0 && beta <= 3.0)) { E->err = "set_beta: beta must lie in [-1, 3] (what f32 carries at q = 1e-9)"; return NMFX_E_ARG; }
     E->beta = beta;
     E->beta_set = true;
+    E->ard_valid = false;                              // (ARD stays set; its relevances are recomputed before the next run)
     static const char* const BETA_NOTE = "the beta-divergence (NMFX_BETA) runs the exact-f32 kernels; the split-bf16 mode does not apply to it";
     if (E->note.find(BETA_NOTE) == std::string::npos) E->note += (E->note.empty() ? "" : "; ") + std::string(BETA_NOTE);
+    return NMFX_OK;
+}
+
+// Automatic relevance determination on the beta path (version 360; kernels_phase.hip)
+int nmfx_set_ard(nmfx_handle_t E, double phi, double a, double b) {
+    if (!E) return NMFX_E_ARG;
+    if (E->sp) { E->err = "set_ard: automatic relevance determination is not available on a sparse handle (dense V, k <= 128)"; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = "set_ard: automatic relevance determination needs k <= 128"; return NMFX_E_ARG; }
+    if (!(std::isfinite(phi) && phi > 0.0 && std::isfinite(a) && a > 0.0 && std::isfinite(b) && b > 0.0)) {
+        E->err = "set_ard: phi, a and b must be finite and > 0"; return NMFX_E_ARG; }
+    if (!E->beta_set) { E->err = "set_ard: no beta set (nmfx_set_beta): automatic relevance determination runs on the beta-divergence"; return NMFX_E_STATE; }
+    NMFX_HIP(hipSetDevice(E->device));
+    { int rc_ = nmfx_ard_alloc(E); if (rc_) return rc_; }
+    E->ard_phi = phi; E->ard_a = a; E->ard_b = b;
+    E->ard = true;
+    E->ard_valid = false;
+    return NMFX_OK;
+}
+
+int nmfx_clear_ard(nmfx_handle_t E) {
+    if (!E) return NMFX_E_ARG;
+    E->ard = false;
+    E->ard_valid = false;
+    return NMFX_OK;
+}
+
+// the relevances of (W, H) where they are not the current ones: at the start of a run, after nmfx_set_beta / nmfx_set_ard
+static int ard_ensure(nmfx_engine* E, const float* W) {
+    if (!E->ard || E->ard_valid) return NMFX_OK;
+    int rc = nmfx_ard_relevance(E, W, false);
+    if (!rc) E->ard_valid = true;
+    return rc;
+}
+
+static int read_state(nmfx_engine* E, DevState* hs);
+int nmfx_get_relevance(nmfx_handle_t E, double* lambda_out) {
+    if (!E || !lambda_out) { if (E) E->err = "get_relevance: lambda_out is NULL"; return NMFX_E_ARG; }
+    if (!E->ard) { E->err = "get_relevance: automatic relevance determination is not set (nmfx_set_ard)"; return NMFX_E_STATE; }
+    if (!E->have_f) { E->err = "get_relevance: set factors first"; return NMFX_E_STATE; }
+    DevState hs; int rc;
+    if ((rc = read_state(E, &hs))) return rc;
+    if (hs.flag && !E->w_in_place) E->wsel = (int)((hs.stop_i + 1) & 1);
+    if ((rc = ard_ensure(E, E->W[E->wsel]))) return rc;
+    NMFX_HIP(hipMemcpyAsync(lambda_out, E->ard_lam, (size_t)E->k * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
     return NMFX_OK;
 }
 
@@ -499,6 +545,7 @@ int nmfx_set_factors(nmfx_handle_t E, const double* w, const double* hmat) {
     E->himg_both = false;
     E->lazy_objective = false;
     E->anls_a_ready = false;
+    E->ard_valid = false;
     if (E->kp <= 128 && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
     NMFX_HIP(hipStreamSynchronize(E->stream));
     return NMFX_OK;
@@ -891,15 +938,25 @@ static int dense_phase_path(nmfx_engine* E, int distance, const char* who, bool*
     return NMFX_OK;
 }
 
+// With nmfx_set_ard in force the penalty is the ARD one: NMFX_BETA alone, no lambda
+static int ard_request_ok(nmfx_engine* E, int distance, double lambda_w, double lambda_h, const char* who) {
+    if (!E->ard) return NMFX_OK;
+    if (distance != NMFX_BETA) { E->err = std::string(who) + ": automatic relevance determination is set (nmfx_set_ard): only NMFX_BETA runs with it"; return NMFX_E_ARG; }
+    if (lambda_w != 0.0 || lambda_h != 0.0) { E->err = std::string(who) + ": automatic relevance determination is set (nmfx_set_ard): lambda_w and lambda_h must be 0 (the penalty is the ARD one)"; return NMFX_E_ARG; }
+    return NMFX_OK;
+}
+
 int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h, int64_t min_iter,
                  double tol1, double tol2, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
     bool dense_phase;
+    { int rc_a = ard_request_ok(E, distance, lambda_w, lambda_h, "mur_run"); if (rc_a) return rc_a; }
     { int rc_p = dense_phase_path(E, distance, "mur_run", &dense_phase); if (rc_p) return rc_p; }
     if (dense_phase) {
         int rc = check_ready(E, first, count); if (rc) return rc;
         E->himg_both = false; E->kl_h_iter = -2;
         E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
+        if ((rc = ard_ensure(E, E->W[first & 1]))) return rc;             // lambda_0, or the relevances a new beta voided
         for (int64_t j = first; j < first + count && !rc; ++j) {
             if ((rc = nmfx_mur_dense_phase_a(E, distance, lambda_w, j))) break;
             E->wsel = (int)((j + 1) & 1);
@@ -924,12 +981,14 @@ int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1
                     int64_t iters_done) {
     int rc;
     bool dense_phase = false;
+    if (E && (rc = ard_request_ok(E, distance, 0.0, 0.0, "mur_finish"))) return rc;
     if (E && (rc = dense_phase_path(E, distance, "mur_finish", &dense_phase))) return rc;
     if (dense_phase) {
         if ((rc = check_ready(E, iters_done, 1))) return rc;
         E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
+        if ((rc = ard_ensure(E, E->W[iters_done & 1]))) return rc;
         if ((rc = nmfx_mur_dense_finish_a(E, distance, iters_done))) return rc;
-        return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
+        return E->ard ? nmfx_ard_finish_b(E, min_iter, tol1, tol2, iters_done) : nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
     }
     if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
     if ((rc = nmfx_mur_finish_a(E, distance, iters_done))) return rc;

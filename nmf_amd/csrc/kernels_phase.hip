@@ -41,6 +41,10 @@
 //   of the kept index that is all padding or carries no weight receives num = den = 0 and its closed form gives 0:
 //   Euclidean 0 / (lam w + 1e-9), KL B = 0 -> 0, the power forms den + lam = 0 -> 0 and w (0 / lam)^gamma = 0 otherwise.
 //
+// Automatic relevance determination (nmfx_set_ard) rides on BetaEntry: the phase kernel is untouched, the update
+// kernels add pen[c] = phi / lambda_c of the entry's component c to the denominator in place of the scalar lam, and two small
+// kernels recompute lambda_c = (|w_c|_1 + |h_c|_1 + b) / c after every H update (ard_sums_kernel, ard_finish_kernel).
+//
 // The power.  q^(beta-1) through the hardware's log2 / exp2 carries a relative error of about |beta-1| |ln q| times that of
 // the logarithm (1e-5 at q = 1e-9): powf, which keeps the logarithm's low part, is within an ulp for every q and is what
 // both BetaEntry and the general-gamma update use.  gamma = 1 and 1/2 are a plain quotient and sqrtf.
@@ -333,10 +337,11 @@ __device__ __forceinline__ float closed_form(int form, float gamma, float f, flo
     return f * (form == CF_ONE ? r : form == CF_HALF ? sqrtf(r) : powf(r, gamma));
 }
 
-// W_new from the slabs' numerators / denominators, summed in slab order
+// W_new from the slabs' numerators / denominators, summed in slab order.  pen (ARD; nullptr otherwise): the per-component
+// penalty [kp] that takes the place of lam
 __global__ __launch_bounds__(256) void phase_w_update_kernel(
     const float* __restrict__ part, int splits, int64_t count, int kp, int k, int form, float gamma,
-    const float* __restrict__ Wold, float lam, float* __restrict__ Wnew, const int* __restrict__ flag)
+    const float* __restrict__ Wold, float lam, const float* __restrict__ pen, float* __restrict__ Wnew, const int* __restrict__ flag)
 {
     if (*flag) return;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -344,17 +349,18 @@ __global__ __launch_bounds__(256) void phase_w_update_kernel(
     if ((int)(i % kp) >= k) { Wnew[i] = 0.f; return; }       // padded factors stay zero: 0/0 must stay out
     float a = part[i], d = part[count + i];
     for (int p = 1; p < splits; ++p) { a += part[(int64_t)(2 * p) * count + i]; d += part[(int64_t)(2 * p + 1) * count + i]; }
-    Wnew[i] = closed_form(form, gamma, Wold[i], a, d, lam);
+    Wnew[i] = closed_form(form, gamma, Wold[i], a, d, pen ? pen[i % kp] : lam);
 }
 
-// H_new after the objective bookkeeping / convergence test (same protocol as MUR-KL)
+// H_new after the objective bookkeeping / convergence test (same protocol as MUR-KL).  pen as above; ardobj (ARD; nullptr
+// otherwise): the penalty of the pair whose objective xf64[0] holds, added to it in f64 before it is recorded
 __global__ __launch_bounds__(256) void phase_h_update_kernel(
     const float* __restrict__ part, int splits, const double* __restrict__ xf64, float* __restrict__ H, int64_t np, int kp,
-    int k, int form, float gamma, float lam, long long j, long long min_iter, double tol1, double tol2,
-    DevState* __restrict__ st, double* __restrict__ obj_hist)
+    int k, int form, float gamma, float lam, const float* __restrict__ pen, const double* __restrict__ ardobj, long long j,
+    long long min_iter, double tol1, double tol2, DevState* __restrict__ st, double* __restrict__ obj_hist)
 {
     if (st->flag) return;
-    const int rule = nmfx_record_objective(st, obj_hist, xf64[0], j, min_iter, tol1, tol2,
+    const int rule = nmfx_record_objective(st, obj_hist, ardobj ? xf64[0] + ardobj[0] : xf64[0], j, min_iter, tol1, tol2,
                                            blockIdx.x == 0 && threadIdx.x == 0);
     if (rule) return;
     const int64_t count = (int64_t)kp * np;
@@ -369,12 +375,108 @@ __global__ __launch_bounds__(256) void phase_h_update_kernel(
         d.x += td.x; d.y += td.y; d.z += td.z; d.w += td.w;
     }
     const float4 h = *reinterpret_cast<const float4*>(H + i);
+    const float l = pen ? pen[i / np] : lam;                 // (np is a multiple of 4: the four entries share a row)
     float4 o;
-    o.x = closed_form(form, gamma, h.x, a.x, d.x, lam);
-    o.y = closed_form(form, gamma, h.y, a.y, d.y, lam);
-    o.z = closed_form(form, gamma, h.z, a.z, d.z, lam);
-    o.w = closed_form(form, gamma, h.w, a.w, d.w, lam);
+    o.x = closed_form(form, gamma, h.x, a.x, d.x, l);
+    o.y = closed_form(form, gamma, h.y, a.y, d.y, l);
+    o.z = closed_form(form, gamma, h.z, a.z, d.z, l);
+    o.w = closed_form(form, gamma, h.w, a.w, d.w, l);
     *reinterpret_cast<float4*>(H + i) = o;
+}
+
+// --------------------------------------------------------------------------
+// ARD: the relevances lambda_c = (|w_c|_1 + |h_c|_1 + b) / c of the components c < k, in f64 from the f32 factors, in two stages
+// with a fixed order of additions (no atomics: two runs are bit-identical).
+//   ard_sums_kernel    blocks [0, nwb): ARD_WROWS rows of W [mp][kp] each, read as whole rows of float4 (thread t of a pass = the
+//                      t-th float4 of a contiguous 4 KiB); a thread keeps four f64 column sums over its rows, thread cg < kp / 4
+//                      then adds the row lanes' sums in lane order -> sums[block][kp]
+//                      blocks [nwb, nwb + k nhc): row c of H [kp][np], columns [ARD_HCOLS chunk, ...), float4 per thread; f64
+//                      per thread, shuffle tree, the four waves in order -> sums[nwb + chunk][c]
+//   ard_finish_kernel  one block; thread c < k adds the W partials in block order, then the H partials in chunk order;
+//                      lam[c] = (sw + sh + b) / cc, pen[c] = (float)(phi / lam[c]); thread 0 adds the terms 1 + log lam[c]
+//                      in component order -> lam[kp] = phi cc Sum.  Padded components (c >= k) get lam = pen = 0 and no term.
+// flag: the run's stop flag (a stopped run keeps the relevances of the pair it stopped at), or nullptr.
+constexpr int ARD_WROWS = 128;       // mp is a multiple of 128
+constexpr int ARD_HCOLS = 2048;
+
+__global__ __launch_bounds__(256) void ard_sums_kernel(
+    const float* __restrict__ W, const float* __restrict__ H, int64_t np, int kp, int k, int nwb, int nhc,
+    double* __restrict__ sums, const int* __restrict__ flag)
+{
+    if (flag && *flag) return;
+    __shared__ double sh[256 * 4];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x < nwb) {
+        const int c4 = kp / 4, lanes = 256 / c4;             // float4 per row (4 .. 32), row lanes (64 .. 8)
+        const int cg = tid % c4, rl = tid / c4;
+        const float* base = W + (int64_t)blockIdx.x * ARD_WROWS * kp + 4 * cg;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (int r = rl; r < ARD_WROWS; r += lanes) {
+            const float4 f = *reinterpret_cast<const float4*>(base + (int64_t)r * kp);
+            s0 += (double)f.x; s1 += (double)f.y; s2 += (double)f.z; s3 += (double)f.w;
+        }
+        sh[tid * 4 + 0] = s0; sh[tid * 4 + 1] = s1; sh[tid * 4 + 2] = s2; sh[tid * 4 + 3] = s3;
+        __syncthreads();
+        if (tid < c4) {
+            double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+            for (int l = 0; l < lanes; ++l) {
+                const double* p = sh + (l * c4 + tid) * 4;
+                t0 += p[0]; t1 += p[1]; t2 += p[2]; t3 += p[3];
+            }
+            double* out = sums + (int64_t)blockIdx.x * kp + 4 * tid;
+            out[0] = t0; out[1] = t1; out[2] = t2; out[3] = t3;
+        }
+    } else {
+        const int hb = (int)blockIdx.x - nwb, c = hb / nhc, chunk = hb % nhc;      // c < k by the grid
+        const int64_t c0 = (int64_t)chunk * ARD_HCOLS, c1 = c0 + ARD_HCOLS < np ? c0 + ARD_HCOLS : np;
+        const float* row = H + (int64_t)c * np;
+        double s = 0.0;
+        for (int64_t at = c0 + 4 * tid; at < c1; at += 1024) {
+            const float4 f = *reinterpret_cast<const float4*>(row + at);
+            s += (((double)f.x + (double)f.y) + (double)f.z) + (double)f.w;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+        if ((tid & 63) == 0) sh[tid >> 6] = s;
+        __syncthreads();
+        if (tid == 0) sums[(int64_t)(nwb + chunk) * kp + c] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    }
+}
+
+__global__ __launch_bounds__(128) void ard_finish_kernel(
+    const double* __restrict__ sums, int nwb, int nhc, int kp, int k, double phi, double b, double cc,
+    double* __restrict__ lam, float* __restrict__ pen, const int* __restrict__ flag)
+{
+    if (flag && *flag) return;
+    __shared__ double term[128];
+    const int t = threadIdx.x;
+    if (t < kp) {
+        double l = 0.0, tm = 0.0;
+        float p = 0.f;
+        if (t < k) {
+            double sw = 0.0, sh = 0.0;
+            for (int i = 0; i < nwb; ++i) sw += sums[(int64_t)i * kp + t];
+            for (int i = 0; i < nhc; ++i) sh += sums[(int64_t)(nwb + i) * kp + t];
+            l = ((sw + sh) + b) / cc;
+            p = (float)(phi / l);
+            tm = 1.0 + log(l);
+        }
+        lam[t] = l; pen[t] = p; term[t] = tm;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double s = 0.0;
+        for (int i = 0; i < k; ++i) s += term[i];
+        lam[kp] = (phi * cc) * s;
+    }
+}
+
+// the closing step of an ARD run: obj[j] = the objective of the last pair + its penalty, and the stop rule
+__global__ void ard_finalize_kernel(const double* __restrict__ xf64, const double* __restrict__ ardobj, long long j, long long min_iter,
+                                    double tol1, double tol2, DevState* __restrict__ st, double* __restrict__ obj_hist)
+{
+    if (st->flag) return;
+    nmfx_record_objective(st, obj_hist, xf64[0] + ardobj[0], j, min_iter, tol1, tol2, threadIdx.x == 0);
 }
 
 // --------------------------------------------------------------------------
@@ -493,7 +595,8 @@ int nmfx_mur_dense_phase_a(nmfx_engine* E, int distance, double lambda_w, int64_
       float gamma;
       const int form = update_form(E, distance, &gamma);
       hipLaunchKernelGGL(phase_w_update_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, E->stream, E->phase_part,
-                         phase_wsplits(E), count, E->kp, E->k, form, gamma, Wold, (float)lambda_w, Wnew, &E->state->flag);
+                         phase_wsplits(E), count, E->kp, E->k, form, gamma, Wold, (float)lambda_w,
+                         E->ard ? (const float*)E->ard_pen : (const float*)nullptr, Wnew, &E->state->flag);
       NMFX_HIP(hipGetLastError()); }
     { ProfScope ps(E, P.hscope);
       if ((rc = phase(E, distance, false, true, Wnew))) return rc; }
@@ -501,13 +604,63 @@ int nmfx_mur_dense_phase_a(nmfx_engine* E, int distance, double lambda_w, int64_
 }
 
 int nmfx_mur_dense_phase_b(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j) {
-    ProfScope ps(E, "h_update");
-    const int64_t n4 = ((int64_t)E->kp * E->np) / 4;
-    float gamma;
-    const int form = update_form(E, distance, &gamma);
-    hipLaunchKernelGGL(phase_h_update_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, E->stream, E->phase_part,
-                       phase_hsplits(E), E->xf64, E->H, E->np, E->kp, E->k, form, gamma, (float)lambda_h, (long long)j,
-                       (long long)min_iter, tol1, tol2, E->state, E->obj_hist);
+    { ProfScope ps(E, "h_update");
+      const int64_t n4 = ((int64_t)E->kp * E->np) / 4;
+      float gamma;
+      const int form = update_form(E, distance, &gamma);
+      hipLaunchKernelGGL(phase_h_update_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, E->stream, E->phase_part,
+                         phase_hsplits(E), E->xf64, E->H, E->np, E->kp, E->k, form, gamma, (float)lambda_h,
+                         E->ard ? (const float*)E->ard_pen : (const float*)nullptr,
+                         E->ard ? (const double*)(E->ard_lam + E->kp) : (const double*)nullptr, (long long)j,
+                         (long long)min_iter, tol1, tol2, E->state, E->obj_hist);
+      NMFX_HIP(hipGetLastError()); }
+    // ARD: the relevances of the pair this iteration leaves, (W_{j+1}, H_{j+1}); skipped where the stop rule has just fired
+    if (E->ard) return nmfx_ard_relevance(E, E->W[(j + 1) & 1], true);
+    return NMFX_OK;
+}
+
+// ---- ARD (nmfx_set_ard) ---------------------------------------------------
+static int ard_wblocks(const nmfx_engine* E) { return (int)(E->mp / ARD_WROWS); }
+static int ard_hchunks(const nmfx_engine* E) { return (int)((E->np + ARD_HCOLS - 1) / ARD_HCOLS); }
+
+// one zeroed ARD buffer, unless it exists: a call that failed half way is completed by the next one
+template <typename T>
+static int ard_buffer(nmfx_engine* E, T** p, size_t count) {
+    if (*p) return NMFX_OK;
+    T* buf = nullptr;
+    NMFX_HIP(hipMalloc(reinterpret_cast<void**>(&buf), count * sizeof(T)));
+    const hipError_t e = hipMemsetAsync(buf, 0, count * sizeof(T), E->stream);
+    if (e != hipSuccess) { (void)hipFree(buf); E->err = std::string("ard_buffer: ") + hipGetErrorString(e); return NMFX_E_HIP; }
+    *p = buf;
+    return NMFX_OK;
+}
+
+// all three buffers or an error: nmfx_set_ard turns ARD on only behind NMFX_OK
+int nmfx_ard_alloc(nmfx_engine* E) {
+    int rc;
+    if ((rc = ard_buffer(E, &E->ard_sums, (size_t)(ard_wblocks(E) + ard_hchunks(E)) * E->kp))) return rc;
+    if ((rc = ard_buffer(E, &E->ard_lam, (size_t)E->kp + 1))) return rc;
+    return ard_buffer(E, &E->ard_pen, (size_t)E->kp);
+}
+
+// lambda, phi / lambda and the penalty of (W, E->H); c = m + n + a + 1
+int nmfx_ard_relevance(nmfx_engine* E, const float* W, bool honour_stop) {
+    ProfScope ps(E, "ard_relevance");
+    const int nwb = ard_wblocks(E), nhc = ard_hchunks(E);
+    const int* flag = honour_stop ? &E->state->flag : nullptr;
+    hipLaunchKernelGGL(ard_sums_kernel, dim3((unsigned)(nwb + E->k * nhc)), dim3(256), 0, E->stream, W, (const float*)E->H, E->np,
+                       E->kp, E->k, nwb, nhc, E->ard_sums, flag);
+    NMFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ard_finish_kernel, dim3(1), dim3(128), 0, E->stream, (const double*)E->ard_sums, nwb, nhc, E->kp, E->k,
+                       E->ard_phi, E->ard_b, (double)E->m + (double)E->n + E->ard_a + 1.0, E->ard_lam, E->ard_pen, flag);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+int nmfx_ard_finish_b(nmfx_engine* E, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    ProfScope ps(E, "small");
+    hipLaunchKernelGGL(ard_finalize_kernel, dim3(1), dim3(64), 0, E->stream, (const double*)E->xf64, (const double*)(E->ard_lam + E->kp),
+                       (long long)j, (long long)min_iter, tol1, tol2, E->state, E->obj_hist);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }

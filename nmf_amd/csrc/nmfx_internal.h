@@ -178,6 +178,13 @@ struct nmfx_engine {
     bool beta_run = false;         // ... or, with is_run set as well, the beta-divergence (dense handles only; it only words that refusal)
     double beta = 0.0;             // nmfx_set_beta: the beta of NMFX_BETA runs (kernels_phase.hip)
     bool beta_set = false;
+    // nmfx_set_ard: automatic relevance determination on the beta path (kernels_phase.hip)
+    bool ard = false;
+    bool ard_valid = false;        // ard_lam (the penalty at ard_lam[kp] included) and ard_pen belong to the current (W, H)
+    double ard_phi = 0.0, ard_a = 0.0, ard_b = 0.0;
+    double* ard_sums = nullptr;    // [W row blocks + H column chunks][kp] f64 partial column sums of W / row sums of H
+    double* ard_lam = nullptr;     // [kp] the relevances lambda_k, then [1] the penalty phi c Sum (1 + log lambda_k)
+    float* ard_pen = nullptr;      // [kp] phi / lambda_k, what the update kernels add to their denominators (0 for k >= K)
     bool pair = false;             // nmfx_mur_pair_*: factor columns [0, 64) and [64, 128) are two independent problems
     int family = 0;                // solver family that has run since nmfx_set_factors (0 none, 1 MUR eu/kl, 2 AO-ADMM, 3 ADMM, 4 ANLS): nmfx_enter_family
     bool w_in_place = false;       // solver updates W[0] in place (all but MUR, which ping-pongs)
@@ -264,6 +271,11 @@ int nmfx_finish_b(nmfx_engine* E, int64_t min_iter, double tol1, double tol2, in
 int nmfx_mur_dense_phase_a(nmfx_engine* E, int distance, double lambda_w, int64_t j);
 int nmfx_mur_dense_phase_b(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
 int nmfx_mur_dense_finish_a(nmfx_engine* E, int distance, int64_t j);
+// ... with nmfx_set_ard in force: the relevances of (W, H) -- W = the buffer that holds the current iterate; honour_stop: skipped once
+// the stop rule has fired -- and the closing step that records the objective plus the penalty
+int nmfx_ard_alloc(nmfx_engine* E);
+int nmfx_ard_relevance(nmfx_engine* E, const float* W, bool honour_stop);
+int nmfx_ard_finish_b(nmfx_engine* E, int64_t min_iter, double tol1, double tol2, int64_t j);
 // One solver family per set of factors: the families keep different device state next to W and H (MUR: W ping-pong and bf16 images of
 // both factors; AO-ADMM / ADMM: duals and auxiliaries; ANLS: warm-start supports), and a family that starts in the middle of another's
 // run would read leftovers.  A second family on the same handle needs nmfx_get_factors -> nmfx_set_factors first (NMFX_E_STATE otherwise).
@@ -348,11 +360,16 @@ int nmfx_sparse_objective_f64(nmfx_engine* E, double* out);
     (E)->err = std::string(__func__) + ": not available on a sparse handle (nmfx_create_csr handles run MUR only)"; \
     return NMFX_E_ARG; } } while (0)
 // ... and of every COMPUTE entry point but nmfx_mur_run / nmfx_mur_finish: those two alone know the per-entry weights of
-// nmfx_upload_weights, so everything else that would compute from V refuses while weights are present.
+// nmfx_upload_weights and the relevances of nmfx_set_ard, so everything else that would compute from V refuses while weights
+// are present (NMFX_E_ARG) or ARD is set (NMFX_E_STATE).
 #define NMFX_DENSE_ONLY(E) do { NMFX_NOT_SPARSE(E); if ((E) && (E)->Om) { \
     (E)->err = std::string(__func__) + ": not available while per-entry weights are present (nmfx_upload_weights): " \
                "only nmfx_mur_run / nmfx_mur_finish compute with weights; nmfx_clear_weights removes them"; \
-    return NMFX_E_ARG; } } while (0)
+    return NMFX_E_ARG; } \
+    if ((E) && (E)->ard) { \
+    (E)->err = std::string(__func__) + ": not available while automatic relevance determination is set (nmfx_set_ard): " \
+               "only nmfx_mur_run / nmfx_mur_finish with NMFX_BETA run it; nmfx_clear_ard turns it off"; \
+    return NMFX_E_STATE; } } while (0)
 
 int nmfx_preload_sparse();
 int nmfx_preload_bf16();

@@ -139,6 +139,20 @@ class Engine:
         """The beta of mur_run / mur_finish with L.BETA (dense handle, k <= 128, -1 <= beta <= 3; include/nmfx.h)."""
         self._ck(self.lib.nmfx_set_beta(self.h, float(beta)))
 
+    def set_ard(self, phi, a, b):
+        """Automatic relevance determination for mur_run / mur_finish with L.BETA (after set_beta; dense handle, k <= 128;
+        lambda_w = lambda_h = 0): dispersion phi and the prior's a, b, all > 0 (include/nmfx.h)."""
+        self._ck(self.lib.nmfx_set_ard(self.h, float(phi), float(a), float(b)))
+
+    def clear_ard(self):
+        self._ck(self.lib.nmfx_clear_ard(self.h))
+
+    def relevance(self):
+        """lambda_c of the current iterate's components, float64 [k] (set_ard in force)."""
+        out = np.empty(self.k, dtype=np.float64)
+        self._ck(self.lib.nmfx_get_relevance(self.h, _ptr(out)))
+        return out
+
     def set_factors(self, w, h):
         w = np.ascontiguousarray(w, dtype=np.float64)
         h = np.ascontiguousarray(h, dtype=np.float64)

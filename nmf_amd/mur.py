@@ -217,13 +217,7 @@ def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol
     if engine is not None:
         raise ValueError('weights=: engine= is not supported (the engine is created for the weighted data)')
     x32, w32 = weighted.prepare(x, weights, k, experiment.distance_type, beta=beta)
-    if nndsvd_init[0]:
-        with np.errstate(invalid='ignore'):
-            start = np.where(w32 > 0, np.asarray(x), 0)
-        init = utils.initial_factors(sp.csr_matrix(start), k, nndsvd_init)      # (the masked path's NNDSVD)
-        del start
-    else:
-        init = utils.initial_factors(x32, k, nndsvd_init)
+    init = weighted_start(x, x32, w32, k, nndsvd_init)
     with Engine(x32.shape[0], x32.shape[1], k, device=device) as eng:
         eng.upload_v(x32)
         eng.upload_weights(w32)
@@ -239,6 +233,16 @@ def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol
         mur.last_referee = None
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def weighted_start(x, x32, w32, k, nndsvd_init):
+    """The start factors of a weighted run (x32, w32 from weighted.prepare): the global RNG's draws as in mur, or the
+    NNDSVD, unweighted and on the host, of x with the zero-weight cells set to 0."""
+    if nndsvd_init[0]:
+        with np.errstate(invalid='ignore'):
+            start = np.where(w32 > 0, np.asarray(x), 0)
+        return utils.initial_factors(sp.csr_matrix(start), k, nndsvd_init)      # (the masked path's NNDSVD)
+    return utils.initial_factors(x32, k, nndsvd_init)
 
 
 def mur_pair(x, k, params, *, min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5, nndsvd_init=(False, 'zero'),

@@ -2,13 +2,18 @@
 
     python tools/beta_perf.py                       # 16384 x 8192, k = 64
     python tools/beta_perf.py --m 2048 --n 1024
+    python tools/beta_perf.py --ard                 # beta = 0.5 with and without automatic relevance determination
 
 On one seeded strictly positive matrix, ms per iteration of
     (a) 'beta' at beta = 0.5 and 1.5     the BetaEntry policy of kernels_phase.hip
     (b) 'is'                             its IsEntry policy: the same kernel without the power
     (c) 'kl' under NMFX_PRECISION=f32    the exact-f32 KL path
 All four run in one process on one stream, alternated: a warm-up batch each, then --reps rounds of one batch of --iters
-iterations each between device events; the best round counts.  One JSON line."""
+iterations each between device events; the best round counts.  One JSON line.
+
+--ard times two legs only, 'beta' at beta = 0.5 plain and with nmfx_set_ard (phi = 0.1, a = 5, the default b), the same way:
+what the per-component penalty and the relevance reduction (two small launches per iteration, (m + n) kp 4 bytes read
+against V's m n 4) add to an iteration."""
 import argparse
 import json
 import os
@@ -41,6 +46,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--ard", action="store_true", help="time beta = 0.5 with and without ARD instead of the four legs")
     a = ap.parse_args()
 
     import torch
@@ -52,18 +58,23 @@ def main():
     h0 = np.ascontiguousarray(rng.uniform(0.1, 1.0, (a.k, a.n)))
     stream = torch.cuda.current_stream().cuda_stream
 
-    def engine(beta=None):
+    def engine(beta=None, ard=False):
         e = Engine(a.m, a.n, a.k)
         e.set_stream(stream)
         e.upload_v(v)
         if beta is not None:
             e.set_beta(beta)
+        if ard:
+            e.set_ard(0.1, 5.0, float(np.sqrt(12.0 * float(v.mean(dtype=np.float64)) / a.k)))
         return e
 
-    legs = {f"beta_{b:g}": (engine(b), L.BETA) for b in a.betas}
-    legs["is"] = (engine(), L.IS)
-    legs["kl_f32"] = (engine(), L.KL)
-    assert legs["kl_f32"][0].precision() == "f32"
+    if a.ard:
+        legs = {"beta_0.5": (engine(0.5), L.BETA), "ard_0.5": (engine(0.5, ard=True), L.BETA)}
+    else:
+        legs = {f"beta_{b:g}": (engine(b), L.BETA) for b in a.betas}
+        legs["is"] = (engine(), L.IS)
+        legs["kl_f32"] = (engine(), L.KL)
+        assert legs["kl_f32"][0].precision() == "f32"
     ms = {name: [] for name in legs}
     done = {}
     for name, (eng, dist) in legs.items():                      # fresh start, warm-up batch
@@ -79,7 +90,11 @@ def main():
     best = {name: min(t) for name, t in ms.items()}
     out = {"m": a.m, "n": a.n, "k": a.k, "iters_per_batch": a.iters}
     out.update({f"{name}_ms_per_iter": round(t, 4) for name, t in best.items()})
-    out.update({f"{name}_over_is": round(best[name] / best["is"], 3) for name in best if name.startswith("beta_")})
+    if a.ard:
+        out["ard_over_beta"] = round(best["ard_0.5"] / best["beta_0.5"], 4)
+        out["ard_extra_ms_per_iter"] = round(best["ard_0.5"] - best["beta_0.5"], 4)
+    else:
+        out.update({f"{name}_over_is": round(best[name] / best["is"], 3) for name in best if name.startswith("beta_")})
     out["all_ms"] = {name: [round(t, 4) for t in ts] for name, ts in ms.items()}
     print(json.dumps(out), flush=True)
     for eng, _ in legs.values():
