@@ -13,10 +13,17 @@
 //     infeasible = {i in F: x_i < 0} u {i in G: y_i < 0};  exchange them (all at once,
 //     with the usual back-up rule: after 3 non-improving full exchanges only the
 //     largest infeasible index) until none is left.
-// One wavefront owns one right-hand side, so the data-dependent control flow is
-// wave-uniform; variable i lives on lane i (and i+64 for k > 64).  The k x k solve
-// is a Gauss-Jordan elimination over the passive pivots in a per-wave LDS
-// workspace (no pivoting: G_FF is SPD).
+// One wavefront owns one right-hand side (two at k = 128), so the data-dependent
+// control flow is wave-uniform; variable i lives on lane i.  The k x k solve is a
+// Gauss-Jordan elimination over the passive pivots on rows held in registers (no
+// pivoting: G_FF is SPD).
+// WARM START: the passive set starts as the support of the previous solution (X on
+// entry: the factor of the last outer iteration, or the initial factor).  Block
+// principal pivoting reaches the unique KKT point from any start; once the supports
+// settle a half-step needs one or two solves per right-hand side instead of a cold
+// start's five to ten.  Iteration 0 solves for the warm-start set; a solve that has
+// not become feasible after 8 KP + 64 exchanges stops there and is counted in
+// st->nnls_capped.
 #include "nmfx_internal.h"
 #include "kernels_small.h"
 
@@ -39,168 +46,15 @@ __device__ __forceinline__ float wave_max(float v) {
 // at zero as well (its dual is zero, it is never selected).  (NaN pivots fail the comparison and are dropped too.)
 #define NMFX_NNLS_PIVOT_EPS 1e-6f
 
-template <int KP>
-__global__ __launch_bounds__(KP <= 64 ? 256 : 128) void nnls_bpp_kernel(
-    const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
-    int64_t sj, int64_t sc, int64_t nprob, int k, DevState* __restrict__ st, const int* __restrict__ todo,
-    const int* __restrict__ inv_bad)
-{
-    if (st->flag) return;
-    constexpr int NV = KP <= 64 ? 1 : KP / 64;          // variables per lane
-    constexpr int NW = KP <= 64 ? 4 : 2;                // waves (problems) per block
-    constexpr int LDM = KP + 1;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t c = (int64_t)blockIdx.x * NW + wave;
-    if (c >= nprob) return;                              // whole wave leaves together
-    if (todo && !*inv_bad && !todo[c]) return;           // solved by nnls_cinv_kernel
-    float* M = lds + (size_t)wave * (KP * LDM + KP);     // [KP][KP+1] augmented rows
-    float* xs = M + KP * LDM;                            // [KP] broadcast copy of x
-
-    int idx[NV]; bool valid[NV], inF[NV], dead[NV];
-    float r[NV], x[NV], y[NV];
-    // WARM START: the passive set starts as the support of the previous solution (X on entry: the
-    // factor of the last outer iteration, or the initial factor).  Block principal pivoting reaches the
-    // unique KKT point from any start; once the supports settle a half-step needs one or two solves
-    // per right-hand side instead of a cold start's five to ten.
-#pragma unroll
-    for (int t = 0; t < NV; ++t) {
-        idx[t] = lane + 64 * t;
-        valid[t] = idx[t] < k;
-        r[t] = valid[t] ? R[(int64_t)idx[t] * sj + c * sc] : 0.f;
-        x[t] = 0.f; y[t] = -r[t]; dead[t] = false;
-        inF[t] = valid[t] && X[(int64_t)idx[t] * sj + c * sc] > 0.f;
-    }
-    float toly;
-    {
-        float ar = 0.f;
-#pragma unroll
-        for (int t = 0; t < NV; ++t) ar = fmaxf(ar, fabsf(r[t]));
-        toly = NMFX_NNLS_TOL * wave_max(ar);
-    }
-    int best = k + 1, spare = 3, iter = 0;
-    for (; iter < 8 * KP + 64; ++iter) {
-        unsigned long long Im[NV];
-        if (iter > 0) {                                  // (iteration 0 solves for the warm-start set first)
-        float ax = 0.f;
-#pragma unroll
-        for (int t = 0; t < NV; ++t) ax = fmaxf(ax, fabsf(x[t]));
-        const float tolx = NMFX_NNLS_TOL * wave_max(ax);
-        int n_inf = 0;
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            const bool bad = valid[t] && !dead[t] && (inF[t] ? (x[t] < -tolx) : (y[t] < -toly));
-            Im[t] = __ballot(bad);
-            n_inf += __popcll(Im[t]);
-        }
-        if (n_inf == 0) break;
-        bool full = true;
-        if (n_inf < best) { best = n_inf; spare = 3; }
-        else if (spare > 0) { --spare; }
-        else full = false;
-        if (!full) {                                     // back-up rule: largest infeasible index only
-#pragma unroll
-            for (int t = NV - 1; t >= 0; --t) {
-                if (Im[t]) {
-                    const int hi = 63 - __clzll((long long)Im[t]);
-                    Im[t] = 1ull << hi;
-#pragma unroll
-                    for (int u = 0; u < t; ++u) Im[u] = 0ull;
-                    break;
-                }
-            }
-        }
-        } else {
-#pragma unroll
-            for (int t = 0; t < NV; ++t) Im[t] = 0ull;
-        }
-        unsigned long long Fm[NV];
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            if ((Im[t] >> lane) & 1ull) inF[t] = !inF[t];
-            Fm[t] = __ballot(inF[t]);
-        }
-        // augmented rows of the passive variables (other rows are never touched).  ALL columns are
-        // copied and eliminated: the non-passive ones multiply x = 0 and never serve as pivots, and
-        // plain full-width loops keep the LDS operations independent and pipelined (the earlier
-        // bit-scan over the passive columns made every read-modify-write wait for the previous one).
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            if (inF[t]) {
-                const float* grow = G + (int64_t)idx[t] * KP;
-                float* mrow = M + idx[t] * LDM;
-#pragma unroll 8
-                for (int cc = 0; cc < KP; ++cc) mrow[cc] = grow[cc] + (cc == idx[t] ? diag_add : 0.f);
-                mrow[KP] = r[t];
-            }
-        }
-        // Gauss-Jordan over the passive pivots (no normalisation: x_i = rhs_i / diag_i at the end)
-        for (int tp = 0; tp < NV; ++tp) {
-            unsigned long long left = Fm[tp];
-            while (left) {
-                const int b = __ffsll((long long)left) - 1;
-                left &= left - 1;
-                const int p = b + 64 * tp;
-                const float* prow = M + p * LDM;
-                if (!(prow[p] > NMFX_NNLS_PIVOT_EPS * (G[(int64_t)p * KP + p] + diag_add))) {   // vanished pivot: drop the variable
-#pragma unroll
-                    for (int t = 0; t < NV; ++t) if (idx[t] == p) { inF[t] = false; dead[t] = true; }
-                    if (lane == 0) atomicAdd(&st->nnls_evicted, 1);
-                    continue;
-                }
-                const float inv = 1.f / prow[p];
-                const int c0 = (p + 1) & ~3;                 // columns <= p of the pivot row are already zero
-#pragma unroll
-                for (int t = 0; t < NV; ++t) {
-                    if (inF[t] && idx[t] != p) {
-                        float* mrow = M + idx[t] * LDM;
-                        const float f = mrow[p] * inv;
-                        for (int cc = p + 1; cc < c0; ++cc) mrow[cc] = fmaf(-f, prow[cc], mrow[cc]);
-#pragma unroll 4
-                        for (int cc = c0; cc < KP; cc += 4) {
-                            const float p0 = prow[cc], p1 = prow[cc + 1], p2 = prow[cc + 2], p3 = prow[cc + 3];
-                            const float m0 = mrow[cc], m1 = mrow[cc + 1], m2 = mrow[cc + 2], m3 = mrow[cc + 3];
-                            mrow[cc] = fmaf(-f, p0, m0); mrow[cc + 1] = fmaf(-f, p1, m1);
-                            mrow[cc + 2] = fmaf(-f, p2, m2); mrow[cc + 3] = fmaf(-f, p3, m3);
-                        }
-                        mrow[KP] = fmaf(-f, prow[KP], mrow[KP]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            x[t] = inF[t] ? M[idx[t] * LDM + KP] / M[idx[t] * LDM + idx[t]] : 0.f;
-            if (idx[t] < KP) xs[idx[t]] = x[t];          // lanes beyond KP own no variable
-        }
-        // dual variables of the active set: y = G x - r   (x = 0 outside the passive set)
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            float acc = 0.f;
-            if (valid[t] && !inF[t]) {
-                const float* grow = G + (int64_t)idx[t] * KP;
-#pragma unroll 8
-                for (int cc = 0; cc < KP; ++cc) acc = fmaf(grow[cc], xs[cc], acc);
-                acc -= r[t];
-            }
-            y[t] = acc;
-        }
-    }
-    if (iter == 8 * KP + 64 && lane == 0) atomicAdd(&st->nnls_capped, 1);
-#pragma unroll
-    for (int t = 0; t < NV; ++t)
-        if (idx[t] < KP) X[(int64_t)idx[t] * sj + c * sc] = (valid[t] && x[t] > 0.f) ? x[t] : 0.f;
-}
-
 #ifdef NMFX_NNLS_STATS          // experiment builds only (tools/anls_perf.py --stats), like the other nmfx_debug_* exports: not part of include/nmfx.h
 __device__ unsigned long long nnls_dbg[8];     // [sum of iterations, max, problems, exchanges in back-up mode, pivots, final support]
 #endif
 
-// Register-resident variant for k <= 64 (one variable per lane, one right-hand side per wave):
+// k <= 64 (one variable per lane, one right-hand side per wave):
 // lane i keeps row i of G in registers, the elimination works on a register copy with the pivot
 // row BROADCAST through the LDS crossbar (ds_bpermute), pivots in static order.
-// No LDS storage, no data-dependent addressing: the LDS version above spends its time in serial
-// read-modify-write chains (34 ms per half-step at 16384 x 8192, k = 64).
+// No LDS storage, no data-dependent addressing (the first form, a per-wave LDS workspace, spent its
+// time in serial read-modify-write chains: 34 ms per half-step at 16384 x 8192, k = 64).
 // The elimination runs over the passive pivots only but over ALL columns: the non-passive columns
 // multiply x = 0, so the passive rows still end with x_i = rhs_i (pivot rows are normalised).
 template <int KP>
@@ -431,14 +285,9 @@ __device__ __forceinline__ void nnls_bpp_reg128_body(
     X[(int64_t)tid * sj + c * sc] = (valid && x > 0.f) ? x : 0.f;
 }
 
-// Two register budgets for the same body: 256 registers (two waves per SIMD; hipcc parks ~40 dwords of the row in
-// scratch) or 512 (one wave per SIMD, no scratch).  NMFX_NNLS128_OCC=1 selects the second; measured in tools/anls_perf.py.
+// 256 registers (two waves per SIMD; hipcc parks ~40 dwords of the row in scratch): the one-wave-per-SIMD build without scratch
+// measured slower.  (The body stays a function of its own: written into the kernel, hipcc schedules it differently.)
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 3))) void nnls_bpp_reg128_kernel(
-    const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
-    int64_t sj, int64_t sc, int64_t nprob, int k, DevState* __restrict__ st, const int* __restrict__ todo,
-    const int* __restrict__ inv_bad)
-{ nnls_bpp_reg128_body(G, diag_add, R, X, sj, sc, nprob, k, st, todo, inv_bad); }
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) void nnls_bpp_reg128_wide_kernel(
     const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
     int64_t sj, int64_t sc, int64_t nprob, int k, DevState* __restrict__ st, const int* __restrict__ todo,
     const int* __restrict__ inv_bad)
@@ -454,7 +303,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // |F| x |F| elimination.  A first version with an f32 inverse was too inaccurate (G^-1 squares the condition number of
 // the data matrix); here G^-1 is formed ONCE per half-step in f64 (nnls_inverse_kernel: in-place Gauss-Jordan of
 // G + diag_add I in LDS, one workgroup) and every per-problem quantity is f64.  Same exchange rules, tolerances, warm
-// start and iteration cap as nnls_bpp_kernel.  What this path does not take it leaves to the elimination kernels, which
+// start and iteration cap (8 KP + 64) as the elimination kernels above.  What this path does not take it leaves to the elimination kernels, which
 // run afterwards on exactly those problems: a half-step whose Gram matrix is singular or too ill-conditioned for an
 // explicit inverse (`inv_bad`: a dead or collinear component at lambda = 0 -- their pivot guard handles it), and
 // single problems whose complement outgrows the workspace (todo[c] = 1).
@@ -688,19 +537,6 @@ static int launch_nnls_reg(nmfx_engine* E, const float* G, float diag_add, const
     return NMFX_OK;
 }
 
-template <int KP>
-static int launch_nnls(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj,
-                       int64_t sc, int64_t nprob, const int* todo, const int* bad) {
-    constexpr int NW = KP <= 64 ? 4 : 2;
-    const size_t shm = (size_t)NW * (KP * (KP + 1) + KP) * sizeof(float);
-    auto kern = nnls_bpp_kernel<KP>;
-    { int rc_ = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc_) return rc_; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((nprob + NW - 1) / NW)), dim3(64 * NW), shm, E->stream, G, diag_add,
-                       R, X, sj, sc, nprob, E->k, E->state, todo, bad);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-
 template <typename T>
 static int lazy_alloc(nmfx_engine* E, T** p, int64_t count) {
     if (*p) return NMFX_OK;
@@ -756,7 +592,6 @@ static int launch_nnls_cinv(nmfx_engine* E, const float* G, float diag_add, cons
 static int nnls(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
                 int64_t nprob) {
     ProfScope ps(E, "nnls");
-    static const bool lds_only = getenv("NMFX_NNLS_LDS") && atoi(getenv("NMFX_NNLS_LDS")) != 0;
     // NMFX_NNLS_CINV=0: elimination kernels only (the round-1 path; A/B runs and tests/test_gpu_knobs.py)
     static const bool cinv = !(getenv("NMFX_NNLS_CINV") && atoi(getenv("NMFX_NNLS_CINV")) == 0);
     const int* todo = nullptr; const int* bad = nullptr;
@@ -771,17 +606,12 @@ static int nnls(nmfx_engine* E, const float* G, float diag_add, const float* R, 
         if (rc) return rc;
     }
     switch (E->kp) {
-        case 16: return lds_only ? launch_nnls<16>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad)
-                                 : launch_nnls_reg<16>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad);
-        case 32: return lds_only ? launch_nnls<32>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad)
-                                 : launch_nnls_reg<32>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad);
-        case 64: return lds_only ? launch_nnls<64>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad)
-                                 : launch_nnls_reg<64>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad);
+        case 16: return launch_nnls_reg<16>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad);
+        case 32: return launch_nnls_reg<32>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad);
+        case 64: return launch_nnls_reg<64>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad);
         default:
-            if (lds_only) return launch_nnls<128>(E, G, diag_add, R, X, sj, sc, nprob, todo, bad);
-            { static const bool wide = getenv("NMFX_NNLS128_OCC") && atoi(getenv("NMFX_NNLS128_OCC")) == 1;
-              hipLaunchKernelGGL(wide ? nnls_bpp_reg128_wide_kernel : nnls_bpp_reg128_kernel, dim3((unsigned)nprob), dim3(128), 0,
-                                 E->stream, G, diag_add, R, X, sj, sc, nprob, E->k, E->state, todo, bad); }
+            hipLaunchKernelGGL(nnls_bpp_reg128_kernel, dim3((unsigned)nprob), dim3(128), 0, E->stream, G, diag_add, R, X, sj, sc, nprob, E->k,
+                               E->state, todo, bad);
             NMFX_HIP(hipGetLastError());
             return NMFX_OK;
     }

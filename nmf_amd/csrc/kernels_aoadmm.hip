@@ -1390,22 +1390,18 @@ int nmfx_aoadmm_alloc(nmfx_engine* E) {
 template <int KP>
 static int launch_prepare(nmfx_engine* E, const float* src, int record_obj, int64_t j, int64_t min_iter,
                           double tol1, double tol2, double fixed_rho) {
-    static const bool scalar = getenv("NMFX_PREPARE_SCALAR") != nullptr;      // the one-barrier-per-pivot kernel
-    if constexpr (KP >= 64) {
-        if (!scalar) {
-            constexpr int NB = KP / 16;
-            constexpr size_t shm = (size_t)(2 * 16 * 17 + 3 * 16 * (KP + 2) + NB * 16 * 17 + 4) * sizeof(double);
-            { int rc_ = nmfx_allow_lds(E, reinterpret_cast<const void*>(ao_prepare_mfma_kernel<KP>), (int)shm); if (rc_) return rc_; }
-            hipLaunchKernelGGL((ao_prepare_mfma_kernel<KP>), dim3(1), dim3(KP * 4 + 64), shm, E->stream, src, E->k, E->Minv,
-                               E->state, record_obj, E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
-                               E->obj_hist, fixed_rho);
-            NMFX_HIP(hipGetLastError());
-            return NMFX_OK;
-        }
+    if constexpr (KP >= 64) {                          // the blocked f64-MFMA kernel
+        constexpr int NB = KP / 16;
+        constexpr size_t shm = (size_t)(2 * 16 * 17 + 3 * 16 * (KP + 2) + NB * 16 * 17 + 4) * sizeof(double);
+        { int rc_ = nmfx_allow_lds(E, reinterpret_cast<const void*>(ao_prepare_mfma_kernel<KP>), (int)shm); if (rc_) return rc_; }
+        hipLaunchKernelGGL((ao_prepare_mfma_kernel<KP>), dim3(1), dim3(KP * 4 + 64), shm, E->stream, src, E->k, E->Minv,
+                           E->state, record_obj, E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
+                           E->obj_hist, fixed_rho);
+    } else {                                           // the scalar one-barrier-per-pivot kernel
+        constexpr int NT = (KP / 4) * (KP / 4) < 64 ? 64 : (KP / 4) * (KP / 4);
+        hipLaunchKernelGGL((ao_prepare_kernel<KP>), dim3(1), dim3(NT), 0, E->stream, src, E->k, E->Minv, E->state,
+                           record_obj, E->xf64, (long long)j, (long long)min_iter, tol1, tol2, E->obj_hist, fixed_rho);
     }
-    constexpr int NT = (KP / 4) * (KP / 4) < 64 ? 64 : (KP / 4) * (KP / 4);
-    hipLaunchKernelGGL((ao_prepare_kernel<KP>), dim3(1), dim3(NT), 0, E->stream, src, E->k, E->Minv, E->state,
-                       record_obj, E->xf64, (long long)j, (long long)min_iter, tol1, tol2, E->obj_hist, fixed_rho);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }
@@ -1852,7 +1848,7 @@ static int ao_w_products(nmfx_engine* E, int64_t j, int64_t min_iter, double tol
 }
 
 // One outer iteration with the inversions beside the products (ao_overlap):
-//   gram(W^T W slabs) | product_h [B^T slabs + objective || (W^T W + rho I)^-1] | pack (+ obj[j], stop rule) | rounds of H |
+//   gram(W^T W slabs) | product_h [B^T slabs + objective || (W^T W + rho I)^-1] | rounds of H (slab sum, obj[j], stop rule) |
 //   gram(H H^T slabs) | product_w [A slabs || (H H^T + rho I)^-1] | rounds of W (they add the A slabs themselves)
 static int aoadmm_eu_iteration_overlap(nmfx_engine* E, int prox_w, double lam_w, int prox_h, double lam_h,
                                        int admm_iter, int64_t min_iter, double tol1, double tol2, int64_t j) {
@@ -1865,12 +1861,9 @@ static int aoadmm_eu_iteration_overlap(nmfx_engine* E, int prox_w, double lam_w,
     int gslabs = 64;
     if ((rc = nmfx_bf16_gram_tn(E, &gslabs))) return rc;
     if ((rc = nmfx_bf16_sk_product(E, 0, true, E->G_part, gslabs, -1.0, "hphase"))) return rc;
-    static const bool packed = getenv("NMFX_AO_PACK") && atoi(getenv("NMFX_AO_PACK")) == 1;      // (A/B: the pack launch of the first form)
-    if (packed) { if ((rc = nmfx_bf16_pack_sk(E, j, min_iter, tol1, tol2))) return rc; }
-    else {         // the rounds of H sum the B^T slabs themselves; their first launch records obj[j] and applies the stop rule
-        E->ao_b_src = E->sk[0].slabs; E->ao_b_cnt = E->sk[0].cnt; E->ao_rec_nobj = E->sk[0].nseg;
-        E->ao_rec_j = j; E->ao_rec_min_iter = min_iter; E->ao_rec_tol1 = tol1; E->ao_rec_tol2 = tol2;
-    }
+    // the rounds of H sum the B^T slabs themselves; their first launch records obj[j] and applies the stop rule
+    E->ao_b_src = E->sk[0].slabs; E->ao_b_cnt = E->sk[0].cnt; E->ao_rec_nobj = E->sk[0].nseg;
+    E->ao_rec_j = j; E->ao_rec_min_iter = min_iter; E->ao_rec_tol1 = tol1; E->ao_rec_tol2 = tol2;
     E->himg_both = false;                              // H changes below
     { ProfScope ps(E, "inner_h");
       rc = ao_fused_subproblem(E, true, nullptr, prox_h, (float)lam_h, admm_iter, E->inner_hist + j * 2, (int)(j & 1)); }

@@ -2341,17 +2341,6 @@ int nmfx_bf16_sk_product(nmfx_engine* E, int side, bool obj, const float* gsrc, 
     return NMFX_OK;
 }
 
-int nmfx_bf16_pack_sk(nmfx_engine* E, int64_t j, int64_t min_iter, double tol1, double tol2) {
-    ProfScope ps(E, "pack");
-    const nmfx_engine::SkPlan& P = E->sk[0];
-    const unsigned grid = (unsigned)(E->np / 64 + E->kp * E->kp / 256 + 1);
-    hipLaunchKernelGGL((pack_t_kernel<128>), dim3(grid), dim3(256), 0, E->stream, P.slabs, P.maxslab, E->np, (const float*)nullptr, 0,
-                       E->obj_part, (int64_t)P.nseg, E->xf32, E->xf64, &E->state->flag, (const int*)P.cnt, E->state, E->obj_hist,
-                       (long long)j, (long long)min_iter, tol1, tol2);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-
 int nmfx_bf16_pack_t(nmfx_engine* E, const float* Gpart, int gsplit, int64_t nobj) {
     ProfScope ps(E, "pack");
     const unsigned grid = (unsigned)(E->np / 64 + E->kp * E->kp / 256 + 1);

@@ -382,8 +382,6 @@ int gx_launch(nmfx_engine* E, int mode, const float* A, int64_t lda, const float
     return NMFX_OK;
 }
 
-bool gx_fuse_update() { static const bool on = !(getenv("NMFX_GX_FUSE_UPDATE") && atoi(getenv("NMFX_GX_FUSE_UPDATE")) == 0); return on; }
-
 int gx_buffers(nmfx_engine* E, bool kl) {
     int rc;
     const int64_t nblk = (E->mp / GX_T) * (E->np / GX_T);
@@ -419,209 +417,23 @@ int gx_split_product(nmfx_engine* E, const float* A, int64_t lda, const float* B
 //   W^T V   ([kp][np])            :  A = W^T images [kp][mp], B = V^T planes [np][mp]
 //   H H^T, W^T W                  :  A = B = H images / W^T images
 // (V planes: built once per upload; factor images: rebuilt by gxt_split_kernel after each update, both orientations in one launch.)
-// Since the later part of r3 this kernel carries the SHORT contractions only (objective, KL quotient: contraction over the factor index,
-// row-major images of W and H^T); every product with a long contraction runs on gxt_gemm_kernel further down, on tiled planes.
-// Block = 128 x 128 outputs, 4 waves x (2 x 2 tiles of 32 x 32), contraction in chunks of 64: four planes [128 rows][64 bf16] in
-// LDS with a row stride of 144 bytes -- an odd multiple of 16, so the 16 rows of a ds_read_b128 lane group (MI355X_MICROARCH.md,
-// LDS table) fall on 16 distinct bank quadruples, and the 8 lanes of a ds_write_b128 group write one contiguous row --, the
-// next chunk prefetched into registers (16 x 16 bytes per thread) while the current one is multiplied; 72 KiB of LDS: two
-// blocks per CU, so one block's barriers and load latencies are covered by the other's MFMAs.
+// The products with a long contraction run on gxt_gemm_kernel / gxt2_gemm_kernel, the SHORT ones (objective, KL quotient: contraction
+// over the factor index) on the persistent gxr_kernel, all on TILED planes (below).
 typedef __bf16 gxb_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float gxb_f32x16 __attribute__((ext_vector_type(16)));
 union GxbFrag { uint4 u; gxb_bf16x8 v; };
 #define GXB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a).v, (b).v, (c), 0, 0, 0)
-constexpr int GXB_KC = 64, GXB_LDB = 144, GXB_PLANE = 128 * GXB_LDB;      // bytes
-constexpr int GXB_SHM = 4 * GXB_PLANE + 64;
-
-template <int MODE, int TERMS = 3>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gxb_gemm_kernel(
-    const unsigned short* __restrict__ Ahi, const unsigned short* __restrict__ Alo, int64_t lda,
-    const unsigned short* __restrict__ Bhi, const unsigned short* __restrict__ Blo, int64_t ldb,
-    float* __restrict__ C, int64_t ldc, int64_t cstride, int64_t K, const float* __restrict__ X, int64_t ldx,
-    double* __restrict__ part, const int* __restrict__ flag, const int* __restrict__ flag2,
-    unsigned short* __restrict__ Qhi = nullptr, unsigned short* __restrict__ Qlo = nullptr)
-{
-    // MODE GX_KLQ (MUR with the KL divergence, mur.py:25,41): the quotient Q = X / (C + 1e-9) leaves as bf16 hi / lo PLANES
-    // [M][N] (row stride ldc) -- the operand layout of the product that consumes it -- and, with part != nullptr, part[block] =
-    // the KL objective of the tile (utils.py:23-26), both exactly as gx_gemm_kernel<.., GX_KLQ> forms them
-    if (*flag || (flag2 && *flag2)) return;
-    extern __shared__ __attribute__((aligned(16))) unsigned char gxb_smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n31 = lane & 31, b = lane >> 5;
-    const int64_t i0 = (int64_t)blockIdx.y * GX_T, j0 = (int64_t)blockIdx.x * GX_T;
-    const int64_t kper = K / gridDim.z, kbeg = kper * blockIdx.z;
-    const int wr = 64 * (wave >> 1), wc = 64 * (wave & 1);
-    // staging: piece p = tid + 256 i (i < 4) of a plane = 16 bytes: row p >> 3, bytes 16 (p & 7) of the row's 128-byte chunk
-    const int prow = tid >> 3, pcol = tid & 7;
-    const unsigned short* sAh = Ahi + (i0 + prow) * lda + kbeg + 8 * pcol;
-    const unsigned short* sAl = Alo + (i0 + prow) * lda + kbeg + 8 * pcol;
-    const unsigned short* sBh = Bhi + (j0 + prow) * ldb + kbeg + 8 * pcol;
-    const unsigned short* sBl = Blo + (j0 + prow) * ldb + kbeg + 8 * pcol;
-    unsigned char* dst = gxb_smem + prow * GXB_LDB + 16 * pcol;
-    // (named registers, no arrays behind a lambda: hipcc parks such a staging array in scratch)
-    uint4 ah0, ah1, ah2, ah3, al0, al1, al2, al3, bh0, bh1, bh2, bh3, bl0, bl1, bl2, bl3;
-#define GXB_LD4(p, ld_, koff, r0_, r1_, r2_, r3_) do { \
-        r0_ = *reinterpret_cast<const uint4*>((p) + (koff)); r1_ = *reinterpret_cast<const uint4*>((p) + 32 * (ld_) + (koff)); \
-        r2_ = *reinterpret_cast<const uint4*>((p) + 64 * (ld_) + (koff)); r3_ = *reinterpret_cast<const uint4*>((p) + 96 * (ld_) + (koff)); } while (0)
-#define GXB_FETCH(koff) do { GXB_LD4(sAh, lda, koff, ah0, ah1, ah2, ah3); GXB_LD4(sAl, lda, koff, al0, al1, al2, al3); \
-        GXB_LD4(sBh, ldb, koff, bh0, bh1, bh2, bh3); GXB_LD4(sBl, ldb, koff, bl0, bl1, bl2, bl3); } while (0)
-#define GXB_ST4(pl, r0_, r1_, r2_, r3_) do { \
-        *reinterpret_cast<uint4*>(dst + (pl) * GXB_PLANE) = r0_; *reinterpret_cast<uint4*>(dst + (pl) * GXB_PLANE + 32 * GXB_LDB) = r1_; \
-        *reinterpret_cast<uint4*>(dst + (pl) * GXB_PLANE + 64 * GXB_LDB) = r2_; *reinterpret_cast<uint4*>(dst + (pl) * GXB_PLANE + 96 * GXB_LDB) = r3_; } while (0)
-    gxb_f32x16 acc[2][2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.f;
-    const unsigned char* fa = gxb_smem + (wr + n31) * GXB_LDB + 16 * b;                    // + 32 rows per tile, + 32 bytes per k-step, + GXB_PLANE: lo
-    const unsigned char* fb = gxb_smem + 2 * GXB_PLANE + (wc + n31) * GXB_LDB + 16 * b;
-    const int nch = (int)(kper / GXB_KC);
-    auto multiply = [&]() {
-#pragma unroll
-        for (int ks = 0; ks < GXB_KC / 16; ++ks) {
-            GxbFrag ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                ah[t].u = *reinterpret_cast<const uint4*>(fa + t * 32 * GXB_LDB + 32 * ks);
-                al[t].u = *reinterpret_cast<const uint4*>(fa + t * 32 * GXB_LDB + 32 * ks + GXB_PLANE);
-                bh[t].u = *reinterpret_cast<const uint4*>(fb + t * 32 * GXB_LDB + 32 * ks);
-                bl[t].u = *reinterpret_cast<const uint4*>(fb + t * 32 * GXB_LDB + 32 * ks + GXB_PLANE);
-            }
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 2; ++tj) {
-                    acc[ti][tj] = GXB_MFMA(ah[ti], bh[tj], acc[ti][tj]);
-                    acc[ti][tj] = GXB_MFMA(al[ti], bh[tj], acc[ti][tj]);
-                    acc[ti][tj] = GXB_MFMA(ah[ti], bl[tj], acc[ti][tj]);
-                    if (TERMS >= 4) acc[ti][tj] = GXB_MFMA(al[ti], bl[tj], acc[ti][tj]);      // (ADMM: its systems carry the caller's fixed rho, kernels_bf16.hip top)
-                }
-        }
-    };
-    GXB_FETCH(0);
-    for (int ch = 0; ch + 1 < nch; ++ch) {
-        __syncthreads();                               // the previous chunk has been multiplied
-        GXB_ST4(0, ah0, ah1, ah2, ah3); GXB_ST4(1, al0, al1, al2, al3); GXB_ST4(2, bh0, bh1, bh2, bh3); GXB_ST4(3, bl0, bl1, bl2, bl3);
-        __syncthreads();
-        { const int64_t koff = (int64_t)(ch + 1) * GXB_KC; GXB_FETCH(koff); }      // the next chunk, while this one is multiplied
-        multiply();
-    }
-    __syncthreads();                                   // the last chunk: nothing left to prefetch but the epilogue's operand
-    GXB_ST4(0, ah0, ah1, ah2, ah3); GXB_ST4(1, al0, al1, al2, al3); GXB_ST4(2, bh0, bh1, bh2, bh3); GXB_ST4(3, bl0, bl1, bl2, bl3);
-    __syncthreads();
-    // acc[ti][tj][r] = C(i0 + wr + 32 ti + (r & 3) + 8 (r >> 2) + 4 b, j0 + wc + 32 tj + n31)
-    float xv[MODE != GX_STORE ? 64 : 1];
-    if constexpr (MODE != GX_STORE) {                  // the epilogue's X tile is requested here and lands under the last chunk's MFMAs
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    xv[(2 * ti + tj) * 16 + r] = X[(i0 + wr + 32 * ti + (r & 3) + 8 * (r >> 2) + 4 * b) * ldx + j0 + wc + 32 * tj + n31];
-    }
-    multiply();
-#undef GXB_LD4
-#undef GXB_FETCH
-#undef GXB_ST4
-    if (MODE == GX_STORE) {
-        float* Cz = C + (int64_t)blockIdx.z * cstride;
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int tj = 0; tj < 2; ++tj)
-                    Cz[(i0 + wr + 32 * ti + (r & 3) + 8 * (r >> 2) + 4 * b) * ldc + j0 + wc + 32 * tj + n31] = acc[ti][tj][r];
-        return;
-    }
-    double tot = 0.0;                                  // GX_RESID: 1/2 sum (X - C)^2 of the tile (utils.py:29)
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float x1 = xv[MODE != GX_STORE ? (2 * ti + tj) * 16 + r : 0], cv = acc[ti][tj][r];
-                float d2;
-                if (MODE == GX_RESID) { const float d = x1 - cv; d2 = d * d; }
-                else {
-                    // (v_rcp_f32 / v_log_f32 as in the tuned MUR-KL kernels, kernels_bf16.hip: the inf / nan cases of utils.py:24 come
-                    //  out the same and are zeroed the same way)
-                    const float qv = x1 * __builtin_amdgcn_rcpf(cv + 1e-9f);
-                    unsigned hi, lo;
-                    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(qv), "v"(0.f));
-                    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(qv - __uint_as_float(hi << 16)), "v"(0.f));
-                    // two adjacent lanes hold adjacent columns: the even lane stores the pair of the hi plane, the odd lane the pair
-                    // of the lo plane -- one 4-byte store per lane instead of two 2-byte stores
-                    const unsigned other = (unsigned)__shfl_xor((int)((n31 & 1) ? hi : lo), 1, 64);
-                    // (the planes in the TILED image of gxt_gemm_kernel, contraction along the columns: row I, columns J, J + 1)
-                    const int64_t I = i0 + wr + 32 * ti + (r & 3) + 8 * (r >> 2) + 4 * b, J = j0 + wc + 32 * tj + (n31 & ~1);
-                    const int rr = (int)(I & 127);
-                    const int64_t at = ((I >> 7) * (ldc / 32) + (J >> 5)) * 4096 + rr * 32 + 8 * ((int)((J & 31) >> 3) ^ ((rr >> 2) & 3)) + (J & 7);
-                    if (n31 & 1) *reinterpret_cast<unsigned*>(Qlo + at) = (other & 0xffffu) | (lo << 16);
-                    else *reinterpret_cast<unsigned*>(Qhi + at) = (hi & 0xffffu) | (other << 16);
-                    d2 = 0.f;
-                    if (part) {
-                        float t = x1 * (__builtin_amdgcn_logf(x1 * __builtin_amdgcn_rcpf(cv)) * 0.69314718055994531f);
-                        t = (t != t || t == __builtin_inff() || t == -__builtin_inff()) ? 0.f : t;
-                        d2 = (t - x1) + cv;
-                    }
-                }
-                if ((r & 3) == 0) s0 += d2; else if ((r & 3) == 1) s1 += d2; else if ((r & 3) == 2) s2 += d2; else s3 += d2;
-            }
-            tot += (double)((s0 + s1) + (s2 + s3));
-        }
-    if (MODE == GX_KLQ && !part) return;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
-    __syncthreads();
-    double* red = reinterpret_cast<double*>(gxb_smem + 4 * GXB_PLANE);
-    if (lane == 0) red[wave] = tot;
-    __syncthreads();
-    if (tid == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = (MODE == GX_RESID ? 0.5 : 1.0) * (((red[0] + red[1]) + red[2]) + red[3]);
-}
-
-bool gxr_on();
-int gxr_launch(nmfx_engine* E, int mode, const unsigned short* Ahi, const unsigned short* Alo, const unsigned short* Bhi, const unsigned short* Blo,
-               int64_t ldq, int64_t M, int64_t N, int64_t K, const float* X, int64_t ldx, double* part, const int* flag2,
-               unsigned short* Qhi, unsigned short* Qlo);
-int gxb_launch(nmfx_engine* E, int mode, const unsigned short* Ahi, const unsigned short* Alo, int64_t lda, const unsigned short* Bhi,
-               const unsigned short* Blo, int64_t ldb, float* C, int64_t ldc, int64_t cstride, int64_t M, int64_t N, int64_t K, int S,
-               const float* X, int64_t ldx, double* part, const int* flag2 = nullptr, unsigned short* Qhi = nullptr, unsigned short* Qlo = nullptr) {
-    // (GX_RESID / GX_KLQ only: the long contractions -- every GX_STORE product -- run on gxt_gemm_kernel below)
-    if (gxr_on() && mode != GX_STORE && S == 1) return gxr_launch(E, mode, Ahi, Alo, Bhi, Blo, ldc, M, N, K, X, ldx, part, flag2, Qhi, Qlo);
-    if (mode == GX_STORE || M % GX_T || N % GX_T || K % ((int64_t)S * GXB_KC)) { E->err = "gxb_launch: shape / mode"; return NMFX_E_ARG; }
-    const dim3 grid((unsigned)(N / GX_T), (unsigned)(M / GX_T), (unsigned)S), block(256);
-    const int* flag = &E->state->flag;
-    int rc;
-    if (mode == GX_KLQ) {                              // (ldc = the contraction length of the product that consumes the Q planes)
-        if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(gxb_gemm_kernel<GX_KLQ>), GXB_SHM))) return rc;
-        hipLaunchKernelGGL((gxb_gemm_kernel<GX_KLQ>), grid, block, GXB_SHM, E->stream, Ahi, Alo, lda, Bhi, Blo, ldb, C, ldc, cstride, K, X, ldx, part, flag, flag2, Qhi, Qlo);
-    } else {
-        if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(gxb_gemm_kernel<GX_RESID>), GXB_SHM))) return rc;
-        hipLaunchKernelGGL((gxb_gemm_kernel<GX_RESID>), grid, block, GXB_SHM, E->stream, Ahi, Alo, lda, Bhi, Blo, ldb, C, ldc, cstride, K, X, ldx, part, flag, flag2);
-    }
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
 
 // ---- the products with a long contraction (V H^T, W^T V, Q H^T, W^T Q', the Gram matrices) on TILED planes filled by LDS-DMA (r3) ------
-// gxb_gemm_kernel stages its operands through registers: per CU and chunk the ds_write_b128 path (~79 B/clk), the texture path and
-// the matrix pipe carry loads within 30 % of each other (matrix pipe 0.47 busy, V H^T 217 us at 16384 x 8192, k = 256).  Here the planes
-// are stored as TILES in the image the LDS wants --
+// The planes are stored as TILES in the image the LDS wants --
 //     tile (row tile rt of 128, chunk c of 32) = 8 KiB contiguous at ((rt (K / 32) + c) 4096) elements:
 //     element (row rr, k) at rr 32 + 8 ((k / 8) ^ ((rr >> 2) & 3)) + k % 8
 // (the 16 rows of a ds_read_b128 lane group then fall on 16 distinct bank quadruples: 4 (rr & 3) + (chunk ^ (rr >> 2 & 3))) -- so a
 // stage is filled by plain linear copies global -> LDS (global_load_lds_dwordx4, 1 KiB per wave instruction, no VGPRs, no
 // ds_write), three stages of a 256 x 128 block tile (48 KiB each: two chunks in flight), eight waves x (2 x 2 tiles of 32 x 32), one
-// barrier per chunk, counted vmcnt; 98 VGPRs.  C[M][N] = sum_t A[i][t] B[j][t], stored (V H^T 175-181 us on the same boxes = 1.2 PFLOP/s
-// of executed bf16 MFMA work = 0.48 of the dense peak).  The short contractions stay on gxb_gemm_kernel: built on this kernel too
-// (X tile requested in front of the first chunk, one 256 x 128 tile per block) they were no faster -- eight chunks per block do not
-// amortise the head of the DMA ring with one block per CU, and register loads of the next tile's X cannot ride in the same
-// in-order vmcnt queue as the DMA stream without serialising with it.
+// barrier per chunk, counted vmcnt; 98 VGPRs.  C[M][N] = sum_t A[i][t] B[j][t], stored (V H^T 175-181 us at 16384 x 8192, k = 256
+// = 1.2 PFLOP/s of executed bf16 MFMA work = 0.48 of the dense peak; the first form, a block per 128 x 128 tile with row-major
+// planes staged through registers and ds_write_b128, took 217 us with the matrix pipe 0.47 busy: LAB_NOTES.md).
 __device__ __forceinline__ unsigned gxt_lds_off(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p; }
 __device__ __forceinline__ void gxt_dma(unsigned long long base, unsigned dst, unsigned voff) {
     unsigned keep;
@@ -634,8 +446,7 @@ __device__ __forceinline__ void gxt_dma_nt(unsigned long long base, unsigned dst
                  : "=&s"(keep) : "s"(base), "s"(dst), "v"(voff) : "memory");
 }
 constexpr int GXT_STAGE = 6 * 8192, GXT_SHM = 3 * GXT_STAGE;
-
-int gx_stagger() { static const int v = getenv("NMFX_GX_STAGGER") ? atoi(getenv("NMFX_GX_STAGGER")) : 1; return v; }
+constexpr int GX_STAGGER = 1;      // the DMA-issue schedule of gxt_gemm_kernel and gxr_kernel (their `stagger` argument)
 
 template <int TERMS>
 __global__ __launch_bounds__(512) void gxt_gemm_kernel(
@@ -738,6 +549,7 @@ __global__ __launch_bounds__(512) void gxt_gemm_kernel(
     // pieces at the same time, the SIMD's matrix pipe idle meanwhile, then queue for it together.  stagger 1: waves 0-3 request chunk
     // c + 2 BEFORE their MFMAs of chunk c, waves 4-7 BEHIND them (the target stage held chunk c - 1, which every wave has left at this
     // iteration's barrier; at the next wait chunk c + 2 is the only younger request either way).  stagger 16: interleaved (above).
+    // The host always passes 1: neither 0 nor 16 measured faster (LAB_NOTES.md).
     const bool inl = stagger & 16;
     const bool early = (stagger & 1) ? wave < 4 : true;
     for (int64_t c = 0; c < nch; ++c) {
@@ -880,8 +692,8 @@ __global__ __launch_bounds__(512) void gxt2_gemm_kernel(
 
 // ---- the SHORT contractions (objective, KL quotient: contraction over the factor index, V-sized output that never leaves the chip as
 // f32) as a PERSISTENT form of the kernel above (r4) ---------------------------------------------------------------------------------
-// gxb_gemm_kernel spent a block per 128 x 128 output tile: with eight 32-deep chunks per tile (k = 256) the head of the operand
-// pipeline, the X tile's round trip and the epilogue were paid once per tile and two blocks per CU had to cover each other's.  Here
+// With a block per output tile and eight 32-deep chunks per tile (k = 256) the head of the operand pipeline, the X tile's round trip
+// and the epilogue are paid once per tile (the first form of these products did, two blocks per CU covering each other's).  Here
 // one 512-thread block per CU walks a run of 256 x 128 output tiles (row-block major, the runs of one XCD next to each other, so
 // that its L2 holds the A planes of its 8 row blocks) and the three-stage LDS-DMA ring of gxt_gemm_kernel runs THROUGH the tile
 // boundaries: while a tile's epilogue executes, the first two chunks of the next tile are already in flight.  Both factors are read
@@ -1174,12 +986,10 @@ __global__ __launch_bounds__(512) void gxr_kernel(
         for (int64_t i = nb + tid; i < npart; i += 512) part[i] = 0.0;
 }
 
-// the switch between the two forms of the short contractions: the factor images are written in the format the chosen kernel reads
-bool gxr_on() { static const bool on = !(getenv("NMFX_GXR") && atoi(getenv("NMFX_GXR")) == 0); return on; }
-
 int gxr_launch(nmfx_engine* E, int mode, const unsigned short* Ahi, const unsigned short* Alo, const unsigned short* Bhi, const unsigned short* Blo,
-               int64_t ldq, int64_t M, int64_t N, int64_t K, const float* X, int64_t ldx, double* part, const int* flag2,
-               unsigned short* Qhi, unsigned short* Qlo) {
+               int64_t ldq, int64_t M, int64_t N, int64_t K, const float* X, int64_t ldx, double* part, const int* flag2 = nullptr,
+               unsigned short* Qhi = nullptr, unsigned short* Qlo = nullptr) {
+    // (ldq = the contraction length of the product that consumes the Q planes; gxb_on(E) guarantees the shape)
     if (M % 128 || N % 128 || K % 128 || K < 256) { E->err = "gxr_launch: shape"; return NMFX_E_ARG; }
     const int64_t T = ((M / 128 + 1) / 2) * (N / 128), npart = (M / GX_T) * (N / GX_T);
     const int nb = (int)std::min<int64_t>(E->ncu, T);
@@ -1189,7 +999,7 @@ int gxr_launch(nmfx_engine* E, int mode, const unsigned short* Ahi, const unsign
 #define GXR_GO(MODE_, OBJ_) do { \
         if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(gxr_kernel<MODE_, OBJ_>), GXT_SHM))) return rc; \
         hipLaunchKernelGGL((gxr_kernel<MODE_, OBJ_>), grid, block, GXT_SHM, E->stream, Ahi, Alo, Bhi, Blo, M, N, K, X, ldx, part, npart, flag, flag2, \
-                           Qhi, Qlo, ldq, gx_stagger()); } while (0)
+                           Qhi, Qlo, ldq, GX_STAGGER); } while (0)
     if (mode == GX_KLQ) { if (part) GXR_GO(GX_KLQ, true); else GXR_GO(GX_KLQ, false); }
     else GXR_GO(GX_RESID, true);
 #undef GXR_GO
@@ -1199,10 +1009,10 @@ int gxr_launch(nmfx_engine* E, int mode, const unsigned short* Ahi, const unsign
 
 // bf16 hi / lo images of M [rows][cols] (f32, row-major) in the formats the product kernels read.  Natural orientation (operand rows =
 // rows of M, contraction along the columns) and transposed orientation (operand rows = columns of M, contraction along the rows),
-// each 0 = not wanted, 1 = row-major planes (gxb_gemm_kernel: the short contractions), 2 = the tiled image above (gxt_gemm_kernel).
+// each wanted (the tiled image above) or not.
 // One 64 x 64 tile per block through LDS; every global store is a 16-byte chunk of eight contraction indices.
-__global__ __launch_bounds__(256) void gxt_split_kernel(const float* __restrict__ M, int64_t rows, int64_t cols, int fmt_n,
-                                                        unsigned short* __restrict__ nhi, unsigned short* __restrict__ nlo, int fmt_t,
+__global__ __launch_bounds__(256) void gxt_split_kernel(const float* __restrict__ M, int64_t rows, int64_t cols, bool want_n,
+                                                        unsigned short* __restrict__ nhi, unsigned short* __restrict__ nlo, bool want_t,
                                                         unsigned short* __restrict__ thi, unsigned short* __restrict__ tlo, const int* __restrict__ flag,
                                                         GxUpd up)
 {
@@ -1229,41 +1039,39 @@ __global__ __launch_bounds__(256) void gxt_split_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int q = threadIdx.x + 256 * i, a = q >> 3, e8 = q & 7;
-        if (fmt_n) {                                   // row r0 + a, contraction indices c0 + 8 e8 ..
+        if (want_n) {                                   // row r0 + a, contraction indices c0 + 8 e8 ..
             const uint4 h = *reinterpret_cast<const uint4*>(&sh[a][8 * e8]), l = *reinterpret_cast<const uint4*>(&sl[a][8 * e8]);
             const int64_t R = r0 + a, Kc = c0 + 8 * e8;
-            int64_t at;
-            if (fmt_n == 1) at = R * cols + Kc;
-            else { const int rr = (int)(R & 127); at = ((R >> 7) * (cols / 32) + (Kc >> 5)) * 4096 + rr * 32 + 8 * ((int)((Kc & 31) >> 3) ^ ((rr >> 2) & 3)); }
+            const int rr = (int)(R & 127);
+            const int64_t at = ((R >> 7) * (cols / 32) + (Kc >> 5)) * 4096 + rr * 32 + 8 * ((int)((Kc & 31) >> 3) ^ ((rr >> 2) & 3));
             *reinterpret_cast<uint4*>(nhi + at) = h; *reinterpret_cast<uint4*>(nlo + at) = l;
         }
-        if (fmt_t) {                                   // operand row c0 + a (a column of M), contraction indices r0 + 8 e8 ..
+        if (want_t) {                                   // operand row c0 + a (a column of M), contraction indices r0 + 8 e8 ..
             union { unsigned short s[8]; uint4 u; } h, l;
 #pragma unroll
             for (int e = 0; e < 8; ++e) { h.s[e] = sh[8 * e8 + e][a]; l.s[e] = sl[8 * e8 + e][a]; }
             const int64_t R = c0 + a, Kc = r0 + 8 * e8;
-            int64_t at;
-            if (fmt_t == 1) at = R * rows + Kc;
-            else { const int rr = (int)(R & 127); at = ((R >> 7) * (rows / 32) + (Kc >> 5)) * 4096 + rr * 32 + 8 * ((int)((Kc & 31) >> 3) ^ ((rr >> 2) & 3)); }
+            const int rr = (int)(R & 127);
+            const int64_t at = ((R >> 7) * (rows / 32) + (Kc >> 5)) * 4096 + rr * 32 + 8 * ((int)((Kc & 31) >> 3) ^ ((rr >> 2) & 3));
             *reinterpret_cast<uint4*>(thi + at) = h.u; *reinterpret_cast<uint4*>(tlo + at) = l.u;
         }
     }
 }
 
-int gxt_split(nmfx_engine* E, const float* M, int64_t rows, int64_t cols, int fmt_n, unsigned short* nhi, unsigned short* nlo, int fmt_t,
+int gxt_split(nmfx_engine* E, const float* M, int64_t rows, int64_t cols, bool want_n, unsigned short* nhi, unsigned short* nlo, bool want_t,
               unsigned short* thi, unsigned short* tlo, bool check_flag, const GxUpd& up = GxUpd()) {
-    hipLaunchKernelGGL(gxt_split_kernel, dim3((unsigned)(cols / 64), (unsigned)(rows / 64)), dim3(256), 0, E->stream, M, rows, cols, fmt_n, nhi, nlo,
-                       fmt_t, thi, tlo, check_flag ? (const int*)&E->state->flag : (const int*)nullptr, up);
+    hipLaunchKernelGGL(gxt_split_kernel, dim3((unsigned)(cols / 64), (unsigned)(rows / 64)), dim3(256), 0, E->stream, M, rows, cols, want_n, nhi, nlo,
+                       want_t, thi, tlo, check_flag ? (const int*)&E->state->flag : (const int*)nullptr, up);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }
-// the factor images of the composed path: W -> Whi / Wlo [mp][kp] row-major (short contractions: objective, quotient) and W^T tiled
-// (W^T V, W^T W); H -> tiled (V H^T, H H^T) and H^T [np][kp] row-major
+// the factor images of the composed path, all tiled: W -> Whi / Wlo [mp][kp] (short contractions: objective, quotient) and W^T
+// (W^T V, W^T W); H (V H^T, H H^T) and H^T [np][kp]
 int gxb_images_w(nmfx_engine* E, const float* W, const GxUpd& up = GxUpd()) {
-    return gxt_split(E, W, E->mp, E->kp, gxr_on() ? 2 : 1, E->Whi[0], E->Wlo[0], 2, E->WThi, E->WTlo, true, up);
+    return gxt_split(E, W, E->mp, E->kp, true, E->Whi[0], E->Wlo[0], true, E->WThi, E->WTlo, true, up);
 }
 int gxb_images_h(nmfx_engine* E, const float* H, const GxUpd& up = GxUpd()) {
-    return gxt_split(E, H, E->kp, E->np, 2, E->Hhi, E->Hlo, gxr_on() ? 2 : 1, E->HThi, E->HTlo, true, up);
+    return gxt_split(E, H, E->kp, E->np, true, E->Hhi, E->Hlo, true, E->HThi, E->HTlo, true, up);
 }
 
 // split-K product on the tiled planes into the slab buffer gx_s, summed into `out` (M: rows of A, N: rows of B, K: contraction)
@@ -1306,10 +1114,10 @@ int gxt_split_product(nmfx_engine* E, const unsigned short* Ahi, const unsigned 
     const int* flag = &E->state->flag;
     if (terms == 4) {
         if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(gxt_gemm_kernel<4>), GXT_SHM))) return rc;
-        hipLaunchKernelGGL((gxt_gemm_kernel<4>), grid, block, GXT_SHM, E->stream, Ahi, Alo, Bhi, Blo, C, N, M * N, M, K, flag, (const int*)nullptr, gx_stagger());
+        hipLaunchKernelGGL((gxt_gemm_kernel<4>), grid, block, GXT_SHM, E->stream, Ahi, Alo, Bhi, Blo, C, N, M * N, M, K, flag, (const int*)nullptr, GX_STAGGER);
     } else {
         if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(gxt_gemm_kernel<3>), GXT_SHM))) return rc;
-        hipLaunchKernelGGL((gxt_gemm_kernel<3>), grid, block, GXT_SHM, E->stream, Ahi, Alo, Bhi, Blo, C, N, M * N, M, K, flag, (const int*)nullptr, gx_stagger());
+        hipLaunchKernelGGL((gxt_gemm_kernel<3>), grid, block, GXT_SHM, E->stream, Ahi, Alo, Bhi, Blo, C, N, M * N, M, K, flag, (const int*)nullptr, GX_STAGGER);
     }
     NMFX_HIP(hipGetLastError());
     if (slabs) { *slabs = C; *nslab = (int)S; return NMFX_OK; }
@@ -1370,7 +1178,7 @@ int gxb_prepare(nmfx_engine* E, const float* W, bool kl = false) {
         (rc = gx_alloc(E, &E->HThi, kp * np)) || (rc = gx_alloc(E, &E->HTlo, kp * np))) return rc;
     if (!E->gxb_v_ready) {
         ProfScope ps(E, "images");
-        if ((rc = gxt_split(E, E->V, mp, np, 2, E->gxb_v[0], E->gxb_v[1], 2, E->gxb_v[2], E->gxb_v[3], false))) return rc;      // both TILED: V (contraction n), V^T (contraction m)
+        if ((rc = gxt_split(E, E->V, mp, np, true, E->gxb_v[0], E->gxb_v[1], true, E->gxb_v[2], E->gxb_v[3], false))) return rc;      // both TILED: V (contraction n), V^T (contraction m)
         E->gxb_v_ready = true;
     }
     if (!E->gxb_img_ready) {
@@ -1388,16 +1196,15 @@ static bool gx_anls_bf16() { static const bool on = !(getenv("NMFX_GX_ANLS_BF16"
 // r4: the denominator products of the Euclidean updates, D = W (H H^T) and E = (W^T W) H, from the factor images and the images of the
 // k x k Gram matrix (three terms, like the numerators they are divided into) instead of an exact-f32 product: 2 m k^2 flop that took
 // 28 us at k = 256 and 110 us at k = 512 on the f32 matrix cores.  Measured (16384 x 8192): W side k = 512 130 -> 102 us per update,
-// k = 256 no gain (the image launch and a 64-block grid eat it): used for the W side from kp = 384 on; H side never (see phase B).  left = true: out [rows][kp] = F G (F images: rows x kp);
-// false: out [kp][cols] = G F^T^T, i.e. G times the factor whose TRANSPOSED images are given (cols x kp)
+// k = 256 no gain (the image launch and a 64-block grid eat it): used for the W side from kp = 384 on.  H side never: 80 against 77 us
+// at k = 512, 51 against 47 at k = 256 -- 32 blocks of 256 x 256 for a kp x np output.  out [rows][kp] = F G (F images: rows x kp)
 static bool gx_bf16_den() { static const bool on = !(getenv("NMFX_GX_DEN_BF16") && atoi(getenv("NMFX_GX_DEN_BF16")) == 0); return on; }
-static int gx_den_product(nmfx_engine* E, bool left, const float* G, const unsigned short* Fhi, const unsigned short* Flo, int64_t ents, float* out) {
+static int gx_den_product(nmfx_engine* E, const float* G, const unsigned short* Fhi, const unsigned short* Flo, int64_t ents, float* out) {
     int rc;
     const int64_t kp = E->kp;
     if ((rc = gx_alloc(E, &E->gx_gimg, 2 * kp * kp))) return rc;
-    if ((rc = gxt_split(E, G, kp, kp, 2, E->gx_gimg, E->gx_gimg + kp * kp, 0, nullptr, nullptr, true))) return rc;      // (G symmetric: rows = either index)
-    if (left) return gxt_split_product(E, Fhi, Flo, E->gx_gimg, E->gx_gimg + kp * kp, out, ents, kp, kp, 0, 3, nullptr, nullptr, false);
-    return gxt_split_product(E, E->gx_gimg, E->gx_gimg + kp * kp, Fhi, Flo, out, kp, ents, kp, 0, 3, nullptr, nullptr, false);
+    if ((rc = gxt_split(E, G, kp, kp, true, E->gx_gimg, E->gx_gimg + kp * kp, false, nullptr, nullptr, true))) return rc;      // (G symmetric: rows = either index)
+    return gxt_split_product(E, Fhi, Flo, E->gx_gimg, E->gx_gimg + kp * kp, out, ents, kp, kp, 0, 3, nullptr, nullptr, false);
 }
 
 // ---- MUR, Euclidean ----------------------------------------------------------------------------------------------------------
@@ -1420,32 +1227,21 @@ int nmfx_generic_mur_phase_a(nmfx_engine* E, int distance, double lambda, int64_
     }
     if (!kl && gxb_on(E)) {                            // the same steps with the V-sized products and the Gram matrices in split bf16
         { ProfScope ps(E, "objective");
-          if ((rc = gxb_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], kp, E->HThi, E->HTlo, kp, nullptr, 0, 0, mp, np, kp, 1, E->V, np, E->gx_part))) return rc; }
+          if ((rc = gxr_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], E->HThi, E->HTlo, 0, mp, np, kp, E->V, np, E->gx_part))) return rc; }
         if ((rc = nmfx_launch_obj_reduce(E, nblk, E->gx_part))) return rc;
         { ProfScope ps(E, "gram_nt");
           if ((rc = gxt_split_product(E, E->Hhi, E->Hlo, E->Hhi, E->Hlo, E->HHt, kp, kp, np, 64))) return rc; }
-        if (gx_fuse_update()) {                        // r4: slab sum, update and the images of W_new in one launch behind D = W (H H^T)
+        {                                              // r4: slab sum, update and the images of W_new in one launch behind D = W (H H^T)
             const float* slabs = nullptr; int nslab = 0;
             { ProfScope ps(E, "wphase");               // A = V H^T
               if ((rc = gxt_split_product(E, E->gxb_v[0], E->gxb_v[1], E->Hhi, E->Hlo, E->A_part, mp, kp, np, 4, 3, &slabs, &nslab))) return rc; }
             ProfScope ps(E, "w_update");
-            if (gxr_on() && gx_bf16_den() && kp >= 384) rc = gx_den_product(E, true, E->HHt, E->Whi[0], E->Wlo[0], mp, E->gx_d);      // (tiled images of W: the persistent kernels' format)
+            if (gx_bf16_den() && kp >= 384) rc = gx_den_product(E, E->HHt, E->Whi[0], E->Wlo[0], mp, E->gx_d);
             else rc = gx_launch<true, false>(E, GX_STORE, W, kp, E->HHt, kp, E->gx_d, kp, 0, mp, kp, kp, 1, nullptr, 0, nullptr);
             if (rc) return rc;
             GxUpd up;
             up.xold = W; up.num = slabs; up.nslab = nslab; up.nstride = mp * kp; up.den = E->gx_d; up.lam = (float)lambda; up.xnew = Wn;
             if ((rc = gxb_images_w(E, Wn, up))) return rc;
-        } else {
-        { ProfScope ps(E, "wphase");                   // A = V H^T
-          if ((rc = gxt_split_product(E, E->gxb_v[0], E->gxb_v[1], E->Hhi, E->Hlo, E->A_part, mp, kp, np, 4))) return rc; }
-        { ProfScope ps(E, "w_update");
-          if ((rc = gx_launch<true, false>(E, GX_STORE, W, kp, E->HHt, kp, E->gx_d, kp, 0, mp, kp, kp, 1, nullptr, 0, nullptr))) return rc;
-          const int64_t c4 = mp * kp / 4;
-          hipLaunchKernelGGL(gx_eu_update_kernel, dim3((unsigned)((c4 + 255) / 256)), dim3(256), 0, E->stream, W, (const float*)E->A_part,
-                             (const float*)E->gx_d, (float)lambda, Wn, c4, (const int*)&E->state->flag);
-          NMFX_HIP(hipGetLastError()); }
-        { ProfScope ps(E, "images");
-          if ((rc = gxb_images_w(E, Wn))) return rc; }
         }
         { ProfScope ps(E, "gram_tn");
           if ((rc = gxt_split_product(E, E->WThi, E->WTlo, E->WThi, E->WTlo, xG, kp, kp, mp, 64))) return rc; }
@@ -1478,8 +1274,7 @@ int nmfx_generic_mur_phase_a(nmfx_engine* E, int distance, double lambda, int64_
         // (W images) x (H^T images) for A = Q H^T, and the H side's Q'^T [np][mp] from (H^T images) x (W_new images) against V^T for
         // B = W_new^T Q' -- so all four V-sized products are the one NT kernel (three terms, like the tuned MUR-KL kernels)
         { ProfScope ps(E, "objective");
-          if ((rc = gxb_launch(E, GX_KLQ, E->Whi[0], E->Wlo[0], kp, E->HThi, E->HTlo, kp, nullptr, np, 0, mp, np, kp, 1, E->V, np, E->gx_part, nullptr,
-                               E->gxb_q[0], E->gxb_q[1]))) return rc; }
+          if ((rc = gxr_launch(E, GX_KLQ, E->Whi[0], E->Wlo[0], E->HThi, E->HTlo, np, mp, np, kp, E->V, np, E->gx_part, nullptr, E->gxb_q[0], E->gxb_q[1]))) return rc; }
         if ((rc = nmfx_launch_obj_reduce(E, nblk, E->gx_part))) return rc;
         { ProfScope ps(E, "wphase");                   // Q H^T
           if ((rc = gxt_split_product(E, E->gxb_q[0], E->gxb_q[1], E->Hhi, E->Hlo, E->A_part, mp, kp, np, 4))) return rc; }
@@ -1492,8 +1287,7 @@ int nmfx_generic_mur_phase_a(nmfx_engine* E, int distance, double lambda, int64_
         { ProfScope ps(E, "images");
           if ((rc = gxb_images_w(E, Wn))) return rc; }
         { ProfScope ps(E, "objective");                // Q'^T = V^T / (H^T W_new^T + 1e-9)  (the second quotient product of the iteration, no objective)
-          if ((rc = gxb_launch(E, GX_KLQ, E->HThi, E->HTlo, kp, E->Whi[0], E->Wlo[0], kp, nullptr, mp, 0, np, mp, kp, 1, E->gxb_vt, mp, nullptr, nullptr,
-                               E->gxb_q[0], E->gxb_q[1]))) return rc; }
+          if ((rc = gxr_launch(E, GX_KLQ, E->HThi, E->HTlo, E->Whi[0], E->Wlo[0], mp, np, mp, kp, E->gxb_vt, mp, nullptr, nullptr, E->gxb_q[0], E->gxb_q[1]))) return rc; }
         { ProfScope ps(E, "hphase");                   // B = W_new^T Q', d = W_new^T 1
           if ((rc = gxt_split_product(E, E->WThi, E->WTlo, E->gxb_q[0], E->gxb_q[1], xB, kp, np, mp, 8))) return rc;
           const int rb = (int)(mp / 64);
@@ -1536,11 +1330,9 @@ int nmfx_generic_mur_phase_b(nmfx_engine* E, int distance, double lambda, int64_
     hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
                        E->state, E->obj_hist);
     NMFX_HIP(hipGetLastError());
-    if (!kl && gxb_on(E) && E->gxb_img_ready && gx_fuse_update()) {
+    if (!kl && gxb_on(E) && E->gxb_img_ready) {
         // r4: the update and the images of the new H in one launch behind E = G H (element-wise, so H is updated in place)
-        if (gxr_on() && gx_bf16_den() && false) rc = gx_den_product(E, false, xG, E->HThi, E->HTlo, np, E->gx_d);      // (measured: 80 against 77 us at k = 512, 51 against 47 at k = 256 -- 32 blocks of 256 x 256 for a kp x np output)
-        else rc = gx_launch<true, false>(E, GX_STORE, xG, kp, E->H, np, E->gx_d, np, 0, kp, np, kp, 1, nullptr, 0, nullptr);
-        if (rc) return rc;
+        if ((rc = gx_launch<true, false>(E, GX_STORE, xG, kp, E->H, np, E->gx_d, np, 0, kp, np, kp, 1, nullptr, 0, nullptr))) return rc;
         GxUpd up;
         up.xold = E->H; up.num = xB; up.nslab = 1; up.den = E->gx_d; up.lam = (float)lambda; up.xnew = E->H;
         if ((rc = gxb_images_h(E, E->H, up))) return rc;
@@ -1578,11 +1370,10 @@ int nmfx_generic_mur_finish_a(nmfx_engine* E, int distance, int64_t j) {
     }
     { ProfScope ps(E, "objective");
       if (!kl && gxb_on(E)) {
-          rc = gxb_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], kp, E->HThi, E->HTlo, kp, nullptr, 0, 0, mp, np, kp, 1, E->V, np, E->gx_part);
+          rc = gxr_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], E->HThi, E->HTlo, 0, mp, np, kp, E->V, np, E->gx_part);
       } else if (!kl) rc = gx_launch<true, false>(E, GX_RESID, E->W[j & 1], kp, E->H, np, nullptr, 0, 0, mp, np, kp, 1, E->V, np, E->gx_part);
       else if (gxb_on(E)) {
-          rc = gxb_launch(E, GX_KLQ, E->Whi[0], E->Wlo[0], kp, E->HThi, E->HTlo, kp, nullptr, np, 0, mp, np, kp, 1, E->V, np, E->gx_part, nullptr,
-                          E->gxb_q[0], E->gxb_q[1]);
+          rc = gxr_launch(E, GX_KLQ, E->Whi[0], E->Wlo[0], E->HThi, E->HTlo, np, mp, np, kp, E->V, np, E->gx_part, nullptr, E->gxb_q[0], E->gxb_q[1]);
       } else rc = gx_launch<true, false>(E, GX_KLQ, E->W[j & 1], kp, E->H, np, E->S, np, 0, mp, np, kp, 1, E->V, np, E->gx_part);
       if (rc) return rc; }
     return nmfx_launch_obj_reduce(E, nblk, E->gx_part);
@@ -1590,52 +1381,6 @@ int nmfx_generic_mur_finish_a(nmfx_engine* E, int distance, int64_t j) {
 
 // ---- AO-ADMM, least-squares loss, prox nn / l1n (nmf/ao_admm.py:46-68, 113-124, 33-43, 259-292) for k > 128 -------------------------
 namespace {
-
-// rho = trace(G) / k, M^-1 = (G + rho I)^-1 (ao_admm.py:53-55, 59: cholesky + cho_solve) by an in-place Gauss-Jordan inversion in
-// f64 without pivoting (the matrix is positive definite: a pivot <= 0 is the reference's LinAlgError -> st->notpd), one workgroup,
-// the matrix in a global f64 work area (L2-resident), pivot row and column through LDS, two barriers per pivot.  fixed_rho >= 0
-// replaces trace / k.  Also opens the sub-problem: inner_stop = inner_count = 0.
-__global__ __launch_bounds__(1024) void gx_prepare_kernel(const float* __restrict__ G, int kp, int k, double* __restrict__ work,
-                                                          float* __restrict__ Minv, DevState* __restrict__ st, double fixed_rho)
-{
-    if (st->flag) return;
-    extern __shared__ double gsh[];                    // row [kp] | col [kp] | 16 partials
-    double* prow = gsh;
-    double* pcol = gsh + kp;
-    double* part = pcol + kp;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    double tr = 0.0;
-    for (int i = tid; i < k; i += nt) tr += (double)G[(int64_t)i * kp + i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tr += __shfl_down(tr, off, 64);
-    if ((tid & 63) == 0) part[tid >> 6] = tr;
-    __syncthreads();
-    double rho = 0.0;
-    for (int w = 0; w < nt / 64; ++w) rho += part[w];
-    rho /= (double)k;
-    if (fixed_rho >= 0.0) rho = fixed_rho;
-    const int64_t kk = (int64_t)kp * kp;
-    for (int64_t e = tid; e < kk; e += nt) work[e] = (double)G[e] + ((e / kp) == (e % kp) ? rho : 0.0);
-    __syncthreads();
-    int bad = 0;
-    for (int p = 0; p < kp; ++p) {
-        for (int i = tid; i < kp; i += nt) { prow[i] = work[(int64_t)p * kp + i]; pcol[i] = work[(int64_t)i * kp + p]; }
-        __syncthreads();
-        const double d = prow[p];
-        if (!(d > 0.0)) bad = 1;
-        const double inv = 1.0 / d;
-        for (int64_t e = tid; e < kk; e += nt) {
-            const int i = (int)(e / kp), j = (int)(e % kp);
-            double v;
-            if (i == p) v = (j == p) ? inv : prow[j] * inv;
-            else v = (j == p) ? -pcol[i] * inv : work[e] - pcol[i] * (prow[j] * inv);
-            work[e] = v;
-        }
-        __syncthreads();
-    }
-    for (int64_t e = tid; e < kk; e += nt) Minv[e] = (float)work[e];
-    if (tid == 0) { st->rho = rho; st->inner_stop = 0; st->inner_count = 0; if (bad) st->notpd = 1; }
-}
 
 // rhs = B + rho (X + U)   (ao_admm.py:59, the argument of cho_solve)
 __global__ __launch_bounds__(256) void gx_rhs_kernel(const float* __restrict__ B, const float* __restrict__ X, const float* __restrict__ U,
@@ -1728,16 +1473,18 @@ __global__ void gx_close_kernel(DevState* __restrict__ st, int32_t* __restrict__
     st->inner_stop = 0;
 }
 
-// M^-1 = (G + rho I)^-1 -> E->Minv, st->rho (fixed_rho < 0: trace(G) / k), the inner-round state reset
-// ---- the same inverse by BLOCKS of 128 (r3) --------------------------------------------------------------------------------------
-// The one-workgroup kernel above walks the whole kp x kp f64 matrix in global memory once per pivot: 6.0 ms at kp = 256, twice per
-// outer iteration -- 12 of the 13.8 ms of an AO-ADMM iteration at 16384 x 8192.  Block Gauss-Jordan over 128-wide blocks instead:
-// per block step p the diagonal block T[p][p] is inverted by the k = 128 solvers' blocked f64-MFMA kernel (kernels_aoadmm.hip,
-// ao_prepare_mfma_kernel: one workgroup, ~40 us; its pivots are those of the unblocked elimination, so "not positive definite"
-// fires on the same condition), and the rest of the step is f64 matrix products spread over the chip (v_mfma_f64_16x16x4_f64, one
-// 16 x 16 tile per wave, operands straight from the L2-resident matrices):
+// ---- M^-1 = (G + rho I)^-1 by BLOCKS of 128 (r3) ------------------------------------------------------------------------------------
+// rho = trace(G) / k (fixed_rho >= 0 replaces it), M^-1 = (G + rho I)^-1 (ao_admm.py:53-55, 59: cholesky + cho_solve) -> E->Minv,
+// st->rho, and the sub-problem opened: inner_stop = inner_count = 0.  Gauss-Jordan in f64 without pivoting (the matrix is positive
+// definite: a pivot <= 0 is the reference's LinAlgError -> st->notpd), over 128-wide blocks: per block step p the diagonal block
+// T[p][p] is inverted by the k = 128 solvers' blocked f64-MFMA kernel (kernels_aoadmm.hip, ao_prepare_mfma_kernel: one workgroup,
+// ~40 us; its pivots are those of the unblocked elimination, so "not positive definite" fires on the same condition), and the rest
+// of the step is f64 matrix products spread over the chip (v_mfma_f64_16x16x4_f64, one 16 x 16 tile per wave, operands straight
+// from the L2-resident matrices):
 //     C = -T[:, p] D^-1;     T'[p][p] = D^-1,  T'[p][J] = D^-1 T[p][J],  T'[I][p] = C[I],  T'[I][J] = T[I][J] + C[I] T[p][J]
-// from the old matrix into the other of two buffers.  3 launches per block step, kp / 128 steps.
+// from the old matrix into the other of two buffers.  3 launches per block step, kp / 128 steps.  (The first form, one workgroup
+// walking the whole kp x kp f64 matrix in global memory once per pivot, took 6.0 ms at kp = 256, twice per outer iteration: 12 of
+// the 13.8 ms of an AO-ADMM iteration at 16384 x 8192.)
 __device__ __forceinline__ gx_f64x4 gx_tile64(const double* __restrict__ A, int64_t lda, const double* __restrict__ B, int64_t ldb,
                                               gx_f64x4 acc, int c, int q)
 {   // acc[r] (row q + 4 r, column c) += sum_t A[row][t] B[t][column], t < 128
@@ -1820,33 +1567,25 @@ int64_t gx_w64_count(int64_t kp) { return 2 * kp * kp + 128 * 128 + kp * 128; }
 
 int gx_prepare(nmfx_engine* E, const float* G, double fixed_rho) {
     ProfScope ps(E, "prepare");
-    static const bool scalar = getenv("NMFX_PREPARE_SCALAR") != nullptr;      // the one-workgroup kernel (A/B runs)
-    if (!scalar) {
-        int rc;
-        const int kp = (int)E->kp, nb = kp / 128;
-        const int64_t kk = (int64_t)kp * kp;
-        double* Tb[2] = {E->gx_w64, E->gx_w64 + kk};
-        double* Dinv = E->gx_w64 + 2 * kk;
-        double* C = Dinv + 128 * 128;
-        hipLaunchKernelGGL(gx_bgj_init_kernel, dim3((unsigned)kp), dim3(256), 0, E->stream, G, kp, E->k, Tb[0], E->state, fixed_rho);
-        NMFX_HIP(hipGetLastError());
-        for (int p = 0; p < nb; ++p) {
-            const double* T = Tb[p & 1];
-            if ((rc = nmfx_launch_inverse64_block(E, T + (int64_t)128 * p * kp + 128 * p, kp, Dinv))) return rc;
-            hipLaunchKernelGGL(gx_bgj_col_kernel, dim3((unsigned)(kp / 16 * 8 / 4)), dim3(256), 0, E->stream, T, kp, p, (const double*)Dinv, C,
-                               (const DevState*)E->state);
-            hipLaunchKernelGGL(gx_bgj_update_kernel, dim3((unsigned)((kp / 16) * (kp / 16) / 4)), dim3(256), 0, E->stream, T, Tb[(p + 1) & 1], kp, p,
-                               (const double*)Dinv, (const double*)C, (const DevState*)E->state);
-            NMFX_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(gx_bgj_finish_kernel, dim3((unsigned)((kk + 255) / 256)), dim3(256), 0, E->stream, (const double*)Tb[nb & 1], kk, E->Minv,
+    int rc;
+    const int kp = (int)E->kp, nb = kp / 128;
+    const int64_t kk = (int64_t)kp * kp;
+    double* Tb[2] = {E->gx_w64, E->gx_w64 + kk};
+    double* Dinv = E->gx_w64 + 2 * kk;
+    double* C = Dinv + 128 * 128;
+    hipLaunchKernelGGL(gx_bgj_init_kernel, dim3((unsigned)kp), dim3(256), 0, E->stream, G, kp, E->k, Tb[0], E->state, fixed_rho);
+    NMFX_HIP(hipGetLastError());
+    for (int p = 0; p < nb; ++p) {
+        const double* T = Tb[p & 1];
+        if ((rc = nmfx_launch_inverse64_block(E, T + (int64_t)128 * p * kp + 128 * p, kp, Dinv))) return rc;
+        hipLaunchKernelGGL(gx_bgj_col_kernel, dim3((unsigned)(kp / 16 * 8 / 4)), dim3(256), 0, E->stream, T, kp, p, (const double*)Dinv, C,
                            (const DevState*)E->state);
+        hipLaunchKernelGGL(gx_bgj_update_kernel, dim3((unsigned)((kp / 16) * (kp / 16) / 4)), dim3(256), 0, E->stream, T, Tb[(p + 1) & 1], kp, p,
+                           (const double*)Dinv, (const double*)C, (const DevState*)E->state);
         NMFX_HIP(hipGetLastError());
-        return NMFX_OK;
     }
-    const size_t shm = (size_t)(2 * E->kp + 16) * sizeof(double);
-    int rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(gx_prepare_kernel), (int)shm); if (rc) return rc;
-    hipLaunchKernelGGL(gx_prepare_kernel, dim3(1), dim3(1024), shm, E->stream, G, (int)E->kp, E->k, E->gx_w64, E->Minv, E->state, fixed_rho);
+    hipLaunchKernelGGL(gx_bgj_finish_kernel, dim3((unsigned)((kk + 255) / 256)), dim3(256), 0, E->stream, (const double*)Tb[nb & 1], kk, E->Minv,
+                       (const DevState*)E->state);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }
@@ -1890,7 +1629,7 @@ int gx_objective_partial(nmfx_engine* E, bool bf = false) {      // 1/2 ||V - W 
     int rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
     { ProfScope ps(E, "objective");
-      if (bf) rc = gxb_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], kp, E->HThi, E->HTlo, kp, nullptr, 0, 0, mp, np, kp, 1, E->V, np, E->gx_part);
+      if (bf) rc = gxr_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], E->HThi, E->HTlo, 0, mp, np, kp, E->V, np, E->gx_part);
       else rc = gx_launch<true, false>(E, GX_RESID, E->W[0], kp, E->H, np, nullptr, 0, 0, mp, np, kp, 1, E->V, np, E->gx_part);
       if (rc) return rc; }
     return nmfx_launch_obj_reduce(E, (mp / GX_T) * (np / GX_T), E->gx_part);

@@ -252,7 +252,6 @@ int nmfx_bf16_pack_t(nmfx_engine* E, const float* Gpart, int gsplit, int64_t nob
 int nmfx_bf16_sk_product(nmfx_engine* E, int side, bool obj, const float* gsrc, int gslabs, double fixed_rho, const char* name);
 // the pack behind it: xf32 = [B^T sums transposed], xf64[0] = objective, recorded as obj[j] with the stop rule (and a pending "not
 // positive definite" of the side job promoted unless the rule fired)
-int nmfx_bf16_pack_sk(nmfx_engine* E, int64_t j, int64_t min_iter, double tol1, double tol2);
 bool nmfx_sk_enabled(const nmfx_engine* E);
 // KL-loss ADMM variants on the split-bf16 kernels (kernels_bf16.hip, r4)
 int nmfx_bf16_kl_state(nmfx_engine* E, bool reset);

@@ -43,7 +43,7 @@ def test_anls_larger_rank_properties():
 @pytest.mark.parametrize("precision", ["f32", "bf16"])
 @pytest.mark.parametrize("shape", [(300, 220, 40), (260, 400, 100)])
 def test_anls_k64_k128_both_precisions_vs_oracle(precision, shape, monkeypatch):
-    """k in (32, 128]: register-resident NNLS (k <= 64) / LDS NNLS (k = 128), products on the
+    """k in (32, 128]: register-resident NNLS (one wave per problem for k <= 64, two for k = 128), products on the
     split-bf16 kernels or on the exact-f32 kernels, against the oracle (scipy NNLS)."""
     from oracle import nmf_ref as R
     from nmf_amd.anls import anls

@@ -147,6 +147,20 @@ def test_aoadmm_eu_k64_k128_both_precisions_vs_oracle(precision, shape, monkeypa
     assert [tuple(r) for r in ao_admm.last_inner_counts] == [tuple(t) for t in ref.trace["inner"]]
 
 
+def test_aoadmm_eu_384x320_k100_vs_oracle():
+    """The shape the alternative-path runs of tests/test_gpu_knobs.py use (k padded to 128: inversions beside the stream-K
+    products, fused rounds), on the default path, with their bar: stop index of the oracle, WH parity below 1e-4."""
+    from oracle import nmf_ref as R
+    from nmf_amd.ao_admm import ao_admm
+    m, n, k = 384, 320, 100
+    v = R.planted_matrix(m, n, 32, seed=m + n + k, dtype=np.float32)
+    kw = dict(reg_w=(0.05, "l1n"), reg_h=(0.05, "l1n"), min_iter=6, max_iter=6, nndsvd_init=(True, "zero"))
+    res = ao_admm(v.copy(), k, **kw)
+    ref = R.ao_admm(v.astype(np.float64), k, **kw)
+    assert res.i == ref.i
+    assert np.linalg.norm(res.w @ res.h - ref.w @ ref.h) / np.linalg.norm(v.astype(np.float64)) < 1e-4
+
+
 def test_aoadmm_bf16_convergence_stop_matches_oracle(monkeypatch):
     """The stop rule fires inside a batch: the lagged objective of the bf16 path must give the
     reference's stop index and leave the pair the reference returns."""

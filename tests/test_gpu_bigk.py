@@ -27,6 +27,21 @@ def test_mur_beyond_128_components_vs_oracle(shape, k, distance):
     np.testing.assert_allclose(res.obj_history, ref.obj_history, rtol=4e-5)
 
 
+def test_mur_eu_whole_256_tiles_both_lambdas_vs_oracle():
+    """512 x 512 at k = 160 pads to whole 256 x 256 tiles (gxt2_gemm_kernel), lambda > 0 on both sides: the fused update launches
+    of W and of H.  The bar of the alternative-path runs (tests/test_gpu_knobs.py): stop index of the oracle, WH parity below 1e-4."""
+    from nmf_amd.mur import mur
+    m, n, k = 512, 512, 160
+    v = R.planted_matrix(m, n, 32, seed=m + n + k, dtype=np.float32)
+    kw = dict(distance_type="eu", lambda_w=0.1, lambda_h=0.05, min_iter=10, max_iter=10)
+    np.random.seed(5)
+    res = mur(v.copy(), k, **kw)
+    np.random.seed(5)
+    ref = R.mur(v.astype(np.float64), k, **kw)
+    assert res.i == ref.i
+    assert np.linalg.norm(res.w @ res.h - ref.w @ ref.h) / np.linalg.norm(v.astype(np.float64)) < 1e-4
+
+
 def test_mur_kl_k160_zero_and_tiny_entries():
     """KL beyond k = 128 on data with exact zeros (utils.py:24 zeroes their 0 log 0), tiny entries and all-zero rows: the quotient
     planes and the objective of the split-bf16 product kernel's KL epilogue (x rcp(zy + 1e-9), x log(x / zy) with inf / nan -> 0)."""
@@ -147,6 +162,19 @@ def test_aoadmm_beyond_128_components_vs_oracle(shape, k, regs):
     assert [tuple(r) for r in ao_admm.last_inner_counts] == [tuple(t) for t in ref.trace["inner"]]
     assert wh_error(res.w, res.h, ref.w, ref.h, v) < WH_TOL
     np.testing.assert_allclose(res.obj_history, ref.obj_history, rtol=1e-4)
+
+
+def test_aoadmm_384x320_k160_vs_oracle():
+    """The shape the alternative-path runs of tests/test_gpu_knobs.py use (mp = np = 384: no whole 256 x 256 tile, k padded to 256:
+    two block steps of the blocked Gram inversion), on the default path, with their bar: stop index of the oracle, WH parity below 1e-4."""
+    from nmf_amd.ao_admm import ao_admm
+    m, n, k = 384, 320, 160
+    v = R.planted_matrix(m, n, 32, seed=m + n + k, dtype=np.float32)
+    kw = dict(reg_w=(0.05, "l1n"), reg_h=(0.05, "l1n"), min_iter=5, max_iter=5, nndsvd_init=(True, "zero"))
+    res = ao_admm(v.copy(), k, **kw)
+    ref = R.ao_admm(v.astype(np.float64), k, **kw)
+    assert res.i == ref.i
+    assert np.linalg.norm(res.w @ res.h - ref.w @ ref.h) / np.linalg.norm(v.astype(np.float64)) < 1e-4
 
 
 @pytest.mark.parametrize("distance,regs,rho", [

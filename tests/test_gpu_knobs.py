@@ -39,8 +39,6 @@ CASES = [
     ({"NMFX_BF16_TERMS": "4"}, "mur", (384, 256, 40), dict(distance_type="kl", min_iter=15, max_iter=15)),
     ({"NMFX_PRECISION": "f32"}, "mur", (384, 256, 40), dict(distance_type="eu", min_iter=15, max_iter=15)),
     ({"NMFX_DROP_V": "1"}, "anls", (320, 256, 40), dict(distance_type="kl", min_iter=4, max_iter=4, nndsvd_init=NNDSVD)),   # row-major V dropped, the KL objective pass brings it back
-    ({"NMFX_NNLS128_OCC": "1"}, "anls", (260, 400, 100), dict(min_iter=3, max_iter=3, lambda_w=0.05, lambda_h=0.02, nndsvd_init=NNDSVD)),
-    ({"NMFX_PREPARE_SCALAR": "1"}, "ao_admm", (384, 320, 100), dict(reg_w=[0.05, "l1n"], reg_h=[0.05, "l1n"], min_iter=6, max_iter=6, nndsvd_init=NNDSVD)),
     ({"NMFX_AO_FUSED": "0"}, "ao_admm", (384, 320, 100), dict(reg_w=[0.05, "l1n"], reg_h=[0.05, "l1n"], min_iter=6, max_iter=6, nndsvd_init=NNDSVD)),
     # r4: the inversions as side jobs of stream-K products are the default at k padded to 128; the launches of round 3, plain (not
     # cyclic) runs, and a worker count that makes every run cross several row blocks (segments per worker > 2)
@@ -56,30 +54,23 @@ CASES = [
     ({"NMFX_KL_FUSE": "0"}, "ao_admm", (384, 320, 40), dict(distance_type="kl", reg_w=[0.02, "l1n"], reg_h=[0, "nn"], min_iter=4, max_iter=4, admm_iter=6, nndsvd_init=NNDSVD)),
     ({"NMFX_KL_GATHER": "0"}, "admm", (384, 320, 100), dict(rho=1.0, distance_type="kl", reg_w=[0, "nn"], reg_h=[0, "nn"], min_iter=5, max_iter=5, nndsvd_init=NNDSVD)),
     ({"NMFX_AO_ROWS_RB": "128"}, "ao_admm", (384, 320, 100), dict(reg_w=[0, "nn"], reg_h=[0, "nn"], min_iter=6, max_iter=6, nndsvd_init=NNDSVD)),
-    ({"NMFX_NNLS_LDS": "1"}, "anls", (320, 256, 40), dict(min_iter=4, max_iter=4, nndsvd_init=NNDSVD)),
     ({"NMFX_NNLS_CINV": "0"}, "anls", (320, 256, 40), dict(min_iter=4, max_iter=4, nndsvd_init=NNDSVD)),      # elimination kernels only
     ({"NMFX_NNLS_CINV": "0"}, "anls", (260, 400, 100), dict(min_iter=3, max_iter=3, lambda_w=0.05, lambda_h=0.02, nndsvd_init=NNDSVD)),
-    # beyond 128 components: the exact-f32 product kernel and the one-workgroup Gram inversion behind the split-bf16 / blocked defaults
+    # beyond 128 components: the exact-f32 product kernel behind the split-bf16 default
     ({"NMFX_PRECISION": "f32"}, "mur", (384, 256, 160), dict(distance_type="eu", min_iter=10, max_iter=10)),
     ({"NMFX_PRECISION": "f32"}, "mur", (384, 256, 160), dict(distance_type="kl", min_iter=10, max_iter=10)),
     ({"NMFX_PRECISION": "f32"}, "ao_admm", (384, 320, 160), dict(reg_w=[0.05, "l1n"], reg_h=[0.05, "l1n"], min_iter=5, max_iter=5, nndsvd_init=NNDSVD)),
-    ({"NMFX_PREPARE_SCALAR": "1"}, "ao_admm", (384, 320, 160), dict(reg_w=[0.05, "l1n"], reg_h=[0.05, "l1n"], min_iter=5, max_iter=5, nndsvd_init=NNDSVD)),
     ({"NMFX_PRECISION": "f32"}, "admm", (384, 320, 160), dict(rho=1.0, reg_w=[0.05, "l1n"], reg_h=[0.05, "l1n"], min_iter=5, max_iter=5, nndsvd_init=NNDSVD)),
-    # the bf16 operand planes "do not fit": the handle falls back to the exact-f32 product kernel (and says so in nmfx_get_note)
-    # r4: the composed path's alternatives -- short contractions on gxb_gemm_kernel, 256 x 128 tiles everywhere, separate update / image launches,
-    # no wave stagger / DMA pieces between the MFMA groups (512 x 512 pads to whole 256 x 256 tiles, so the default run takes gxt2_gemm_kernel)
-    ({"NMFX_GXR": "0"}, "mur", (384, 256, 160), dict(distance_type="eu", min_iter=10, max_iter=10)),
-    ({"NMFX_GXR": "0"}, "mur", (384, 256, 160), dict(distance_type="kl", min_iter=10, max_iter=10)),
+    # r4: the composed path's alternatives -- 256 x 128 tiles everywhere (512 x 512 pads to whole 256 x 256 tiles, so the default run takes
+    # gxt2_gemm_kernel), temporal requests for the once-read operand, the exact-f32 denominator, the exact-f32 products of ANLS and of
+    # the any-rank rounds
     ({"NMFX_GXT2": "0"}, "mur", (512, 512, 160), dict(distance_type="eu", min_iter=10, max_iter=10)),
     ({"NMFX_GXT2": "0"}, "mur", (512, 512, 160), dict(distance_type="kl", min_iter=10, max_iter=10)),
     ({"NMFX_GXT_NT": "0"}, "mur", (1024, 768, 160), dict(distance_type="eu", lambda_w=0.1, lambda_h=0.05, min_iter=8, max_iter=8)),
-    ({"NMFX_GX_FUSE_UPDATE": "0"}, "mur", (512, 512, 160), dict(distance_type="eu", lambda_w=0.1, lambda_h=0.05, min_iter=10, max_iter=10)),
     ({"NMFX_GX_DEN_BF16": "0"}, "mur", (512, 256, 400), dict(distance_type="eu", lambda_w=0.05, lambda_h=0.02, min_iter=8, max_iter=8)),   # k pads to 512: exact-f32 denominator W (H H^T)
-    ({"NMFX_GX_STAGGER": "0"}, "mur", (384, 256, 160), dict(distance_type="kl", min_iter=10, max_iter=10)),
-    ({"NMFX_GX_STAGGER": "16"}, "mur", (384, 256, 160), dict(distance_type="eu", min_iter=10, max_iter=10)),
-    ({"NMFX_GXR": "0"}, "ao_admm", (384, 320, 160), dict(reg_w=[0.05, "l1n"], reg_h=[0.05, "l1n"], min_iter=5, max_iter=5, nndsvd_init=NNDSVD)),
     ({"NMFX_GX_ANLS_BF16": "0"}, "anls", (256, 192, 144), dict(min_iter=2, max_iter=2, lambda_w=0.05, lambda_h=0.02, nndsvd_init=NNDSVD)),   # ANLS beyond 128 on the exact-f32 products
     ({"NMFX_GX_ROUNDS_F32": "1"}, "ao_admm", (384, 320, 160), dict(reg_w=[0.05, "l1n"], reg_h=[0, "nn"], min_iter=5, max_iter=5, nndsvd_init=NNDSVD)),   # exact-f32 inner products of the any-rank rounds
+    # the bf16 operand planes "do not fit": the handle falls back to the exact-f32 product kernel (and says so in nmfx_get_note)
     ({"NMFX_GXB_NOFIT": "1"}, "mur", (384, 256, 160), dict(distance_type="kl", min_iter=10, max_iter=10)),
     ({"NMFX_GXB_NOFIT": "1"}, "ao_admm", (384, 320, 160), dict(reg_w=[0.05, "l1n"], reg_h=[0.05, "l1n"], min_iter=5, max_iter=5, nndsvd_init=NNDSVD)),
 ]
@@ -88,7 +79,7 @@ CASES = [
 @pytest.mark.parametrize("env,method,shape,kwargs", CASES, ids=[f"{list(c[0].items())[0][0]}={list(c[0].items())[0][1]}-{c[1]}-{c[3].get('distance_type', '')}" for c in CASES])
 def test_alternative_paths_keep_parity(env, method, shape, kwargs):
     spec = json.dumps({"method": method, "shape": list(shape), "kwargs": kwargs})
-    # (NMF_AMD_NO_TORCH: the child never touches torch; its import is 1.5 s of each of these fifty processes)
+    # (NMF_AMD_NO_TORCH: the child never touches torch; its import is 1.5 s of each of these child processes)
     out = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}, spec], env=dict(os.environ, NMF_AMD_NO_TORCH="1", **env),
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]

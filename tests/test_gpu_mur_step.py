@@ -78,6 +78,11 @@ def test_composed_whole_tiles(kind, precision):
     run_case(512, 512, 160, kind, precision=precision, lam=(0.1, 0.0))
 
 
+# ... with lambda > 0 on both sides: both fused update launches (update + images behind the denominator product) carry their lambda
+def test_composed_whole_tiles_both_lambdas():
+    run_case(512, 512, 160, "eu", precision="bf16", lam=(0.1, 0.05))
+
+
 # m = 128 * 257 + 1, n = 384: 258 row blocks of 128, more than the 256 CUs; split-bf16 (1, 85) -- 514 groups of 64 rows over
 # 85 H slabs --, exact-f32 (1, 85)
 @pytest.mark.parametrize("precision", ["bf16", "f32"])
@@ -168,13 +173,8 @@ KNOBS = [
     ({"NMFX_BF16_TERMS": "4"}, (384, 256, 100), "kl", (0.0, 0.1)),
     ({"NMFX_TEMPORAL": "0"}, (640, 384, 64), "eu", (0.0, 0.0)),            # small V is temporal by default
     ({"NMFX_TEMPORAL": "1"}, (5120, 5121, 64), "eu", (0.0, 0.0)),          # V + V^T > 192 MiB: non-temporal by default
-    ({"NMFX_GXR": "0"}, (384, 256, 160), "eu", (0.1, 0.0)),                # composed path: 256 x 128 tiles, short contractions
-    ({"NMFX_GXR": "0"}, (384, 256, 160), "kl", (0.0, 0.0)),
-    ({"NMFX_GXT2": "0"}, (512, 512, 160), "eu", (0.0, 0.0)),               # whole 256 x 256 tiles, taken by default here
-    ({"NMFX_GX_FUSE_UPDATE": "0"}, (512, 512, 160), "eu", (0.1, 0.05)),
+    ({"NMFX_GXT2": "0"}, (512, 512, 160), "eu", (0.0, 0.0)),               # composed path: whole 256 x 256 tiles, taken by default here
     ({"NMFX_GX_DEN_BF16": "0"}, (512, 256, 400), "eu", (0.05, 0.0)),       # k pads to 512: exact-f32 denominator
-    ({"NMFX_GX_STAGGER": "0"}, (384, 256, 160), "kl", (0.0, 0.0)),
-    ({"NMFX_GX_STAGGER": "16"}, (384, 256, 160), "eu", (0.0, 0.0)),
     ({"NMFX_GXB_NOFIT": "1"}, (384, 256, 160), "kl", (0.0, 0.1)),          # the exact-f32 product kernel beyond 128 components
 ]
 

@@ -39,5 +39,4 @@ for k, dist in cases:
             if cnt:
                 prof[name] = round(ms / cnt * 1e3, 1)
         hist = e.objective_history(10 + steps + 10) if hasattr(e, "objective_history") else None
-        print(json.dumps({"k": k, "distance": "eu" if dist == 0 else "kl", "ms_per_iter": round(dt * 1e3, 4), "kernels_us": prof,
-                          "env": {x: os.environ.get(x) for x in ("NMFX_GXR", "NMFX_GX_STAGGER")}}), flush=True)
+        print(json.dumps({"k": k, "distance": "eu" if dist == 0 else "kl", "ms_per_iter": round(dt * 1e3, 4), "kernels_us": prof}), flush=True)
