@@ -232,6 +232,26 @@ int nmfx_mur_run(nmfx_handle_t h, int distance, double lambda_w, double lambda_h
 int nmfx_mur_finish(nmfx_handle_t h, int distance, int64_t min_iter, double tol1,
                     double tol2, int64_t iters_done);
 
+/* ---- fold-in (version 370): H for new data against a fixed W -----------------
+ * The reference has nothing of the kind.  After nmfx_upload_v (the new data) and nmfx_set_factors(w, h0), iteration j applies
+ * the H half-step of nmfx_mur_run for the same loss and W is never updated:
+ *   NMFX_EU    H <- H (W^T V) / (W^T (W H) + lambda_h H + 1e-9)                          (nmf/mur.py:36-49 with w fixed)
+ *   NMFX_KL    A = H (W^T (V / (W H + 1e-9))),  B = W^T 1,  H <- 2 A / (B + sqrt(B^2 + 4 lambda_h A)),  0 where B = 0
+ *   NMFX_IS, NMFX_BETA (after nmfx_set_beta), and every loss with the weights of nmfx_upload_weights: the H step stated at
+ *   nmfx_mur_run, nmfx_upload_weights and nmfx_set_beta, a zero denominator gives 0.
+ * obj[j] is the objective of (W, H_j), obj[0] that of the start h0, recorded in f64 with the iteration contract and the stop
+ * rule of nmfx_mur_run (`first` = iterations already run; nmfx_foldin_finish records the objective of the last pair).  One
+ * step is ONE pass over V: the H phase also sums the objective of the pair it starts from (kernels_phase.hip).
+ * V is never modified; two runs are bit-identical.  Legal on a dense handle with k <= 128; the kernels are exact f32
+ * whatever the precision mode and nmfx_get_note says so after the first call.  Refused, with a message and nothing launched:
+ * a sparse handle, k > 128 and an unknown distance (NMFX_E_ARG); NMFX_BETA without a beta, a handle with nmfx_set_ard in
+ * force (the relevances are not used in fold-in: nmfx_clear_ard first), no V or no factors (NMFX_E_STATE).
+ * W is read from the one buffer that holds it (after nmfx_set_factors; nmfx_get_factors returns it unchanged); a later
+ * nmfx_mur_run on the same handle needs nmfx_set_factors first, like a change of solver. */
+int nmfx_foldin_run(nmfx_handle_t h, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2,
+                    int64_t first, int64_t count);
+int nmfx_foldin_finish(nmfx_handle_t h, int distance, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
+
 /* Row-sharded form: phase A = everything up to the rank-local partial sums
  * [W^T V | W^T W | objective], phase B = H update from the (all-reduced) sums.
  * Between the two the caller sum-all-reduces the exchange buffers over ranks

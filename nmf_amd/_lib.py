@@ -52,6 +52,8 @@ SIGNATURES = {
     "nmfx_get_objectives": (_i32, [_vp, _i64, _i64, _vp]),
     "nmfx_mur_run": (_i32, [_vp, _i32, _dbl, _dbl, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_mur_finish": (_i32, [_vp, _i32, _i64, _dbl, _dbl, _i64]),
+    "nmfx_foldin_run": (_i32, [_vp, _i32, _dbl, _i64, _dbl, _dbl, _i64, _i64]),
+    "nmfx_foldin_finish": (_i32, [_vp, _i32, _i64, _dbl, _dbl, _i64]),
     "nmfx_mur_phase_a": (_i32, [_vp, _i32, _dbl, _i64]),
     "nmfx_mur_phase_b": (_i32, [_vp, _i32, _dbl, _i64, _dbl, _dbl, _i64]),
     "nmfx_mur_finish_a": (_i32, [_vp, _i32, _i64]),

@@ -125,7 +125,7 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
 
 extern "C" {
 
-int nmfx_version(void) { return 360; }      // 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 370; }      // 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -993,6 +993,48 @@ int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1
     if (E && E->sp) return nmfx_sparse_mur_finish(E, distance, min_iter, tol1, tol2, iters_done);
     if ((rc = nmfx_mur_finish_a(E, distance, iters_done))) return rc;
     return nmfx_mur_finish_b(E, min_iter, tol1, tol2, iters_done);
+}
+
+// ---- fold-in (version 370; kernels_phase.hip) ----------------
+// What both entry points refuse, nothing launched
+static const char* const FOLDIN_NOTE = "fold-in (nmfx_foldin_run) runs the exact-f32 kernels whatever the precision mode";
+static int foldin_ok(nmfx_engine* E, int distance, const char* who) {
+    if (E->sp) { E->err = std::string(who) + ": fold-in is not available on a sparse handle (dense V, k <= 128)"; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = std::string(who) + ": fold-in needs k <= 128"; return NMFX_E_ARG; }
+    if (distance != NMFX_EU && distance != NMFX_KL && distance != NMFX_IS && distance != NMFX_BETA) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
+    if (distance == NMFX_BETA && !E->beta_set) { E->err = std::string(who) + ": NMFX_BETA without a beta (nmfx_set_beta)"; return NMFX_E_STATE; }
+    if (E->ard) { E->err = std::string(who) + ": automatic relevance determination is set (nmfx_set_ard): fold-in does not use the relevances, nmfx_clear_ard first"; return NMFX_E_STATE; }
+    if (!E->have_v || !E->have_f) { E->err = std::string(who) + ": upload V and set factors first"; return NMFX_E_STATE; }
+    return NMFX_OK;
+}
+
+// W stays in the buffer that holds it (after nmfx_set_factors: W[0]); only H moves
+static const float* foldin_enter(nmfx_engine* E, int distance) {
+    E->himg_both = false; E->kl_h_iter = -2;
+    E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
+    E->w_in_place = true;
+    if (E->note.find(FOLDIN_NOTE) == std::string::npos) E->note += (E->note.empty() ? "" : "; ") + std::string(FOLDIN_NOTE);
+    return E->W[E->wsel];
+}
+
+int nmfx_foldin_run(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count) {
+    if (!E) return NMFX_E_ARG;
+    int rc;
+    if ((rc = foldin_ok(E, distance, "foldin_run"))) return rc;
+    if ((rc = check_ready(E, first, count))) return rc;
+    const float* W = foldin_enter(E, distance);
+    for (int64_t j = first; j < first + count && !rc; ++j) rc = nmfx_foldin_step(E, distance, lambda_h, min_iter, tol1, tol2, j, W);
+    return rc;
+}
+
+int nmfx_foldin_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
+    if (!E) return NMFX_E_ARG;
+    int rc;
+    if ((rc = foldin_ok(E, distance, "foldin_finish"))) return rc;
+    if ((rc = check_ready(E, iters_done, 1))) return rc;
+    const float* W = foldin_enter(E, distance);
+    if ((rc = nmfx_foldin_finish_a(E, distance, W))) return rc;
+    return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
 }
 
 // ---- profiling -------------------------------------------------------------

@@ -9,7 +9,8 @@
 // numerator and a denominator entry in registers and feeds each into a second MFMA product: two accumulators per output
 // tile.  The quotients never leave the registers.  The W phase also sums the objective terms of the pair it starts from
 // (f32 per stage, f64 across stages).  Slabs [num | den] of the split contracted dimension are summed in slab order by the
-// update kernels: no atomics, two runs are bit-identical.
+// update kernels: no atomics, two runs are bit-identical.  Fold-in (nmfx_foldin_run, W fixed) runs the H phase alone and lets
+// IT sum the objective of the pair it starts from: one pass over V per step (the end of this file).
 //
 // The policies.  q = T + 1e-9, W' = the new W, H likewise with W' and lam_h.
 //   IsEntry          num = v / q^2             den = 1 / q       term  v / q - log(v / q) - 1
@@ -64,7 +65,8 @@
 
 // --------------------------------------------------------------------------
 // The per-entry policies.  OMEGA: the kernel loads the Omega slice (w is 1 otherwise).  SELECT: num and den are selected
-// to 0 where the cell is not live; the objective term always is.  live(v, w, inside): inside = row < m and column < n.
+// to 0 where the cell is not live; the objective term always is.  FOLDIN_ONLY: the policy exists for fold-in alone (see
+// PlainEntry).  live(v, w, inside): inside = row < m and column < n.
 // entry<OBJ>(args, v, w, T, nu, de, term): num, den and -- OBJ only -- the objective term of one cell.  OBJ_SCALE: what the
 // block's objective sum is multiplied by.  Args: the policy's run-time parameters, a kernel argument passed by value.
 // --------------------------------------------------------------------------
@@ -72,7 +74,7 @@ struct NoArgs {};
 
 struct IsEntry {
     using Args = NoArgs;
-    static constexpr bool OMEGA = false, SELECT = false;
+    static constexpr bool OMEGA = false, SELECT = false, FOLDIN_ONLY = false;
     static constexpr double OBJ_SCALE = 1.0;
     static __device__ __forceinline__ bool live(float v, float, bool) { return v > 0.f; }
     template <bool OBJ>
@@ -88,7 +90,7 @@ struct IsEntry {
 template <int LOSS>
 struct WtEntry {
     using Args = NoArgs;
-    static constexpr bool OMEGA = true, SELECT = true;
+    static constexpr bool OMEGA = true, SELECT = true, FOLDIN_ONLY = false;
     static constexpr double OBJ_SCALE = LOSS == NMFX_EU ? 0.5 : 1.0;
     static __device__ __forceinline__ bool live(float, float w, bool) { return w > 0.f; }
     template <bool OBJ>
@@ -116,6 +118,34 @@ struct WtEntry {
     }
 };
 
+// The Omega-free Euclidean and KL policies of fold-in (nmfx_foldin_run): the per-entry functions of WtEntry<EU | KL> with
+// om = 1, no Omega stream, live cells by index (a zero of V is data).  FOLDIN_ONLY: instantiated in the two combinations
+// fold-in launches alone, the H phase with objective and the objective-only pass (launch_phase).
+template <int LOSS>
+struct PlainEntry {
+    using Args = NoArgs;
+    static constexpr bool OMEGA = false, SELECT = true, FOLDIN_ONLY = true;
+    static constexpr double OBJ_SCALE = LOSS == NMFX_EU ? 0.5 : 1.0;
+    static __device__ __forceinline__ bool live(float, float, bool inside) { return inside; }
+    template <bool OBJ>
+    static __device__ __forceinline__ void entry(const Args&, float v, float, float T, float& nu, float& de, float& term) {
+        if (LOSS == NMFX_EU) {
+            const float d = v - T;
+            if (OBJ) term = d * d;
+            nu = v;
+            de = T;
+        } else {
+            if (OBJ) {
+                float tl = v * logf(v / T);
+                tl = (tl != tl || tl == __builtin_inff()) ? 0.f : tl;
+                term = (tl - v) + T;
+            }
+            nu = v / (T + 1e-9f);
+            de = 1.f;
+        }
+    }
+};
+
 // beta and what the host derives from it (in f64, then rounded)
 struct BetaArgs {
     float beta, bm1;       // beta, beta - 1
@@ -126,7 +156,7 @@ struct BetaArgs {
 template <bool WT>
 struct BetaEntry {
     using Args = BetaArgs;
-    static constexpr bool OMEGA = WT, SELECT = true;
+    static constexpr bool OMEGA = WT, SELECT = true, FOLDIN_ONLY = false;
     static constexpr double OBJ_SCALE = 1.0;
     static __device__ __forceinline__ bool live(float, float w, bool inside) { return WT ? w > 0.f : inside; }
     template <bool OBJ>
@@ -485,8 +515,9 @@ struct PhasePath { const char* who; const char* wscope; const char* hscope; };
 static const PhasePath PATH_IS = {"IS", "is_wphase", "is_hphase"};
 static const PhasePath PATH_WT = {"weighted MUR", "wt_wphase", "wt_hphase"};
 static const PhasePath PATH_BETA = {"MUR-beta", "beta_wphase", "beta_hphase"};
+static const PhasePath PATH_PLAIN = {"fold-in", "plain_objective", "plain_hphase"};      // (PlainEntry: fold-in alone)
 static const PhasePath& phase_path(const nmfx_engine* E, int distance) {
-    return distance == NMFX_BETA ? PATH_BETA : E->Om ? PATH_WT : PATH_IS;
+    return distance == NMFX_BETA ? PATH_BETA : E->Om ? PATH_WT : distance == NMFX_IS ? PATH_IS : PATH_PLAIN;
 }
 
 // Splits of the contracted dimension: enough blocks for two per CU, at least 8 stages (2 per wave) each
@@ -529,54 +560,71 @@ static int update_form(const nmfx_engine* E, int distance, float* gamma) {
 }
 
 template <typename Entry, int KP, int NE>
-static int launch_phase(nmfx_engine* E, const PhasePath& P, const typename Entry::Args& ea, bool wph, bool upd, const float* W) {
+static int launch_phase(nmfx_engine* E, const PhasePath& P, const typename Entry::Args& ea, bool wph, bool upd, bool obj, const float* W) {
     const int splits = wph ? phase_wsplits(E) : phase_hsplits(E);
     dim3 grid((unsigned)((wph ? E->mp : E->np) / (16 * NE)), (unsigned)splits), block(256);
     const size_t panel = (size_t)KP * (16 * NE + 4) * sizeof(float);
     const size_t red = (size_t)2 * (KP / 16) * NE * 64 * sizeof(f32x4);
     const size_t shm = std::max(panel, red);
     { int rc_ = nmfx_need_v(E); if (rc_) return rc_; }
-    if (wph) {
+    // One objective partial per block, on either grid.  Both grids fit the buffer nmfx_create sized: a phase grid has
+    // blocks_x * splits <= blocks_x * ceil(2 ncu / blocks_x) < 2 ncu + blocks_x blocks (phase_splits), blocks_x is at most
+    // mp / 32 or np / 32, and obj_part_cap is 2 (max(mp, np) / 64 + 64) + 2 ncu or more.  Checked all the same.
+    if (obj) {
+        if ((int64_t)grid.x * grid.y > E->obj_part_cap) { E->err = std::string(P.who) + ": objective partials exceed their buffer"; return NMFX_E_ARG; }
         E->obj_count = (int64_t)grid.x * grid.y;
-        if (E->obj_count > E->obj_part_cap) { E->err = std::string(P.who) + ": objective partials exceed their buffer"; return NMFX_E_ARG; }
     }
 #define NMFX_PHASELAUNCH(WP, UP, OB) \
     hipLaunchKernelGGL((phase_kernel<Entry, KP, NE, WP, UP, OB>), grid, block, shm, E->stream, E->V, E->Om, E->np, W, E->H, \
                        E->phase_part, E->obj_part, E->np, E->mp, E->m, E->n, ea, &E->state->flag)
-    if (wph) { if (upd) NMFX_PHASELAUNCH(true, true, true); else NMFX_PHASELAUNCH(true, false, true); }
-    else NMFX_PHASELAUNCH(false, true, false);
+    // the four combinations: W phase (with the objective), objective only, H phase, H phase with the objective (fold-in)
+    if constexpr (Entry::FOLDIN_ONLY) {
+        if (wph && !upd && obj) NMFX_PHASELAUNCH(true, false, true);
+        else if (!wph && upd && obj) NMFX_PHASELAUNCH(false, true, true);
+        else { E->err = std::string(P.who) + ": this policy runs fold-in alone"; return NMFX_E_ARG; }
+    } else {
+        if (wph) { if (upd) NMFX_PHASELAUNCH(true, true, true); else NMFX_PHASELAUNCH(true, false, true); }
+        else if (obj) NMFX_PHASELAUNCH(false, true, true);
+        else NMFX_PHASELAUNCH(false, true, false);
+    }
 #undef NMFX_PHASELAUNCH
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }
 
 template <typename Entry>
-static int phase_kp(nmfx_engine* E, const PhasePath& P, const typename Entry::Args& ea, bool wph, bool upd, const float* W) {
+static int phase_kp(nmfx_engine* E, const PhasePath& P, const typename Entry::Args& ea, bool wph, bool upd, bool obj, const float* W) {
     switch (E->kp) {
-        case 16: return launch_phase<Entry, 16, 4>(E, P, ea, wph, upd, W);
-        case 32: return launch_phase<Entry, 32, 4>(E, P, ea, wph, upd, W);
-        case 64: return launch_phase<Entry, 64, 4>(E, P, ea, wph, upd, W);
-        case 128: return launch_phase<Entry, 128, 2>(E, P, ea, wph, upd, W);
+        case 16: return launch_phase<Entry, 16, 4>(E, P, ea, wph, upd, obj, W);
+        case 32: return launch_phase<Entry, 32, 4>(E, P, ea, wph, upd, obj, W);
+        case 64: return launch_phase<Entry, 64, 4>(E, P, ea, wph, upd, obj, W);
+        case 128: return launch_phase<Entry, 128, 2>(E, P, ea, wph, upd, obj, W);
     }
     E->err = std::string(P.who) + ": unsupported padded rank";
     return NMFX_E_ARG;
 }
 
-// the policy of a call: NMFX_BETA with or without weights, any other distance with weights, NMFX_IS without
-static int phase(nmfx_engine* E, int distance, bool wph, bool upd, const float* W) {
+// the policy of a call: NMFX_BETA with or without weights, any other distance with weights, NMFX_IS without; fold-in
+// alone (foldin) also runs the Euclidean and KL losses without weights.  obj: the objective is summed (every W-side pass)
+static int phase(nmfx_engine* E, int distance, bool wph, bool upd, const float* W, bool foldin = false) {
+    const bool obj = wph || foldin;
     if (distance == NMFX_BETA) {
         if (!E->beta_set) { E->err = "MUR-beta: no beta set (nmfx_set_beta)"; return NMFX_E_STATE; }
         const BetaArgs ba = beta_args(E);
-        return E->Om ? phase_kp<BetaEntry<true>>(E, PATH_BETA, ba, wph, upd, W) : phase_kp<BetaEntry<false>>(E, PATH_BETA, ba, wph, upd, W);
+        return E->Om ? phase_kp<BetaEntry<true>>(E, PATH_BETA, ba, wph, upd, obj, W) : phase_kp<BetaEntry<false>>(E, PATH_BETA, ba, wph, upd, obj, W);
     }
     if (E->Om) {
         switch (distance) {
-            case NMFX_EU: return phase_kp<WtEntry<NMFX_EU>>(E, PATH_WT, NoArgs{}, wph, upd, W);
-            case NMFX_KL: return phase_kp<WtEntry<NMFX_KL>>(E, PATH_WT, NoArgs{}, wph, upd, W);
-            case NMFX_IS: return phase_kp<WtEntry<NMFX_IS>>(E, PATH_WT, NoArgs{}, wph, upd, W);
+            case NMFX_EU: return phase_kp<WtEntry<NMFX_EU>>(E, PATH_WT, NoArgs{}, wph, upd, obj, W);
+            case NMFX_KL: return phase_kp<WtEntry<NMFX_KL>>(E, PATH_WT, NoArgs{}, wph, upd, obj, W);
+            case NMFX_IS: return phase_kp<WtEntry<NMFX_IS>>(E, PATH_WT, NoArgs{}, wph, upd, obj, W);
         }
     } else if (distance == NMFX_IS) {
-        return phase_kp<IsEntry>(E, PATH_IS, NoArgs{}, wph, upd, W);
+        return phase_kp<IsEntry>(E, PATH_IS, NoArgs{}, wph, upd, obj, W);
+    } else if (foldin && distance == NMFX_EU) {
+        return phase_kp<PlainEntry<NMFX_EU>>(E, PATH_PLAIN, NoArgs{}, wph, upd, obj, W);
+    } else if (foldin && distance == NMFX_KL) {
+        return phase_kp<PlainEntry<NMFX_KL>>(E, PATH_PLAIN, NoArgs{}, wph, upd, obj, W);
     }
     E->err = "Unknown distance type.";
     return NMFX_E_ARG;
@@ -669,6 +717,27 @@ int nmfx_mur_dense_finish_a(nmfx_engine* E, int distance, int64_t j) {
     int rc;
     { ProfScope ps(E, "objective");
       if ((rc = phase(E, distance, true, false, E->W[j & 1]))) return rc; }
+    return nmfx_launch_obj_reduce(E, E->obj_count);
+}
+
+// ---- fold-in (nmfx_foldin_run) -----------------------------
+// One step with W fixed: the H phase, which here also sums the objective of the pair (W, H_j) it starts from; the reduce;
+// phase_h_update_kernel, which records that objective, applies the stop rule and then updates H.  One pass over V.
+int nmfx_foldin_step(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j, const float* W) {
+    const PhasePath& P = phase_path(E, distance);
+    int rc;
+    if ((rc = phase_ensure(E))) return rc;
+    { ProfScope ps(E, P.hscope);
+      if ((rc = phase(E, distance, false, true, W, true))) return rc; }
+    if ((rc = nmfx_launch_obj_reduce(E, E->obj_count))) return rc;
+    return nmfx_mur_dense_phase_b(E, distance, lambda_h, min_iter, tol1, tol2, j);
+}
+
+// the objective of the last pair: the objective-only pass
+int nmfx_foldin_finish_a(nmfx_engine* E, int distance, const float* W) {
+    int rc;
+    { ProfScope ps(E, "objective");
+      if ((rc = phase(E, distance, true, false, W, true))) return rc; }
     return nmfx_launch_obj_reduce(E, E->obj_count);
 }
 

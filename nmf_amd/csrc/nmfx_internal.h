@@ -270,6 +270,10 @@ int nmfx_finish_b(nmfx_engine* E, int64_t min_iter, double tol1, double tol2, in
 int nmfx_mur_dense_phase_a(nmfx_engine* E, int distance, double lambda_w, int64_t j);
 int nmfx_mur_dense_phase_b(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j);
 int nmfx_mur_dense_finish_a(nmfx_engine* E, int distance, int64_t j);
+// ... and fold-in (nmfx_foldin_run / nmfx_foldin_finish): one step on H with W fixed -- H phase with the objective of (W, H_j), reduce,
+// H update behind the stop rule -- and the objective-only pass over the last pair.  Without weights NMFX_EU and NMFX_KL run here too
+int nmfx_foldin_step(nmfx_engine* E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j, const float* W);
+int nmfx_foldin_finish_a(nmfx_engine* E, int distance, const float* W);
 // ... with nmfx_set_ard in force: the relevances of (W, H) -- W = the buffer that holds the current iterate; honour_stop: skipped once
 // the stop rule has fired -- and the closing step that records the objective plus the penalty
 int nmfx_ard_alloc(nmfx_engine* E);

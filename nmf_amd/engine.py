@@ -211,6 +211,14 @@ class Engine:
         self._ck(self.lib.nmfx_mur_finish(self.h, dist, int(min_iter), float(tol1), float(tol2),
                                           int(iters_done)))
 
+    def foldin_run(self, dist, lambda_h, min_iter, tol1, tol2, first, count):
+        """`count` H half-steps of MUR for the loss `dist` with W fixed, from iteration `first` (include/nmfx.h, fold-in)."""
+        self._ck(self.lib.nmfx_foldin_run(self.h, dist, float(lambda_h), int(min_iter), float(tol1), float(tol2),
+                                          int(first), int(count)))
+
+    def foldin_finish(self, dist, min_iter, tol1, tol2, iters_done):
+        self._ck(self.lib.nmfx_foldin_finish(self.h, dist, int(min_iter), float(tol1), float(tol2), int(iters_done)))
+
     def mur_phase_a(self, dist, lambda_w, j):
         self._ck(self.lib.nmfx_mur_phase_a(self.h, dist, float(lambda_w), int(j)))
 

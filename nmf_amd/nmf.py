@@ -41,6 +41,20 @@ class NMF:
         if saving:
             self.save_factorization()
 
+    def transform(self, data, **kw):
+        """H for new `data` against the dictionary self.w of the last factorize (nmf_amd.transform.transform): returns
+        TransformResults(h, i, obj_history, experiment).  distance_type, and beta with it, default to what that factorize
+        used; every keyword of transform may be given."""
+        if self.results is None or self.w is None:
+            raise RuntimeError('NMF.transform needs a dictionary: call factorize first')
+        from .transform import transform
+        exp = self.results.experiment
+        if 'distance_type' not in kw:
+            kw['distance_type'] = getattr(exp, 'distance_type', 'kl')
+            if kw['distance_type'] == 'beta' and 'beta' not in kw:
+                kw['beta'] = getattr(exp, 'beta', None)
+        return transform(data, self.w, **kw)
+
     def save_factorization(self, save_dir='./results', save_name=None):
         """Write results to `save_dir`/`save_name`.npz; the default name follows
         the grammar of nmf/nmf.py:95-126, e.g. nmf_ao_admm_3_eu_0:nn_0.5:l1n_random."""
