@@ -167,3 +167,18 @@ def drive(engine, run_batch, finish, max_iter, tol1, tol2, before_line=None, ref
         return stop_i, history[:stop_i + 2]
     logging.info('Max iteration reached.')
     return max_iter - 1, history
+
+
+NEVER = 10 ** 15      # a min_iter no run reaches: the device's stop rule stays off
+
+
+def run_loop(engine, run, run_head, finish, finish_head, min_iter, max_iter, tol1, tol2, referee=None):
+    """The tail of a MUR-family run: `run` / `finish` are the engine's mur_run / mur_finish or foldin_run / foldin_finish,
+    `run_head` / `finish_head` their arguments in front of (min_iter, tol1, tol2, ...).  Returns drive's (i, obj_history).
+    A referee that walked has taken the stop rule over: the closing bookkeeping then leaves the device's rule off."""
+    logging.info('Entering Main Loop.')
+    return drive(
+        engine,
+        lambda first, count: run(*run_head, min_iter, tol1, tol2, first, count),
+        lambda done: finish(*finish_head, NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
+        max_iter, tol1, tol2, referee=referee)

@@ -14,17 +14,17 @@ a > 0, b > 0 and c = F + N + a + 1:
 Iteration t: the W half-step and the H half-step with lambda_t, then lambda_{t+1} from (W_{t+1}, H_{t+1}); lambda_0 comes
 from the start factors.  obj_history[t] = C(W_t, H_t, lambda_t) under the usual tol1 / tol2 stop rule.  The loop runs on the
 device (nmfx_set_ard, include/nmfx.h); `objective` evaluates C in float64 on the host."""
-import logging
 from collections import namedtuple
 
 import numpy as np
 
 from . import _lib as L
+from . import losses
 from . import utils
 from . import weighted
-from ._driver import drive
+from ._driver import run_loop
 from .engine import Engine
-from .mur import BetaExperiment, _check_beta_input, _check_beta_request, check_beta, weighted_start
+from .mur import BetaExperiment, check_beta_request, weighted_start
 
 ArdResults = namedtuple('ArdResults', 'w h i obj_history experiment relevance k_eff')
 ArdExperiment = namedtuple('Experiment', BetaExperiment._fields + ('phi', 'a', 'b'))
@@ -105,18 +105,18 @@ def mur_ard(x, k, *, beta, phi, a=5.0, b=None, weights=None, prune_tol=1e-3, min
 
     Returns ArdResults(w, h, i, obj_history, experiment, relevance, k_eff): relevance = (lambda_c - B) / B per component
     (float64 [k], B = b / (F + N + a + 1) the floor of lambda), k_eff = #{c : relevance_c > prune_tol max relevance}."""
-    beta = check_beta('beta', beta)
+    beta = losses.check_beta('beta', beta)
     phi, a = _positive('phi', phi), _positive('a', a)
     if b is not None:
         b = _positive('b', b)
     else:
         _check_default_b(a)                                     # (before the data is looked at)
     prune_tol = _check_prune_tol(prune_tol)
-    _check_beta_request(x, k, None, beta)
+    check_beta_request(x, k, None, beta)
     if weights is not None:
         x32, w32 = weighted.prepare(x, weights, k, 'beta', beta=beta)
     else:
-        _check_beta_input(x, beta)
+        losses.check_f32_image(x, 'beta', beta)
         x32, w32 = x, None
     if b is None:
         b = _positive('b', default_b(x, k, a, weights))        # (all-zero data: mean(x) = 0 leaves no default)
@@ -125,22 +125,13 @@ def mur_ard(x, k, *, beta, phi, a=5.0, b=None, weights=None, prune_tol=1e-3, min
     if w32 is not None:                                         # the starts of mur(..., distance_type='beta'), with and without weights=
         init = weighted_start(x, x32, w32, k, nndsvd_init)
     else:
-        init = utils.initial_factors(x32, k, nndsvd_init, defer_device=True)
-    with Engine(x32.shape[0], x32.shape[1], k, device=device) as eng:
-        eng.upload_v(x32)
-        if w32 is not None:
-            eng.upload_weights(w32)
-            eng.set_factors(*init)
-        else:
-            eng.set_factors(*utils.device_initial_factors(eng, x32, k, nndsvd_init, init))
-        eng.set_beta(beta)
+        host = utils.initial_factors(x32, k, nndsvd_init, defer_device=True)
+
+        def init(eng):                                          # (an NNDSVD start is computed on the device, from the uploaded x)
+            return utils.device_initial_factors(eng, x32, k, nndsvd_init, host)
+    with Engine.for_phase(x32, k, init, weights=w32, beta=beta, device=device) as eng:
         eng.set_ard(phi, a, b)
-        logging.info('Entering Main Loop.')
-        i, history = drive(
-            eng,
-            lambda first, count: eng.mur_run(L.BETA, 0.0, 0.0, min_iter, tol1, tol2, first, count),
-            lambda done: eng.mur_finish(L.BETA, min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
+        i, history = run_loop(eng, eng.mur_run, (L.BETA, 0.0, 0.0), eng.mur_finish, (L.BETA,), min_iter, max_iter, tol1, tol2)
         w, h = eng.get_factors()
         rel = relevance(eng.relevance(), x32.shape, a, b)
     return ArdResults(w=w, h=h, i=i, obj_history=history, experiment=experiment, relevance=rel,

@@ -71,6 +71,24 @@ class Engine:
             raise
         return self
 
+    @classmethod
+    def for_phase(cls, x, k, factors, weights=None, beta=None, device=0):
+        """A fresh dense handle on the exact-f32 phase path (kernels_phase.hip), ready to run: `x` uploaded, then `weights`
+        where present, the start factors set -- `factors` is (w0, h0), or a function of the engine that returns them (a start
+        computed on the device from the uploaded x) --, then beta where present.  Usable as a context manager."""
+        self = cls(x.shape[0], x.shape[1], k, device=device)
+        try:
+            self.upload_v(x)
+            if weights is not None:
+                self.upload_weights(weights)
+            self.set_factors(*(factors(self) if callable(factors) else factors))
+            if beta is not None:
+                self.set_beta(beta)
+        except Exception:
+            self.close()
+            raise
+        return self
+
     def _ck(self, rc):
         L.check(rc, self.h)
 

@@ -25,6 +25,7 @@ from itertools import product
 import numpy as np
 
 from .engine import Engine
+from . import losses
 from . import utils
 from ._driver import Referee
 
@@ -48,15 +49,16 @@ def factorize_grid(data, method='mur', *, features, lambda_w=(0.0,), lambda_h=(0
         raise ValueError(f"{method}: distance_type='beta' / beta= (the beta-divergence) is a loss of mur only")
     if method == 'mur' and (common.get('distance_type') == 'beta' or common.get('beta') is not None):
         # checked once, before any engine exists; 'beta' never lifts and runs sequentially like 'is'
-        from .mur import _check_beta_input, _check_beta_request, check_beta
-        b = check_beta(common.get('distance_type', 'kl'), common.get('beta'))
-        _check_beta_request(data, max(features), None, b)
-        _check_beta_input(data, b)
+        from .mur import check_beta_request
+        b = losses.check_beta(common.get('distance_type', 'kl'), common.get('beta'))
+        check_beta_request(data, max(features), None, b)
+        losses.check_f32_image(data, 'beta', b)
     if method != 'mur' and common.get('distance_type') == 'is':
         raise ValueError(f"{method}: distance_type='is' (Itakura-Saito) is a loss of mur only")
     if method == 'mur' and common.get('distance_type') == 'is':     # checked once, before any engine exists; 'is' never lifts
-        from .mur import _check_is_input
-        _check_is_input(data, max(features))
+        from .mur import check_is_request
+        check_is_request(data, max(features))
+        losses.check_f32_image(data, 'is')
     elif method == 'mur' and common.get('distance_type') != 'beta':     # the lift of negative data happens once, in place (nmf/mur.py:99-101)
         lowest = np.min(data)
         if lowest < 0:

@@ -7,6 +7,7 @@ positions are never read, and neither `x` nor `mask` is modified."""
 import numpy as np
 import scipy.sparse as sp
 
+from . import losses
 from .sparse import MAX_K
 
 ROWS = 1024          # rows of a dense mask handled at a time (no m x n temporaries)
@@ -17,7 +18,7 @@ def check_k(k):
         raise ValueError(f'masked input supports 1 <= k <= {MAX_K} components (got k = {k})')
 
 
-def _dtype(x):
+def value_dtype(x):
     if np.issubdtype(x.dtype, np.complexfloating):
         raise TypeError('masked input must be real')
     return np.float32 if x.dtype == np.float32 else np.float64
@@ -96,7 +97,7 @@ def observed(x, mask, k=None):
         raise ValueError(f'mask has shape {tuple(mask.shape)}, data has shape {tuple(x.shape)}')
     if x.shape[0] >= 2 ** 31 or x.shape[1] >= 2 ** 31:
         raise ValueError('masked input: each dimension must be below 2^31')
-    dtype = _dtype(x)
+    dtype = value_dtype(x)
     if np.issubdtype(mask.dtype, np.complexfloating):
         raise TypeError('mask must be real')
     row_ptr, col_idx = _positions(mask, x.shape)
@@ -116,15 +117,8 @@ def check_positive(c):
 
 def check_positive_values(vals):
     """check_positive on the observed values themselves (a 1-D array)."""
-    if not vals.size:
-        return
-    with np.errstate(over='ignore', under='ignore'):            # (the device holds float32: judge that image)
-        lowest, highest = np.float32(np.min(vals)), np.float32(np.max(vals))
-    if not lowest > 0:
-        raise ValueError("distance_type='is': an observed value is 0, or underflows to 0 in float32 (the Itakura-Saito "
-                         "divergence needs strictly positive data; leave such entries out of the mask)")
-    if not np.isfinite(highest):
-        raise ValueError("distance_type='is': an observed value is beyond the float32 range")
+    if vals.size:
+        losses.check_f32_image(vals, 'is', context='observed')
 
 
 def objective(x, w, h, mask, distance_type='eu', chunk=1 << 20):
@@ -134,8 +128,7 @@ def objective(x, w, h, mask, distance_type='eu', chunk=1 << 20):
         is  Sum_M [x / q - log(x / q) - 1],  q = wh + 1e-9       (every observed x must be > 0)
     With the training mask it is the objective `mur(x, k, mask=...)` records; with a held-out mask it scores the fit
     there."""
-    if distance_type not in ('eu', 'kl', 'is'):
-        raise KeyError('Distance type unknown: use "kl" or "eu"')
+    losses.check_loss(distance_type, ('eu', 'kl', 'is'))
     c = observed(x, mask)
     if distance_type == 'is':
         check_positive(c)
@@ -147,16 +140,5 @@ def objective(x, w, h, mask, distance_type='eu', chunk=1 << 20):
     for a in range(0, c.nnz, chunk):
         b = min(c.nnz, a + chunk)
         wh = np.einsum('ij,ji->i', w[rows[a:b]], h[:, cols[a:b]])
-        xa = xv[a:b]
-        if distance_type == 'eu':
-            s += 0.5 * float(np.sum((xa - wh) ** 2))
-        elif distance_type == 'is':
-            r = xa / (wh + 1e-9)
-            s += float(np.sum(r - np.log(r) - 1.0))
-        else:
-            with np.errstate(divide='ignore', invalid='ignore'):
-                t = xa * np.log(xa / wh)
-            t = np.where(t == np.inf, 0, t)
-            t = np.where(np.isnan(t), 0, t)
-            s += float(np.sum(t - xa + wh))
+        s += float(np.sum(losses.cells(distance_type, xv[a:b], wh)))
     return s

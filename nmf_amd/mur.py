@@ -10,16 +10,16 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib as L
+from . import losses
 from . import masked
 from . import sparse
 from . import utils
 from . import weighted
-from ._driver import Referee, Results, drive
+from ._driver import BATCH, NEVER, Referee, Results, run_loop
 from .engine import Engine
 
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h')
 BetaExperiment = namedtuple('Experiment', Experiment._fields + ('beta',))      # distance_type='beta' alone: one trailing field
-BETA_RANGE = (-1.0, 3.0)          # what float32 carries: q^(beta - 2) x at q = 1e-9
 
 
 def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5,
@@ -40,25 +40,23 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
     (nmf_amd.weighted; not together with mask= or engine=).  Returns Results(w, h, i, obj_history, experiment) with float64 w, h."""
     experiment = Experiment('mur', k, distance_type, nndsvd_init, max_iter, tol1, tol2,
                             lambda_w, lambda_h)
-    if distance_type not in ('eu', 'kl', 'is', 'beta'):
-        raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31
-    dist = {'eu': L.EU, 'kl': L.KL, 'is': L.IS, 'beta': L.BETA}[distance_type]
-    beta = check_beta(distance_type, beta)
+    losses.check_loss(distance_type)
+    dist = losses.CODES[distance_type]
+    beta = losses.check_beta(distance_type, beta)
+    loop = (lambda_w, lambda_h, min_iter, max_iter, tol1, tol2)
     if dist == L.BETA:
         experiment = BetaExperiment(*experiment, beta)
-        _check_beta_request(x, k, mask, beta)
+        check_beta_request(x, k, mask, beta)
     if weights is not None:
-        return _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h,
-                             nndsvd_init, device, engine, beta)
-    if dist == L.BETA:
-        _check_beta_input(x, beta)
+        return _mur_weighted(x, weights, mask, k, dist, experiment, loop, nndsvd_init, device, engine, beta)
     if dist == L.IS and mask is None:
-        _check_is_input(x, k)
+        check_is_request(x, k)
+    if dist == L.BETA or (dist == L.IS and mask is None):
+        losses.check_f32_image(x, distance_type, beta)         # (not lifted by its minimum, never modified)
     if mask is not None:
-        return _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init,
-                           device, engine)
+        return _mur_masked(x, mask, k, dist, experiment, loop, nndsvd_init, device, engine)
     if sparse.is_sparse(x):
-        return _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine)
+        return _mur_sparse(x, k, dist, experiment, loop, nndsvd_init, device, engine)
 
     # negative data is lifted IN PLACE on the caller's array (nmf/mur.py:99-101)
     lowest = np.min(x)
@@ -75,57 +73,32 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
         eng.set_factors(w0, h0)
         if dist == L.BETA:
             eng.set_beta(beta)
-        logging.info('Entering Main Loop.')
-        NEVER = 10 ** 15
         referee = None
         if distance_type == 'eu':                   # (the float64 objective kernel is the Euclidean one)
             referee = Referee(eng, lambda i: eng.mur_run(dist, lambda_w, lambda_h, NEVER, tol1, tol2, i, 1), min_iter, tol1, tol2)
-        i, history = drive(
-            eng,
-            lambda first, count: eng.mur_run(dist, lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
-            lambda done: eng.mur_finish(dist, NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=referee)
-        mur.last_referee = referee                  # diagnostic: guard in force, iterations walked with the float64 objective
-        w, h = eng.get_factors()
+        return _run(eng, dist, experiment, loop, referee)
+
+
+def _run(eng, dist, experiment, loop, referee=None):
+    """The iterations on an engine that is ready to run, and the Results."""
+    lambda_w, lambda_h, min_iter, max_iter, tol1, tol2 = loop
+    i, history = run_loop(eng, eng.mur_run, (dist, lambda_w, lambda_h), eng.mur_finish, (dist,), min_iter, max_iter, tol1, tol2,
+                          referee=referee)
+    mur.last_referee = referee                      # diagnostic: guard in force, iterations walked with the float64 objective
+    w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
 
 
-def _check_is_input(x, k):
-    """Itakura-Saito without a mask, checked before any device work: dense, strictly positive, k <= 128.  The data is
-    not lifted by its minimum (the loss is scale-invariant, not shift-invariant) and never modified."""
+def check_is_request(x, k):
+    """What Itakura-Saito without a mask runs on, checked before any device work: dense x, k <= 128."""
     if sparse.is_sparse(x):
         raise ValueError("distance_type='is': the zeros of a sparse matrix have infinite Itakura-Saito divergence; "
                          "pass mask= (for instance the matrix's own pattern) to fit the stored entries only")
     if int(k) > 128:
         raise ValueError(f"distance_type='is' supports k <= 128 components on dense input (got k = {k})")
-    # the device holds float32: a positive value that underflows to 0 there (or overflows to inf) is refused, not dropped
-    with np.errstate(over='ignore', under='ignore'):
-        lowest, highest = np.float32(np.min(x)), np.float32(np.max(x))
-    if not lowest > 0:                                          # (NaN included)
-        raise ValueError("distance_type='is': the data must be strictly positive in float32 (an entry is <= 0, NaN or "
-                         "below the float32 range); it is not lifted by its minimum")
-    if not np.isfinite(highest):
-        raise ValueError("distance_type='is': an entry is infinite or beyond the float32 range")
 
 
-def check_beta(distance_type, beta):
-    """beta= belongs to distance_type='beta' and to nothing else; returns it as a float (None for the other losses)."""
-    if distance_type != 'beta':
-        if beta is not None:
-            raise ValueError(f"beta= is the parameter of distance_type='beta' (got beta={beta!r} with distance_type={distance_type!r})")
-        return None
-    if beta is None:
-        raise ValueError("distance_type='beta' needs beta= (a number in [-1, 3]; 0, 1 and 2 are the IS, KL and Euclidean losses)")
-    try:
-        b = float(beta)
-    except (TypeError, ValueError):
-        raise ValueError(f"distance_type='beta': beta must be a real number (got beta={beta!r})") from None
-    if not np.isfinite(b) or not BETA_RANGE[0] <= b <= BETA_RANGE[1]:
-        raise ValueError(f"distance_type='beta': beta must be finite and lie in [-1, 3], the range float32 carries (got beta={beta!r})")
-    return b
-
-
-def _check_beta_request(x, k, mask, beta):
+def check_beta_request(x, k, mask, beta):
     """What distance_type='beta' runs on, checked before any device work: dense x, no mask=, k <= 128."""
     if mask is not None:
         raise ValueError(f"distance_type='beta' (beta={beta}): mask= is not supported; pass the 0 / 1 pattern as weights= "
@@ -137,30 +110,7 @@ def _check_beta_request(x, k, mask, beta):
         raise ValueError(f"distance_type='beta' (beta={beta}) supports k <= 128 components (got k = {k})")
 
 
-def _check_beta_input(x, beta):
-    """The beta-divergence without weights: _check_is_input's value checks, with "> 0" relaxed to ">= 0" for beta > 0 (a
-    zero is data there: d_beta(0 | q) = q^beta / beta).  Not lifted by its minimum, never modified."""
-    with np.errstate(over='ignore', under='ignore'):            # (the device holds float32: judge that image)
-        lowest, highest = np.float32(np.min(x)), np.float32(np.max(x))
-    if beta > 0:
-        if not lowest >= 0:                                     # (NaN included)
-            raise ValueError(f"distance_type='beta' (beta={beta}): the data must be non-negative (an entry is negative or NaN); "
-                             "it is not lifted by its minimum")
-        xa = np.asarray(x)
-        if xa.dtype != np.float32:                              # a zero is data, so a positive value must not underflow to one
-            for a in range(0, xa.shape[0], 1024):
-                blk = xa[a:a + 1024]
-                with np.errstate(under='ignore', over='ignore'):
-                    if np.any((blk > 0) & (blk.astype(np.float32) == 0)):
-                        raise ValueError(f"distance_type='beta' (beta={beta}): a positive entry is below the float32 range")
-    elif not lowest > 0:
-        raise ValueError(f"distance_type='beta' (beta={beta}): for beta <= 0 the data must be strictly positive in float32 (an "
-                         "entry is <= 0, NaN or below the float32 range); it is not lifted by its minimum")
-    if not np.isfinite(highest):
-        raise ValueError(f"distance_type='beta' (beta={beta}): an entry is infinite or beyond the float32 range")
-
-
-def _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine):
+def _mur_sparse(x, k, dist, experiment, loop, nndsvd_init, device, engine):
     """MUR on scipy.sparse input (kernels_sparse.hip): the caller's matrix is copied into canonical CSR and never modified.
     The recorded objective is evaluated in float64 from the non-zeros plus k x k terms, so the Euclidean stop rule needs
     no float64 referee here ("Sparse V")."""
@@ -170,18 +120,10 @@ def _mur_sparse(x, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w
     init = utils.initial_factors(xs, k, nndsvd_init)
     with Engine.for_sparse(xs, k, device=device) as eng:
         eng.set_factors(*init)
-        logging.info('Entering Main Loop.')
-        i, history = drive(
-            eng,
-            lambda first, count: eng.mur_run(dist, lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
-            lambda done: eng.mur_finish(dist, min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
-        mur.last_referee = None
-        w, h = eng.get_factors()
-    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+        return _run(eng, dist, experiment, loop)
 
 
-def _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init, device, engine):
+def _mur_masked(x, mask, k, dist, experiment, loop, nndsvd_init, device, engine):
     """Masked MUR (kernels_sparse.hip on a masked handle): the observed entries of x, stored zeros included, are the data;
     the rest is unknown.  Everything is validated before any device work; nothing of the caller's is modified.  Same start
     (the global RNG's draws as in mur; NNDSVD of x with the unobserved entries set to 0), Results, printed lines and batching
@@ -194,19 +136,10 @@ def _mur_masked(x, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, la
     init = utils.initial_factors(xs, k, nndsvd_init)
     with Engine.for_sparse(xs, k, device=device, masked=True) as eng:
         eng.set_factors(*init)
-        logging.info('Entering Main Loop.')
-        i, history = drive(
-            eng,
-            lambda first, count: eng.mur_run(dist, lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
-            lambda done: eng.mur_finish(dist, min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
-        mur.last_referee = None
-        w, h = eng.get_factors()
-    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+        return _run(eng, dist, experiment, loop)
 
 
-def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol1, tol2, lambda_w, lambda_h, nndsvd_init,
-                  device, engine, beta=None):
+def _mur_weighted(x, weights, mask, k, dist, experiment, loop, nndsvd_init, device, engine, beta=None):
     """MUR with per-entry weights (kernels_phase.hip on a dense handle, exact f32): Sum omega * loss(x, wh).  Everything
     is validated before any device work; nothing of the caller's is modified or lifted.  Same start as the masked path
     (the global RNG's draws as in mur; NNDSVD, unweighted and on the host, of x with the zero-weight cells set to 0),
@@ -218,21 +151,8 @@ def _mur_weighted(x, weights, mask, k, dist, experiment, min_iter, max_iter, tol
         raise ValueError('weights=: engine= is not supported (the engine is created for the weighted data)')
     x32, w32 = weighted.prepare(x, weights, k, experiment.distance_type, beta=beta)
     init = weighted_start(x, x32, w32, k, nndsvd_init)
-    with Engine(x32.shape[0], x32.shape[1], k, device=device) as eng:
-        eng.upload_v(x32)
-        eng.upload_weights(w32)
-        eng.set_factors(*init)
-        if dist == L.BETA:
-            eng.set_beta(beta)
-        logging.info('Entering Main Loop.')
-        i, history = drive(
-            eng,
-            lambda first, count: eng.mur_run(dist, lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
-            lambda done: eng.mur_finish(dist, min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
-        mur.last_referee = None
-        w, h = eng.get_factors()
-    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+    with Engine.for_phase(x32, k, init, weights=w32, beta=beta, device=device) as eng:
+        return _run(eng, dist, experiment, loop)
 
 
 def weighted_start(x, x32, w32, k, nndsvd_init):
@@ -284,7 +204,6 @@ def mur_pair(x, k, params, *, min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-
         eng.set_factors(w0, h0)
         logging.info('Entering Main Loop.')
         done, rules = 0, [0, 0]
-        from ._driver import BATCH
         while done < max_iter and not all(rules):
             count = min(BATCH, max_iter - done)
             eng.mur_pair_run(lws, lhs, min_iter, tol1, tol2, done, count)

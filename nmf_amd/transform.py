@@ -8,17 +8,15 @@ objective of (w, h_t), obj_history[0] that of the start.  Every loss of `mur` on
 'beta' with beta=, each with or without weights= -- for 1 <= k <= 128.  A step is one pass over x on the device
 (nmfx_foldin_run, kernels_phase.hip).  x is never lifted by its minimum and nothing of the caller's is modified.  A dense
 hold-out pattern is weights= with a 0 / 1 array; `nmf_amd.weighted.objective` scores the result under any weights."""
-import logging
 from collections import namedtuple
 
 import numpy as np
 
-from . import _lib as L
+from . import losses
 from . import sparse
 from . import weighted
-from ._driver import drive
+from ._driver import run_loop
 from .engine import Engine
-from .mur import _check_beta_input, _check_is_input, check_beta
 
 TransformResults = namedtuple('TransformResults', 'h i obj_history experiment')
 Experiment = namedtuple('Experiment', 'method components distance_type max_iter tol1 tol2 lambda_h')
@@ -31,7 +29,7 @@ def _check_factor(name, a, shape=None):
     a = np.asarray(a)
     if a.ndim != 2:
         raise ValueError(f'transform: {name} must be 2-D (got {a.ndim}-D)')
-    if a.dtype == object or not (np.issubdtype(a.dtype, np.number) or a.dtype == bool) or np.issubdtype(a.dtype, np.complexfloating):
+    if not losses.is_real(a):
         raise ValueError(f'transform: {name} must be a real array')
     if shape is not None and tuple(a.shape) != tuple(shape):
         raise ValueError(f'transform: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}')
@@ -41,15 +39,6 @@ def _check_factor(name, a, shape=None):
     if a.size and np.min(a) < 0:
         raise ValueError(f'transform: {name} has a negative entry')
     return a
-
-
-def _check_plain_input(x):
-    """'eu' and 'kl' without weights: finite and >= 0 in float32; a zero is data, so a positive value must not underflow to
-    one (the rules of mur._check_beta_input for beta > 0)."""
-    try:
-        _check_beta_input(x, 1.0)
-    except ValueError as e:
-        raise ValueError(str(e).replace("distance_type='beta' (beta=1.0)", 'transform')) from None
 
 
 def transform(x, w, *, distance_type='kl', beta=None, weights=None, h0=None, min_iter=100, max_iter=100000,
@@ -62,7 +51,7 @@ def transform(x, w, *, distance_type='kl', beta=None, weights=None, h0=None, min
     There is no mask= (a TypeError, like any unknown keyword): a dense 0 / 1 pattern is weights=."""
     if distance_type not in ('eu', 'kl', 'is', 'beta'):
         raise ValueError(f"transform: distance_type must be 'eu', 'kl', 'is' or 'beta' (got {distance_type!r})")
-    beta = check_beta(distance_type, beta)
+    beta = losses.check_beta(distance_type, beta)
     if sparse.is_sparse(x):
         raise TypeError('transform: scipy.sparse input is not supported; pass a dense array (a dense 0 / 1 hold-out '
                         'pattern is weights=)')
@@ -87,34 +76,19 @@ def transform(x, w, *, distance_type='kl', beta=None, weights=None, h0=None, min
         except TypeError as e:
             raise ValueError(f'transform: {e}') from None
     else:
-        if xa.dtype == object or not (np.issubdtype(xa.dtype, np.number) or xa.dtype == bool) or np.issubdtype(xa.dtype, np.complexfloating):
+        if not losses.is_real(xa):
             raise ValueError('transform: x must be a real array')
-        if distance_type == 'is':
-            _check_is_input(xa, k)
-        elif distance_type == 'beta':
-            _check_beta_input(xa, beta)
-        else:
-            _check_plain_input(xa)
+        # 'eu' and 'kl' are not lifted here: finite and >= 0 in float32, a zero is data, in transform's own name
+        losses.check_f32_image(xa, distance_type, beta, label='transform' if distance_type in ('eu', 'kl') else None)
         x32, w32 = xa, None
     experiment = Experiment('transform', k, distance_type, max_iter, tol1, tol2, lambda_h)
     if distance_type == 'beta':
         experiment = BetaExperiment(*experiment, beta)
     if h64 is None:
         h64 = np.abs(np.random.randn(k, n))
-    dist = {'eu': L.EU, 'kl': L.KL, 'is': L.IS, 'beta': L.BETA}[distance_type]
+    dist = losses.CODES[distance_type]
 
-    with Engine(m, n, k, device=device) as eng:
-        eng.upload_v(x32)
-        if w32 is not None:
-            eng.upload_weights(w32)
-        eng.set_factors(w64, h64)
-        if dist == L.BETA:
-            eng.set_beta(beta)
-        logging.info('Entering Main Loop.')
-        i, history = drive(
-            eng,
-            lambda first, count: eng.foldin_run(dist, lambda_h, min_iter, tol1, tol2, first, count),
-            lambda done: eng.foldin_finish(dist, min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
+    with Engine.for_phase(x32, k, (w64, h64), weights=w32, beta=beta, device=device) as eng:
+        i, history = run_loop(eng, eng.foldin_run, (dist, lambda_h), eng.foldin_finish, (dist,), min_iter, max_iter, tol1, tol2)
         _, h = eng.get_factors()
     return TransformResults(h=h, i=i, obj_history=history, experiment=experiment)

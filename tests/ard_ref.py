@@ -13,6 +13,7 @@ import numpy as np
 
 from beta_ref import _terms, beta_objective, gamma
 from oracle import nmf_ref as R
+from ref_loop import ref_loop
 
 
 def ard_c(shape, a):
@@ -78,19 +79,14 @@ def ard_mur(x, k, beta, phi, a, b, om=None, *, min_iter=100, max_iter=100000, to
         w, h = R.start_factors(xs, k, nndsvd_init, rng)
     else:
         w, h = w0.copy(), h0.copy()
-    lam = ard_lambda(w, h, a, b)
-    hist = [ard_objective(x, w, h, lam, beta, phi, a, b, om)]
-    trace = {"snap": {}, "stop_rule": 0}
-    i = -1
-    for i in range(max_iter):
-        w = ard_w_step(x, w, h, lam, beta, phi, om)
-        h = ard_h_step(x, w, h, lam, beta, phi, om)
-        lam = ard_lambda(w, h, a, b)
-        hist.append(ard_objective(x, w, h, lam, beta, phi, a, b, om))
-        if i > min_iter:
-            rule = R.stop_rule(hist[-1], hist[-2], tol1, tol2)
-            if rule:
-                trace["stop_rule"] = rule
-                break
-    trace["lam"] = lam
-    return R.Outcome(w, h, i, hist, trace)
+    lam = [ard_lambda(w, h, a, b)]                         # lambda travels with the pair: the H step leaves the next one
+
+    def h_step(w, h):
+        h = ard_h_step(x, w, h, lam[0], beta, phi, om)
+        lam[0] = ard_lambda(w, h, a, b)
+        return h
+
+    out = ref_loop(w, h, lambda w, h: ard_w_step(x, w, h, lam[0], beta, phi, om), h_step,
+                   lambda w, h: ard_objective(x, w, h, lam[0], beta, phi, a, b, om), min_iter, max_iter, tol1, tol2)
+    out.trace["lam"] = lam[0]
+    return out

@@ -16,6 +16,7 @@ Function shapes as tests/weighted_ref.py."""
 import numpy as np
 
 from oracle import nmf_ref as R
+from ref_loop import ref_loop
 
 EPS = 1e-9
 
@@ -91,16 +92,5 @@ def beta_mur(x, k, beta, om=None, *, min_iter=100, max_iter=100000, tol1=1e-5, t
         w, h = R.start_factors(_known(x, om)[0], k, nndsvd_init, rng)
     else:
         w, h = w0.copy(), h0.copy()
-    hist = [beta_objective(x, w, h, beta, om)]
-    trace = {"snap": {}, "stop_rule": 0}
-    i = -1
-    for i in range(max_iter):
-        w = beta_w_step(x, w, h, beta, lambda_w, om)
-        h = beta_h_step(x, w, h, beta, lambda_h, om)
-        hist.append(beta_objective(x, w, h, beta, om))
-        if i > min_iter:
-            rule = R.stop_rule(hist[-1], hist[-2], tol1, tol2)
-            if rule:
-                trace["stop_rule"] = rule
-                break
-    return R.Outcome(w, h, i, hist, trace)
+    return ref_loop(w, h, lambda w, h: beta_w_step(x, w, h, beta, lambda_w, om), lambda w, h: beta_h_step(x, w, h, beta, lambda_h, om),
+                    lambda w, h: beta_objective(x, w, h, beta, om), min_iter, max_iter, tol1, tol2)

@@ -12,6 +12,7 @@ hold NaN, inf or negative values)."""
 import numpy as np
 
 from oracle import nmf_ref as R
+from ref_loop import ref_loop
 
 EPS = 1e-9
 
@@ -72,16 +73,5 @@ def is_mur(x, k, m=None, *, min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5,
         w, h = R.start_factors(start, k, nndsvd_init, rng)
     else:
         w, h = w0.copy(), h0.copy()
-    hist = [is_objective(x, w, h, m)]
-    trace = {"snap": {}, "stop_rule": 0}
-    i = -1
-    for i in range(max_iter):
-        w = is_w_step(x, w, h, lambda_w, m)
-        h = is_h_step(x, w, h, lambda_h, m)
-        hist.append(is_objective(x, w, h, m))
-        if i > min_iter:
-            rule = R.stop_rule(hist[-1], hist[-2], tol1, tol2)
-            if rule:
-                trace["stop_rule"] = rule
-                break
-    return R.Outcome(w, h, i, hist, trace)
+    return ref_loop(w, h, lambda w, h: is_w_step(x, w, h, lambda_w, m), lambda w, h: is_h_step(x, w, h, lambda_h, m),
+                    lambda w, h: is_objective(x, w, h, m), min_iter, max_iter, tol1, tol2)

@@ -12,6 +12,7 @@ tests/test_masked_input.py)."""
 import numpy as np
 
 from oracle import nmf_ref as R
+from ref_loop import ref_loop
 
 
 def _observed(x, m):
@@ -75,16 +76,6 @@ def masked_mur(x, m, k, *, distance_type="kl", min_iter=100, max_iter=100000, to
         w, h = R.start_factors(_observed(x, m), k, nndsvd_init, rng)
     else:
         w, h = w0.copy(), h0.copy()
-    hist = [masked_objective(distance_type, x, m, w @ h)]
-    trace = {"snap": {}, "stop_rule": 0}
-    i = -1
-    for i in range(max_iter):
-        w = masked_w_step(distance_type, x, m, w, h, lambda_w)
-        h = masked_h_step(distance_type, x, m, w, h, lambda_h)
-        hist.append(masked_objective(distance_type, x, m, w @ h))
-        if i > min_iter:
-            rule = R.stop_rule(hist[-1], hist[-2], tol1, tol2)
-            if rule:
-                trace["stop_rule"] = rule
-                break
-    return R.Outcome(w, h, i, hist, trace)
+    return ref_loop(w, h, lambda w, h: masked_w_step(distance_type, x, m, w, h, lambda_w),
+                    lambda w, h: masked_h_step(distance_type, x, m, w, h, lambda_h),
+                    lambda w, h: masked_objective(distance_type, x, m, w @ h), min_iter, max_iter, tol1, tol2)

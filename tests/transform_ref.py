@@ -17,7 +17,7 @@ from beta_ref import beta_h_step, beta_objective
 from is_ref import is_h_step, is_objective
 from mur_step import objective as plain_objective
 from mur_step import ref_h
-from oracle import nmf_ref as R
+from ref_loop import ref_loop
 from weighted_ref import weighted_h_step, weighted_objective
 
 
@@ -48,15 +48,5 @@ def transform_ref(x, w, kind="kl", *, beta=None, om=None, h0=None, min_iter=100,
     w = np.asarray(w, dtype=np.float64)
     k, n = w.shape[1], np.asarray(x).shape[1]
     h = np.abs(rng.randn(k, n)) if h0 is None else np.array(h0, dtype=np.float64)
-    hist = [objective(kind, x, w, h, om, beta)]
-    trace = {"snap": {}, "stop_rule": 0}
-    i = -1
-    for i in range(max_iter):
-        h = h_step(kind, x, w, h, lambda_h, om, beta)
-        hist.append(objective(kind, x, w, h, om, beta))
-        if i > min_iter:
-            rule = R.stop_rule(hist[-1], hist[-2], tol1, tol2)
-            if rule:
-                trace["stop_rule"] = rule
-                break
-    return R.Outcome(w, h, i, hist, trace)
+    return ref_loop(w, h, None, lambda w, h: h_step(kind, x, w, h, lambda_h, om, beta),
+                    lambda w, h: objective(kind, x, w, h, om, beta), min_iter, max_iter, tol1, tol2)

@@ -16,6 +16,7 @@ mur_h_step and the IS rule (pinned by tests/test_weighted_input.py)."""
 import numpy as np
 
 from oracle import nmf_ref as R
+from ref_loop import ref_loop
 
 EPS = 1e-9
 
@@ -90,16 +91,6 @@ def weighted_mur(x, om, k, *, distance_type="kl", min_iter=100, max_iter=100000,
         w, h = R.start_factors(_known(x, om)[0], k, nndsvd_init, rng)
     else:
         w, h = w0.copy(), h0.copy()
-    hist = [weighted_objective(distance_type, x, om, w, h)]
-    trace = {"snap": {}, "stop_rule": 0}
-    i = -1
-    for i in range(max_iter):
-        w = weighted_w_step(distance_type, x, om, w, h, lambda_w)
-        h = weighted_h_step(distance_type, x, om, w, h, lambda_h)
-        hist.append(weighted_objective(distance_type, x, om, w, h))
-        if i > min_iter:
-            rule = R.stop_rule(hist[-1], hist[-2], tol1, tol2)
-            if rule:
-                trace["stop_rule"] = rule
-                break
-    return R.Outcome(w, h, i, hist, trace)
+    return ref_loop(w, h, lambda w, h: weighted_w_step(distance_type, x, om, w, h, lambda_w),
+                    lambda w, h: weighted_h_step(distance_type, x, om, w, h, lambda_h),
+                    lambda w, h: weighted_objective(distance_type, x, om, w, h), min_iter, max_iter, tol1, tol2)
