@@ -402,7 +402,7 @@ extern "C" int nmfx_mur_run_sharded(nmfx_handle_t E, int distance, double lambda
         // (kl_h_iter == j - 1), or rebuilds them.  The captured pair must make the choice the eager loop makes at that point,
         // or the replays would rebuild in every other iteration (slower, and another summation order): capture iteration "0" as
         // the successor of iteration "-1" when that holds now, and bring a reused graph's assumption about by an eager pair.
-        const bool klfresh = distance == NMFX_KL && E->kl_h_iter == j - 1;
+        const bool klfresh = distance == NMFX_KL && E->derived.kl_h_iter == j - 1;
         if (pairs > 0 && c->exec && c->g_klfresh && !klfresh) {
             for (int e = 0; e < 2; ++e, ++j) if ((rc = sharded_iteration(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, j, chunks))) return rc;
             pairs = (end - j) / 2;
@@ -413,12 +413,12 @@ extern "C" int nmfx_mur_run_sharded(nmfx_handle_t E, int distance, double lambda
                               c->g_t1 == tol1 && c->g_t2 == tol2 && c->g_chunks == chunks && c->g_hist == E->obj_hist &&
                               c->g_stream == E->stream && c->g_precision == E->precision && c->g_exchange == c->exchange;
             if (!same) {
-                const bool fresh_now = distance == NMFX_KL && E->kl_h_iter == j - 1;
-                if (fresh_now) E->kl_h_iter = -1;
+                const bool fresh_now = distance == NMFX_KL && E->derived.kl_h_iter == j - 1;
+                if (fresh_now) E->derived.kl_h_iter = -1;
                 if (capture_pair(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, chunks) != NMFX_OK) {
                     c->graph_failed = true;       // e.g. a collective that cannot be captured: the eager loop takes over for good
                     drop_graph(c);
-                    E->kl_h_iter = -2;
+                    E->derived.kl_h_iter = -2;
                 } else c->g_klfresh = fresh_now;
             }
             if (c->exec) {
@@ -427,7 +427,7 @@ extern "C" int nmfx_mur_run_sharded(nmfx_handle_t E, int distance, double lambda
                 c->replays += pairs;
                 j += 2 * pairs;
                 if ((rc = nmfx_shift_iteration_base(E, -j))) return rc;
-                E->kl_h_iter = (distance == NMFX_KL && E->kl_h_iter >= 0) ? j - 1 : -2;      // (the capture left the index of ITS second iteration)
+                E->derived.kl_h_iter = (distance == NMFX_KL && E->derived.kl_h_iter >= 0) ? j - 1 : -2;      // (the capture left the index of ITS second iteration)
             }
         }
     }

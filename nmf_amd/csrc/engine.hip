@@ -123,6 +123,34 @@ int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need) {
     return NMFX_OK;
 }
 
+// ---- the entry guard (nmfx_internal.h) ---------------------------
+int nmfx_enter(nmfx_engine* E, const nmfx_entry& a) {
+    if (!a.pre_after_bad) E->derived.drop(a.pre);
+    if (!E->have_v || !E->have_f) { E->err = E->sp ? "upload the CSR matrix and set factors first" : "upload V and set factors first"; return NMFX_E_STATE; }
+    if (!a.bad.empty() && !a.bad_last) { E->err = a.bad; return a.bad_rc; }
+    if (a.pre_after_bad) E->derived.drop(a.pre);
+    const bool pair = a.family == NMFX_FAM_MUR_PAIR;
+    const int fam = pair ? NMFX_FAM_MUR : a.family;
+    if (fam != NMFX_FAM_NONE) {
+        if (E->run.family && E->run.family != fam) {
+            E->err = "another solver has run on this handle since nmfx_set_factors: read the factors back and set them again "
+                     "(nmfx_get_factors, nmfx_set_factors) before a different solver continues from them";
+            return NMFX_E_STATE;
+        }
+        E->run.family = fam;
+    }
+    if (fam == NMFX_FAM_MUR) {                         // one k = 128 problem or two stacked ones: chosen at the start of the run
+        if (!pair && E->run.pair) { E->err = "this handle runs two stacked problems (nmfx_mur_pair_run): nmfx_set_factors before a single-problem run"; return NMFX_E_STATE; }
+        if (pair && !E->run.pair && E->run.started) { E->err = "pair mode cannot continue a run that was started as one k = 128 problem (nmfx_set_factors first)"; return NMFX_E_STATE; }
+        E->run.pair = pair;
+        E->run.started = true;
+    }
+    if (!a.bad.empty()) { E->err = a.bad; return a.bad_rc; }
+    E->derived.void_all_but(a.keep);
+    NMFX_HIP(hipSetDevice(E->device));
+    return nmfx_ensure_obj_capacity(E, pair ? 2 * (a.first + a.count) + 8 : a.first + a.count + 2);
+}
+
 extern "C" {
 
 int nmfx_version(void) { return 370; }      // 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
@@ -287,8 +315,9 @@ int nmfx_reset_stream(nmfx_handle_t E) {
 
 int nmfx_set_precision(nmfx_handle_t E, int mode) {
     NMFX_NOT_SPARSE(E);
-    if (E) { E->himg_both = false; E->wimg_ok = false; E->gxb_img_ready = false; }
     if (!E || (mode != 0 && mode != 1)) { if (E) E->err = "precision must be 0 (f32) or 1 (split bf16)"; return NMFX_E_ARG; }
+    // kept: what does not consist of bf16 images of the factors (the KL leftovers are tied to their iteration index instead)
+    E->derived.void_all_but(NMFX_D_kl_h_iter | NMFX_D_lazy_objective | NMFX_D_anls_a_ready | NMFX_D_kl_bt_ready | NMFX_D_ard_valid);
     if (E->precision != mode) nmfx_comm_invalidate(E);
     E->precision = mode;
     return NMFX_OK;
@@ -338,10 +367,10 @@ static int copy_rows_in(nmfx_engine* E, float* dst, const void* host, int dtype,
 
 int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int64_t row0, int64_t rows) {
     NMFX_NOT_SPARSE(E);
-    if (E) E->anls_a_ready = false;
     if (!E) return NMFX_E_ARG;
     if (!host || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
         E->err = "upload_v: bad row range or leading dimension"; return NMFX_E_ARG; }
+    E->derived.drop(NMFX_D_anls_a_ready);              // (products with V)
     NMFX_HIP(hipSetDevice(E->device));
     if (rows == 0) return NMFX_OK;
     if (E->have_v) { int rc_ = nmfx_need_v(E); if (rc_) return rc_; }       // (rows of a V whose row-major copy was dropped)
@@ -377,7 +406,7 @@ int nmfx_upload_weights(nmfx_handle_t E, const void* host, int dtype, int64_t ld
         E->Om = buf;
         if (E->note.find(WEIGHTS_NOTE) == std::string::npos) E->note += (E->note.empty() ? "" : "; ") + std::string(WEIGHTS_NOTE);
     }
-    E->anls_a_ready = false;
+    E->derived.drop(NMFX_D_anls_a_ready);
     if (rows == 0) return NMFX_OK;
     return copy_rows_in(E, E->Om + row0 * E->np, host, dtype, ld, rows, "upload_weights");
 }
@@ -389,6 +418,7 @@ int nmfx_clear_weights(nmfx_handle_t E) {
     NMFX_HIP(hipStreamSynchronize(E->stream));
     NMFX_HIP(hipFree(E->Om));
     E->Om = nullptr;
+    E->derived.drop(NMFX_D_anls_a_ready);
     const std::string w(WEIGHTS_NOTE);
     size_t at = E->note.find(w);
     if (at != std::string::npos) {
@@ -408,7 +438,7 @@ int nmfx_set_beta(nmfx_handle_t E, double beta) {
     if (!(beta >= -1.0 && beta <= 3.0)) { E->err = "set_beta: beta must lie in [-1, 3] (what f32 carries at q = 1e-9)"; return NMFX_E_ARG; }
     E->beta = beta;
     E->beta_set = true;
-    E->ard_valid = false;                              // (ARD stays set; its relevances are recomputed before the next run)
+    E->derived.drop(NMFX_D_ard_valid);                 // (ARD stays set; its relevances are recomputed before the next run)
     static const char* const BETA_NOTE = "the beta-divergence (NMFX_BETA) runs the exact-f32 kernels; the split-bf16 mode does not apply to it";
     if (E->note.find(BETA_NOTE) == std::string::npos) E->note += (E->note.empty() ? "" : "; ") + std::string(BETA_NOTE);
     return NMFX_OK;
@@ -426,22 +456,22 @@ int nmfx_set_ard(nmfx_handle_t E, double phi, double a, double b) {
     { int rc_ = nmfx_ard_alloc(E); if (rc_) return rc_; }
     E->ard_phi = phi; E->ard_a = a; E->ard_b = b;
     E->ard = true;
-    E->ard_valid = false;
+    E->derived.drop(NMFX_D_ard_valid);
     return NMFX_OK;
 }
 
 int nmfx_clear_ard(nmfx_handle_t E) {
     if (!E) return NMFX_E_ARG;
     E->ard = false;
-    E->ard_valid = false;
+    E->derived.drop(NMFX_D_ard_valid);
     return NMFX_OK;
 }
 
 // the relevances of (W, H) where they are not the current ones: at the start of a run, after nmfx_set_beta / nmfx_set_ard
 static int ard_ensure(nmfx_engine* E, const float* W) {
-    if (!E->ard || E->ard_valid) return NMFX_OK;
+    if (!E->ard || E->derived.ard_valid) return NMFX_OK;
     int rc = nmfx_ard_relevance(E, W, false);
-    if (!rc) E->ard_valid = true;
+    if (!rc) E->derived.ard_valid = true;
     return rc;
 }
 
@@ -452,8 +482,8 @@ int nmfx_get_relevance(nmfx_handle_t E, double* lambda_out) {
     if (!E->have_f) { E->err = "get_relevance: set factors first"; return NMFX_E_STATE; }
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
-    if (hs.flag && !E->w_in_place) E->wsel = (int)((hs.stop_i + 1) & 1);
-    if ((rc = ard_ensure(E, E->W[E->wsel]))) return rc;
+    if (hs.flag && !E->run.w_in_place) E->run.wsel = (int)((hs.stop_i + 1) & 1);
+    if ((rc = ard_ensure(E, E->W[E->run.wsel]))) return rc;
     NMFX_HIP(hipMemcpyAsync(lambda_out, E->ard_lam, (size_t)E->k * sizeof(double), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
     return NMFX_OK;
@@ -461,10 +491,10 @@ int nmfx_get_relevance(nmfx_handle_t E, double* lambda_out) {
 
 int nmfx_upload_v_device(nmfx_handle_t E, const void* dev, int dtype, int64_t ld, int64_t row0, int64_t rows) {
     NMFX_NOT_SPARSE(E);
-    if (E) E->anls_a_ready = false;
     if (!E) return NMFX_E_ARG;
     if (!dev || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
         E->err = "upload_v_device: bad row range or leading dimension"; return NMFX_E_ARG; }
+    E->derived.drop(NMFX_D_anls_a_ready);
     NMFX_HIP(hipSetDevice(E->device));
     if (rows == 0) return NMFX_OK;
     if (E->have_v) { int rc_ = nmfx_need_v(E); if (rc_) return rc_; }
@@ -532,20 +562,10 @@ int nmfx_set_factors(nmfx_handle_t E, const double* w, const double* hmat) {
     for (int i = 0; i < 10; ++i)
         if (zero[i]) NMFX_HIP(hipMemsetAsync(zero[i], 0, (size_t)zc[i] * 4, E->stream));
     hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, E->stream, E->state);
-    E->wsel = 0;
     E->have_f = true;
     E->bf_ready = false;
-    E->gxb_img_ready = false;
-    E->kl_h_iter = -2;
-    E->wimg_ok = false;
-    E->family = 0;
-    E->is_run = false;
-    E->pair = false;
-    E->family_started = false;
-    E->himg_both = false;
-    E->lazy_objective = false;
-    E->anls_a_ready = false;
-    E->ard_valid = false;
+    E->derived.void_all_but(NMFX_D_NONE);
+    E->run.reset();
     if (E->kp <= 128 && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
     NMFX_HIP(hipStreamSynchronize(E->stream));
     return NMFX_OK;
@@ -563,8 +583,8 @@ int nmfx_get_factors(nmfx_handle_t E, double* w, double* hmat) {
     if (E->sp) return nmfx_sparse_get_factors(E, w, hmat);
     DevState hs; int rc;
     if ((rc = read_state(E, &hs))) return rc;
-    if (hs.flag && !E->w_in_place) E->wsel = (int)((hs.stop_i + 1) & 1);
-    if (w) { if ((rc = get_padded(E, E->W[E->wsel], w, E->m, E->k, E->mp, E->kp))) return rc; }
+    if (hs.flag && !E->run.w_in_place) E->run.wsel = (int)((hs.stop_i + 1) & 1);
+    if (w) { if ((rc = get_padded(E, E->W[E->run.wsel], w, E->m, E->k, E->mp, E->kp))) return rc; }
     if (hmat) { if ((rc = get_padded(E, E->H, hmat, E->k, E->n, E->kp, E->np))) return rc; }
     return NMFX_OK;
 }
@@ -610,7 +630,7 @@ int nmfx_get_state(nmfx_handle_t E, int* stop_rule, int64_t* stop_i, int64_t* n_
     if (stop_i) *stop_i = hs.stop_i;
     if (n_obj) *n_obj = hs.n_obj;
     // the iterate the reference would return: W_{stop_i+1} once stopped
-    if (hs.flag && !E->w_in_place) E->wsel = (int)((hs.stop_i + 1) & 1);
+    if (hs.flag && !E->run.w_in_place) E->run.wsel = (int)((hs.stop_i + 1) & 1);
     return NMFX_OK;
 }
 
@@ -743,22 +763,21 @@ int nmfx_shift_iteration_base(nmfx_handle_t E, int64_t delta) {
 }
 
 // ---- MUR -------------------------------------------------------------------
-static int check_ready(nmfx_engine* E, int64_t first, int64_t count, bool mur_entry = true) {
-    E->anls_a_ready = false;                           // (another solver's products overwrite A_part)
-    if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-    if (mur_entry) {
-        int rc_ = nmfx_enter_family(E, 1); if (rc_) return rc_;
-        if (E->pair) { E->err = "this handle runs two stacked problems (nmfx_mur_pair_run): nmfx_set_factors before a single-problem run"; return NMFX_E_STATE; }
-        E->family_started = true;
-    }
-    if (first < 0 || count < 0) { E->err = "negative iteration range"; return NMFX_E_ARG; }
-    NMFX_HIP(hipSetDevice(E->device));
-    return nmfx_ensure_obj_capacity(E, first + count + 2);
+// What a MUR entry point keeps.  An iteration of the loss `distance`: the images of the k > 128 loop, and for KL the leftovers of
+// the H epilogue (the H images and row-sum partials of iteration j are good for the KL W phase of iteration j + 1 only if NOTHING
+// else has written H or those buffers in between: every other loss and every other solver voids them).  A closing step
+// changes no factor and keeps both; nmfx_mur_finish_b, which closes the runs of EVERY row-sharded solver, keeps all but the
+// ANLS products (its reduce goes through A_part's neighbours); the dense phase path keeps the relevances instead.
+static unsigned mur_keep(int distance) { return NMFX_D_gxb_img_ready | (distance == NMFX_KL ? NMFX_D_kl_h_iter : NMFX_D_NONE); }
+static const unsigned MUR_KEEP_CLOSING = NMFX_D_gxb_img_ready | NMFX_D_kl_h_iter;
+static const unsigned KEEP_FINISH_B = NMFX_D_ALL & ~NMFX_D_anls_a_ready;
+// (pre: a run-level or closing entry point has only ever voided the ANLS products before it asked; a phase voids all it does not keep)
+static int mur_enter(nmfx_engine* E, int64_t first, int64_t count, unsigned keep, int family = NMFX_FAM_MUR, unsigned pre = NMFX_D_anls_a_ready) {
+    nmfx_entry a = {family, first, count, keep, pre};
+    if (first < 0 || count < 0) { a.bad = "negative iteration range"; a.bad_last = true; }
+    return nmfx_enter(E, a);
 }
 
-// (kl_h_iter: the H images and row-sum partials the KL H epilogue of iteration j leaves for the KL W phase of iteration j + 1 are
-// only good if NOTHING else has written H or those buffers in between -- every entry point of another solver, and the
-// Euclidean MUR phases, void them; ADVICE r2: only nmfx_set_factors did)
 // The Itakura-Saito divergence (NMFX_IS) runs through nmfx_mur_run / nmfx_mur_finish only (dense k <= 128, masked sparse)
 static int refuse_is(nmfx_engine* E, const char* who) {
     E->err = std::string(who) + ": the Itakura-Saito divergence (IS) is available through nmfx_mur_run / nmfx_mur_finish only";
@@ -769,35 +788,30 @@ static int refuse_beta(nmfx_engine* E, const char* who) {
     E->err = std::string(who) + ": the beta-divergence (NMFX_BETA) is available through nmfx_mur_run / nmfx_mur_finish only";
     return NMFX_E_ARG;
 }
-#define NMFX_NO_IS(E, distance) do { if ((E) && (distance) == NMFX_IS) return refuse_is((E), __func__); \
-                                     if ((E) && (distance) == NMFX_BETA) return refuse_beta((E), __func__); } while (0)
+#define NMFX_EU_KL_ONLY(E, distance) do { if ((E) && (distance) == NMFX_IS) return refuse_is((E), __func__); \
+                                          if ((E) && (distance) == NMFX_BETA) return refuse_beta((E), __func__); } while (0)
+// First statements of every phase-level MUR entry point (a macro: the refusals name the entry point)
+#define NMFX_MUR_PHASE_ENTRY(E, distance) do { NMFX_DENSE_ONLY(E); NMFX_EU_KL_ONLY(E, distance); if (!(E)) return NMFX_E_ARG; } while (0)
+// ... and what follows them where the call is one step of iteration j of a Euclidean / KL run (the f64 referee applies again)
+static int mur_phase_enter(nmfx_engine* E, int64_t j, unsigned keep) {
+    E->run.mur_loss(NMFX_EU);
+    return mur_enter(E, j, 1, keep, NMFX_FAM_MUR, (NMFX_D_kl_h_iter | NMFX_D_himg_both | NMFX_D_anls_a_ready) & ~keep);
+}
+static bool mur_bf16(const nmfx_engine* E) { return E->precision == 1 && nmfx_bf16_supported(E); }
 
 int nmfx_mur_phase_a(nmfx_handle_t E, int distance, double lambda_w, int64_t j) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (E) E->himg_both = false;
-    if (!E) return NMFX_E_ARG;
-    if (distance != NMFX_KL) E->kl_h_iter = -2;
-    E->is_run = false;                                 // (a Euclidean / KL phase: the f64 referee applies again)
-    int rc = check_ready(E, j, 1); if (rc) return rc;
+    NMFX_MUR_PHASE_ENTRY(E, distance);
+    int rc = mur_phase_enter(E, j, mur_keep(distance)); if (rc) return rc;
     if (E->kp > 128 && (distance == NMFX_EU || distance == NMFX_KL)) return nmfx_generic_mur_phase_a(E, distance, lambda_w, j);
-    if (distance == NMFX_EU)
-        return (E->precision == 1 && nmfx_bf16_supported(E)) ? nmfx_mur_eu_phase_a_bf16(E, lambda_w, j)
-                                                             : nmfx_mur_eu_phase_a(E, lambda_w, j);
-    if (distance == NMFX_KL)
-        return (E->precision == 1 && nmfx_bf16_supported(E)) ? nmfx_mur_kl_phase_a_bf16(E, lambda_w, j)
-                                                             : nmfx_mur_kl_phase_a(E, lambda_w, j);
+    if (distance == NMFX_EU) return mur_bf16(E) ? nmfx_mur_eu_phase_a_bf16(E, lambda_w, j) : nmfx_mur_eu_phase_a(E, lambda_w, j);
+    if (distance == NMFX_KL) return mur_bf16(E) ? nmfx_mur_kl_phase_a_bf16(E, lambda_w, j) : nmfx_mur_kl_phase_a(E, lambda_w, j);
     E->err = "Unknown distance type."; return NMFX_E_ARG;
 }
 
 // Phase A in pieces (chunked exchange; Euclidean loss on the split-bf16 path only -- nmfx_mur_chunk_info says whether)
-static bool mur_chunkable(nmfx_engine* E, int distance) {
-    return distance == NMFX_EU && E->precision == 1 && nmfx_bf16_supported(E);
-}
+static bool mur_chunkable(nmfx_engine* E, int distance) { return distance == NMFX_EU && mur_bf16(E); }
 int nmfx_mur_chunk_info(nmfx_handle_t E, int distance, int64_t* unit, int64_t* n_padded, int64_t* k_padded) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (!E) return NMFX_E_ARG;
+    NMFX_MUR_PHASE_ENTRY(E, distance);
     const bool ok = mur_chunkable(E, distance);
     if (unit) *unit = ok ? 128 : 0;
     if (n_padded) *n_padded = E->np;
@@ -805,20 +819,13 @@ int nmfx_mur_chunk_info(nmfx_handle_t E, int distance, int64_t* unit, int64_t* n
     return NMFX_OK;
 }
 int nmfx_mur_phase_a_head(nmfx_handle_t E, int distance, double lambda_w, int64_t j) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (!E) return NMFX_E_ARG;
-    E->himg_both = false;
-    E->kl_h_iter = -2;
-    E->is_run = false;
-    int rc = check_ready(E, j, 1); if (rc) return rc;
+    NMFX_MUR_PHASE_ENTRY(E, distance);
+    int rc = mur_phase_enter(E, j, mur_keep(NMFX_EU)); if (rc) return rc;
     if (!mur_chunkable(E, distance)) { E->err = "phase_a_head: Euclidean loss on the split-bf16 path only (nmfx_mur_chunk_info)"; return NMFX_E_ARG; }
     return nmfx_mur_eu_phase_a_head_bf16(E, lambda_w, j);
 }
-int nmfx_mur_phase_a_cols(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (!E) return NMFX_E_ARG;
+int nmfx_mur_phase_a_cols(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {      // (a continuation of phase_a_head: no guard of its own)
+    NMFX_MUR_PHASE_ENTRY(E, distance);
     if (!mur_chunkable(E, distance)) { E->err = "phase_a_cols: Euclidean loss on the split-bf16 path only (nmfx_mur_chunk_info)"; return NMFX_E_ARG; }
     NMFX_HIP(hipSetDevice(E->device));
     return nmfx_mur_eu_phase_a_cols_bf16(E, c0, c1);
@@ -826,31 +833,21 @@ int nmfx_mur_phase_a_cols(nmfx_handle_t E, int distance, int64_t c0, int64_t c1)
 
 int nmfx_mur_phase_b(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1,
                      double tol2, int64_t j) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (E) E->himg_both = false;
-    if (!E) return NMFX_E_ARG;
-    if (distance != NMFX_KL) E->kl_h_iter = -2;
-    E->is_run = false;                                 // (a Euclidean / KL phase: the f64 referee applies again)
-    int rc = check_ready(E, j, 1); if (rc) return rc;
-    E->wsel = (int)((j + 1) & 1);
-    E->w_in_place = false;
+    NMFX_MUR_PHASE_ENTRY(E, distance);
+    int rc = mur_phase_enter(E, j, mur_keep(distance)); if (rc) return rc;
+    E->run.ping_pong(j);
     if (E->kp > 128 && (distance == NMFX_EU || distance == NMFX_KL)) return nmfx_generic_mur_phase_b(E, distance, lambda_h, min_iter, tol1, tol2, j);
     if (distance == NMFX_EU)
-        return (E->precision == 1 && nmfx_bf16_supported(E))
-                   ? nmfx_mur_eu_phase_b_bf16(E, lambda_h, min_iter, tol1, tol2, j)
-                   : nmfx_mur_eu_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
+        return mur_bf16(E) ? nmfx_mur_eu_phase_b_bf16(E, lambda_h, min_iter, tol1, tol2, j) : nmfx_mur_eu_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
     if (distance == NMFX_KL)
-        return (E->precision == 1 && nmfx_bf16_supported(E))
-                   ? nmfx_mur_kl_phase_b_bf16(E, lambda_h, min_iter, tol1, tol2, j)
-                   : nmfx_mur_kl_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
+        return mur_bf16(E) ? nmfx_mur_kl_phase_b_bf16(E, lambda_h, min_iter, tol1, tol2, j) : nmfx_mur_kl_phase_b(E, lambda_h, min_iter, tol1, tol2, j);
     E->err = "Unknown distance type."; return NMFX_E_ARG;
 }
 
 // Phase B by column slices (reduce-scatter / all-gather exchange, include/nmfx.h)
 int nmfx_mur_slice_info(nmfx_handle_t E, int distance, int world, int64_t* cols, int64_t* elems) {
     NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
+    NMFX_EU_KL_ONLY(E, distance);
     if (!E || world < 1) return NMFX_E_ARG;
     const bool ok = mur_chunkable(E, distance) && E->xworld == world && (E->np / 64) % world == 0;
     const int64_t c = ok ? E->np / world : 0;
@@ -865,32 +862,22 @@ static int slice_args(nmfx_engine* E, int distance, int64_t c0, int64_t c1, cons
 }
 int nmfx_mur_phase_b_slice(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t j,
                            int64_t c0, int64_t c1) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (!E) return NMFX_E_ARG;
-    E->himg_both = false;
-    E->kl_h_iter = -2;
-    E->is_run = false;
-    int rc = check_ready(E, j, 1); if (rc) return rc;
+    NMFX_MUR_PHASE_ENTRY(E, distance);
+    int rc = mur_phase_enter(E, j, mur_keep(NMFX_EU)); if (rc) return rc;
     if ((rc = slice_args(E, distance, c0, c1, "phase_b_slice"))) return rc;
-    E->wsel = (int)((j + 1) & 1);
-    E->w_in_place = false;
+    E->run.ping_pong(j);
     return nmfx_mur_eu_phase_b_slice_bf16(E, lambda_h, min_iter, tol1, tol2, j, (int)(c0 / 64), (int)((c1 - c0) / 64));
 }
-int nmfx_mur_phase_b_rest(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (!E) return NMFX_E_ARG;
+int nmfx_mur_phase_b_rest(nmfx_handle_t E, int distance, int64_t c0, int64_t c1) {      // (a continuation of phase_b_slice: no guard of its own)
+    NMFX_MUR_PHASE_ENTRY(E, distance);
     int rc = slice_args(E, distance, c0, c1, "phase_b_rest"); if (rc) return rc;
     NMFX_HIP(hipSetDevice(E->device));
     return nmfx_mur_eu_phase_b_rest_bf16(E, (int)(c0 / 64), (int)((c1 - c0) / 64));
 }
 
 int nmfx_mur_finish_a(nmfx_handle_t E, int distance, int64_t j) {
-    NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
-    if (!E) return NMFX_E_ARG;
-    int rc = check_ready(E, j, 1); if (rc) return rc;
+    NMFX_MUR_PHASE_ENTRY(E, distance);
+    int rc = mur_enter(E, j, 1, MUR_KEEP_CLOSING); if (rc) return rc;
     if (E->kp > 128 && (distance == NMFX_EU || distance == NMFX_KL)) return nmfx_generic_mur_finish_a(E, distance, j);
     if (distance == NMFX_EU) return nmfx_mur_eu_finish_a(E, j);
     if (distance == NMFX_KL) return nmfx_mur_kl_finish_a(E, j);
@@ -900,14 +887,14 @@ int nmfx_mur_finish_a(nmfx_handle_t E, int distance, int64_t j) {
 int nmfx_mur_finish_b(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t j) {
     NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
-    int rc = check_ready(E, j, 1, false); if (rc) return rc;       // (the closing step of EVERY row-sharded solver, not only MUR's)
+    int rc = mur_enter(E, j, 1, KEEP_FINISH_B, NMFX_FAM_NONE); if (rc) return rc;       // (the closing step of EVERY row-sharded solver, not only MUR's)
     return nmfx_finish_b(E, min_iter, tol1, tol2, j);
 }
 
 // IS on a dense handle: the tuned exact-f32 kernels of kernels_phase.hip, k <= 128, whatever the precision mode says
 static int is_dense_ok(nmfx_engine* E, const char* who) {
     if (E->kp > 128) { E->err = std::string(who) + ": the Itakura-Saito divergence (IS) needs k <= 128 on a dense handle"; return NMFX_E_ARG; }
-    if (E->precision == 1 && nmfx_bf16_supported(E) && E->note.find("Itakura-Saito") == std::string::npos)
+    if (mur_bf16(E) && E->note.find("Itakura-Saito") == std::string::npos)
         E->note += (E->note.empty() ? "" : "; ") + std::string("the Itakura-Saito divergence (IS) runs the exact-f32 kernels; the split-bf16 mode does not apply to it");
     return NMFX_OK;
 }
@@ -953,27 +940,26 @@ int nmfx_mur_run(nmfx_handle_t E, int distance, double lambda_w, double lambda_h
     { int rc_a = ard_request_ok(E, distance, lambda_w, lambda_h, "mur_run"); if (rc_a) return rc_a; }
     { int rc_p = dense_phase_path(E, distance, "mur_run", &dense_phase); if (rc_p) return rc_p; }
     if (dense_phase) {
-        int rc = check_ready(E, first, count); if (rc) return rc;
-        E->himg_both = false; E->kl_h_iter = -2;
-        E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
+        int rc = mur_enter(E, first, count, NMFX_D_ard_valid); if (rc) return rc;
+        E->run.mur_loss(distance);
         if ((rc = ard_ensure(E, E->W[first & 1]))) return rc;             // lambda_0, or the relevances a new beta voided
         for (int64_t j = first; j < first + count && !rc; ++j) {
             if ((rc = nmfx_mur_dense_phase_a(E, distance, lambda_w, j))) break;
-            E->wsel = (int)((j + 1) & 1);
-            E->w_in_place = false;
+            E->run.ping_pong(j);
             rc = nmfx_mur_dense_phase_b(E, distance, lambda_h, min_iter, tol1, tol2, j);
         }
         return rc;
     }
     if (E->sp) return nmfx_sparse_mur_run(E, distance, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
-    int rc = check_ready(E, first, count); if (rc) return rc;
-    E->is_run = false;
-    E->fused_pack = true;            // nothing is exchanged between the phases here
+    // (the guard of the run as a whole keeps what a closing step keeps: what the loss voids is up to the phases it goes through)
+    int rc = mur_enter(E, first, count, MUR_KEEP_CLOSING); if (rc) return rc;
+    E->run.mur_loss(NMFX_EU);
+    E->run.fused_pack = true;        // nothing is exchanged between the phases here
     for (int64_t j = first; j < first + count && !rc; ++j) {
         if ((rc = nmfx_mur_phase_a(E, distance, lambda_w, j))) break;
         rc = nmfx_mur_phase_b(E, distance, lambda_h, min_iter, tol1, tol2, j);
     }
-    E->fused_pack = false;
+    E->run.fused_pack = false;
     return rc;
 }
 
@@ -984,8 +970,8 @@ int nmfx_mur_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1
     if (E && (rc = ard_request_ok(E, distance, 0.0, 0.0, "mur_finish"))) return rc;
     if (E && (rc = dense_phase_path(E, distance, "mur_finish", &dense_phase))) return rc;
     if (dense_phase) {
-        if ((rc = check_ready(E, iters_done, 1))) return rc;
-        E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
+        if ((rc = mur_enter(E, iters_done, 1, MUR_KEEP_CLOSING | NMFX_D_ard_valid))) return rc;
+        E->run.mur_loss(distance);
         if ((rc = ard_ensure(E, E->W[iters_done & 1]))) return rc;
         if ((rc = nmfx_mur_dense_finish_a(E, distance, iters_done))) return rc;
         return E->ard ? nmfx_ard_finish_b(E, min_iter, tol1, tol2, iters_done) : nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
@@ -1008,31 +994,31 @@ static int foldin_ok(nmfx_engine* E, int distance, const char* who) {
     return NMFX_OK;
 }
 
-// W stays in the buffer that holds it (after nmfx_set_factors: W[0]); only H moves
-static const float* foldin_enter(nmfx_engine* E, int distance) {
-    E->himg_both = false; E->kl_h_iter = -2;
-    E->is_run = distance == NMFX_IS || distance == NMFX_BETA; E->beta_run = distance == NMFX_BETA;
-    E->w_in_place = true;
+// Both entry points: the refusals, the guard (H moves, nothing derived from it is kept), then W stays in the buffer that holds
+// it (after nmfx_set_factors: W[0]) -- *W
+static int foldin_enter(nmfx_engine* E, int distance, const char* who, int64_t first, int64_t count, const float** W) {
+    int rc;
+    if ((rc = foldin_ok(E, distance, who))) return rc;
+    if ((rc = mur_enter(E, first, count, NMFX_D_NONE))) return rc;
+    E->run.mur_loss(distance);
+    E->run.w_in_place = true;
     if (E->note.find(FOLDIN_NOTE) == std::string::npos) E->note += (E->note.empty() ? "" : "; ") + std::string(FOLDIN_NOTE);
-    return E->W[E->wsel];
+    *W = E->W[E->run.wsel];
+    return NMFX_OK;
 }
 
 int nmfx_foldin_run(nmfx_handle_t E, int distance, double lambda_h, int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
-    int rc;
-    if ((rc = foldin_ok(E, distance, "foldin_run"))) return rc;
-    if ((rc = check_ready(E, first, count))) return rc;
-    const float* W = foldin_enter(E, distance);
+    const float* W;
+    int rc = foldin_enter(E, distance, "foldin_run", first, count, &W);
     for (int64_t j = first; j < first + count && !rc; ++j) rc = nmfx_foldin_step(E, distance, lambda_h, min_iter, tol1, tol2, j, W);
     return rc;
 }
 
 int nmfx_foldin_finish(nmfx_handle_t E, int distance, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
     if (!E) return NMFX_E_ARG;
-    int rc;
-    if ((rc = foldin_ok(E, distance, "foldin_finish"))) return rc;
-    if ((rc = check_ready(E, iters_done, 1))) return rc;
-    const float* W = foldin_enter(E, distance);
+    const float* W;
+    int rc = foldin_enter(E, distance, "foldin_finish", iters_done, 1, &W); if (rc) return rc;
     if ((rc = nmfx_foldin_finish_a(E, distance, W))) return rc;
     return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
 }
@@ -1075,10 +1061,10 @@ int nmfx_profile_get(nmfx_handle_t E, const char* name, double* total_ms, int64_
 // every launch, which costs the W phase ~10 us that no real iteration pays.
 int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int reps, double* ms_per_launch) {
     NMFX_DENSE_ONLY(E);
-    NMFX_NO_IS(E, distance);
+    NMFX_EU_KL_ONLY(E, distance);
     if (!E || !which || reps <= 0 || !ms_per_launch) return NMFX_E_ARG;
     const std::string w(which);
-    int rc = check_ready(E, 0, 0, !(w.rfind("ao_", 0) == 0 || w.rfind("sk_", 0) == 0)); if (rc) return rc;
+    int rc = mur_enter(E, 0, 0, KEEP_FINISH_B, w.rfind("ao_", 0) == 0 || w.rfind("sk_", 0) == 0 ? NMFX_FAM_NONE : NMFX_FAM_MUR); if (rc) return rc;
     const bool wph = w == "wphase";
     // r4, the two V-sized products of AO-ADMM at k padded to 128 (after at least one nmfx_aoadmm_run on the handle, so that the images
     // and Gram slabs exist): "ao_hphase" / "ao_wphase" = the (row block) x (split) launches, "sk_hphase" / "sk_wphase" = the stream-K
@@ -1087,10 +1073,10 @@ int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int re
     if (ao && !(E->precision == 1 && E->kp == 128 && E->bf_ready && E->HThi)) { E->err = "profile_repeat: AO-ADMM products need a split-bf16 k = 128 run first"; return NMFX_E_STATE; }
     if (!ao && !wph && w != "hphase") { E->err = "profile_repeat: which must be wphase or hphase"; return NMFX_E_ARG; }
     if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
-    const bool bf = E->precision == 1 && nmfx_bf16_supported(E);
+    const bool bf = mur_bf16(E);
     const bool kl = distance == NMFX_KL;
     if (bf) {
-        if (!E->bf_ready) E->wsel = 0;
+        if (!E->bf_ready) E->run.wsel = 0;
         if ((rc = nmfx_bf16_prepare(E))) return rc;
         if (kl && (rc = nmfx_bf16_images_h(E, true))) return rc;          // H^T images: the Z operand of the KL H phase
     }
@@ -1106,9 +1092,9 @@ int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int re
             else rc = nmfx_bf16_sk_product(E, hside ? 0 : 1, hside, side ? (hside ? E->G_part : E->HHt_part) : nullptr, hside ? 64 : 32, -1.0,
                                            hside ? "hphase" : "wphase_noobj");
         }
-        else if (bf) rc = wph ? nmfx_bf16_vht(E, true, E->wsel, "wphase", kl, 3) : nmfx_bf16_vtw(E, false, "hphase", kl, 3);
+        else if (bf) rc = wph ? nmfx_bf16_vht(E, true, E->run.wsel, "wphase", kl, 3) : nmfx_bf16_vtw(E, false, "hphase", kl, 3);
         else if (kl) { E->err = "profile_repeat: KL only in the split-bf16 mode"; rc = NMFX_E_ARG; }
-        else rc = wph ? nmfx_launch_wphase(E, E->W[E->wsel], true, true) : nmfx_launch_hphase(E, E->W[E->wsel], nmfx_hphase_can_fuse_gram(E));
+        else rc = wph ? nmfx_launch_wphase(E, E->W[E->run.wsel], true, true) : nmfx_launch_hphase(E, E->W[E->run.wsel], nmfx_hphase_can_fuse_gram(E));
     }
     E->prof = was;
     if (rc) { hipEventDestroy(a); hipEventDestroy(b); return rc; }

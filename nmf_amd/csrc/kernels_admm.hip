@@ -201,8 +201,8 @@ static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double
     if ((rc = nmfx_bf16_kl_state(E, false))) return rc;
     // ---- h_aux = (w_aux^T w_aux + rho I)^-1 (w_aux^T S + rho (h + dual_h)) ----
     if ((rc = nmfx_bf16_images_w(E, E->auxW, 0))) return rc;           // (w_aux)^T images: Y
-    const bool have_bt = fuse && E->kl_bt_ready;                       // (left by the auxiliaries launch of the iteration before)
-    E->kl_bt_ready = false;
+    const bool have_bt = fuse && E->derived.kl_bt_ready;               // (left by the auxiliaries launch of the iteration before)
+    E->derived.drop(NMFX_D_kl_bt_ready);
     if (!have_bt && (rc = nmfx_bf16_kl_product(E, 0, 4, nullptr, E->kl_s_side != 0))) return rc;
     if (E->kp == 64 && !gather) rc = nmfx_bf16_pack_t(E, E->G_part, nmfx_bf16_g_slabs(E), nobj32);    // (the product's Gram by-product)
     else {
@@ -239,11 +239,10 @@ static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double
         E->kl_s_side = 1;
         if ((rc = nmfx_bf16_kl_orient(E, 0, false, true))) return rc;  // (kl_S[1] stays valid: the W-side product of the next iteration reads it)
     } else {
-        if (fuse) { if ((rc = nmfx_bf16_vaux_fused(E, 0, nullptr, nullptr, 0, true))) return rc; E->kl_bt_ready = true; }
+        if (fuse) { if ((rc = nmfx_bf16_vaux_fused(E, 0, nullptr, nullptr, 0, true))) return rc; E->derived.kl_bt_ready = true; }
         else if ((rc = nmfx_bf16_vaux(E, 0))) return rc;
         E->kl_s_side = 0;
     }
-    E->wimg_ok = false; E->himg_both = false;
     return admm_kl_objective_bf16(E);                                  // KL objective of (w, h) (admm.py:324)
 }
 
@@ -273,7 +272,7 @@ extern "C" int nmfx_prox_apply(nmfx_handle_t E, int side, int prox, double rho, 
     int rc;
     if ((rc = nmfx_small_k_only(E, "prox_apply"))) return rc;
     if ((rc = admm_alloc(E))) return rc;
-    E->wsel = 0; E->w_in_place = true;
+    E->run.in_place();
     return nmfx_launch_prox_l1inf(E, side == 1, prox == NMFX_PROX_L1INF_T, rho, lambda, 1.0, update_dual != 0);
 }
 
@@ -281,25 +280,21 @@ extern "C" int nmfx_prox_apply(nmfx_handle_t E, int side, int prox, double rho, 
 // with the objective partials of the initial pair (admm.py:289)
 static int admm_begin(nmfx_engine* E, int distance, double rho, int prox_w, int prox_h, int64_t first, int64_t count, bool whole_run = false) {
     if (!E) return NMFX_E_ARG;
-    E->anls_a_ready = false; E->kl_h_iter = -2;
-    E->himg_both = false;
-    if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-    if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown loss type."; return NMFX_E_ARG; }
+    // (ADMM rebuilds every image it reads; the slabs a fused auxiliaries launch left for the coming iteration are trusted inside
+    //  a call only, not across calls: nothing is kept)
+    nmfx_entry a = {NMFX_FAM_ADMM, first, count, NMFX_D_NONE, NMFX_D_anls_a_ready | NMFX_D_kl_h_iter | NMFX_D_himg_both};
     auto bad = [](int p) { return p != NMFX_PROX_NN && p != NMFX_PROX_L1N && p != NMFX_PROX_L2N && p != NMFX_PROX_L1INF && p != NMFX_PROX_L1INF_T; };
-    if (bad(prox_w) || bad(prox_h)) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
+    if (distance != NMFX_EU && distance != NMFX_KL) a.bad = "Unknown loss type.";
+    else if (bad(prox_w) || bad(prox_h)) a.bad = "Unknown prox_type.";
     // rho = 0 is a plain Gram solve in the reference (np.linalg.solve, admm.py:230); negative values make the shifted
     // system indefinite -- the elimination then reports "not positive definite" like any singular system
-    if (first < 0 || count < 0 || !(rho >= 0.0)) { E->err = "negative iteration range or rho"; return NMFX_E_ARG; }
-    NMFX_HIP(hipSetDevice(E->device));
-    int rc;
-    if ((rc = nmfx_enter_family(E, 3))) return rc;
+    else if (first < 0 || count < 0 || !(rho >= 0.0)) a.bad = "negative iteration range or rho";
+    int rc = nmfx_enter(E, a); if (rc) return rc;
     if ((rc = admm_alloc(E))) return rc;
     if (distance == NMFX_KL && (rc = nmfx_kl_state_alloc(E))) return rc;
     if ((prox_w == NMFX_PROX_L2N && !E->Pw) || (prox_h == NMFX_PROX_L2N && !E->Ph)) {
         E->err = "l2n prox needs nmfx_set_l2n_operator first"; return NMFX_E_STATE; }
-    if ((rc = nmfx_ensure_obj_capacity(E, first + count + 2))) return rc;
-    E->wsel = 0;
-    E->w_in_place = true;
+    E->run.in_place();
     if (first == 0 && count > 0) {
         NMFX_HIP(hipMemcpyAsync(E->auxW, E->W[0], (size_t)E->mp * E->kp * 4, hipMemcpyDeviceToDevice, E->stream));
         NMFX_HIP(hipMemcpyAsync(E->auxH, E->H, (size_t)E->kp * E->np * 4, hipMemcpyDeviceToDevice, E->stream));
@@ -339,7 +334,6 @@ extern "C" int nmfx_admm_run(nmfx_handle_t E, int distance, double rho, int prox
                              int64_t count) {
     NMFX_DENSE_ONLY(E);
     int rc = admm_begin(E, distance, rho, prox_w, prox_h, first, count, true); if (rc) return rc;
-    E->kl_bt_ready = false;    // (slabs a fused auxiliaries launch left for this iteration are not trusted across calls)
     if (E->kp > 128)           // composed from the generic product kernel (kernels_generic.hip)
         return nmfx_generic_admm_run(E, distance, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, first, count);
     for (int64_t j = first; j < first + count; ++j) {

@@ -627,7 +627,7 @@ static int anls_objective(nmfx_engine* E) {
     int rc;
     // distance_type = 'kl' (anls.py:108,118 + utils.py:21-26): the KL objective of the least-squares iterates,
     // by the exact-f32 objective pass in either arithmetic mode
-    E->anls_a_ready = false;
+    E->derived.drop(NMFX_D_anls_a_ready);
     if (E->anls_dist == NMFX_KL) return nmfx_launch_wphase(E, E->W[0], false, true, true);
     if (!anls_bf16(E)) return nmfx_launch_wphase(E, E->W[0], false, true);
     if ((rc = nmfx_bf16_prepare(E))) return rc;
@@ -639,7 +639,7 @@ static int anls_objective(nmfx_engine* E) {
     static const bool fuse = !(getenv("NMFX_ANLS_FUSE_OBJ") && atoi(getenv("NMFX_ANLS_FUSE_OBJ")) == 0);
     if (!fuse) return nmfx_bf16_objective(E, 1, "objective");
     if ((rc = nmfx_bf16_vht(E, true, 1, "wphase", false, 4))) return rc;
-    E->anls_a_ready = true;
+    E->derived.anls_a_ready = true;
     return NMFX_OK;
 }
 
@@ -651,11 +651,11 @@ static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, d
     if (anls_bf16(E)) {     // the same steps with the products on the split-bf16 kernels (kp = 64 / 128)
         const bool byprod = E->kp == 64;                                   // Gram matrices as by-products
         if ((rc = nmfx_bf16_prepare(E))) return rc;
-        if (!E->anls_a_ready) {                                            // (else: A_part and the H H^T slabs come from the objective pass)
+        if (!E->derived.anls_a_ready) {                                            // (else: A_part and the H H^T slabs come from the objective pass)
             if ((rc = nmfx_bf16_images_h(E, false))) return rc;
             if ((rc = nmfx_bf16_vht(E, false, 0, "wphase_noobj"))) return rc;
         }
-        E->anls_a_ready = false;
+        E->derived.drop(NMFX_D_anls_a_ready);          // (used up: the NNLS below moves W)
         if (!byprod && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
         if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, kk, E->HHt))) return rc;
         if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->bf_wsplit, E->mp * E->kp, E->Asum))) return rc;
@@ -696,27 +696,26 @@ static int anls_iteration(nmfx_engine* E, double lam_w, double lam_h, int64_t mi
     return anls_h(E, lam_h);
 }
 
-static int anls_ready(nmfx_engine* E, int64_t j, double lam) {
+// Every ANLS entry point: the guard, then the solver's own buffer.  Between ANLS calls the products of the fused objective pass
+// stay trusted (k <= 128; the generic loop beyond that keeps nothing); bad = a negative index, count or lambda
+static int anls_ready(nmfx_engine* E, int64_t first, int64_t count, bool bad, bool whole_run = false) {
     if (!E) return NMFX_E_ARG;
-    if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-    if (j < 0 || lam < 0) { E->err = "bad range or lambda"; return NMFX_E_ARG; }
-    { int rc_ = nmfx_enter_family(E, 4); if (rc_) return rc_; }      // (beyond 128 components the phases are composed from the generic kernels: r4)
-    NMFX_HIP(hipSetDevice(E->device));
-    if (!E->Asum) {
+    nmfx_entry a = {NMFX_FAM_ANLS, first, count, E->kp <= 128 ? NMFX_D_anls_a_ready : NMFX_D_NONE, NMFX_D_himg_both | NMFX_D_kl_h_iter};
+    if (bad) a.bad = "bad range or lambda";
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    if (!E->Asum && !(whole_run && E->kp > 128)) {     // (the summed V H^T; the generic loop beyond 128 components has its own scratch)
         NMFX_HIP(hipMalloc(reinterpret_cast<void**>(&E->Asum), (size_t)E->mp * E->kp * sizeof(float)));
         NMFX_HIP(hipMemsetAsync(E->Asum, 0, (size_t)E->mp * E->kp * sizeof(float), E->stream));
     }
-    E->wsel = 0;
-    E->w_in_place = true;
-    return nmfx_ensure_obj_capacity(E, j + 3);
+    E->run.in_place();
+    return NMFX_OK;
 }
 
 // ---- row-sharded form: objective partial -> [all-reduce f64] -> phase_w -> [all-reduce f32]
 // -> phase_h ----
 extern "C" int nmfx_anls_phase_objective(nmfx_handle_t E, int64_t j) {
     NMFX_DENSE_ONLY(E);
-    if (E) { E->himg_both = false; E->kl_h_iter = -2; }
-    int rc = anls_ready(E, j, 0.0); if (rc) return rc;
+    int rc = anls_ready(E, j, 1, j < 0); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_anls_phase(E, 0, 0.0, 0, 0.0, 0.0, j);
     if (j == 0 && (rc = anls_objective(E))) return rc;   // obj[0] partials
     return nmfx_launch_obj_reduce(E);
@@ -725,16 +724,14 @@ extern "C" int nmfx_anls_phase_objective(nmfx_handle_t E, int64_t j) {
 extern "C" int nmfx_anls_phase_w(nmfx_handle_t E, double lambda_w, int64_t min_iter, double tol1, double tol2,
                                  int64_t j) {
     NMFX_DENSE_ONLY(E);
-    if (E) { E->himg_both = false; E->kl_h_iter = -2; }
-    int rc = anls_ready(E, j, lambda_w); if (rc) return rc;
+    int rc = anls_ready(E, j, 1, j < 0 || lambda_w < 0); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_anls_phase(E, 1, lambda_w, min_iter, tol1, tol2, j);
     return anls_w_and_products(E, lambda_w, min_iter, tol1, tol2, j);
 }
 
 extern "C" int nmfx_anls_phase_h(nmfx_handle_t E, double lambda_h, int64_t j) {
     NMFX_DENSE_ONLY(E);
-    if (E) { E->himg_both = false; E->kl_h_iter = -2; }
-    int rc = anls_ready(E, j, lambda_h); if (rc) return rc;
+    int rc = anls_ready(E, j, 1, j < 0 || lambda_h < 0); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_anls_phase(E, 2, lambda_h, 0, 0.0, 0.0, j);
     return anls_h(E, lambda_h);
 }
@@ -743,34 +740,16 @@ extern "C" int nmfx_anls_set_distance(nmfx_handle_t E, int distance) {
     NMFX_NOT_SPARSE(E);
     if (!E || (distance != NMFX_EU && distance != NMFX_KL)) { if (E) E->err = "Unknown distance type."; return NMFX_E_ARG; }
     E->anls_dist = distance;
-    E->anls_a_ready = false;
+    E->derived.drop(NMFX_D_anls_a_ready);              // (the objective pass that leaves the products is the Euclidean one)
     return NMFX_OK;
 }
 
 extern "C" int nmfx_anls_run(nmfx_handle_t E, double lambda_w, double lambda_h, int64_t min_iter, double tol1,
                              double tol2, int64_t first, int64_t count) {
     NMFX_DENSE_ONLY(E);
-    if (E) { E->himg_both = false; E->kl_h_iter = -2; }
-    if (!E) return NMFX_E_ARG;
-    if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-    if (first < 0 || count < 0 || lambda_w < 0 || lambda_h < 0) { E->err = "bad range or lambda"; return NMFX_E_ARG; }
-    NMFX_HIP(hipSetDevice(E->device));
-    int rc;
-    if ((rc = nmfx_enter_family(E, 4))) return rc;
-    if (E->kp > 128) {         // one workgroup per right-hand side, systems in a global f64 work area (kernels_generic.hip)
-        if ((rc = nmfx_ensure_obj_capacity(E, first + count + 2))) return rc;
-        E->wsel = 0;
-        E->w_in_place = true;
-        E->anls_a_ready = false;
-        return nmfx_generic_anls_run(E, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
-    }
-    if (!E->Asum) {
-        NMFX_HIP(hipMalloc(reinterpret_cast<void**>(&E->Asum), (size_t)E->mp * E->kp * sizeof(float)));
-        NMFX_HIP(hipMemsetAsync(E->Asum, 0, (size_t)E->mp * E->kp * sizeof(float), E->stream));
-    }
-    if ((rc = nmfx_ensure_obj_capacity(E, first + count + 2))) return rc;
-    E->wsel = 0;
-    E->w_in_place = true;
+    int rc = anls_ready(E, first, count, first < 0 || count < 0 || lambda_w < 0 || lambda_h < 0, true); if (rc) return rc;
+    // beyond 128 components: one workgroup per right-hand side, systems in a global f64 work area (kernels_generic.hip)
+    if (E->kp > 128) return nmfx_generic_anls_run(E, lambda_w, lambda_h, min_iter, tol1, tol2, first, count);
     if (first == 0 && count > 0 && (rc = anls_objective(E))) return rc;   // obj[0]
     for (int64_t j = first; j < first + count; ++j)
         if ((rc = anls_iteration(E, lambda_w, lambda_h, min_iter, tol1, tol2, j))) return rc;

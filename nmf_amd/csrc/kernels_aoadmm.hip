@@ -1563,9 +1563,9 @@ static bool ao_bf16(const nmfx_engine* E) { return E->precision == 1 && nmfx_bf1
 static int ao_bf16_objective_product(nmfx_engine* E) {   // Bt_part, obj_part (and G_part for kp = 64) of the current pair
     int rc;
     if ((rc = nmfx_bf16_prepare(E))) return rc;
-    if (!E->wimg_ok && (rc = nmfx_bf16_images_w(E, E->W[0], 0))) return rc;       // (r3: the fused W-side launches leave them)
-    E->wimg_ok = true;
-    if (!E->himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;   // (the W side of the previous iteration built both)
+    if (!E->derived.wimg_ok && (rc = nmfx_bf16_images_w(E, E->W[0], 0))) return rc;       // (r3: the fused W-side launches leave them)
+    E->derived.wimg_ok = true;
+    if (!E->derived.himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;   // (the W side of the previous iteration built both)
     return nmfx_bf16_vtw(E, true, "hphase", false, 3);
 }
 
@@ -1597,15 +1597,15 @@ static int ao_h_products(nmfx_engine* E) {
 // objective partials of the pair the iteration has just produced (f32 path: a pass over V now;
 // bf16 path: nothing, the next H-side product or ao_final_objective computes it)
 static int ao_new_pair_objective(nmfx_engine* E) {
-    E->lazy_objective = ao_bf16(E);
-    if (E->lazy_objective) return NMFX_OK;
+    E->derived.lazy_objective = ao_bf16(E);
+    if (E->derived.lazy_objective) return NMFX_OK;
     return nmfx_launch_wphase(E, E->W[0], false, true);
 }
 
 // xf64[0] = objective partial of the current pair (end of a run)
 static int ao_final_objective(nmfx_engine* E) {
     int rc;
-    if (E->lazy_objective) {
+    if (E->derived.lazy_objective) {
         if ((rc = ao_bf16_objective_product(E))) return rc;
         return nmfx_launch_obj_reduce(E, (int64_t)(E->np / 128) * E->bt_split);
     }
@@ -1752,7 +1752,7 @@ static int ao_fused_subproblem(nmfx_engine* E, bool cols, float* W, int prox, fl
         }
         if (rc) { E->ao_images = false; return rc; }
     }
-    if (E->ao_images) { if (cols) E->himg_both = true; else E->wimg_ok = true; }
+    if (E->ao_images) { if (cols) E->derived.himg_both = true; else E->derived.wimg_ok = true; }
     E->ao_images = false;                              // (the row-sharded entry points launch the same kernels without images)
     return NMFX_OK;
 }
@@ -1813,7 +1813,7 @@ static int ao_h_solve(nmfx_engine* E, int prox_h, double lam_h, int admm_iter, i
                       double tol2, int64_t j) {
     int rc;
     if ((rc = nmfx_launch_prepare(E, E->xf32 + (int64_t)E->kp * E->np, 1, j, min_iter, tol1, tol2, -1.0))) return rc;
-    E->himg_both = false;                              // H changes below
+    E->derived.drop(NMFX_D_himg_both);                 // H changes below
     ProfScope ps(E, "inner_h");
     if (ao_is_l1inf(prox_h)) return ao_l1inf_subproblem(E, true, prox_h, lam_h, admm_iter, E->inner_hist + j * 2);
     if (ao_fused_enabled(E, admm_iter))
@@ -1828,7 +1828,7 @@ static int ao_w_products(nmfx_engine* E, int64_t j, int64_t min_iter, double tol
     E->ao_a_slabs = 0;
     if (ao_bf16(E)) {
         // the images of the H the sub-problem above produced (and of H^T, for the next H-side product): left by its fused launches, or built here
-        if (!E->himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;
+        if (!E->derived.himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;
         if ((rc = nmfx_bf16_vht(E, false, 0, "wphase_noobj", false, 3))) return rc;      // kp = 64: H H^T slabs as a by-product
         const bool byprod = E->kp == 64;
         int hslabs = E->gsplit;                        // k = 128: H H^T from the images just built (four-term split products, like W^T W)
@@ -1855,26 +1855,26 @@ static int aoadmm_eu_iteration_overlap(nmfx_engine* E, int prox_w, double lam_w,
     int rc;
     float* W = E->W[0];
     if ((rc = nmfx_bf16_prepare(E))) return rc;
-    if (!E->wimg_ok && (rc = nmfx_bf16_images_w(E, E->W[0], 0))) return rc;
-    E->wimg_ok = true;
-    if (!E->himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;
+    if (!E->derived.wimg_ok && (rc = nmfx_bf16_images_w(E, E->W[0], 0))) return rc;
+    E->derived.wimg_ok = true;
+    if (!E->derived.himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;
     int gslabs = 64;
     if ((rc = nmfx_bf16_gram_tn(E, &gslabs))) return rc;
     if ((rc = nmfx_bf16_sk_product(E, 0, true, E->G_part, gslabs, -1.0, "hphase"))) return rc;
     // the rounds of H sum the B^T slabs themselves; their first launch records obj[j] and applies the stop rule
     E->ao_b_src = E->sk[0].slabs; E->ao_b_cnt = E->sk[0].cnt; E->ao_rec_nobj = E->sk[0].nseg;
     E->ao_rec_j = j; E->ao_rec_min_iter = min_iter; E->ao_rec_tol1 = tol1; E->ao_rec_tol2 = tol2;
-    E->himg_both = false;                              // H changes below
+    E->derived.drop(NMFX_D_himg_both);                 // H changes below
     { ProfScope ps(E, "inner_h");
       rc = ao_fused_subproblem(E, true, nullptr, prox_h, (float)lam_h, admm_iter, E->inner_hist + j * 2, (int)(j & 1)); }
     E->ao_b_src = nullptr; E->ao_b_cnt = nullptr;
     if (rc) return rc;
-    if (!E->himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;
+    if (!E->derived.himg_both && (rc = nmfx_bf16_images_h(E, true))) return rc;
     int hslabs = 32;                                   // (HHt_part holds at least 40 slabs)
     if ((rc = nmfx_bf16_gram_h(E, &hslabs))) return rc;
     if ((rc = nmfx_bf16_sk_product(E, 1, false, E->HHt_part, hslabs, -1.0, "wphase_noobj"))) return rc;
     E->ao_a_slabs = E->sk[1].maxslab; E->ao_a_src = E->sk[1].slabs; E->ao_a_cnt = E->sk[1].cnt;
-    E->wimg_ok = false;                                // W changes below
+    E->derived.drop(NMFX_D_wimg_ok);                   // W changes below
     { ProfScope ps(E, "inner_w");
       rc = ao_fused_subproblem(E, false, W, prox_w, (float)lam_w, admm_iter, E->inner_hist + j * 2 + 1, (int)(j & 1)); }
     E->ao_a_slabs = 0; E->ao_a_src = nullptr; E->ao_a_cnt = nullptr;
@@ -1894,7 +1894,7 @@ static int aoadmm_eu_iteration(nmfx_engine* E, int prox_w, double lam_w, int pro
     if ((rc = ao_h_solve(E, prox_h, lam_h, admm_iter, min_iter, tol1, tol2, j))) return rc;
     // ---- W sub-problem: admm_ls_update(v.T, h.T, w.T, dual_w.T) ----
     if ((rc = ao_w_products(E, j, min_iter, tol1, tol2, ao_is_l1inf(prox_w) || !ao_fused_enabled(E, admm_iter)))) return rc;
-    E->wimg_ok = false;                                // W changes below
+    E->derived.drop(NMFX_D_wimg_ok);                   // W changes below
     if (ao_is_l1inf(prox_w)) {                         // (the summed right-hand side moves to Asum: auxW receives the aux matrix)
         ProfScope ps(E, "inner_w");
         if ((rc = nmfx_admm_state_alloc(E))) return rc;
@@ -1968,7 +1968,7 @@ static int ao_kl_objective(nmfx_engine* E) {
     int rc;
     if ((rc = nmfx_bf16_prepare(E))) return rc;
     if ((rc = nmfx_bf16_images_w(E, E->W[0], 0))) return rc;
-    E->wimg_ok = true;
+    E->derived.wimg_ok = true;
     if ((rc = nmfx_bf16_images_h(E, false))) return rc;
     return nmfx_bf16_kl_objective(E);
 }
@@ -1987,7 +1987,7 @@ static int aoadmm_kl_iteration_bf16(nmfx_engine* E, int prox_w, double lam_w, in
     // a transposed copy as before); only dual_v changes orientation between the sub-problems
     static const bool gather = !(getenv("NMFX_KL_GATHER") && atoi(getenv("NMFX_KL_GATHER")) == 0);
     if ((rc = nmfx_bf16_kl_orient(E, 0, true, !gather))) return rc;
-    if (!E->wimg_ok && (rc = nmfx_bf16_images_w(E, W, 0))) return rc;  // W^T images: Y of the products and of the auxiliaries (left by the objective pass)
+    if (!E->derived.wimg_ok && (rc = nmfx_bf16_images_w(E, W, 0))) return rc;  // W^T images: Y of the products and of the auxiliaries (left by the objective pass)
     // r5: the auxiliaries of round r also form the product of round r + 1 (S stays in registers; NMFX_KL_FUSE=0: separate launches).  At k padded to
     // 64 the products' Gram by-product (W^T W, H H^T) is that of round 0's launch: the slabs stay where they are, the fixed factor does not change
     static const bool fuse = !(getenv("NMFX_KL_FUSE") && atoi(getenv("NMFX_KL_FUSE")) == 0);
@@ -2035,7 +2035,7 @@ static int aoadmm_kl_iteration_bf16(nmfx_engine* E, int prox_w, double lam_w, in
     }
     if (admm_iter > 0) E->kl_s_side = 1;
     if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1))) return rc;
-    E->himg_both = false;
+    E->derived.drop(NMFX_D_himg_both);
     return ao_kl_objective(E);                                         // KL objective of the new pair (utils.py:21-26)
 }
 
@@ -2044,37 +2044,34 @@ extern "C" int nmfx_aoadmm_run(nmfx_handle_t E, int distance, int prox_w, double
                                int64_t first, int64_t count) {
     NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
-    if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-    if (distance != NMFX_EU && distance != NMFX_KL) { E->err = "Unknown loss function type."; return NMFX_E_ARG; }
     auto known = [](int p) { return p == NMFX_PROX_NN || p == NMFX_PROX_L1N || p == NMFX_PROX_L1INF || p == NMFX_PROX_L1INF_T; };
-    if (!known(prox_w) || !known(prox_h)) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     const bool any_l1inf = ao_is_l1inf(prox_w) || ao_is_l1inf(prox_h);
-    if (any_l1inf && E->kp > 128) {
-        E->err = "ao_admm with prox 'l1inf' / 'l1inf_transpose': at most 128 components in this build"; return NMFX_E_ARG; }
-    if (first < 0 || count < 0 || admm_iter < 0) { E->err = "negative range"; return NMFX_E_ARG; }
-    NMFX_HIP(hipSetDevice(E->device));
-    E->anls_a_ready = false; E->kl_h_iter = -2;
-    int rc;
-    if ((rc = nmfx_enter_family(E, 2))) return rc;
+    // (KL loss with 'l1inf*': the exact-f32 launches -- the operator's rounds read the f32 right-hand sides those leave; the runs
+    //  end after a few outer iterations anyway, in the reference's LinAlgError)
+    const bool kl_bf = distance == NMFX_KL && ao_kl_bf16(E) && !any_l1inf;
+    // Between nmfx_aoadmm_run calls the Euclidean loss trusts the images its fused launches left and the objective that rides on the
+    // next product; the KL loss the W images its objective pass left, unless that pass is about to run again or has not run
+    nmfx_entry a = {NMFX_FAM_AOADMM, first, count, distance == NMFX_EU ? NMFX_D_wimg_ok | NMFX_D_himg_both | NMFX_D_lazy_objective
+                                                   : kl_bf && (first == 0 || E->obj_count <= 0) ? NMFX_D_NONE : NMFX_D_wimg_ok,
+                    NMFX_D_anls_a_ready | NMFX_D_kl_h_iter};
+    a.pre_after_bad = true;
+    if (distance != NMFX_EU && distance != NMFX_KL) a.bad = "Unknown loss function type.";
+    else if (!known(prox_w) || !known(prox_h)) a.bad = "Unknown prox_type.";
+    else if (any_l1inf && E->kp > 128) a.bad = "ao_admm with prox 'l1inf' / 'l1inf_transpose': at most 128 components in this build";
+    else if (first < 0 || count < 0 || admm_iter < 0) a.bad = "negative range";
+    int rc = nmfx_enter(E, a); if (rc) return rc;
     if ((rc = nmfx_aoadmm_alloc(E))) return rc;
     if (distance == NMFX_KL && (rc = nmfx_kl_state_alloc(E))) return rc;
     if ((rc = nmfx_ensure_inner_capacity(E, first + count + 1))) return rc;
-    if ((rc = nmfx_ensure_obj_capacity(E, first + count + 2))) return rc;
-    E->wsel = 0;
-    E->w_in_place = true;
+    E->run.in_place();
     if (E->kp > 128)           // composed from the generic product kernel (kernels_generic.hip)
         return distance == NMFX_EU
             ? nmfx_generic_aoadmm_run(E, prox_w, lambda_w, prox_h, lambda_h, admm_iter, min_iter, tol1, tol2, first, count)
             : nmfx_generic_aoadmm_kl_run(E, prox_w, lambda_w, prox_h, lambda_h, admm_iter, min_iter, tol1, tol2, first, count);
-    if (distance != NMFX_EU) { E->lazy_objective = false; E->himg_both = false; }
-    // (KL loss with 'l1inf*': the exact-f32 launches -- the operator's rounds read the f32 right-hand sides those leave; the runs
-    //  end after a few outer iterations anyway, in the reference's LinAlgError)
-    const bool kl_bf = distance == NMFX_KL && ao_kl_bf16(E) && !any_l1inf;
     if (distance == NMFX_KL && any_l1inf) {
         if ((rc = nmfx_admm_state_alloc(E))) return rc;     // auxH / Asum of the "solve only" rounds
         if ((rc = ao_fused_alloc(E, admm_iter))) return rc; // bkX: X_prev
     }
-    if (kl_bf && (first == 0 || E->obj_count <= 0)) E->wimg_ok = false;
     if (first == 0 && count > 0 && !(distance == NMFX_EU && ao_bf16(E))) {   // obj[0] of the initial factors (ao_admm.py:256)
         if (kl_bf) rc = ao_kl_objective(E);
         else rc = nmfx_launch_wphase(E, E->W[0], false, true, distance == NMFX_KL);
@@ -2091,23 +2088,23 @@ extern "C" int nmfx_aoadmm_run(nmfx_handle_t E, int distance, int prox_w, double
 }
 
 // ---- row-sharded form (Euclidean loss) -----------------------------------------
-static int ao_sharded_ready(nmfx_engine* E, int64_t j, bool any_k = false) {
+// The phase calls keep the H images and the riding objective of the Euclidean loss between them and rebuild the W images themselves;
+// the KL phases (kl: they need the m x n auxiliaries too) keep nothing
+static int ao_sharded_ready(nmfx_engine* E, int64_t j, bool any_k = false, bool kl = false) {
     if (!E) return NMFX_E_ARG;
-    if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-    if (j < 0) { E->err = "negative iteration index"; return NMFX_E_ARG; }
-    NMFX_HIP(hipSetDevice(E->device));
-    E->anls_a_ready = false; E->kl_h_iter = -2;
-    E->wimg_ok = false; E->ao_images = false;          // (the phase entry points rebuild the W images themselves)
-    int rc;
+    nmfx_entry a = {NMFX_FAM_AOADMM, j, 1, kl ? NMFX_D_NONE : NMFX_D_himg_both | NMFX_D_lazy_objective,
+                    NMFX_D_anls_a_ready | NMFX_D_kl_h_iter | NMFX_D_wimg_ok};
+    a.pre_after_bad = true;
     // beyond 128 components (r4): the least-squares phases are composed from the generic kernels (kernels_generic.hip,
     // nmfx_generic_aoadmm_phase_*; r5: any number of components the handle takes); the fused W sub-problem stays at k <= 128
-    if (!any_k && (rc = nmfx_small_k_only(E, "row-sharded AO-ADMM with the speculative (fused) W rounds"))) return rc;
-    if ((rc = nmfx_enter_family(E, 2))) return rc;
+    if (j < 0) a.bad = "negative iteration index";
+    else if (!any_k && E->kp > 128) a.bad = nmfx_small_k_text("row-sharded AO-ADMM with the speculative (fused) W rounds");
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    E->ao_images = false;
     if ((rc = nmfx_aoadmm_alloc(E))) return rc;
+    if (kl && (rc = nmfx_kl_state_alloc(E))) return rc;
     if ((rc = nmfx_ensure_inner_capacity(E, j + 2))) return rc;
-    if ((rc = nmfx_ensure_obj_capacity(E, j + 3))) return rc;
-    E->wsel = 0;
-    E->w_in_place = true;
+    E->run.in_place();
     return NMFX_OK;
 }
 
@@ -2171,28 +2168,8 @@ extern "C" int nmfx_aoadmm_phase_w_close(nmfx_handle_t E, int admm_iter, int64_t
 //   then nmfx_aoadmm_kl_phase_w_close: bookkeeping + the KL objective partials of the new pair.
 // After the inner stop has fired the remaining rounds are no-ops on every rank (the decision is taken from replicated /
 // all-reduced numbers), their exchanges move stale buffers that nothing reads.
-static int ao_kl_sharded_ready(nmfx_engine* E, int64_t j) {
-    if (E && E->kp > 128) {                            // r5: beyond 128 components the phases are composed from the generic kernels (any k the handle takes)
-        if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-        if (j < 0) { E->err = "negative iteration index"; return NMFX_E_ARG; }
-        NMFX_HIP(hipSetDevice(E->device));
-        E->anls_a_ready = false; E->kl_h_iter = -2;
-        E->wimg_ok = false; E->ao_images = false;
-        int rc;
-        if ((rc = nmfx_enter_family(E, 2))) return rc;
-        if ((rc = nmfx_aoadmm_alloc(E))) return rc;
-        if ((rc = nmfx_kl_state_alloc(E))) return rc;
-        if ((rc = nmfx_ensure_inner_capacity(E, j + 2))) return rc;
-        if ((rc = nmfx_ensure_obj_capacity(E, j + 3))) return rc;
-        E->wsel = 0; E->w_in_place = true;
-        E->lazy_objective = false; E->himg_both = false;
-        return NMFX_OK;
-    }
-    int rc = ao_sharded_ready(E, j); if (rc) return rc;
-    if ((rc = nmfx_kl_state_alloc(E))) return rc;
-    E->lazy_objective = false; E->himg_both = false;
-    return NMFX_OK;
-}
+// (r5: beyond 128 components the KL phases are composed from the generic kernels, for any k the handle takes)
+static int ao_kl_sharded_ready(nmfx_engine* E, int64_t j) { return ao_sharded_ready(E, j, E && E->kp > 128, true); }
 static bool kl_prox_ok(int p) { return p == NMFX_PROX_NN || p == NMFX_PROX_L1N; }
 
 extern "C" int nmfx_aoadmm_kl_phase_h_products(nmfx_handle_t E, int64_t j, int round) {
@@ -2304,8 +2281,8 @@ extern "C" int nmfx_objective_partial(nmfx_handle_t E) {
     NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     NMFX_HIP(hipSetDevice(E->device));
-    if (E->kp > 128 && (E->family == 2 || E->family == 3)) return NMFX_OK;      // (the composed AO-ADMM / ADMM phases close every iteration with it: xf64[0] holds it)
-    if (E->kp > 128 && E->family == 4) return nmfx_generic_anls_phase(E, 0, 0.0, 0, 0.0, 0.0, 0);
+    if (E->kp > 128 && (E->run.family == 2 || E->run.family == 3)) return NMFX_OK;      // (the composed AO-ADMM / ADMM phases close every iteration with it: xf64[0] holds it)
+    if (E->kp > 128 && E->run.family == 4) return nmfx_generic_anls_phase(E, 0, 0.0, 0, 0.0, 0.0, 0);
     return ao_final_objective(E);
 }
 

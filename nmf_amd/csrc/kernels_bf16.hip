@@ -1843,7 +1843,7 @@ static int launch_xyt32_t(nmfx_engine* E, const float* X, int64_t ldx, int64_t R
         if (forced == 1 || (forced < 0 && small)) kern = xyt32_bf16_kernel<OBJ, TERMS, KL, KP, 1, true, WITH_A>;
     }
     if constexpr (OBJ && !KL && KP == 128 && TERMS == 3 && WITH_A) {
-        if (E->pair) kern = xyt32_bf16_kernel<OBJ, TERMS, KL, KP, 2>;     // two stacked problems: one objective each
+        if (E->run.pair) kern = xyt32_bf16_kernel<OBJ, TERMS, KL, KP, 2>;     // two stacked problems: one objective each
     }
     int rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm); if (rc) return rc;
     hipLaunchKernelGGL(kern, grid, block, shm, E->stream, X, ldx, Yhi, Ylo, ldy, Zhi, Zlo, Apart, E->obj_part,
@@ -1912,8 +1912,8 @@ int nmfx_bf16_kl_h_epilogue(nmfx_engine* E, float lam, int64_t j, int64_t min_it
                        E->xf32, E->xf64, E->H, E->np, E->kp, E->k, lam, (long long)j, (long long)min_iter, tol1, tol2,
                        E->state, E->obj_hist, E->Hhi, E->Hlo, E->HThi, E->HTlo, E->kl_part);
     NMFX_HIP(hipGetLastError());
-    E->himg_both = true;
-    E->kl_h_iter = j;
+    E->derived.himg_both = true;
+    E->derived.kl_h_iter = j;
     return NMFX_OK;
 }
 
@@ -1958,7 +1958,7 @@ int nmfx_bf16_prepare(nmfx_engine* E) {
         E->V = nullptr;
     }
     E->bf_ready = true;
-    if ((rc = nmfx_bf16_images_w(E, E->W[E->wsel], E->wsel))) return rc;
+    if ((rc = nmfx_bf16_images_w(E, E->W[E->run.wsel], E->run.wsel))) return rc;
     return nmfx_bf16_images_h(E, false);
 }
 
@@ -1975,7 +1975,7 @@ int nmfx_bf16_images_w(nmfx_engine* E, const float* W, int buf) {      // Whi/Wl
 int nmfx_bf16_images_h(nmfx_engine* E, bool transposed, const float* src) {   // Hhi/Hlo ([kp][np]) (+ HThi/HTlo ([np][kp])) of src (default H)
     ProfScope ps(E, "images");
     int rc;
-    E->himg_both = transposed && !src;
+    E->derived.himg_both = transposed && !src;
     if (transposed) {
         if ((rc = lazy_alloc(E, &E->HThi, (int64_t)E->kp * E->np))) return rc;
         if ((rc = lazy_alloc(E, &E->HTlo, (int64_t)E->kp * E->np))) return rc;
@@ -2567,7 +2567,7 @@ static int mur_eu_phase_b_bf16_k128(nmfx_engine* E, double lambda_h, int64_t min
 
 int nmfx_mur_eu_phase_a_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
     int rc;
-    if (!E->bf_ready) E->wsel = (int)(j & 1);   // the images of the current W are built from W[j & 1]
+    if (!E->bf_ready) E->run.wsel = (int)(j & 1);   // the images of the current W are built from W[j & 1]
     if ((rc = nmfx_bf16_prepare(E))) return rc;
     if (E->kp != 64) return mur_eu_phase_a_bf16_k128(E, lambda_w, j);
     const int cur = (int)(j & 1), nxt = cur ^ 1;
@@ -2582,14 +2582,14 @@ int nmfx_mur_eu_phase_a_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
     rc = launch_xyt(E, false, E->Vt, E->mp, E->np, (int)(E->mp / 64), E->bt_split, E->WThi, E->WTlo, E->mp,
                     nullptr, nullptr, E->Bt_part, E->G_part, "hphase", false, E->gram_ng_h, 3);
     if (rc) return rc;
-    if (E->fused_pack) return NMFX_OK;          // single GPU: h_update reads the slabs itself
+    if (E->run.fused_pack) return NMFX_OK;          // single GPU: h_update reads the slabs itself
     return nmfx_launch_pack_from(E, E->Bt_part, E->bt_split, E->G_part, nmfx_bf16_g_slabs(E), E->obj_count);
 }
 
 int nmfx_mur_eu_phase_b_bf16(nmfx_engine* E, double lambda_h, int64_t min_iter, double tol1, double tol2,
                              int64_t j) {
     if (E->kp != 64) return mur_eu_phase_b_bf16_k128(E, lambda_h, min_iter, tol1, tol2, j);
-    return launch_h_update_bf16<64>(E, E->fused_pack, (float)lambda_h, j, min_iter, tol1, tol2);
+    return launch_h_update_bf16<64>(E, E->run.fused_pack, (float)lambda_h, j, min_iter, tol1, tol2);
 }
 
 // Phase B in two parts for the reduce-scatter / all-gather exchange (r5): `slice` updates the column blocks
@@ -2666,7 +2666,7 @@ __global__ __launch_bounds__(256) void mur_pack_cols_kernel(
 
 int nmfx_mur_eu_phase_a_head_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
     int rc;
-    if (!E->bf_ready) E->wsel = (int)(j & 1);
+    if (!E->bf_ready) E->run.wsel = (int)(j & 1);
     if ((rc = nmfx_bf16_prepare(E))) return rc;
     const int cur = (int)(j & 1), nxt = cur ^ 1;
     if (E->kp != 64) {
@@ -2725,18 +2725,12 @@ int nmfx_mur_eu_phase_a_cols_bf16(nmfx_engine* E, int64_t c0, int64_t c1) {
 // fired keeps the iterate the reference returns while the other one goes on (see mur_w_update_bf16_kernel).
 static int pair_ready(nmfx_engine* E, int64_t first, int64_t count) {
     if (!E) return NMFX_E_ARG;
-    E->anls_a_ready = false; E->himg_both = false; E->kl_h_iter = -2;
-    if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
-    if (first < 0 || count < 0) { E->err = "negative iteration range"; return NMFX_E_ARG; }
-    if (E->kp != 128 || !(E->precision == 1 && nmfx_bf16_supported(E))) {
-        E->err = "pair mode needs a handle created with k = 128 (two problems of k <= 64) on the split-bf16 path"; return NMFX_E_STATE; }
-    if (E->xworld > 0 || E->comm) { E->err = "pair mode is a single-GPU form"; return NMFX_E_STATE; }
-    int rc;
-    if ((rc = nmfx_enter_family(E, 1))) return rc;
-    if (!E->pair && E->family_started) { E->err = "pair mode cannot continue a run that was started as one k = 128 problem (nmfx_set_factors first)"; return NMFX_E_STATE; }
-    E->pair = true; E->family_started = true;
-    NMFX_HIP(hipSetDevice(E->device));
-    return nmfx_ensure_obj_capacity(E, 2 * (first + count) + 8);
+    nmfx_entry a = {NMFX_FAM_MUR_PAIR, first, count, NMFX_D_NONE, NMFX_D_anls_a_ready | NMFX_D_himg_both | NMFX_D_kl_h_iter};      // (a Euclidean iteration on the k = 128 kernels keeps nothing)
+    if (first < 0 || count < 0) a.bad = "negative iteration range";
+    else if (E->kp != 128 || !(E->precision == 1 && nmfx_bf16_supported(E))) {
+        a.bad = "pair mode needs a handle created with k = 128 (two problems of k <= 64) on the split-bf16 path"; a.bad_rc = NMFX_E_STATE; }
+    else if (E->xworld > 0 || E->comm) { a.bad = "pair mode is a single-GPU form"; a.bad_rc = NMFX_E_STATE; }
+    return nmfx_enter(E, a);
 }
 
 __global__ __launch_bounds__(256) void pair_finalize_kernel(const double* __restrict__ osrc, int64_t nobj, long long j, long long min_iter,
@@ -2760,14 +2754,14 @@ __global__ __launch_bounds__(256) void pair_finalize_kernel(const double* __rest
 
 static int pair_iteration(nmfx_engine* E, const double* lw, const double* lh, int64_t min_iter, double tol1, double tol2, int64_t j) {
     int rc;
-    if (!E->bf_ready) E->wsel = (int)(j & 1);
+    if (!E->bf_ready) E->run.wsel = (int)(j & 1);
     if ((rc = nmfx_bf16_prepare(E))) return rc;
     const int cur = (int)(j & 1), nxt = cur ^ 1;
     const int64_t kk = (int64_t)E->kp * E->kp;
     const int64_t nobj = (int64_t)(E->mp / 128) * E->bf_wsplit;
     { ProfScope ps(E, "sum_hht");
       if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc; }
-    if ((rc = nmfx_bf16_vht(E, true, cur, "wphase", false, 3))) return rc;          // (E->pair: two objective partials per block)
+    if ((rc = nmfx_bf16_vht(E, true, cur, "wphase", false, 3))) return rc;          // (E->run.pair: two objective partials per block)
     { ProfScope ps(E, "w_update");
       constexpr int KP = 128;
       constexpr size_t shm = (size_t)(KP * (KP + 16) + 64 * (KP + 4)) * sizeof(float) + (size_t)2 * KP * 66 * sizeof(unsigned short);
@@ -2781,8 +2775,8 @@ static int pair_iteration(nmfx_engine* E, const double* lw, const double* lh, in
     if ((rc = nmfx_bf16_gram_tn(E, &gslabs))) return rc;
     if ((rc = nmfx_bf16_vtw(E, false, "hphase", false, 3))) return rc;
     if ((rc = nmfx_launch_pack_from(E, E->Bt_part, E->bt_split, E->G_part, gslabs, nobj))) return rc;
-    E->wsel = (int)((j + 1) & 1);
-    E->w_in_place = false;
+    E->run.wsel = (int)((j + 1) & 1);
+    E->run.w_in_place = false;
     { ProfScope ps(E, "h_update");
       constexpr int KP = 128;
       constexpr size_t shm = (size_t)(KP * (KP + 4) + KP * 80 + 64 * (KP + 4)) * sizeof(float);
@@ -2814,7 +2808,7 @@ extern "C" int nmfx_mur_pair_run(nmfx_handle_t E, const double* lambda_w, const 
 extern "C" int nmfx_mur_pair_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
     NMFX_DENSE_ONLY(E);
     int rc = pair_ready(E, iters_done, 1); if (rc) return rc;
-    if (!E->bf_ready) E->wsel = (int)(iters_done & 1);
+    if (!E->bf_ready) E->run.wsel = (int)(iters_done & 1);
     if ((rc = nmfx_bf16_prepare(E))) return rc;
     if ((rc = nmfx_bf16_vht(E, true, (int)(iters_done & 1), "wphase", false, 3))) return rc;      // (its A output is scratch here)
     hipLaunchKernelGGL(pair_finalize_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->obj_part,
@@ -2862,7 +2856,7 @@ extern "C" int nmfx_pair_get_factors(nmfx_handle_t E, int p, int k_p, double* w,
     if (E->kp != 128) { E->err = "pair_get_factors: handle was not created with k = 128"; return NMFX_E_STATE; }
     DevState hs; int rc;
     if ((rc = pair_state(E, &hs))) return rc;
-    const int buf = hs.pflag[p] ? (int)((hs.pstop_i[p] + 1) & 1) : E->wsel;
+    const int buf = hs.pflag[p] ? (int)((hs.pstop_i[p] + 1) & 1) : E->run.wsel;
     if (w) {
         std::vector<float> tmp((size_t)E->m * k_p);
         NMFX_HIP(hipMemcpy2DAsync(tmp.data(), (size_t)k_p * 4, E->W[buf] + 64 * p, (size_t)E->kp * 4, (size_t)k_p * 4, (size_t)E->m,

@@ -1154,7 +1154,7 @@ int gxb_prepare(nmfx_engine* E, const float* W, bool kl = false) {
         static const bool pretend = getenv("NMFX_GXB_NOFIT") != nullptr;          // (tests: take the fall back without filling the device)
         if (need && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (pretend || free_b < need + ((size_t)256 << 20))) {
             E->gxb_disabled = true;
-            E->gxb_img_ready = false;
+            E->derived.drop(NMFX_D_gxb_img_ready);
             nmfx_comm_invalidate(E);               // (a captured graph of a sharded run would replay the split-bf16 launches)
             char buf[256];
             snprintf(buf, sizeof buf, "%sk > 128: %.1f GiB free, the bf16 operand planes need %.1f GiB more: exact-f32 product kernel on this handle",
@@ -1181,10 +1181,10 @@ int gxb_prepare(nmfx_engine* E, const float* W, bool kl = false) {
         if ((rc = gxt_split(E, E->V, mp, np, true, E->gxb_v[0], E->gxb_v[1], true, E->gxb_v[2], E->gxb_v[3], false))) return rc;      // both TILED: V (contraction n), V^T (contraction m)
         E->gxb_v_ready = true;
     }
-    if (!E->gxb_img_ready) {
+    if (!E->derived.gxb_img_ready) {
         ProfScope ps(E, "images");
         if ((rc = gxb_images_w(E, W)) || (rc = gxb_images_h(E, E->H))) return rc;
-        E->gxb_img_ready = true;
+        E->derived.gxb_img_ready = true;
     }
     return NMFX_OK;
 }
@@ -1212,7 +1212,7 @@ int nmfx_generic_mur_phase_a(nmfx_engine* E, int distance, double lambda, int64_
     int rc;
     const bool kl = distance == NMFX_KL;
     if ((rc = gx_buffers(E, kl && !gxb_on(E)))) return rc;
-    if (!gxb_on(E)) E->gxb_img_ready = false;          // (exact-f32 iterations rewrite W and H without their images)
+    if (!gxb_on(E)) E->derived.drop(NMFX_D_gxb_img_ready);  // (exact-f32 iterations rewrite W and H without their images)
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
     const float* W = E->W[j & 1];
     float* Wn = E->W[(j + 1) & 1];
@@ -1296,7 +1296,7 @@ int nmfx_generic_mur_phase_a(nmfx_engine* E, int distance, double lambda, int64_
           if ((rc = nmfx_launch_sum_partials(E, E->gx_s, rb, kp, xS))) return rc; }
         return NMFX_OK;
     }
-    E->gxb_img_ready = false;                          // (the exact-f32 KL loop rewrites W and H without their images)
+    E->derived.drop(NMFX_D_gxb_img_ready);             // (the exact-f32 KL loop rewrites W and H without their images)
     { ProfScope ps(E, "objective");                    // Q = V / (W H + 1e-9) and the KL objective of the pair entering the iteration
       if ((rc = gx_launch<true, false>(E, GX_KLQ, W, kp, E->H, np, E->S, np, 0, mp, np, kp, 1, E->V, np, E->gx_part))) return rc; }
     if ((rc = nmfx_launch_obj_reduce(E, nblk, E->gx_part))) return rc;
@@ -1330,7 +1330,7 @@ int nmfx_generic_mur_phase_b(nmfx_engine* E, int distance, double lambda, int64_
     hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
                        E->state, E->obj_hist);
     NMFX_HIP(hipGetLastError());
-    if (!kl && gxb_on(E) && E->gxb_img_ready) {
+    if (!kl && gxb_on(E) && E->derived.gxb_img_ready) {
         // r4: the update and the images of the new H in one launch behind E = G H (element-wise, so H is updated in place)
         if ((rc = gx_launch<true, false>(E, GX_STORE, xG, kp, E->H, np, E->gx_d, np, 0, kp, np, kp, 1, nullptr, 0, nullptr))) return rc;
         GxUpd up;
@@ -1342,14 +1342,14 @@ int nmfx_generic_mur_phase_b(nmfx_engine* E, int distance, double lambda, int64_
         hipLaunchKernelGGL(gx_eu_update_kernel, dim3((unsigned)((c4 + 255) / 256)), dim3(256), 0, E->stream, (const float*)E->H, (const float*)xB,
                            (const float*)E->gx_d, (float)lambda, E->H, c4, (const int*)&E->state->flag);
         NMFX_HIP(hipGetLastError());
-        if (gxb_on(E) && E->gxb_img_ready &&           // (images of the new H for the next iteration's split-bf16 products)
+        if (gxb_on(E) && E->derived.gxb_img_ready &&           // (images of the new H for the next iteration's split-bf16 products)
             (rc = gxb_images_h(E, E->H))) return rc;
     } else {
         const int64_t cnt = kp * np;
         hipLaunchKernelGGL((gx_kl_update_kernel<true>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, E->stream, (const float*)E->H, (const float*)xB,
                            (const float*)xS, (float)lambda, E->H, kp, np, E->k, (const int*)&E->state->flag);
         NMFX_HIP(hipGetLastError());
-        if (gxb_on(E) && E->gxb_img_ready &&
+        if (gxb_on(E) && E->derived.gxb_img_ready &&
             (rc = gxb_images_h(E, E->H))) return rc;
     }
     NMFX_HIP(hipGetLastError());
@@ -1639,7 +1639,6 @@ int gx_objective_partial(nmfx_engine* E, bool bf = false) {      // 1/2 ||V - W 
 
 int nmfx_generic_aoadmm_run(nmfx_engine* E, int prox_w, double lam_w, int prox_h, double lam_h, int admm_iter, int64_t min_iter,
                             double tol1, double tol2, int64_t first, int64_t count) {
-    E->gxb_img_ready = false;                          // (this solver rewrites W and H without the images of the k > 128 MUR loop)
     int rc;
     if ((rc = gx_buffers(E, false))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
@@ -1653,7 +1652,7 @@ int nmfx_generic_aoadmm_run(nmfx_engine* E, int prox_w, double lam_w, int prox_h
     // terms as in the tuned AO-ADMM (kernels_bf16.hip, top); the Gram matrices, whose shifted inverse the rounds apply, stay exact f32
     bool bf = gxb_on(E);
     if (bf) { rc = gxb_prepare(E, W); if (rc == GXB_NOFIT) bf = false; else if (rc) return rc; }
-    E->gxb_img_ready = false;                          // (valid inside this call only: the MUR loop keeps the images of W[j & 1])
+    E->derived.drop(NMFX_D_gxb_img_ready);             // (valid inside this call only: the MUR loop keeps the images of W[j & 1])
     if (first == 0 && count > 0 && (rc = gx_objective_partial(E, bf))) return rc;      // obj[0] (ao_admm.py:256)
     for (int64_t j = first; j < first + count; ++j) {
         hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
@@ -1728,7 +1727,6 @@ __global__ void gx_decide_global_kernel(const double* __restrict__ n, DevState* 
 int nmfx_generic_aoadmm_phase(nmfx_engine* E, int phase, int prox, double lam, int admm_iter, int64_t min_iter, double tol1, double tol2,
                               int64_t j, int round) {
     int rc;
-    E->gxb_img_ready = false;
     if ((rc = gx_buffers(E, false))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
     if ((rc = gx_alloc(E, &E->gx_r, std::max(mp, np) * kp))) return rc;
@@ -1742,9 +1740,9 @@ int nmfx_generic_aoadmm_phase(nmfx_engine* E, int phase, int prox, double lam, i
     // have updated.  So they are (re)built from the factors at the head of every outer iteration (phase 0: whatever ran on this handle
     // before, the images are those of the current pair) and left alone in the other phases -- r4 rebuilt both factors' images in EVERY
     // phase call, the admm_iter W rounds of phase 3 included.  The planes of V and the buffers are made on first use.
-    if (phase != 0) E->gxb_img_ready = true;
+    if (phase != 0) E->derived.gxb_img_ready = true;
     if (bf) { rc = gxb_prepare(E, W); if (rc == GXB_NOFIT) bf = false; else if (rc) return rc; }
-    E->gxb_img_ready = false;
+    E->derived.drop(NMFX_D_gxb_img_ready);
     switch (phase) {
     case 0:
         if (j == 0 && (rc = gx_objective_partial(E, bf))) return rc;              // obj[0] (ao_admm.py:256)
@@ -1922,7 +1920,6 @@ int gx_admm_prox(nmfx_engine* E, bool hside, int prox, double rho, double lam) {
 
 int nmfx_generic_aoadmm_kl_run(nmfx_engine* E, int prox_w, double lam_w, int prox_h, double lam_h, int admm_iter, int64_t min_iter,
                                double tol1, double tol2, int64_t first, int64_t count) {
-    E->gxb_img_ready = false;                          // (this solver rewrites W and H without the images of the k > 128 MUR loop)
     int rc;
     if ((rc = gx_admm_buffers(E))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
@@ -1957,7 +1954,6 @@ int nmfx_generic_aoadmm_kl_run(nmfx_engine* E, int prox_w, double lam_w, int pro
 //   4 w_close:          the decision of the last round, bookkeeping, the KL objective partial of the new pair -> xf64[0]
 int nmfx_generic_aoadmm_kl_phase(nmfx_engine* E, int phase, int prox, double lam, int admm_iter, int64_t min_iter, double tol1, double tol2,
                                  int64_t j, int round) {
-    E->gxb_img_ready = false;
     int rc;
     if ((rc = gx_admm_buffers(E))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
@@ -2038,7 +2034,6 @@ int nmfx_generic_aoadmm_kl_phase(nmfx_engine* E, int phase, int prox, double lam
 //             operators, the duals and v_aux row-local), and the objective partial of the new (w, h) -> xf64[0]
 struct GxAdmm { bool kl, bf; const float* data; float *xB, *xG; };
 static int gx_admm_setup(nmfx_engine* E, int distance, int prox_w, int prox_h, GxAdmm* c) {
-    E->gxb_img_ready = false;                          // (this solver rewrites W and H without the images of the k > 128 MUR loop)
     int rc;
     if ((rc = gx_admm_buffers(E))) return rc;
     c->kl = distance == NMFX_KL;
@@ -2049,7 +2044,7 @@ static int gx_admm_setup(nmfx_engine* E, int distance, int prox_w, int prox_h, G
     // systems carry the caller's fixed rho, kernels_bf16.hip top), the objective's W H from the images of (w, h) (three terms)
     c->bf = !c->kl && gxb_on(E);
     if (c->bf) { rc = gxb_prepare(E, E->W[0]); if (rc == GXB_NOFIT) c->bf = false; else if (rc) return rc; }
-    E->gxb_img_ready = false;
+    E->derived.drop(NMFX_D_gxb_img_ready);
     return NMFX_OK;
 }
 
@@ -2328,7 +2323,6 @@ int gx_nnls(nmfx_engine* E, const float* G, double diag_add, const float* R, flo
 // ANLS outer iterations (anls.py:111-126): rows of W from G = H H^T + 2 lw I, r = rows of V H^T; columns of H from G = W^T W + 2 lh I,
 // r = columns of W^T V; the objective (Euclidean or KL, E->anls_dist) of the new pair
 int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count) {
-    E->gxb_img_ready = false;                          // (this solver rewrites W and H without the images of the k > 128 MUR loop)
     int rc;
     if ((rc = gx_buffers(E, false))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
@@ -2341,7 +2335,7 @@ int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t mi
     // whose conditioning decides the active sets, and the KL objective stay exact f32
     bool bf = gxb_on(E) && gx_anls_bf16();
     if (bf) { rc = gxb_prepare(E, W); if (rc == GXB_NOFIT) bf = false; else if (rc) return rc; }
-    E->gxb_img_ready = false;                          // (valid inside this call only)
+    E->derived.drop(NMFX_D_gxb_img_ready);             // (valid inside this call only)
     if (first == 0 && count > 0 && (rc = kl ? gx_kl_objective_partial(E) : gx_objective_partial(E, bf))) return rc;     // obj[0] (anls.py:108)
     for (int64_t j = first; j < first + count; ++j) {
         hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
@@ -2374,7 +2368,6 @@ int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t mi
 // 1 obj[j] + stop rule, H H^T (replicated), V H^T and the NNLS rows of W (rank-local), then [W^T V | W^T W] of the rank's rows into
 // the f32 exchange buffer; 2 the NNLS columns of H from the all-reduced sums (replicated)
 int nmfx_generic_anls_phase(nmfx_engine* E, int phase, double lam, int64_t min_iter, double tol1, double tol2, int64_t j) {
-    E->gxb_img_ready = false;
     int rc;
     if ((rc = gx_buffers(E, false))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
@@ -2405,8 +2398,8 @@ int nmfx_generic_anls_phase(nmfx_engine* E, int phase, double lam, int64_t min_i
 extern "C" int nmfx_objective_f64(nmfx_handle_t E, double* out) {
     if (!E || !out) { if (E) E->err = "objective_f64: out is NULL"; return NMFX_E_ARG; }
     if (E->Om) { E->err = "objective_f64: evaluates the unweighted Euclidean objective; not available while per-entry weights are present (nmfx_upload_weights; nmfx_clear_weights removes them)"; return NMFX_E_ARG; }
-    if (E->is_run && E->beta_run) { E->err = "objective_f64: evaluates the Euclidean objective; not available while the handle runs the beta-divergence (NMFX_BETA)"; return NMFX_E_ARG; }
-    if (E->is_run) { E->err = "objective_f64: evaluates the Euclidean objective; not available while the handle runs the Itakura-Saito divergence (IS)"; return NMFX_E_ARG; }
+    if (E->run.loss == NMFX_LOSS_BETA) { E->err = "objective_f64: evaluates the Euclidean objective; not available while the handle runs the beta-divergence (NMFX_BETA)"; return NMFX_E_ARG; }
+    if (E->run.loss == NMFX_LOSS_IS) { E->err = "objective_f64: evaluates the Euclidean objective; not available while the handle runs the Itakura-Saito divergence (IS)"; return NMFX_E_ARG; }
     if (E->sp) return nmfx_sparse_objective_f64(E, out);
     if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
     NMFX_HIP(hipSetDevice(E->device));
@@ -2414,7 +2407,7 @@ extern "C" int nmfx_objective_f64(nmfx_handle_t E, double* out) {
     if ((rc = nmfx_need_v(E))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp, nblk = (mp / GX_T) * (np / GX_T);
     if ((rc = gx_alloc(E, &E->gx_part, nblk + 64))) return rc;
-    const float* W = E->W[E->wsel];
+    const float* W = E->W[E->run.wsel];
     hipLaunchKernelGGL(gx_resid64_kernel, dim3((unsigned)(np / GX_T), (unsigned)(mp / GX_T)), dim3(256), 0, E->stream, W, kp, (const float*)E->H, np, kp,
                        (const float*)E->V, np, E->gx_part);
     hipLaunchKernelGGL(gx_sum64_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_part, nblk, E->gx_part + nblk);

@@ -366,7 +366,7 @@ static int launch_h_row_sums(nmfx_engine* E) {
 
 int nmfx_mur_kl_phase_a_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
     int rc;
-    if (!E->bf_ready) E->wsel = (int)(j & 1);
+    if (!E->bf_ready) E->run.wsel = (int)(j & 1);
     if ((rc = nmfx_bf16_prepare(E))) return rc;
     const int cur = (int)(j & 1), nxt = cur ^ 1;
     const float* Wold = E->W[cur];
@@ -374,7 +374,7 @@ int nmfx_mur_kl_phase_a_bf16(nmfx_engine* E, double lambda_w, int64_t j) {
     // the images of H in both layouts and b = 1 H^T (HHt is unused by KL; its first kp floats hold the sums): left by the
     // H epilogue of iteration j - 1 (images as they are, the sums as partials: one small launch), or built from H itself
     // (first iteration, new factors, another solver in between)
-    const bool fresh = E->kl_part && E->kl_h_iter == j - 1;
+    const bool fresh = E->kl_part && E->derived.kl_h_iter == j - 1;
     if (!fresh && (rc = nmfx_bf16_images_h(E, true))) return rc;
     if (fresh) {
         ProfScope ps(E, "row_sums");

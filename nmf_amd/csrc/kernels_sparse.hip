@@ -657,7 +657,7 @@ static int sp_iteration(nmfx_engine* E, int loss, double lw, double lh, int64_t 
     if (!S->masked) {
       ProfScope ps(E, "sp_stats");
       if ((rc = launch_stats<KP>(E, S->Ht, E->n, 1, flag))) return rc; }
-    E->wsel = (int)((j + 1) & 1);
+    E->run.wsel = (int)((j + 1) & 1);
     return NMFX_OK;
 }
 
@@ -673,17 +673,14 @@ static int sp_objective_pass(nmfx_engine* E, int loss, const float* W, const int
                      default: rc = call<256>; break; }
 
 static int sp_ready(nmfx_engine* E, int distance, int64_t first, int64_t count) {
-    if (!E->have_v || !E->have_f) { E->err = "upload the CSR matrix and set factors first"; return NMFX_E_STATE; }
-    if (distance == NMFX_IS && !E->sp->masked) {
-        E->err = "the Itakura-Saito divergence (IS) is infinite at the zeros of an unmasked sparse V: make the handle masked (nmfx_set_masked)";
-        return NMFX_E_ARG;
-    }
-    if (distance != NMFX_EU && distance != NMFX_KL && distance != NMFX_IS) { E->err = "Unknown distance type."; return NMFX_E_ARG; }
-    if (first < 0 || count < 0) { E->err = "negative iteration range"; return NMFX_E_ARG; }
-    int rc = nmfx_enter_family(E, 1); if (rc) return rc;
-    E->is_run = distance == NMFX_IS;
-    NMFX_HIP(hipSetDevice(E->device));
-    return nmfx_ensure_obj_capacity(E, first + count + 2);
+    nmfx_entry a = {NMFX_FAM_MUR, first, count, NMFX_D_NONE, NMFX_D_NONE};      // (a sparse handle derives nothing from (W, H) that outlives a call)
+    if (distance == NMFX_IS && !E->sp->masked)
+        a.bad = "the Itakura-Saito divergence (IS) is infinite at the zeros of an unmasked sparse V: make the handle masked (nmfx_set_masked)";
+    else if (distance != NMFX_EU && distance != NMFX_KL && distance != NMFX_IS) a.bad = "Unknown distance type.";
+    else if (first < 0 || count < 0) a.bad = "negative iteration range";
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    E->run.mur_loss(distance);
+    return NMFX_OK;
 }
 
 int nmfx_sparse_mur_run(nmfx_engine* E, int distance, double lw, double lh, int64_t min_iter, double tol1, double tol2,
@@ -722,7 +719,7 @@ static int sync_wsel(nmfx_engine* E) {
     DevState hs;
     NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
-    if (hs.flag) E->wsel = (int)((hs.stop_i + 1) & 1);
+    if (hs.flag) E->run.wsel = (int)((hs.stop_i + 1) & 1);
     return NMFX_OK;
 }
 
@@ -730,7 +727,7 @@ int nmfx_sparse_objective_f64(nmfx_engine* E, double* out) {
     if (!E->have_v || !E->have_f) { E->err = "upload the CSR matrix and set factors first"; return NMFX_E_STATE; }
     int rc;
     if ((rc = sync_wsel(E))) return rc;
-    if ((rc = objective_pass(E, NMFX_EU, E->W[E->wsel], nullptr))) return rc;
+    if ((rc = objective_pass(E, NMFX_EU, E->W[E->run.wsel], nullptr))) return rc;
     if ((rc = launch_objective(E, NMFX_EU, E->xf64 + 1, false, 0, 0, 0.0, 0.0))) return rc;
     NMFX_HIP(hipMemcpyAsync(out, E->xf64 + 1, sizeof(double), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
@@ -765,11 +762,9 @@ int nmfx_sparse_set_factors(nmfx_engine* E, const double* w, const double* hmat)
         NMFX_HIP(hipMemcpyAsync(E->sp->Ht, t.data(), t.size() * 4, hipMemcpyHostToDevice, E->stream));
         NMFX_HIP(hipStreamSynchronize(E->stream));
     }
-    E->wsel = 0;
     E->have_f = true;
-    E->family = 0;
-    E->is_run = false;
-    E->w_in_place = false;
+    E->derived.void_all_but(NMFX_D_NONE);
+    E->run.reset();
     int rc;
     if (!E->sp->masked && (rc = stats_both(E))) return rc;
     NMFX_HIP(hipStreamSynchronize(E->stream));
@@ -782,7 +777,7 @@ int nmfx_sparse_get_factors(nmfx_engine* E, double* w, double* hmat) {
     const int64_t m = E->m, n = E->n, k = E->k, kp = E->kp;
     if (w) {
         std::vector<float> t((size_t)(m * kp));
-        NMFX_HIP(hipMemcpyAsync(t.data(), E->W[E->wsel], t.size() * 4, hipMemcpyDeviceToHost, E->stream));
+        NMFX_HIP(hipMemcpyAsync(t.data(), E->W[E->run.wsel], t.size() * 4, hipMemcpyDeviceToHost, E->stream));
         NMFX_HIP(hipStreamSynchronize(E->stream));
         for (int64_t r = 0; r < m; ++r)
             for (int64_t c = 0; c < k; ++c) w[r * k + c] = (double)t[(size_t)(r * kp + c)];

@@ -61,6 +61,64 @@ struct DevState {          // lives in device memory, written by kernels
 
 struct ProfSlot { double ms = 0; int64_t n = 0; };
 
+// ---- what a handle derives from the current (W, H) and trusts in a later call -----------------------------------------------
+// ONE list: the fields of nmfx_engine::derived, their NMFX_D_* bits and void_all_but() are generated from it, so an item that is
+// added here is voided by every entry point that does not name it in its keep set (nmfx_enter below), and no item exists outside
+// it.  X(name, type, value that says "nothing valid", what a valid value promises).  DESIGN.md 4.8 has the table of who writes,
+// reads and keeps each.
+#define NMFX_DERIVED_ITEMS(X) \
+    X(wimg_ok, bool, false,        "Whi/Wlo[0] and WThi/WTlo are the images of the current W[0] (AO-ADMM: left by the fused W-side launches)") \
+    X(himg_both, bool, false,      "Hhi/Hlo AND HThi/HTlo are the images of the current H (AO-ADMM skips a rebuild)") \
+    X(lazy_objective, bool, false, "AO-ADMM split-bf16: the objective of the current pair rides on the next H-side product") \
+    X(kl_h_iter, int64_t, -2,      "MUR-KL split-bf16: the outer iteration whose H epilogue left the H partials of kl_part and the H / H^T images (good for iteration + 1 only)") \
+    X(anls_a_ready, bool, false,   "ANLS: A_part and the H H^T slabs are those of the current (W, H) (left by the fused objective pass)") \
+    X(kl_bt_ready, bool, false,    "ADMM-KL: Bt_part holds w_aux^T S of the coming iteration (left by the fused auxiliaries launch)") \
+    X(gxb_img_ready, bool, false,  "k > 128: Whi/Wlo[0], WThi/WTlo, Hhi/Hlo, HThi/HTlo are the images of the current (W, H) of the MUR loop") \
+    X(ard_valid, bool, false,      "ard_lam (the penalty at ard_lam[kp] included) and ard_pen belong to the current (W, H)")
+
+enum {
+#define NMFX_X(name, type, none, what) NMFX_DPOS_##name,
+    NMFX_DERIVED_ITEMS(NMFX_X)
+#undef NMFX_X
+    NMFX_DPOS_COUNT
+};
+enum : unsigned {
+#define NMFX_X(name, type, none, what) NMFX_D_##name = 1u << NMFX_DPOS_##name,
+    NMFX_DERIVED_ITEMS(NMFX_X)
+#undef NMFX_X
+    NMFX_D_NONE = 0u, NMFX_D_ALL = (1u << NMFX_DPOS_COUNT) - 1u
+};
+struct nmfx_derived {
+#define NMFX_X(name, type, none, what) type name = none;
+    NMFX_DERIVED_ITEMS(NMFX_X)
+#undef NMFX_X
+    void void_all_but(unsigned keep) {
+#define NMFX_X(name, type, none, what) if (!(keep & NMFX_D_##name)) name = none;
+        NMFX_DERIVED_ITEMS(NMFX_X)
+#undef NMFX_X
+    }
+    void drop(unsigned items) { void_all_but(~items); }      // a producer's own "this is about to change" / "this has been used up"
+};
+
+// What the run since nmfx_set_factors is: the solver family (one per set of factors, nmfx_enter), and for MUR the loss kind, the
+// W buffer that holds the iterate and whether two problems are stacked.  reset() is nmfx_set_factors'.
+enum { NMFX_FAM_NONE = 0, NMFX_FAM_MUR = 1, NMFX_FAM_AOADMM = 2, NMFX_FAM_ADMM = 3, NMFX_FAM_ANLS = 4,
+       NMFX_FAM_MUR_PAIR = 5 };                         // (asked of nmfx_enter only: family NMFX_FAM_MUR in pair mode)
+enum { NMFX_LOSS_PLAIN = 0, NMFX_LOSS_IS = 1, NMFX_LOSS_BETA = 2 };      // MUR: Euclidean / KL, or a loss nmfx_objective_f64 has to refuse (and how it words that)
+struct nmfx_run {
+    int family = NMFX_FAM_NONE;    // solver family that has run since nmfx_set_factors
+    bool started = false;          // a MUR run has begun since nmfx_set_factors (pair mode must be chosen at its start)
+    bool pair = false;             // nmfx_mur_pair_*: factor columns [0, 64) and [64, 128) are two independent problems
+    int loss = NMFX_LOSS_PLAIN;
+    bool fused_pack = false;       // inside nmfx_mur_run (single GPU): no pack launch, h_update reads the slabs
+    bool w_in_place = false;       // the solver updates W[0] in place (all but MUR, which ping-pongs)
+    int wsel = 0;                  // W buffer holding the current iterate
+    void reset() { *this = nmfx_run(); }
+    void in_place() { wsel = 0; w_in_place = true; }                         // AO-ADMM, ADMM, ANLS
+    void ping_pong(int64_t j) { wsel = (int)((j + 1) & 1); w_in_place = false; }   // MUR: iteration j leaves W_{j+1} in the other buffer
+    void mur_loss(int distance) { loss = distance == NMFX_BETA ? NMFX_LOSS_BETA : distance == NMFX_IS ? NMFX_LOSS_IS : NMFX_LOSS_PLAIN; }
+};
+
 struct nmfx_engine {
     int device = 0;
     int64_t m = 0, n = 0;          // logical local shape
@@ -79,7 +137,6 @@ struct nmfx_engine {
     int64_t Bt_chunk_cap = 0;
     int chunk_gslabs = 0;          // ... and the number of W^T W slabs its first chunk / the Gram kernel left
     float* kl_part = nullptr;      // MUR-KL, split-bf16: [np/64][kp] row-sum partials of H | [mp/64][kp] column-sum partials of W (the fused epilogues)
-    int64_t kl_h_iter = -2;        // outer iteration whose H epilogue wrote the H partials and the H / H^T images (valid for iteration + 1 only)
     float* A_part = nullptr;       // [wsplit][mp][kp]
     float* B_part = nullptr;       // [hsplit][kp][np]
     float* phase_part = nullptr;   // MUR-IS, weighted MUR and MUR-beta (kernels_phase.hip): [splits][numerator | denominator] slabs of the phase in flight, allocated on first use
@@ -108,7 +165,6 @@ struct nmfx_engine {
     float* gxb_vt = nullptr;       // MUR-KL beyond k = 128: V^T [np][mp] in f32 (the quotient of the H side is formed transposed)
     bool gxb_vt_ready = false;
     unsigned short* gxb_q[2] = {nullptr, nullptr};   // ... bf16 hi / lo planes of the quotient V / (W H + 1e-9): [mp][np], then [np][mp]
-    bool gxb_img_ready = false;    // Whi/Wlo[0], WThi/WTlo, Hhi/Hlo, HThi/HTlo are the images of the current (W, H) of the k > 128 MUR loop
     struct nmfx_comm* comm = nullptr;      // RCCL communicator of a row-sharded run (comm.hip), or none
     double* obj_hist = nullptr;    // device, capacity obj_cap
     int64_t obj_cap = 0;
@@ -123,11 +179,9 @@ struct nmfx_engine {
     float* kl_S[2] = {nullptr, nullptr}; float* kl_DV[2] = {nullptr, nullptr};   // ... split-bf16 form (r4): tile-major, [0] rows n (like Vt), [1] rows m (like Vtile)
     int kl_side = 0;               // the orientation that holds the current dual_v
     int kl_s_side = 0;             // ... and the one whose buffer holds the current S = v_aux + dual_v
-    bool kl_bt_ready = false;      // ADMM-KL: Bt_part holds w_aux^T S of the coming iteration (left by the fused auxiliaries launch)
     // split-bf16 mode (kernels_bf16.hip): V^T and bf16 hi/lo images of the factors
     int precision = 0;             // 0 = f32 MFMA, 1 = split bf16 (k padded to 64 only)
     bool bf_ready = false;
-    bool fused_pack = false;       // nmfx_mur_run (single GPU): no pack launch, h_update reads the slabs
     int xrank = -1, xworld = 0;    // nmfx_set_exchange_rank: the objective partial travels INSIDE the f32 exchange buffer (see NMFX_XTAIL)
     int ncu = 256, bt_split = 1, bf_wsplit = 1;
     int gram_ng_w = 1, gram_ng_h = 1;   // row blocks sharing the Gram by-product of the W / H phase (kp = 64)
@@ -138,10 +192,7 @@ struct nmfx_engine {
     const float* ao_b_src = nullptr; const int* ao_b_cnt = nullptr;   // AO-ADMM H side, behind a stream-K product: B^T slabs the fused rounds sum themselves (+ what their first launch records)
     int ao_rec_nobj = 0; int64_t ao_rec_j = 0, ao_rec_min_iter = 0; double ao_rec_tol1 = 0.0, ao_rec_tol2 = 0.0;
     const float* ao_a_src = nullptr; const int* ao_a_cnt = nullptr;   // ... the slab buffer (default A_part) and, behind a stream-K product, the slabs per 128-row block
-    bool wimg_ok = false;          // Whi/Wlo[0] and WThi/WTlo are the images of the current W[0] (AO-ADMM: left by the fused W-side launches)
     bool ao_images = false;        // the fused round kernels being launched write the images of the factor they update
-    bool himg_both = false;        // Hhi/Hlo AND HThi/HTlo are the images of the current H (AO-ADMM skips a rebuild)
-    bool lazy_objective = false;   // AO-ADMM split-bf16: the objective of the current pair rides on the next H-side product
     bool drop_v = false;           // split-bf16 mode: free the row-major V once Vtile / Vt exist (rebuilt on demand, nmfx_need_v)
     std::string note;              // what nmfx_create decided on its own (precision fallback, dropped V): nmfx_get_note
     float* Vtile = nullptr;        // V, tile-major: [mp/128][np/64] tiles of [128][64] (bf16-path W phase)
@@ -170,24 +221,17 @@ struct nmfx_engine {
     // split configuration
     int wsplit = 1, hsplit = 1, gsplit = 1;
     bool have_v = false, have_f = false;
+    nmfx_derived derived;          // state computed from the current (W, H): NMFX_DERIVED_ITEMS
+    nmfx_run run;                  // what the run since nmfx_set_factors is
     int anls_dist = NMFX_EU;       // objective ANLS reports (anls.py:108,118): the iterates are least-squares either way
-    bool anls_a_ready = false;    // ANLS: A_part / H H^T slabs of the CURRENT (W, H) are valid (produced by the fused objective pass)
-    int wsel = 0;                  // W buffer holding the current iterate
-    bool family_started = false;   // a MUR run has begun since nmfx_set_factors (pair mode must be chosen at its start)
-    bool is_run = false;           // the MUR run since nmfx_set_factors uses the Itakura-Saito divergence (nmfx_objective_f64 is Euclidean: refused)
-    bool beta_run = false;         // ... or, with is_run set as well, the beta-divergence (dense handles only; it only words that refusal)
     double beta = 0.0;             // nmfx_set_beta: the beta of NMFX_BETA runs (kernels_phase.hip)
     bool beta_set = false;
     // nmfx_set_ard: automatic relevance determination on the beta path (kernels_phase.hip)
     bool ard = false;
-    bool ard_valid = false;        // ard_lam (the penalty at ard_lam[kp] included) and ard_pen belong to the current (W, H)
     double ard_phi = 0.0, ard_a = 0.0, ard_b = 0.0;
     double* ard_sums = nullptr;    // [W row blocks + H column chunks][kp] f64 partial column sums of W / row sums of H
     double* ard_lam = nullptr;     // [kp] the relevances lambda_k, then [1] the penalty phi c Sum (1 + log lambda_k)
     float* ard_pen = nullptr;      // [kp] phi / lambda_k, what the update kernels add to their denominators (0 for k >= K)
-    bool pair = false;             // nmfx_mur_pair_*: factor columns [0, 64) and [64, 128) are two independent problems
-    int family = 0;                // solver family that has run since nmfx_set_factors (0 none, 1 MUR eu/kl, 2 AO-ADMM, 3 ADMM, 4 ANLS): nmfx_enter_family
-    bool w_in_place = false;       // solver updates W[0] in place (all but MUR, which ping-pongs)
     struct nmfx_sparse* sp = nullptr;   // a sparse handle (nmfx_create_csr): CSR / CSC of V, H^T, Grams (kernels_sparse.hip); MUR only
     // profiling
     bool prof = false;
@@ -282,15 +326,24 @@ int nmfx_ard_finish_b(nmfx_engine* E, int64_t min_iter, double tol1, double tol2
 // One solver family per set of factors: the families keep different device state next to W and H (MUR: W ping-pong and bf16 images of
 // both factors; AO-ADMM / ADMM: duals and auxiliaries; ANLS: warm-start supports), and a family that starts in the middle of another's
 // run would read leftovers.  A second family on the same handle needs nmfx_get_factors -> nmfx_set_factors first (NMFX_E_STATE otherwise).
-inline int nmfx_enter_family(nmfx_engine* E, int fam) {
-    if (E->family && E->family != fam) {
-        E->err = "another solver has run on this handle since nmfx_set_factors: read the factors back and set them again "
-                 "(nmfx_get_factors, nmfx_set_factors) before a different solver continues from them";
-        return NMFX_E_STATE;
-    }
-    E->family = fam;
-    return NMFX_OK;
-}
+//
+// nmfx_enter is the guard every compute entry point passes after its own refusals.  In this order: "upload V and set factors
+// first"; the caller's own argument refusal `bad`; the family; MUR's pair rule; `bad` where the caller ranks it last (MUR's "negative
+// iteration range").  An accepted call then voids everything derived from (W, H) that is not in `keep`, makes the device current
+// and grows the objective history to first + count + 2 entries (pair mode: two per iteration).  A refused call voids `pre` alone:
+// what its entry point has always voided before it asked anything (MUR-KL rebuilds its leftovers in another summation order than
+// it continues from them, so when a refused call voids them decides bits of the calls behind it).  `pre` goes first, or behind
+// `bad` where pre_after_bad says so (AO-ADMM).  Solver-specific allocations stay with the solver, behind the guard.
+struct nmfx_entry {
+    int family;                    // NMFX_FAM_*; NMFX_FAM_NONE joins none (nmfx_mur_finish_b, the closing step of every sharded solver)
+    int64_t first, count;
+    unsigned keep;                 // NMFX_D_* the call goes on trusting
+    unsigned pre;                  // NMFX_D_* voided even where the call is refused
+    std::string bad = std::string();   // the caller's refusal, already worded (empty: none)
+    int bad_rc = NMFX_E_ARG;
+    bool bad_last = false, pre_after_bad = false;
+};
+int nmfx_enter(nmfx_engine* E, const nmfx_entry& a);      // engine.hip
 int nmfx_ensure_obj_capacity(nmfx_engine* E, int64_t need);
 void nmfx_comm_free(nmfx_engine* E);      // comm.hip
 void nmfx_comm_invalidate(nmfx_engine* E);   // nmfx_set_precision: renegotiate, drop the captured graph, objective back to the f64 buffer
@@ -311,9 +364,10 @@ int nmfx_generic_admm_phase(nmfx_engine* E, int phase, int distance, double rho,
 int nmfx_generic_anls_phase(nmfx_engine* E, int phase, double lam, int64_t min_iter, double tol1, double tol2, int64_t j);
 int nmfx_preload_generic();
 // the tuned kernels keep k x k matrices and k-wide panels on chip: everything but MUR ends at k = 128
+inline std::string nmfx_small_k_text(const char* what) { return std::string(what) + ": not available with more than 128 components in this build"; }
 inline int nmfx_small_k_only(nmfx_engine* E, const char* what) {
     if (E->kp <= 128) return NMFX_OK;
-    E->err = std::string(what) + ": not available with more than 128 components in this build";
+    E->err = nmfx_small_k_text(what);
     return NMFX_E_ARG;
 }
 int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need);
