@@ -25,7 +25,8 @@ def test_anls_matches_reference(name):
 
 def test_anls_larger_rank_properties():
     """k = 40 (> 32, one variable per lane, 64-wide workspace): KKT conditions of the
-    returned H against the returned W, checked in float64 on the host."""
+    returned H against the returned W, checked in float64 on the host.  (Every half-step, problem by problem, at every
+    padding and workspace edge: tests/test_gpu_anls_step.py.)"""
     from nmf_amd.anls import anls
     from oracle import nmf_ref as R
     v = R.planted_matrix(300, 200, 40, seed=2, dtype=np.float64)
@@ -44,7 +45,8 @@ def test_anls_larger_rank_properties():
 @pytest.mark.parametrize("shape", [(300, 220, 40), (260, 400, 100)])
 def test_anls_k64_k128_both_precisions_vs_oracle(precision, shape, monkeypatch):
     """k in (32, 128]: register-resident NNLS (one wave per problem for k <= 64, two for k = 128), products on the
-    split-bf16 kernels or on the exact-f32 kernels, against the oracle (scipy NNLS)."""
+    split-bf16 kernels or on the exact-f32 kernels, against the oracle (scipy NNLS).  A norm over the final pair; which NNLS
+    kernel solved which problem, and each problem's own solution: tests/test_gpu_anls_step.py."""
     from oracle import nmf_ref as R
     from nmf_amd.anls import anls
     monkeypatch.setenv("NMFX_PRECISION", precision)

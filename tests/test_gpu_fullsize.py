@@ -260,7 +260,8 @@ def test_anls_16384x8192_k64_kkt_of_both_half_steps():
     solutions are characterised by their KKT conditions, so those are checked in float64 instead -- H >= 0 with the gradient
     G H - W^T V zero on its support and non-negative off it (the last half-step of an iteration), the same for the rows of
     W against the H they were solved for -- together with objective == directly evaluated objective and monotone descent.
-    Exercises the f64 inverse + complement NNLS path and its fallback counters at scale."""
+    Exercises the f64 inverse + complement NNLS path and its fallback counters at scale.  (The same conditions per problem at
+    small shapes, with the values against float64 Lawson-Hanson, at every rank edge and regime: tests/test_gpu_anls_step.py.)"""
     from nmf_amd.engine import Engine
     m, n, k, iters = 16384, 8192, 64, 3
     v = R.planted_matrix(m, n, k, seed=0, dtype=np.float32)
