@@ -14,19 +14,11 @@
 #include "kernels_small.h"
 #include <vector>
 
-template <typename T>
-static int lazy_alloc(nmfx_engine* E, T** p, int64_t count) {
-    if (*p) return NMFX_OK;
-    NMFX_HIP(hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T)));
-    NMFX_HIP(hipMemsetAsync(*p, 0, (size_t)count * sizeof(T), E->stream));
-    return NMFX_OK;
-}
-
 static int admm_alloc(nmfx_engine* E) {
     int rc;
     if ((rc = nmfx_aoadmm_alloc(E))) return rc;
-    if ((rc = lazy_alloc(E, &E->auxH, (int64_t)E->kp * E->np))) return rc;
-    if ((rc = lazy_alloc(E, &E->Asum, E->mp * E->kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->auxH, (int64_t)E->kp * E->np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->Asum, E->mp * E->kp))) return rc;
     return NMFX_OK;
 }
 
@@ -45,126 +37,70 @@ static int admm_objective(nmfx_engine* E) {
     return nmfx_bf16_objective(E, 1, "objective");
 }
 
-// first half of an iteration: this rank's [w_aux^T V | w_aux^T w_aux | objective partial] into the exchange buffers
-// (row-sharded runs all-reduce them here)
-static int admm_eu_products(nmfx_engine* E) {
+// first half of an iteration: this rank's [w_aux^T data | w_aux^T w_aux | objective partial] into the exchange buffers
+// (row-sharded runs all-reduce them here).  data: nullptr = V (Euclidean loss), or S = v_aux + dual_v (KL loss, admm.py:303-305:
+// exact f32 only, the split-bf16 KL iteration below is a run of its own)
+static int admm_products(nmfx_engine* E, const float* data) {
     int rc;
-    const bool bf = admm_bf16(E);
-    if (bf) {       // w_aux^T V and w_aux^T w_aux on the split-bf16 kernel (kp = 64: the Gram is its by-product)
+    if (!data && admm_bf16(E)) {    // w_aux^T V and w_aux^T w_aux on the split-bf16 kernel (kp = 64: the Gram is its by-product)
         const int64_t nobj = E->obj_count;             // the objective pass that ended the previous iteration
         if ((rc = nmfx_bf16_images_w(E, E->auxW, 0))) return rc;
         if ((rc = nmfx_bf16_vtw(E, false, "hphase"))) return rc;
-        if (E->kp == 64) rc = nmfx_bf16_pack_t(E, E->G_part, nmfx_bf16_g_slabs(E), nobj);
-        else {
-            if ((rc = nmfx_launch_gram_tn(E, E->auxW, E->mp, E->G_part, E->gsplit))) return rc;
-            rc = nmfx_bf16_pack_t(E, E->G_part, E->gsplit, nobj);
-        }
-        if (rc) return rc;
-    } else {
+        if (E->kp == 64) return nmfx_bf16_pack_t(E, E->G_part, nmfx_bf16_g_slabs(E), nobj);
+        if ((rc = nmfx_launch_gram_tn(E, E->auxW, E->mp, E->G_part, E->gsplit))) return rc;
+        return nmfx_bf16_pack_t(E, E->G_part, E->gsplit, nobj);
+    }
     const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
     if (!fuse_g && (rc = nmfx_launch_gram_tn(E, E->auxW, E->mp, E->G_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_hphase(E, E->auxW, fuse_g))) return rc;
-    if ((rc = nmfx_launch_pack(E))) return rc;
-    }
-    return NMFX_OK;
-}
-
-static int admm_eu_update(nmfx_engine* E, double rho, int prox_w, double lam_w, int prox_h, double lam_h,
-                          int64_t min_iter, double tol1, double tol2, int64_t j) {
-    int rc;
-    float* W = E->W[0];
-    const int64_t kk = (int64_t)E->kp * E->kp;
-    const bool bf = admm_bf16(E);
-    // ---- h_aux and the H half ----
-    if ((rc = nmfx_launch_prepare(E, E->xf32 + (int64_t)E->kp * E->np, 1, j, min_iter, tol1, tol2, rho))) return rc;
-    { ProfScope ps(E, "inner_h");
-      if (prox_h == NMFX_PROX_L2N) {
-          if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 1, prox_h, (float)lam_h, 0))) return rc;
-          if ((rc = nmfx_inner_cols(E, E->Ph, E->auxH, 2, prox_h, (float)lam_h, 0))) return rc;
-      } else if (prox_h == NMFX_PROX_L1INF || prox_h == NMFX_PROX_L1INF_T) {   // couples whole rows / columns: its own launch
-          if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 1, prox_h, (float)lam_h, 0))) return rc;
-          if ((rc = nmfx_launch_prox_l1inf(E, true, prox_h == NMFX_PROX_L1INF_T, rho, lam_h, 1.0, true))) return rc;
-      } else if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 0, prox_h, (float)lam_h, 0))) return rc; }
-    // ---- w_aux (from the NEW h_aux) and the W half ----
-    if (bf) {
-        const bool byprod = E->kp == 64;               // h_aux h_aux^T as a by-product
-        if ((rc = nmfx_bf16_images_h(E, false, E->auxH))) return rc;
-        if ((rc = nmfx_bf16_vht(E, false, 0, "wphase_noobj"))) return rc;
-        if (!byprod && (rc = nmfx_launch_gram_nt(E, E->auxH, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-        { ProfScope ps(E, "sums");
-          if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, kk, E->HHt))) return rc;
-          if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->bf_wsplit, E->mp * E->kp, E->Asum))) return rc; }
-    } else {
-    if ((rc = nmfx_launch_gram_nt(E, E->auxH, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_wphase(E, W, true, false, false, E->auxH))) return rc;
-    { ProfScope ps(E, "sums");
-      if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
-      if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum))) return rc; }
-    }
-    if ((rc = nmfx_launch_prepare(E, E->HHt, 0, j, min_iter, tol1, tol2, rho))) return rc;
-    { ProfScope ps(E, "inner_w");
-      if (prox_w == NMFX_PROX_L2N) {
-          if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 1, prox_w, (float)lam_w, 0))) return rc;
-          if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Pw, E->auxW, 2, prox_w, (float)lam_w, 0))) return rc;
-      } else if (prox_w == NMFX_PROX_L1INF || prox_w == NMFX_PROX_L1INF_T) {
-          if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 1, prox_w, (float)lam_w, 0))) return rc;
-          if ((rc = nmfx_launch_prox_l1inf(E, false, prox_w == NMFX_PROX_L1INF_T, rho, lam_w, 1.0, true))) return rc;
-      } else if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 0, prox_w, (float)lam_w, 0))) return rc; }
-    // ---- objective of (w, h) (admm.py:324) ----
-    return admm_objective(E);
-}
-
-static int admm_eu_iteration(nmfx_engine* E, double rho, int prox_w, double lam_w, int prox_h, double lam_h,
-                             int64_t min_iter, double tol1, double tol2, int64_t j) {
-    int rc;
-    if ((rc = admm_eu_products(E))) return rc;
-    return admm_eu_update(E, rho, prox_w, lam_w, prox_h, lam_h, min_iter, tol1, tol2, j);
-}
-
-// KL loss (admm.py:303-315): the Gram right-hand sides multiply S = v_aux + dual_v, and
-// v_aux / dual_v are refreshed from w_aux @ h_aux at the end of the iteration.
-static int admm_kl_products(nmfx_engine* E) {
-    int rc;
-    const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
-    if (!fuse_g && (rc = nmfx_launch_gram_tn(E, E->auxW, E->mp, E->G_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_hphase(E, E->auxW, fuse_g, E->S))) return rc;
+    if ((rc = nmfx_launch_hphase(E, E->auxW, fuse_g, data))) return rc;
     return nmfx_launch_pack(E);
 }
 
-static int admm_kl_update(nmfx_engine* E, double rho, int prox_w, double lam_w, int prox_h, double lam_h,
-                          int64_t min_iter, double tol1, double tol2, int64_t j) {
+// one half of an iteration behind its `prepare`: x_aux = M^-1 (rhs + rho (x + dual)), x = prox(x_aux, dual), dual += x - x_aux
+// (cols: the H half, rhs in xf32; else the W half, rhs in Asum).  'l2n' is a second product with the fixed operator; the 'l1inf'
+// operators couple whole rows / columns and have a launch of their own; the others run inside the round kernel
+static int admm_half(nmfx_engine* E, bool cols, int prox, double rho, double lam) {
+    int rc;
+    ProfScope ps(E, cols ? "inner_h" : "inner_w");
+    auto round = [&](const float* M, int mode) {
+        return cols ? nmfx_inner_cols(E, M, E->auxH, mode, prox, (float)lam, 0)
+                    : nmfx_inner_rows(E, E->Asum, E->W[0], M, E->auxW, mode, prox, (float)lam, 0); };
+    if (prox == NMFX_PROX_L2N) {
+        if ((rc = round(E->Minv, 1))) return rc;
+        return round(cols ? E->Ph : E->Pw, 2);
+    }
+    if (prox == NMFX_PROX_L1INF || prox == NMFX_PROX_L1INF_T) {
+        if ((rc = round(E->Minv, 1))) return rc;
+        return nmfx_launch_prox_l1inf(E, cols, prox == NMFX_PROX_L1INF_T, rho, lam, 1.0, true);
+    }
+    return round(E->Minv, 0);
+}
+
+// second half: h_aux and the H half, w_aux (from the NEW h_aux) and the W half, then -- KL: v_aux / dual_v from w_aux @ h_aux
+// (admm.py:311-314) and -- the objective partials of (w, h) (admm.py:324)
+static int admm_update(nmfx_engine* E, const float* data, double rho, int prox_w, double lam_w, int prox_h, double lam_h,
+                       int64_t min_iter, double tol1, double tol2, int64_t j) {
     int rc;
     float* W = E->W[0];
     const int64_t kk = (int64_t)E->kp * E->kp;
+    const bool bf = !data && admm_bf16(E);
+    const bool byprod = bf && E->kp == 64;             // h_aux h_aux^T as a by-product of the split-bf16 product
     if ((rc = nmfx_launch_prepare(E, E->xf32 + (int64_t)E->kp * E->np, 1, j, min_iter, tol1, tol2, rho))) return rc;
-    if (prox_h == NMFX_PROX_L2N) {
-        if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 1, prox_h, (float)lam_h, 0))) return rc;
-        if ((rc = nmfx_inner_cols(E, E->Ph, E->auxH, 2, prox_h, (float)lam_h, 0))) return rc;
-    } else if (prox_h == NMFX_PROX_L1INF || prox_h == NMFX_PROX_L1INF_T) {
-        if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 1, prox_h, (float)lam_h, 0))) return rc;
-        if ((rc = nmfx_launch_prox_l1inf(E, true, prox_h == NMFX_PROX_L1INF_T, rho, lam_h, 1.0, true))) return rc;
-    } else if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 0, prox_h, (float)lam_h, 0))) return rc;
-    if ((rc = nmfx_launch_gram_nt(E, E->auxH, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_wphase(E, W, true, false, false, E->auxH, E->S))) return rc;
-    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
-    if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum))) return rc;
+    if ((rc = admm_half(E, true, prox_h, rho, lam_h))) return rc;
+    if (bf) {
+        if ((rc = nmfx_bf16_images_h(E, false, E->auxH))) return rc;
+        if ((rc = nmfx_bf16_vht(E, false, 0, "wphase_noobj"))) return rc;
+    }
+    if (!byprod && (rc = nmfx_launch_gram_nt(E, E->auxH, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
+    if (!bf && (rc = nmfx_launch_wphase(E, W, true, false, false, E->auxH, data))) return rc;
+    { ProfScope ps(E, "sums");
+      if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, kk, E->HHt))) return rc;
+      if ((rc = nmfx_launch_sum_partials(E, E->A_part, bf ? E->bf_wsplit : E->wsplit, E->mp * E->kp, E->Asum))) return rc; }
     if ((rc = nmfx_launch_prepare(E, E->HHt, 0, j, min_iter, tol1, tol2, rho))) return rc;
-    if (prox_w == NMFX_PROX_L2N) {
-        if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 1, prox_w, (float)lam_w, 0))) return rc;
-        if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Pw, E->auxW, 2, prox_w, (float)lam_w, 0))) return rc;
-    } else if (prox_w == NMFX_PROX_L1INF || prox_w == NMFX_PROX_L1INF_T) {
-        if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 1, prox_w, (float)lam_w, 0))) return rc;
-        if ((rc = nmfx_launch_prox_l1inf(E, false, prox_w == NMFX_PROX_L1INF_T, rho, lam_w, 1.0, true))) return rc;
-    } else if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 0, prox_w, (float)lam_w, 0))) return rc;
+    if ((rc = admm_half(E, false, prox_w, rho, lam_w))) return rc;
+    if (!data) return admm_objective(E);
     if ((rc = nmfx_launch_kl_vaux(E, E->auxW, E->auxH))) return rc;
     return nmfx_launch_wphase(E, W, false, true, true);
-}
-
-static int admm_kl_iteration(nmfx_engine* E, double rho, int prox_w, double lam_w, int prox_h, double lam_h,
-                             int64_t min_iter, double tol1, double tol2, int64_t j) {
-    int rc;
-    if ((rc = admm_kl_products(E))) return rc;
-    return admm_kl_update(E, rho, prox_w, lam_w, prox_h, lam_h, min_iter, tol1, tol2, j);
 }
 
 // The KL-loss iteration on the split-bf16 kernels (r4; one GPU, k padded to 64 or 128; NMFX_KL_BF16=0 keeps the exact-f32 launches):
@@ -172,8 +108,7 @@ static int admm_kl_iteration(nmfx_engine* E, double rho, int prox_w, double lam_
 // (kl_S[0]), S h_aux^T on the one the auxiliaries write (kl_S[1], rows m) --, the two halves as in the exact path, then the m x n
 // auxiliaries where the product w_aux h_aux stands in the accumulators (admm.py:311-314) and the transposed copy of the new S.
 static bool admm_kl_bf16(const nmfx_engine* E) {
-    static const bool on = !(getenv("NMFX_KL_BF16") && atoi(getenv("NMFX_KL_BF16")) == 0);
-    return on && admm_bf16(E);
+    return nmfx_kl_bf16_on() && admm_bf16(E);
 }
 
 static int admm_kl_objective_bf16(nmfx_engine* E) {     // KL(V, w h) partials from the images of (w, h): one pass over the tile-major V
@@ -187,7 +122,6 @@ static int admm_kl_objective_bf16(nmfx_engine* E) {     // KL(V, w h) partials f
 static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double lam_w, int prox_h, double lam_h,
                                   int64_t min_iter, double tol1, double tol2, int64_t j) {
     int rc;
-    float* W = E->W[0];
     const int64_t kk = (int64_t)E->kp * E->kp;
     const int64_t nobj32 = E->obj_count;                               // partials of the KL objective pass that closed the iteration before
     // r5 (NMFX_KL_GATHER, default on): no transposed copy of S -- a product reads it from the buffer of the other orientation through the
@@ -195,8 +129,7 @@ static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double
     // Z = h_aux^T images), where their launch can also form w_aux^T S, the first product of the NEXT iteration, from S in registers
     // (NMFX_KL_FUSE, default on; w_aux does not change in between).  NMFX_KL_GATHER=0: the r4 sequence (auxiliaries in the orientation
     // of V, S transposed at the end of every iteration).
-    static const bool gather = !(getenv("NMFX_KL_GATHER") && atoi(getenv("NMFX_KL_GATHER")) == 0);
-    static const bool fuse = gather && !(getenv("NMFX_KL_FUSE") && atoi(getenv("NMFX_KL_FUSE")) == 0);
+    const bool gather = nmfx_kl_gather_on(), fuse = gather && nmfx_kl_fuse_on();
     if ((rc = nmfx_bf16_prepare(E))) return rc;
     if ((rc = nmfx_bf16_kl_state(E, false))) return rc;
     // ---- h_aux = (w_aux^T w_aux + rho I)^-1 (w_aux^T S + rho (h + dual_h)) ----
@@ -211,13 +144,7 @@ static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double
     }
     if (rc) return rc;
     if ((rc = nmfx_launch_prepare(E, E->xf32 + (int64_t)E->kp * E->np, 1, j, min_iter, tol1, tol2, rho))) return rc;
-    if (prox_h == NMFX_PROX_L2N) {
-        if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 1, prox_h, (float)lam_h, 0))) return rc;
-        if ((rc = nmfx_inner_cols(E, E->Ph, E->auxH, 2, prox_h, (float)lam_h, 0))) return rc;
-    } else if (prox_h == NMFX_PROX_L1INF || prox_h == NMFX_PROX_L1INF_T) {
-        if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 1, prox_h, (float)lam_h, 0))) return rc;
-        if ((rc = nmfx_launch_prox_l1inf(E, true, prox_h == NMFX_PROX_L1INF_T, rho, lam_h, 1.0, true))) return rc;
-    } else if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 0, prox_h, (float)lam_h, 0))) return rc;
+    if ((rc = admm_half(E, true, prox_h, rho, lam_h))) return rc;
     // ---- w_aux from the NEW h_aux ----
     if ((rc = nmfx_bf16_images_h(E, gather, E->auxH))) return rc;      // h_aux images: Y of the product (and, transposed, Z of the auxiliaries in the orientation of V^T)
     if ((rc = nmfx_bf16_kl_product(E, 1, 4, nullptr, E->kl_s_side != 1))) return rc;
@@ -225,13 +152,7 @@ static int admm_kl_iteration_bf16(nmfx_engine* E, double rho, int prox_w, double
     if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
     if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->bf_wsplit, E->mp * E->kp, E->Asum))) return rc;
     if ((rc = nmfx_launch_prepare(E, E->HHt, 0, j, min_iter, tol1, tol2, rho))) return rc;
-    if (prox_w == NMFX_PROX_L2N) {
-        if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 1, prox_w, (float)lam_w, 0))) return rc;
-        if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Pw, E->auxW, 2, prox_w, (float)lam_w, 0))) return rc;
-    } else if (prox_w == NMFX_PROX_L1INF || prox_w == NMFX_PROX_L1INF_T) {
-        if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 1, prox_w, (float)lam_w, 0))) return rc;
-        if ((rc = nmfx_launch_prox_l1inf(E, false, prox_w == NMFX_PROX_L1INF_T, rho, lam_w, 1.0, true))) return rc;
-    } else if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 0, prox_w, (float)lam_w, 0))) return rc;
+    if ((rc = admm_half(E, false, prox_w, rho, lam_w))) return rc;
     // ---- v_aux, dual_v from w_aux h_aux; the new S ----
     if ((rc = nmfx_bf16_images_w(E, E->auxW, 0))) return rc;           // the new w_aux: Z (orientation of V) / Y (orientation of V^T)
     if (!gather) {
@@ -252,7 +173,7 @@ extern "C" int nmfx_set_l2n_operator(nmfx_handle_t E, int which, const double* p
     NMFX_HIP(hipSetDevice(E->device));
     float** dst = which == 0 ? &E->Pw : &E->Ph;
     int rc;
-    if ((rc = lazy_alloc(E, dst, (int64_t)E->kp * E->kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, dst, (int64_t)E->kp * E->kp))) return rc;
     std::vector<float> tmp((size_t)E->kp * E->kp, 0.f);
     for (int i = 0; i < E->k; ++i)
         for (int c = 0; c < E->k; ++c) tmp[(size_t)i * E->kp + c] = (float)p[(size_t)i * E->k + c];
@@ -314,7 +235,7 @@ extern "C" int nmfx_admm_phase_products(nmfx_handle_t E, int distance, double rh
     NMFX_DENSE_ONLY(E);
     int rc = admm_begin(E, distance, rho, prox_w, prox_h, j, 1); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_admm_phase(E, 0, distance, rho, prox_w, 0.0, prox_h, 0.0, 0, 0.0, 0.0, j);      // (r4)
-    return distance == NMFX_EU ? admm_eu_products(E) : admm_kl_products(E);
+    return admm_products(E, distance == NMFX_KL ? E->S : nullptr);
 }
 
 extern "C" int nmfx_admm_phase_update(nmfx_handle_t E, int distance, double rho, int prox_w, double lambda_w, int prox_h,
@@ -325,8 +246,7 @@ extern "C" int nmfx_admm_phase_update(nmfx_handle_t E, int distance, double rho,
     if (!E->auxH || j < 0) { E->err = "admm_phase_update: call nmfx_admm_phase_products first"; return NMFX_E_STATE; }
     NMFX_HIP(hipSetDevice(E->device));
     if (E->kp > 128) return nmfx_generic_admm_phase(E, 1, distance, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j);
-    return distance == NMFX_EU ? admm_eu_update(E, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j)
-                               : admm_kl_update(E, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j);
+    return admm_update(E, distance == NMFX_KL ? E->S : nullptr, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j);
 }
 
 extern "C" int nmfx_admm_run(nmfx_handle_t E, int distance, double rho, int prox_w, double lambda_w, int prox_h,
@@ -336,11 +256,10 @@ extern "C" int nmfx_admm_run(nmfx_handle_t E, int distance, double rho, int prox
     int rc = admm_begin(E, distance, rho, prox_w, prox_h, first, count, true); if (rc) return rc;
     if (E->kp > 128)           // composed from the generic product kernel (kernels_generic.hip)
         return nmfx_generic_admm_run(E, distance, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, first, count);
+    const float* data = distance == NMFX_KL ? E->S : nullptr;
     for (int64_t j = first; j < first + count; ++j) {
-        rc = distance == NMFX_EU
-            ? admm_eu_iteration(E, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j)
-            : admm_kl_bf16(E) ? admm_kl_iteration_bf16(E, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j)
-                              : admm_kl_iteration(E, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j);
+        if (data && admm_kl_bf16(E)) rc = admm_kl_iteration_bf16(E, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j);
+        else if (!(rc = admm_products(E, data))) rc = admm_update(E, data, rho, prox_w, lambda_w, prox_h, lambda_h, min_iter, tol1, tol2, j);
         if (rc) return rc;
     }
     return NMFX_OK;

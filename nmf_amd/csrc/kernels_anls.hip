@@ -537,22 +537,14 @@ static int launch_nnls_reg(nmfx_engine* E, const float* G, float diag_add, const
     return NMFX_OK;
 }
 
-template <typename T>
-static int lazy_alloc(nmfx_engine* E, T** p, int64_t count) {
-    if (*p) return NMFX_OK;
-    NMFX_HIP(hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T)));
-    NMFX_HIP(hipMemsetAsync(*p, 0, (size_t)count * sizeof(T), E->stream));
-    return NMFX_OK;
-}
-
 // the inverse-based pass (see nnls_cinv_kernel); leaves *todo / *bad for the elimination kernel that follows
 template <int KP>
 static int launch_nnls_cinv(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
                             int64_t nprob, const int** todo, const int** bad) {
     int rc;
-    if ((rc = lazy_alloc(E, &E->nnls_ginv, (int64_t)KP * KP + 2))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->nnls_ginv, (int64_t)KP * KP + 2))) return rc;
     { const int64_t need = E->mp > E->np ? E->mp : E->np;
-      if ((rc = lazy_alloc(E, &E->nnls_todo, need))) return rc; }
+      if ((rc = nmfx_lazy_alloc(E, &E->nnls_todo, need))) return rc; }
     int* inv_bad = reinterpret_cast<int*>(E->nnls_ginv + (int64_t)KP * KP);
     if constexpr (KP >= 64) {                           // the blocked f64-MFMA Gauss-Jordan of the AO-ADMM `prepare` (153 -> ~20 us at k = 64)
         if ((rc = nmfx_launch_inverse64(E, G, (double)diag_add, E->nnls_ginv, inv_bad))) return rc;
@@ -593,7 +585,7 @@ static int nnls(nmfx_engine* E, const float* G, float diag_add, const float* R, 
                 int64_t nprob) {
     ProfScope ps(E, "nnls");
     // NMFX_NNLS_CINV=0: elimination kernels only (the round-1 path; A/B runs and tests/test_gpu_knobs.py)
-    static const bool cinv = !(getenv("NMFX_NNLS_CINV") && atoi(getenv("NMFX_NNLS_CINV")) == 0);
+    static const bool cinv = nmfx_knob_on("NMFX_NNLS_CINV");
     const int* todo = nullptr; const int* bad = nullptr;
     int rc;
     if (cinv) {
@@ -636,7 +628,7 @@ static int anls_objective(nmfx_engine* E) {
     // The objective pass over V is the W-side product of the NEXT iteration as well: V H^T with the residual objective of
     // (W, H) in one launch (the MUR W phase), instead of an objective-only pass now and a product pass over the same V
     // then.  (NMFX_ANLS_FUSE_OBJ=0: the two separate passes.)
-    static const bool fuse = !(getenv("NMFX_ANLS_FUSE_OBJ") && atoi(getenv("NMFX_ANLS_FUSE_OBJ")) == 0);
+    static const bool fuse = nmfx_knob_on("NMFX_ANLS_FUSE_OBJ");
     if (!fuse) return nmfx_bf16_objective(E, 1, "objective");
     if ((rc = nmfx_bf16_vht(E, true, 1, "wphase", false, 4))) return rc;
     E->derived.anls_a_ready = true;

@@ -1359,31 +1359,23 @@ __global__ __launch_bounds__(256) void ao_norm_gather_kernel(
 }
 
 // ---- host sequencing -----------------------------------------------------
-template <typename T>
-static int lazy_alloc(nmfx_engine* E, T** p, int64_t count) {
-    if (*p) return NMFX_OK;
-    NMFX_HIP(hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T)));
-    NMFX_HIP(hipMemsetAsync(*p, 0, (size_t)count * sizeof(T), E->stream));
-    return NMFX_OK;
-}
-
 
 int nmfx_kl_state_alloc(nmfx_engine* E) {      // m x n auxiliaries of the KL-loss ADMM variants
     int rc;
-    if ((rc = lazy_alloc(E, &E->S, E->mp * E->np))) return rc;
-    if ((rc = lazy_alloc(E, &E->DV, E->mp * E->np))) return rc;
-    if ((rc = lazy_alloc(E, &E->auxH, (int64_t)E->kp * E->np))) return rc;
-    if ((rc = lazy_alloc(E, &E->Asum, E->mp * E->kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->S, E->mp * E->np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->DV, E->mp * E->np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->auxH, (int64_t)E->kp * E->np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->Asum, E->mp * E->kp))) return rc;
     return NMFX_OK;
 }
 
 int nmfx_aoadmm_alloc(nmfx_engine* E) {
     int rc;
-    if ((rc = lazy_alloc(E, &E->dualW, E->mp * E->kp))) return rc;
-    if ((rc = lazy_alloc(E, &E->dualH, (int64_t)E->kp * E->np))) return rc;
-    if ((rc = lazy_alloc(E, &E->auxW, E->mp * E->kp))) return rc;      // A = V H^T summed over splits
-    if ((rc = lazy_alloc(E, &E->Minv, (int64_t)E->kp * E->kp))) return rc;
-    if ((rc = lazy_alloc(E, &E->nrm_part, 2 * std::max(E->mp, E->np) / 64 * 4 + 64))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->dualW, E->mp * E->kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->dualH, (int64_t)E->kp * E->np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->auxW, E->mp * E->kp))) return rc;      // A = V H^T summed over splits
+    if ((rc = nmfx_lazy_alloc(E, &E->Minv, (int64_t)E->kp * E->kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->nrm_part, 2 * std::max(E->mp, E->np) / 64 * 4 + 64))) return rc;
     return NMFX_OK;
 }
 
@@ -1573,7 +1565,7 @@ static int ao_bf16_objective_product(nmfx_engine* E) {   // Bt_part, obj_part (a
 // products (stream-K partition over ncu - 1 workers, kernels_bf16.hip) instead of as launches of their own, the Gram slabs are summed
 // by the side job, the objective is recorded by the pack.  NMFX_AO_OVERLAP=0 keeps the launches of round 3.
 static bool ao_overlap(const nmfx_engine* E, int admm_iter) {
-    static const bool on = !(getenv("NMFX_AO_OVERLAP") && atoi(getenv("NMFX_AO_OVERLAP")) == 0);
+    static const bool on = nmfx_knob_on("NMFX_AO_OVERLAP");
     return on && ao_bf16(E) && nmfx_sk_enabled(E) && admm_iter >= 2 && E->kp >= 16;
 }
 
@@ -1616,15 +1608,15 @@ static int ao_final_objective(nmfx_engine* E) {
 // the round-by-round kernels (they remain the path of the row-sharded W sub-problem, whose norms
 // cross ranks every round).
 static bool ao_fused_enabled(const nmfx_engine* E, int admm_iter) {
-    static const bool on = !(getenv("NMFX_AO_FUSED") && atoi(getenv("NMFX_AO_FUSED")) == 0);
+    static const bool on = nmfx_knob_on("NMFX_AO_FUSED");
     return on && admm_iter >= 2 && E->kp >= 16;
 }
 
 static int ao_fused_alloc(nmfx_engine* E, int admm_iter) {
     int rc;
     const int64_t big = std::max(E->mp, E->np) * E->kp;
-    if ((rc = lazy_alloc(E, &E->bkX, big))) return rc;
-    if ((rc = lazy_alloc(E, &E->bkU, big))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->bkX, big))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->bkU, big))) return rc;
     const int64_t need = (int64_t)admm_iter * std::max(E->mp / 64, E->np / 32) * 4 + 64;
     if (need > E->nrm_rounds_cap) {
         if (E->nrm_rounds) { NMFX_HIP(hipStreamSynchronize(E->stream)); hipFree(E->nrm_rounds); E->nrm_rounds = nullptr; }
@@ -1726,16 +1718,16 @@ __global__ __launch_bounds__(256) void nrm_table_kernel(const double* __restrict
 // Two launches without the hint (speculate all rounds, decide + repair), three with it (see fused_plan; NMFX_AO_HINT=0
 // turns it off).  `parity` alternates between consecutive sub-problems of the same side: the hint slot read / written.
 static int ao_fused_subproblem(nmfx_engine* E, bool cols, float* W, int prox, float lam, int admm_iter, int32_t* slot, int parity) {
-    static const bool hinted = !(getenv("NMFX_AO_HINT") && atoi(getenv("NMFX_AO_HINT")) == 0);
+    static const bool hinted = nmfx_knob_on("NMFX_AO_HINT");
     int rc;
     if ((rc = ao_fused_alloc(E, admm_iter))) return rc;
     // r3: in a split-bf16 run the launches below leave the bf16 images of the factor they update (NMFX_AO_IMG=0: the separate
     // `images` launches of round 2; a sub-problem of zero rounds has no launch that writes anything)
-    static const bool img_on = !(getenv("NMFX_AO_IMG") && atoi(getenv("NMFX_AO_IMG")) == 0);
+    static const bool img_on = nmfx_knob_on("NMFX_AO_IMG");
     E->ao_images = img_on && ao_bf16(E) && admm_iter > 0 && W == (cols ? nullptr : E->W[0]) && E->Whi[0] && E->Hhi;
     if (E->ao_images && cols) {
-        if ((rc = lazy_alloc(E, &E->HThi, (int64_t)E->kp * E->np))) return rc;
-        if ((rc = lazy_alloc(E, &E->HTlo, (int64_t)E->kp * E->np))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->HThi, (int64_t)E->kp * E->np))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->HTlo, (int64_t)E->kp * E->np))) return rc;
     }
     const int* hint_rd = hinted ? &E->state->ao_hint[cols ? 0 : 1][parity & 1] : nullptr;
     int* hint_wr = hinted ? &E->state->ao_hint[cols ? 0 : 1][(parity & 1) ^ 1] : nullptr;
@@ -1847,6 +1839,19 @@ static int ao_w_products(nmfx_engine* E, int64_t j, int64_t min_iter, double tol
     return nmfx_launch_prepare(E, E->HHt, 0, j, min_iter, tol1, tol2, -1.0);
 }
 
+// round `r` of the W sub-problem.  decided: where the stop decision of the round before is read: nullptr = this handle's own norm
+// sums; row-sharded: the all-reduced sums at E->xf64 + 1, and this rank's sums of the round follow them there
+static int ao_w_round(nmfx_engine* E, int prox_w, double lam_w, int r, const double* decided) {
+    int rc;
+    if ((rc = inner_rows(E, E->W[0], prox_w, (float)lam_w, r, r > 0 ? decided : nullptr))) return rc;
+    return decided ? nmfx_gather_round_norms(E, (int)(E->mp / 64), r) : NMFX_OK;
+}
+
+// behind the last round: the inner-iteration bookkeeping of the W sub-problem (ao_new_pair_objective follows it)
+static int ao_w_close(nmfx_engine* E, int admm_iter, int64_t j, const double* decided) {
+    return nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1, decided);
+}
+
 // One outer iteration with the inversions beside the products (ao_overlap):
 //   gram(W^T W slabs) | product_h [B^T slabs + objective || (W^T W + rho I)^-1] | rounds of H (slab sum, obj[j], stop rule) |
 //   gram(H H^T slabs) | product_w [A slabs || (H H^T + rho I)^-1] | rounds of W (they add the A slabs themselves)
@@ -1906,50 +1911,74 @@ static int aoadmm_eu_iteration(nmfx_engine* E, int prox_w, double lam_w, int pro
       if (ao_fused_enabled(E, admm_iter)) {
           if ((rc = ao_fused_subproblem(E, false, W, prox_w, (float)lam_w, admm_iter, E->inner_hist + j * 2 + 1, (int)(j & 1)))) return rc;
       } else {
-          for (int r = 0; r < admm_iter; ++r) if ((rc = inner_rows(E, W, prox_w, (float)lam_w, r))) return rc;
-          if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1))) return rc;
+          for (int r = 0; r < admm_iter; ++r) if ((rc = ao_w_round(E, prox_w, lam_w, r, nullptr))) return rc;
+          if ((rc = ao_w_close(E, admm_iter, j, nullptr))) return rc;
       } }
     // ---- objective of the new pair (utils.py:29), summed by the next pack / finish ----
     return ao_new_pair_objective(E);
 }
 
+// ---- the exact-f32 KL iteration (ao_admm.py:71-101, 274-289) in steps: a run loops over them, nmfx_aoadmm_kl_phase_* call one each ----
+// W^T S of round `r` (round 0: and W^T W) packed into the exchange buffers
+static int ao_kl_h_products(nmfx_engine* E, int r) {
+    int rc;
+    float* W = E->W[0];
+    const int* stop = r > 0 ? &E->state->inner_stop : nullptr;
+    const bool fuse_g = r == 0 && nmfx_hphase_can_fuse_gram(E);
+    if (r == 0 && !fuse_g && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
+    if ((rc = nmfx_launch_hphase(E, W, fuse_g, E->S, stop))) return rc;
+    return nmfx_launch_pack(E, stop);
+}
+
+// round `r` of the H sub-problem behind its products (round 0: and behind `prepare`): solve / prox / dual step, then v_aux, dual_v
+static int ao_kl_h_round(nmfx_engine* E, int prox_h, double lam_h, int r) {
+    int rc;
+    if (ao_is_l1inf(prox_h)) rc = ao_l1inf_round(E, true, prox_h, lam_h, r);      // (r5: the reference runs these too, until its Cholesky fails)
+    else rc = nmfx_inner_cols(E, E->Minv, E->auxH, 0, prox_h, (float)lam_h, r);
+    if (rc) return rc;
+    return nmfx_launch_kl_vaux(E, E->W[0], E->auxH, &E->state->inner_stop);
+}
+// inner-iteration bookkeeping of the H sub-problem, then H H^T and (H H^T + rho I)^-1 for the W side
+static int ao_kl_h_close(nmfx_engine* E, int admm_iter, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    int rc;
+    if ((rc = nmfx_inner_finish(E, (int)(E->np / 64), admm_iter, E->inner_hist + j * 2))) return rc;
+    if ((rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
+    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, (int64_t)E->kp * E->kp, E->HHt))) return rc;
+    return nmfx_launch_prepare(E, E->HHt, 0, j, min_iter, tol1, tol2, -1.0);
+}
+
+// round `r` of the W sub-problem (transposed data): S H^T, solve / prox / dual step, v_aux, dual_v.  decided: as for ao_w_round
+static int ao_kl_w_round(nmfx_engine* E, int prox_w, double lam_w, int r, const double* decided) {
+    int rc;
+    float* W = E->W[0];
+    const int* stop = &E->state->inner_stop;
+    if ((rc = nmfx_launch_wphase(E, W, true, false, false, E->H, E->S, stop))) return rc;
+    if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum))) return rc;
+    if (ao_is_l1inf(prox_w)) rc = ao_l1inf_round(E, false, prox_w, lam_w, r);
+    else rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 0, prox_w, (float)lam_w, r, r > 0 ? decided : nullptr);
+    if (rc) return rc;
+    if ((rc = nmfx_launch_kl_vaux(E, E->auxW, E->H, stop))) return rc;
+    return decided ? nmfx_gather_round_norms(E, (int)(E->mp / 64), r) : NMFX_OK;
+}
+// bookkeeping of the W sub-problem and the KL objective partials of the new pair (utils.py:21-26)
+static int ao_kl_w_close(nmfx_engine* E, int admm_iter, int64_t j, const double* decided) {
+    int rc;
+    if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1, decided))) return rc;
+    return nmfx_launch_wphase(E, E->W[0], false, true, true);
+}
+
 static int aoadmm_kl_iteration(nmfx_engine* E, int prox_w, double lam_w, int prox_h, double lam_h,
                                int admm_iter, int64_t min_iter, double tol1, double tol2, int64_t j) {
     int rc;
-    float* W = E->W[0];
-    const int64_t kk = (int64_t)E->kp * E->kp;
-    const int* stop = &E->state->inner_stop;
-    // ---- H sub-problem ----
-    const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
-    if (!fuse_g && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_hphase(E, W, fuse_g, E->S))) return rc;
-    if ((rc = nmfx_launch_pack(E))) return rc;
+    if ((rc = ao_kl_h_products(E, 0))) return rc;
     if ((rc = nmfx_launch_prepare(E, E->xf32 + (int64_t)E->kp * E->np, 1, j, min_iter, tol1, tol2, -1.0))) return rc;
     for (int r = 0; r < admm_iter; ++r) {
-        if (r > 0) {
-            if ((rc = nmfx_launch_hphase(E, W, false, E->S, stop))) return rc;
-            if ((rc = nmfx_launch_pack(E, stop))) return rc;
-        }
-        if (ao_is_l1inf(prox_h)) rc = ao_l1inf_round(E, true, prox_h, lam_h, r);      // (r5: the reference runs these too, until its Cholesky fails)
-        else rc = nmfx_inner_cols(E, E->Minv, E->auxH, 0, prox_h, (float)lam_h, r);
-        if (rc) return rc;
-        if ((rc = nmfx_launch_kl_vaux(E, W, E->auxH, stop))) return rc;
+        if (r > 0 && (rc = ao_kl_h_products(E, r))) return rc;
+        if ((rc = ao_kl_h_round(E, prox_h, lam_h, r))) return rc;
     }
-    if ((rc = nmfx_inner_finish(E, (int)(E->np / 64), admm_iter, E->inner_hist + j * 2))) return rc;
-    // ---- W sub-problem (transposed data) ----
-    if ((rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
-    if ((rc = nmfx_launch_prepare(E, E->HHt, 0, j, min_iter, tol1, tol2, -1.0))) return rc;
-    for (int r = 0; r < admm_iter; ++r) {
-        if ((rc = nmfx_launch_wphase(E, W, true, false, false, E->H, E->S, stop))) return rc;
-        if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum))) return rc;
-        if (ao_is_l1inf(prox_w)) rc = ao_l1inf_round(E, false, prox_w, lam_w, r);
-        else rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 0, prox_w, (float)lam_w, r);
-        if (rc) return rc;
-        if ((rc = nmfx_launch_kl_vaux(E, E->auxW, E->H, stop))) return rc;
-    }
-    if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1))) return rc;
-    return nmfx_launch_wphase(E, W, false, true, true);            // KL objective (utils.py:21-26)
+    if ((rc = ao_kl_h_close(E, admm_iter, min_iter, tol1, tol2, j))) return rc;
+    for (int r = 0; r < admm_iter; ++r) if ((rc = ao_kl_w_round(E, prox_w, lam_w, r, nullptr))) return rc;
+    return ao_kl_w_close(E, admm_iter, j, nullptr);
 }
 
 // The KL-loss iteration on the split-bf16 kernels (r4; k padded to 64 or 128, one GPU; NMFX_KL_BF16=0 keeps the exact-f32 launches
@@ -1959,8 +1988,7 @@ static int aoadmm_kl_iteration(nmfx_engine* E, int prox_w, double lam_w, int pro
 // rows m for W) and are transposed at the two switches of an outer iteration.  16384 x 8192, k = 128, ten rounds each: 26.0 -> see
 // DESIGN 4b (the exact-f32 auxiliaries alone took 933 us per round).
 static bool ao_kl_bf16(const nmfx_engine* E) {
-    static const bool on = !(getenv("NMFX_KL_BF16") && atoi(getenv("NMFX_KL_BF16")) == 0);
-    return on && ao_bf16(E);
+    return nmfx_kl_bf16_on() && ao_bf16(E);
 }
 
 // KL(V, W H) partials of the current pair from the images of W and H (split-bf16 product, one pass over the tile-major V)
@@ -1985,12 +2013,12 @@ static int aoadmm_kl_iteration_bf16(nmfx_engine* E, int prox_w, double lam_w, in
     // ---- H sub-problem (state in the orientation of V^T) ----
     // r5: the first product of a sub-problem reads S where the other sub-problem's auxiliaries left it (transposing requests, NMFX_KL_GATHER=0:
     // a transposed copy as before); only dual_v changes orientation between the sub-problems
-    static const bool gather = !(getenv("NMFX_KL_GATHER") && atoi(getenv("NMFX_KL_GATHER")) == 0);
+    const bool gather = nmfx_kl_gather_on();
     if ((rc = nmfx_bf16_kl_orient(E, 0, true, !gather))) return rc;
     if (!E->derived.wimg_ok && (rc = nmfx_bf16_images_w(E, W, 0))) return rc;  // W^T images: Y of the products and of the auxiliaries (left by the objective pass)
     // r5: the auxiliaries of round r also form the product of round r + 1 (S stays in registers; NMFX_KL_FUSE=0: separate launches).  At k padded to
     // 64 the products' Gram by-product (W^T W, H H^T) is that of round 0's launch: the slabs stay where they are, the fixed factor does not change
-    static const bool fuse = !(getenv("NMFX_KL_FUSE") && atoi(getenv("NMFX_KL_FUSE")) == 0);
+    const bool fuse = nmfx_kl_fuse_on();
     for (int r = 0; r < admm_iter; ++r) {
         if (r == 0 || !fuse) {
             E->xyt_flag2 = r > 0 ? stop : nullptr;
@@ -2140,11 +2168,7 @@ extern "C" int nmfx_aoadmm_phase_w_round(nmfx_handle_t E, int prox_w, double lam
     if (prox_w != NMFX_PROX_NN && prox_w != NMFX_PROX_L1N) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
     if (E->kp > 128) return nmfx_generic_aoadmm_phase(E, 3, prox_w, lambda_w, 0, 0, 0.0, 0.0, 0, round);
-    if ((rc = inner_rows(E, E->W[0], prox_w, (float)lambda_w, round, round > 0 ? E->xf64 + 1 : nullptr))) return rc;
-    hipLaunchKernelGGL(ao_norm_gather_kernel, dim3(1), dim3(256), 0, E->stream, E->state, E->nrm_part,
-                       (int)(E->mp / 64), round, E->xf64 + 1);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
+    return ao_w_round(E, prox_w, lambda_w, round, E->xf64 + 1);
 }
 
 // After the last round's all-reduce: inner-iteration bookkeeping and the objective partials of
@@ -2154,7 +2178,7 @@ extern "C" int nmfx_aoadmm_phase_w_close(nmfx_handle_t E, int admm_iter, int64_t
     NMFX_DENSE_ONLY(E);
     int rc = ao_sharded_ready(E, j, true); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_phase(E, 4, 0, 0.0, admm_iter, 0, 0.0, 0.0, j, 0);
-    if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1, E->xf64 + 1))) return rc;
+    if ((rc = ao_w_close(E, admm_iter, j, E->xf64 + 1))) return rc;
     return ao_new_pair_objective(E);
 }
 
@@ -2177,17 +2201,8 @@ extern "C" int nmfx_aoadmm_kl_phase_h_products(nmfx_handle_t E, int64_t j, int r
     int rc = ao_kl_sharded_ready(E, j); if (rc) return rc;
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 0, 0, 0.0, 0, 0, 0.0, 0.0, j, round);
-    float* W = E->W[0];
-    if (round == 0) {
-        if (j == 0 && (rc = nmfx_launch_wphase(E, W, false, true, true))) return rc;      // obj[0] partials (ao_admm.py:256)
-        const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
-        if (!fuse_g && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
-        if ((rc = nmfx_launch_hphase(E, W, fuse_g, E->S))) return rc;
-        return nmfx_launch_pack(E);
-    }
-    const int* stop = &E->state->inner_stop;
-    if ((rc = nmfx_launch_hphase(E, W, false, E->S, stop))) return rc;
-    return nmfx_launch_pack(E, stop);
+    if (round == 0 && j == 0 && (rc = nmfx_launch_wphase(E, E->W[0], false, true, true))) return rc;      // obj[0] partials (ao_admm.py:256)
+    return ao_kl_h_products(E, round);
 }
 
 extern "C" int nmfx_aoadmm_kl_phase_h_round(nmfx_handle_t E, int prox_h, double lambda_h, int round, int64_t min_iter,
@@ -2198,8 +2213,7 @@ extern "C" int nmfx_aoadmm_kl_phase_h_round(nmfx_handle_t E, int prox_h, double 
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 1, prox_h, lambda_h, 0, min_iter, tol1, tol2, j, round);
     if (round == 0 && (rc = nmfx_launch_prepare(E, E->xf32 + (int64_t)E->kp * E->np, 1, j, min_iter, tol1, tol2, -1.0))) return rc;
-    if ((rc = nmfx_inner_cols(E, E->Minv, E->auxH, 0, prox_h, (float)lambda_h, round))) return rc;
-    return nmfx_launch_kl_vaux(E, E->W[0], E->auxH, &E->state->inner_stop);
+    return ao_kl_h_round(E, prox_h, lambda_h, round);
 }
 
 extern "C" int nmfx_aoadmm_kl_phase_h_close(nmfx_handle_t E, int admm_iter, int64_t min_iter, double tol1, double tol2,
@@ -2207,11 +2221,7 @@ extern "C" int nmfx_aoadmm_kl_phase_h_close(nmfx_handle_t E, int admm_iter, int6
     NMFX_DENSE_ONLY(E);
     int rc = ao_kl_sharded_ready(E, j); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 2, 0, 0.0, admm_iter, min_iter, tol1, tol2, j, 0);
-    const int64_t kk = (int64_t)E->kp * E->kp;
-    if ((rc = nmfx_inner_finish(E, (int)(E->np / 64), admm_iter, E->inner_hist + j * 2))) return rc;
-    if ((rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
-    return nmfx_launch_prepare(E, E->HHt, 0, j, min_iter, tol1, tol2, -1.0);
+    return ao_kl_h_close(E, admm_iter, min_iter, tol1, tol2, j);
 }
 
 // One round of the W sub-problem on this rank's rows; leaves this rank's norm sums of the round in the f64 exchange
@@ -2222,25 +2232,14 @@ extern "C" int nmfx_aoadmm_kl_phase_w_round(nmfx_handle_t E, int prox_w, double 
     if (!kl_prox_ok(prox_w)) { E->err = "Unknown prox_type."; return NMFX_E_ARG; }
     if (round < 0) { E->err = "negative round"; return NMFX_E_ARG; }
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 3, prox_w, lambda_w, 0, 0, 0.0, 0.0, 0, round);
-    float* W = E->W[0];
-    const int* stop = &E->state->inner_stop;
-    if ((rc = nmfx_launch_wphase(E, W, true, false, false, E->H, E->S, stop))) return rc;
-    if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum))) return rc;
-    if ((rc = nmfx_inner_rows(E, E->Asum, W, E->Minv, E->auxW, 0, prox_w, (float)lambda_w, round,
-                              round > 0 ? E->xf64 + 1 : nullptr))) return rc;
-    if ((rc = nmfx_launch_kl_vaux(E, E->auxW, E->H, stop))) return rc;
-    hipLaunchKernelGGL(ao_norm_gather_kernel, dim3(1), dim3(256), 0, E->stream, E->state, E->nrm_part,
-                       (int)(E->mp / 64), round, E->xf64 + 1);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
+    return ao_kl_w_round(E, prox_w, lambda_w, round, E->xf64 + 1);
 }
 
 extern "C" int nmfx_aoadmm_kl_phase_w_close(nmfx_handle_t E, int admm_iter, int64_t j) {
     NMFX_DENSE_ONLY(E);
     int rc = ao_kl_sharded_ready(E, j); if (rc) return rc;
     if (E->kp > 128) return nmfx_generic_aoadmm_kl_phase(E, 4, 0, 0.0, admm_iter, 0, 0.0, 0.0, j, 0);
-    if ((rc = nmfx_inner_finish(E, (int)(E->mp / 64), admm_iter, E->inner_hist + j * 2 + 1, E->xf64 + 1))) return rc;
-    return nmfx_launch_wphase(E, E->W[0], false, true, true);                             // KL objective partials (utils.py:21-26)
+    return ao_kl_w_close(E, admm_iter, j, E->xf64 + 1);
 }
 
 // Row-sharded W sub-problem with ONE exchange instead of one per round: all admm_iter rounds run speculatively on

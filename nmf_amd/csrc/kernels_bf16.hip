@@ -1819,14 +1819,6 @@ __global__ __launch_bounds__(512) void mur_h_unpack_bf16_kernel(
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <typename T>
-static int lazy_alloc(nmfx_engine* E, T** p, int64_t count) {
-    if (*p) return NMFX_OK;
-    NMFX_HIP(hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T)));
-    NMFX_HIP(hipMemsetAsync(*p, 0, (size_t)count * sizeof(T), E->stream));
-    return NMFX_OK;
-}
-
 bool nmfx_bf16_supported(const nmfx_engine* E) { return (E->kp == 64 || E->kp == 128) && E->mp % 128 == 0 && E->np % 128 == 0; }
 
 template <bool OBJ, int TERMS, bool KL = false, int KP = 64, bool WITH_A = true>
@@ -1886,7 +1878,7 @@ static int launch_xyt(nmfx_engine* E, bool obj, const float* X, int64_t ldx, int
 }
 
 static int kl_part_alloc(nmfx_engine* E) {
-    return lazy_alloc(E, &E->kl_part, (int64_t)(E->np / 64 + E->mp / 64) * E->kp);
+    return nmfx_lazy_alloc(E, &E->kl_part, (int64_t)(E->np / 64 + E->mp / 64) * E->kp);
 }
 
 // W_new, its images in both layouts (buffer `nxt`), and the column-sum partials kl_part[np/64 ..][kp] (mp / 64 of them)
@@ -1906,8 +1898,8 @@ int nmfx_bf16_kl_h_epilogue(nmfx_engine* E, float lam, int64_t j, int64_t min_it
     ProfScope ps(E, "h_update");
     int rc;
     if ((rc = kl_part_alloc(E))) return rc;
-    if ((rc = lazy_alloc(E, &E->HThi, (int64_t)E->kp * E->np))) return rc;
-    if ((rc = lazy_alloc(E, &E->HTlo, (int64_t)E->kp * E->np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->HThi, (int64_t)E->kp * E->np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->HTlo, (int64_t)E->kp * E->np))) return rc;
     hipLaunchKernelGGL(kl_h_epilogue_kernel, dim3((unsigned)(E->np / 64), (unsigned)(E->kp / 64)), dim3(256), 0, E->stream,
                        E->xf32, E->xf64, E->H, E->np, E->kp, E->k, lam, (long long)j, (long long)min_iter, tol1, tol2,
                        E->state, E->obj_hist, E->Hhi, E->Hlo, E->HThi, E->HTlo, E->kl_part);
@@ -1923,16 +1915,16 @@ int nmfx_bf16_prepare(nmfx_engine* E) {
     int rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
     if ((rc = nmfx_need_v(E))) return rc;              // (a second prepare after new factors / new rows of V)
-    if ((rc = lazy_alloc(E, &E->Vt, mp * np))) return rc;
-    if ((rc = lazy_alloc(E, &E->Vtile, mp * np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->Vt, mp * np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->Vtile, mp * np))) return rc;
     for (int b = 0; b < 2; ++b) {
-        if ((rc = lazy_alloc(E, &E->Whi[b], mp * kp))) return rc;
-        if ((rc = lazy_alloc(E, &E->Wlo[b], mp * kp))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->Whi[b], mp * kp))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->Wlo[b], mp * kp))) return rc;
     }
-    if ((rc = lazy_alloc(E, &E->WThi, mp * kp))) return rc;
-    if ((rc = lazy_alloc(E, &E->WTlo, mp * kp))) return rc;
-    if ((rc = lazy_alloc(E, &E->Hhi, kp * np))) return rc;
-    if ((rc = lazy_alloc(E, &E->Hlo, kp * np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->WThi, mp * kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->WTlo, mp * kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->Hhi, kp * np))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->Hlo, kp * np))) return rc;
     // splits of the H phase: rows of V^T are columns of V
     // one 512-thread block per CU: grid = (rows / 128) x splits ~ number of CUs
     const int64_t rbt = np / 128, cbt = mp / 64;
@@ -1947,7 +1939,7 @@ int nmfx_bf16_prepare(nmfx_engine* E) {
     // (a chain of dependent L2 reads), so keep that product at 16 -- short shards already have many splits
     E->gram_ng_w = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, 16 / ws2), mp / 128));
     E->gram_ng_h = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(4, 16 / hs2), np / 128));
-    if ((rc = lazy_alloc(E, &E->Bt_part, hs2 * np * kp))) return rc;
+    if ((rc = nmfx_lazy_alloc(E, &E->Bt_part, hs2 * np * kp))) return rc;
     hipLaunchKernelGGL(transpose_tiled_kernel, dim3((unsigned)(np / 64), (unsigned)(mp / 64)), dim3(256), 0, E->stream,
                        E->V, np, E->Vt, mp);
     hipLaunchKernelGGL(retile_kernel, dim3((unsigned)(np / 64), (unsigned)(mp / 128)), dim3(256), 0, E->stream,
@@ -1977,8 +1969,8 @@ int nmfx_bf16_images_h(nmfx_engine* E, bool transposed, const float* src) {   //
     int rc;
     E->derived.himg_both = transposed && !src;
     if (transposed) {
-        if ((rc = lazy_alloc(E, &E->HThi, (int64_t)E->kp * E->np))) return rc;
-        if ((rc = lazy_alloc(E, &E->HTlo, (int64_t)E->kp * E->np))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->HThi, (int64_t)E->kp * E->np))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->HTlo, (int64_t)E->kp * E->np))) return rc;
     }
     hipLaunchKernelGGL(split_images_kernel, dim3((unsigned)(E->np / 64), (unsigned)(E->kp / 64)), dim3(256), 0, E->stream,
                        src ? src : E->H, (int64_t)E->kp, E->np, E->np, E->Hhi, E->Hlo, transposed ? E->HThi : nullptr,
@@ -2018,8 +2010,8 @@ int nmfx_bf16_kl_state(nmfx_engine* E, bool reset) {
     int rc;
     const int64_t cnt = E->mp * E->np;
     for (int i = 0; i < 2; ++i) {
-        if ((rc = lazy_alloc(E, &E->kl_S[i], cnt))) return rc;
-        if ((rc = lazy_alloc(E, &E->kl_DV[i], cnt))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->kl_S[i], cnt))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->kl_DV[i], cnt))) return rc;
     }
     if (reset) {           // v_aux = dual_v = 0 (ao_admm.py:28-30, admm.py:31-35: both names are bound to ONE array of zeros)
         for (int i = 0; i < 2; ++i) {
@@ -2225,7 +2217,7 @@ __global__ __launch_bounds__(256) void pack_t_kernel(
 
 // ---- stream-K plan (see xyt32_bf16_kernel<..., SK>) ----
 bool nmfx_sk_enabled(const nmfx_engine* E) {
-    static const bool on = !(getenv("NMFX_SK") && atoi(getenv("NMFX_SK")) == 0);
+    static const bool on = nmfx_knob_on("NMFX_SK");
     return on && E->kp == 128 && E->precision == 1 && nmfx_bf16_supported(E);
 }
 
@@ -2268,7 +2260,7 @@ static int sk_plan(nmfx_engine* E, int side) {
     workers = deal(lo, &ends);
     std::vector<int4> seg;
     std::vector<int> first(workers + 1), cnt(rb, 0);
-    static const bool cyclic = !(getenv("NMFX_SK_CYCLIC") && atoi(getenv("NMFX_SK_CYCLIC")) == 0);
+    static const bool cyclic = nmfx_knob_on("NMFX_SK_CYCLIC");
     for (int64_t w = 0; w < workers; ++w) {
         first[w] = (int)seg.size();
         int64_t u = w ? ends[w - 1] : 0, tau = 0;      // tau: groups this worker has done before the segment (its clock)
@@ -2525,7 +2517,7 @@ static int bf16_gram_images(nmfx_engine* E, const unsigned short* hi, const unsi
     const bool fold = S > keep;
     float* dst = out;
     if (fold) {
-        if ((rc = lazy_alloc(E, &E->G_big, (int64_t)256 * kk))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &E->G_big, (int64_t)256 * kk))) return rc;
         dst = E->G_big;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)S), dim3(KP * 4), shm, E->stream, hi, lo, ld, nsteps, dst, &E->state->flag);

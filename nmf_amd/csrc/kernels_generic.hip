@@ -1191,14 +1191,14 @@ int gxb_prepare(nmfx_engine* E, const float* W, bool kl = false) {
 
 }  // namespace
 
-static bool gx_anls_bf16() { static const bool on = !(getenv("NMFX_GX_ANLS_BF16") && atoi(getenv("NMFX_GX_ANLS_BF16")) == 0); return on; }
+static bool gx_anls_bf16() { static const bool on = nmfx_knob_on("NMFX_GX_ANLS_BF16"); return on; }
 
 // r4: the denominator products of the Euclidean updates, D = W (H H^T) and E = (W^T W) H, from the factor images and the images of the
 // k x k Gram matrix (three terms, like the numerators they are divided into) instead of an exact-f32 product: 2 m k^2 flop that took
 // 28 us at k = 256 and 110 us at k = 512 on the f32 matrix cores.  Measured (16384 x 8192): W side k = 512 130 -> 102 us per update,
 // k = 256 no gain (the image launch and a 64-block grid eat it): used for the W side from kp = 384 on.  H side never: 80 against 77 us
 // at k = 512, 51 against 47 at k = 256 -- 32 blocks of 256 x 256 for a kp x np output.  out [rows][kp] = F G (F images: rows x kp)
-static bool gx_bf16_den() { static const bool on = !(getenv("NMFX_GX_DEN_BF16") && atoi(getenv("NMFX_GX_DEN_BF16")) == 0); return on; }
+static bool gx_bf16_den() { static const bool on = nmfx_knob_on("NMFX_GX_DEN_BF16"); return on; }
 static int gx_den_product(nmfx_engine* E, const float* G, const unsigned short* Fhi, const unsigned short* Flo, int64_t ents, float* out) {
     int rc;
     const int64_t kp = E->kp;
@@ -1565,6 +1565,24 @@ __global__ __launch_bounds__(256) void gx_bgj_finish_kernel(const double* __rest
 // work area gx_w64: two kp x kp matrices, D^-1 [128][128], C [kp][128]
 int64_t gx_w64_count(int64_t kp) { return 2 * kp * kp + 128 * 128 + kp * 128; }
 
+// the buffers of the composed ADMM-family iterations
+int gx_admm_buffers(nmfx_engine* E) {
+    int rc;
+    const int64_t mp = E->mp, np = E->np, kp = E->kp;
+    if ((rc = gx_buffers(E, false))) return rc;
+    if ((rc = gx_alloc(E, &E->gx_r, std::max(mp, np) * kp))) return rc;
+    if ((rc = gx_alloc(E, &E->gx_w64, gx_w64_count(kp)))) return rc;
+    return gx_alloc(E, &E->gx_nrm, std::max(mp, np) * kp / 1024 * 4 + 64);
+}
+
+// obj[j] from xf64[0] and the stop rule of the outer loop (it sets the flag every later launch of the iteration reads)
+int gx_record(nmfx_engine* E, int64_t j, int64_t min_iter, double tol1, double tol2) {
+    hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
+                       E->state, E->obj_hist);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
 int gx_prepare(nmfx_engine* E, const float* G, double fixed_rho) {
     ProfScope ps(E, "prepare");
     int rc;
@@ -1590,102 +1608,8 @@ int gx_prepare(nmfx_engine* E, const float* G, double fixed_rho) {
     return NMFX_OK;
 }
 
-// one sub-problem (ao_admm.py:46-68) on the factor X ([rows][cols] with the factor index along `cols` for W: rows = m,
-// cols = kp -- or along `rows` for H: rows = kp, cols = n), its dual U, the Gram matrix G and the cross product B
-int gx_ao_subproblem(nmfx_engine* E, bool hside, const float* G, const float* B, float* X, float* U, int prox, float lam, int admm_iter,
-                     int32_t* slot) {
-    int rc;
-    const int64_t kp = E->kp, rows = hside ? kp : E->mp, cols = hside ? E->np : kp, cnt4 = rows * cols / 4;
-    if ((rc = gx_prepare(E, G, -1.0))) return rc;
-    ProfScope ps(E, hside ? "inner_h" : "inner_w");
-    static const bool one_launch = !(getenv("NMFX_GX_ROUNDS") && atoi(getenv("NMFX_GX_ROUNDS")) == 4);
-    if (one_launch && kp <= 512) {                     // r4: one launch per round (kernels_aoadmm.hip, ao_round_*_any_kernel)
-        for (int r = 0; r < admm_iter; ++r)
-            if ((rc = nmfx_round_any(E, hside, B, X, U, prox, lam, r))) return rc;
-        return nmfx_inner_finish(E, (int)((hside ? E->np : E->mp) / 64), admm_iter, slot);
-    }
-    const int nblk = (int)((cnt4 + 255) / 256);
-    const int* stop = &E->state->inner_stop;
-    for (int r = 0; r < admm_iter; ++r) {
-        if (r == 0) {                                  // (later rounds: the prox launch of the round before has left the right-hand side)
-            hipLaunchKernelGGL(gx_rhs_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, B, (const float*)X, (const float*)U, E->gx_r, cnt4,
-                               (const DevState*)E->state);
-            NMFX_HIP(hipGetLastError());
-        }
-        if (hside) rc = gx_launch<true, false>(E, GX_STORE, E->Minv, kp, E->gx_r, cols, E->gx_d, cols, 0, kp, cols, kp, 1, nullptr, 0, nullptr, stop);
-        else rc = gx_launch<true, false>(E, GX_STORE, E->gx_r, kp, E->Minv, kp, E->gx_d, kp, 0, rows, kp, kp, 1, nullptr, 0, nullptr, stop);
-        if (rc) return rc;
-        hipLaunchKernelGGL(gx_prox_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, (const float*)E->gx_d, X, U, prox, lam, cnt4, E->gx_nrm,
-                           (const DevState*)E->state, r + 1 < admm_iter ? B : (const float*)nullptr, E->gx_r);
-        hipLaunchKernelGGL(gx_decide_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->state);
-        NMFX_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(gx_close_kernel, dim3(1), dim3(1), 0, E->stream, E->state, slot);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-
-int gx_objective_partial(nmfx_engine* E, bool bf = false) {      // 1/2 ||V - W H||^2 of the current pair -> xf64[0]  (bf: from the images of W[0] and H^T)
-    int rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp;
-    { ProfScope ps(E, "objective");
-      if (bf) rc = gxr_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], E->HThi, E->HTlo, 0, mp, np, kp, E->V, np, E->gx_part);
-      else rc = gx_launch<true, false>(E, GX_RESID, E->W[0], kp, E->H, np, nullptr, 0, 0, mp, np, kp, 1, E->V, np, E->gx_part);
-      if (rc) return rc; }
-    return nmfx_launch_obj_reduce(E, (mp / GX_T) * (np / GX_T), E->gx_part);
-}
-
-}  // namespace
-
-int nmfx_generic_aoadmm_run(nmfx_engine* E, int prox_w, double lam_w, int prox_h, double lam_h, int admm_iter, int64_t min_iter,
-                            double tol1, double tol2, int64_t first, int64_t count) {
-    int rc;
-    if ((rc = gx_buffers(E, false))) return rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp;
-    if ((rc = gx_alloc(E, &E->gx_r, std::max(mp, np) * kp))) return rc;
-    if ((rc = gx_alloc(E, &E->gx_w64, gx_w64_count(kp)))) return rc;
-    if ((rc = gx_alloc(E, &E->gx_nrm, std::max(mp, np) * kp / 1024 * 4 + 64))) return rc;
-    float* W = E->W[0];
-    float* xB = E->xf32;
-    float* xG = E->xf32 + kp * np;
-    // split-bf16 runs: the three V-sized products (W^T V, V H^T, the objective's W H) from the V planes and the factor images, three
-    // terms as in the tuned AO-ADMM (kernels_bf16.hip, top); the Gram matrices, whose shifted inverse the rounds apply, stay exact f32
-    bool bf = gxb_on(E);
-    if (bf) { rc = gxb_prepare(E, W); if (rc == GXB_NOFIT) bf = false; else if (rc) return rc; }
-    E->derived.drop(NMFX_D_gxb_img_ready);             // (valid inside this call only: the MUR loop keeps the images of W[j & 1])
-    if (first == 0 && count > 0 && (rc = gx_objective_partial(E, bf))) return rc;      // obj[0] (ao_admm.py:256)
-    for (int64_t j = first; j < first + count; ++j) {
-        hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
-                           E->state, E->obj_hist);
-        NMFX_HIP(hipGetLastError());
-        // H sub-problem: G = W^T W, B = W^T V
-        { ProfScope ps(E, "gram_tn");
-          if ((rc = gx_split_product<false, false>(E, W, kp, W, kp, xG, kp, kp, mp, 64))) return rc; }
-        { ProfScope ps(E, "hphase");
-          if (bf) rc = gxt_split_product(E, E->WThi, E->WTlo, E->gxb_v[2], E->gxb_v[3], xB, kp, np, mp, 8);
-          else rc = gx_split_product<false, false>(E, W, kp, E->V, np, xB, kp, np, mp, 8);
-          if (rc) return rc; }
-        if ((rc = gx_ao_subproblem(E, true, xG, xB, E->H, E->dualH, prox_h, (float)lam_h, admm_iter, E->inner_hist + j * 2))) return rc;
-        if (bf) { ProfScope ps(E, "images");
-                  if ((rc = gxb_images_h(E, E->H))) return rc; }
-        // W sub-problem on the transposed data: G = H H^T, B^T = V H^T
-        { ProfScope ps(E, "gram_nt");
-          if ((rc = gx_split_product<true, true>(E, E->H, np, E->H, np, E->HHt, kp, kp, np, 64))) return rc; }
-        { ProfScope ps(E, "wphase");
-          if (bf) rc = gxt_split_product(E, E->gxb_v[0], E->gxb_v[1], E->Hhi, E->Hlo, E->A_part, mp, kp, np, 4);
-          else rc = gx_split_product<true, true>(E, E->V, np, E->H, np, E->A_part, mp, kp, np, 1);
-          if (rc) return rc; }
-        if ((rc = gx_ao_subproblem(E, false, E->HHt, E->A_part, W, E->dualW, prox_w, (float)lam_w, admm_iter, E->inner_hist + j * 2 + 1))) return rc;
-        if (bf) { ProfScope ps(E, "images");
-                  if ((rc = gxb_images_w(E, W))) return rc; }
-        if ((rc = gx_objective_partial(E, bf))) return rc;
-    }
-    return NMFX_OK;
-}
-
 // (r5) the W side of a row-sharded sub-problem: a round's norm sums of the rank's rows for the caller's all-reduce, and the stop decision
 // of the round before from the all-reduced sums
-namespace {
 __global__ __launch_bounds__(256) void gx_gather_norms_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out, const DevState* __restrict__ st)
 {
     __shared__ double sh[4][4];
@@ -1713,7 +1637,153 @@ __global__ void gx_decide_global_kernel(const double* __restrict__ n, DevState* 
     st->inner_count += 1;
     if (n[0] < 1e-4 * n[1] && n[2] < 1e-4 * n[3]) st->inner_stop = 1;
 }
+
+// The sub-problems (ao_admm.py:46-68) work on the factor X ([rows][cols] with the factor index along `cols` for W: rows = m, cols = kp
+// -- or along `rows` for H: rows = kp, cols = n), its dual U and the cross product B, behind gx_prepare of the Gram matrix.  Up to 512
+// padded components a round is one launch (r4: kernels_aoadmm.hip, ao_round_*_any_kernel; NMFX_GX_ROUNDS=4 keeps the long form in
+// a run), beyond that the rhs / solve / prox launches.  decided: nullptr = the stop decision of a round from the handle's own norm
+// sums; row-sharded W side (E->xf64 + 1) = of the round BEFORE from the all-reduced sums there, and the rank's sums of this round
+// follow them there for the caller's all-reduce
+bool gx_ao_long_form(const nmfx_engine* E, bool sharded) {
+    static const bool one_launch = !(getenv("NMFX_GX_ROUNDS") && atoi(getenv("NMFX_GX_ROUNDS")) == 4);
+    return E->kp > 512 || (!sharded && !one_launch);
+}
+
+int gx_decide_global(nmfx_engine* E, const double* decided) {
+    hipLaunchKernelGGL(gx_decide_global_kernel, dim3(1), dim3(1), 0, E->stream, decided, E->state);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+// round `r`; leave_rhs: the prox launch leaves the right-hand side of the round after it
+int gx_ao_round(nmfx_engine* E, bool hside, const float* B, float* X, float* U, int prox, float lam, int r, bool leave_rhs, const double* decided) {
+    int rc;
+    const int64_t kp = E->kp, rows = hside ? kp : E->mp, cols = hside ? E->np : kp, cnt4 = rows * cols / 4;
+    if (!gx_ao_long_form(E, decided != nullptr)) {
+        if ((rc = nmfx_round_any(E, hside, B, X, U, prox, lam, r, r > 0 ? decided : nullptr))) return rc;
+        return decided ? nmfx_gather_round_norms(E, (int)(E->mp / 64), r) : NMFX_OK;
+    }
+    const int nblk = (int)((cnt4 + 255) / 256);
+    const int* stop = &E->state->inner_stop;
+    if (r == 0) {                                      // (later rounds: the prox launch of the round before has left the right-hand side)
+        hipLaunchKernelGGL(gx_rhs_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, B, (const float*)X, (const float*)U, E->gx_r, cnt4,
+                           (const DevState*)E->state);
+        NMFX_HIP(hipGetLastError());
+    } else if (decided && (rc = gx_decide_global(E, decided))) return rc;
+    if (hside) rc = gx_launch<true, false>(E, GX_STORE, E->Minv, kp, E->gx_r, cols, E->gx_d, cols, 0, kp, cols, kp, 1, nullptr, 0, nullptr, stop);
+    else rc = gx_launch<true, false>(E, GX_STORE, E->gx_r, kp, E->Minv, kp, E->gx_d, kp, 0, rows, kp, kp, 1, nullptr, 0, nullptr, stop);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gx_prox_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, (const float*)E->gx_d, X, U, prox, lam, cnt4, E->gx_nrm,
+                       (const DevState*)E->state, leave_rhs ? B : (const float*)nullptr, E->gx_r);
+    if (decided) hipLaunchKernelGGL(gx_gather_norms_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->xf64 + 1, (const DevState*)E->state);
+    else hipLaunchKernelGGL(gx_decide_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->state);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+// behind the last round: the inner-round bookkeeping of the sub-problem
+int gx_ao_finish(nmfx_engine* E, bool hside, int admm_iter, int32_t* slot, const double* decided) {
+    int rc;
+    if (!gx_ao_long_form(E, decided != nullptr)) return nmfx_inner_finish(E, (int)((hside ? E->np : E->mp) / 64), admm_iter, slot, decided);
+    if (decided && admm_iter > 0 && (rc = gx_decide_global(E, decided))) return rc;
+    hipLaunchKernelGGL(gx_close_kernel, dim3(1), dim3(1), 0, E->stream, E->state, slot);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+int gx_ao_subproblem(nmfx_engine* E, bool hside, const float* B, float* X, float* U, int prox, float lam, int admm_iter, int32_t* slot) {
+    int rc;
+    ProfScope ps(E, hside ? "inner_h" : "inner_w");
+    for (int r = 0; r < admm_iter; ++r)
+        if ((rc = gx_ao_round(E, hside, B, X, U, prox, lam, r, r + 1 < admm_iter, nullptr))) return rc;
+    return gx_ao_finish(E, hside, admm_iter, slot, nullptr);
+}
+
+int gx_objective_partial(nmfx_engine* E, bool bf = false) {      // 1/2 ||V - W H||^2 of the current pair -> xf64[0]  (bf: from the images of W[0] and H^T)
+    int rc;
+    const int64_t mp = E->mp, np = E->np, kp = E->kp;
+    { ProfScope ps(E, "objective");
+      if (bf) rc = gxr_launch(E, GX_RESID, E->Whi[0], E->Wlo[0], E->HThi, E->HTlo, 0, mp, np, kp, E->V, np, E->gx_part);
+      else rc = gx_launch<true, false>(E, GX_RESID, E->W[0], kp, E->H, np, nullptr, 0, 0, mp, np, kp, 1, E->V, np, E->gx_part);
+      if (rc) return rc; }
+    return nmfx_launch_obj_reduce(E, (mp / GX_T) * (np / GX_T), E->gx_part);
+}
+
 }  // namespace
+
+// ---- the Euclidean AO-ADMM iteration in steps: nmfx_generic_aoadmm_run runs them in a loop, nmfx_generic_aoadmm_phase one per call ----
+// Split-bf16 runs (*bf): the three V-sized products (W^T V, V H^T, the objective's W H) from the V planes and the factor images, three
+// terms as in the tuned AO-ADMM (kernels_bf16.hip, top); the Gram matrices, whose shifted inverse the rounds apply, stay exact f32.
+// The images are READ by the products of the H and the W side only, and each sub-problem rebuilds those of the factor it has updated:
+// they are (re)built from the factors at the head of a call unless `images_stand` (the phase calls behind h_products).  The planes of V
+// and the buffers are made on first use.
+static int gx_ao_setup(nmfx_engine* E, bool images_stand, bool* bf) {
+    int rc;
+    if ((rc = gx_admm_buffers(E))) return rc;
+    *bf = gxb_on(E);
+    if (images_stand) E->derived.gxb_img_ready = true;
+    if (*bf) { rc = gxb_prepare(E, E->W[0]); if (rc == GXB_NOFIT) *bf = false; else if (rc) return rc; }
+    E->derived.drop(NMFX_D_gxb_img_ready);             // (valid inside this call only: the MUR loop keeps the images of W[j & 1])
+    return NMFX_OK;
+}
+
+// H side: G = W^T W behind the k n part of the f32 exchange buffer, B = W^T V at its head
+static int gx_ao_h_products(nmfx_engine* E, bool bf) {
+    int rc;
+    const int64_t mp = E->mp, np = E->np, kp = E->kp;
+    float* W = E->W[0];
+    { ProfScope ps(E, "gram_tn");
+      if ((rc = gx_split_product<false, false>(E, W, kp, W, kp, E->xf32 + kp * np, kp, kp, mp, 64))) return rc; }
+    ProfScope ps(E, "hphase");
+    if (bf) return gxt_split_product(E, E->WThi, E->WTlo, E->gxb_v[2], E->gxb_v[3], E->xf32, kp, np, mp, 8);
+    return gx_split_product<false, false>(E, W, kp, E->V, np, E->xf32, kp, np, mp, 8);
+}
+
+static int gx_ao_h_solve(nmfx_engine* E, bool bf, int prox_h, float lam_h, int admm_iter, int64_t j) {
+    int rc;
+    if ((rc = gx_prepare(E, E->xf32 + E->kp * E->np, -1.0))) return rc;
+    if ((rc = gx_ao_subproblem(E, true, E->xf32, E->H, E->dualH, prox_h, lam_h, admm_iter, E->inner_hist + j * 2))) return rc;
+    if (!bf) return NMFX_OK;
+    ProfScope ps(E, "images");
+    return gxb_images_h(E, E->H);
+}
+
+// W side on the transposed data: G = H H^T and its shifted inverse, B^T = V H^T
+static int gx_ao_w_products(nmfx_engine* E, bool bf) {
+    int rc;
+    const int64_t mp = E->mp, np = E->np, kp = E->kp;
+    { ProfScope ps(E, "gram_nt");
+      if ((rc = gx_split_product<true, true>(E, E->H, np, E->H, np, E->HHt, kp, kp, np, 64))) return rc; }
+    { ProfScope ps(E, "wphase");
+      if (bf) rc = gxt_split_product(E, E->gxb_v[0], E->gxb_v[1], E->Hhi, E->Hlo, E->A_part, mp, kp, np, 4);
+      else rc = gx_split_product<true, true>(E, E->V, np, E->H, np, E->A_part, mp, kp, np, 1);
+      if (rc) return rc; }
+    return gx_prepare(E, E->HHt, -1.0);
+}
+
+// behind the W sub-problem: the objective partial of the new pair -> xf64[0]
+static int gx_ao_new_pair(nmfx_engine* E, bool bf) {
+    int rc;
+    if (bf) { ProfScope ps(E, "images");
+              if ((rc = gxb_images_w(E, E->W[0]))) return rc; }
+    return gx_objective_partial(E, bf);
+}
+
+int nmfx_generic_aoadmm_run(nmfx_engine* E, int prox_w, double lam_w, int prox_h, double lam_h, int admm_iter, int64_t min_iter,
+                            double tol1, double tol2, int64_t first, int64_t count) {
+    bool bf;
+    int rc = gx_ao_setup(E, false, &bf); if (rc) return rc;
+    if (first == 0 && count > 0 && (rc = gx_objective_partial(E, bf))) return rc;      // obj[0] (ao_admm.py:256)
+    for (int64_t j = first; j < first + count; ++j) {
+        if ((rc = gx_record(E, j, min_iter, tol1, tol2))) return rc;
+        if ((rc = gx_ao_h_products(E, bf))) return rc;
+        if ((rc = gx_ao_h_solve(E, bf, prox_h, (float)lam_h, admm_iter, j))) return rc;
+        if ((rc = gx_ao_w_products(E, bf))) return rc;
+        if ((rc = gx_ao_subproblem(E, false, E->A_part, E->W[0], E->dualW, prox_w, (float)lam_w, admm_iter, E->inner_hist + j * 2 + 1))) return rc;
+        if ((rc = gx_ao_new_pair(E, bf))) return rc;
+    }
+    return NMFX_OK;
+}
 
 // The same iteration in the pieces a ROW-SHARDED run needs (r4; nmfx_aoadmm_phase_* dispatch here beyond 128 components, k <= 512 with one launch per W round,
 // beyond that the rhs / solve / prox launches of gx_ao_subproblem):
@@ -1726,76 +1796,22 @@ __global__ void gx_decide_global_kernel(const double* __restrict__ n, DevState* 
 //   4 w_close:    inner-round bookkeeping, the objective partial of the new pair -> xf64[0]
 int nmfx_generic_aoadmm_phase(nmfx_engine* E, int phase, int prox, double lam, int admm_iter, int64_t min_iter, double tol1, double tol2,
                               int64_t j, int round) {
-    int rc;
-    if ((rc = gx_buffers(E, false))) return rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp;
-    if ((rc = gx_alloc(E, &E->gx_r, std::max(mp, np) * kp))) return rc;
-    if ((rc = gx_alloc(E, &E->gx_w64, gx_w64_count(kp)))) return rc;
-    if ((rc = gx_alloc(E, &E->gx_nrm, std::max(mp, np) * kp / 1024 * 4 + 64))) return rc;
-    float* W = E->W[0];
-    float* xB = E->xf32;
-    float* xG = E->xf32 + kp * np;
-    bool bf = gxb_on(E);
-    // The bf16 images of W and H are READ by the products of phases 0 and 2 only; phases 1 and 4 rebuild the images of the factor they
-    // have updated.  So they are (re)built from the factors at the head of every outer iteration (phase 0: whatever ran on this handle
-    // before, the images are those of the current pair) and left alone in the other phases -- r4 rebuilt both factors' images in EVERY
-    // phase call, the admm_iter W rounds of phase 3 included.  The planes of V and the buffers are made on first use.
-    if (phase != 0) E->derived.gxb_img_ready = true;
-    if (bf) { rc = gxb_prepare(E, W); if (rc == GXB_NOFIT) bf = false; else if (rc) return rc; }
-    E->derived.drop(NMFX_D_gxb_img_ready);
+    bool bf;
+    int rc = gx_ao_setup(E, phase != 0, &bf); if (rc) return rc;
     switch (phase) {
     case 0:
         if (j == 0 && (rc = gx_objective_partial(E, bf))) return rc;              // obj[0] (ao_admm.py:256)
-        { ProfScope ps(E, "gram_tn");
-          if ((rc = gx_split_product<false, false>(E, W, kp, W, kp, xG, kp, kp, mp, 64))) return rc; }
-        { ProfScope ps(E, "hphase");
-          if (bf) rc = gxt_split_product(E, E->WThi, E->WTlo, E->gxb_v[2], E->gxb_v[3], xB, kp, np, mp, 8);
-          else rc = gx_split_product<false, false>(E, W, kp, E->V, np, xB, kp, np, mp, 8);
-          return rc; }
+        return gx_ao_h_products(E, bf);
     case 1:
-        hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
-                           E->state, E->obj_hist);
-        NMFX_HIP(hipGetLastError());
-        if ((rc = gx_ao_subproblem(E, true, xG, xB, E->H, E->dualH, prox, (float)lam, admm_iter, E->inner_hist + j * 2))) return rc;
-        if (bf) { ProfScope ps(E, "images");
-                  if ((rc = gxb_images_h(E, E->H))) return rc; }
-        return NMFX_OK;
+        if ((rc = gx_record(E, j, min_iter, tol1, tol2))) return rc;
+        return gx_ao_h_solve(E, bf, prox, (float)lam, admm_iter, j);
     case 2:
-        { ProfScope ps(E, "gram_nt");
-          if ((rc = gx_split_product<true, true>(E, E->H, np, E->H, np, E->HHt, kp, kp, np, 64))) return rc; }
-        { ProfScope ps(E, "wphase");
-          if (bf) rc = gxt_split_product(E, E->gxb_v[0], E->gxb_v[1], E->Hhi, E->Hlo, E->A_part, mp, kp, np, 4);
-          else rc = gx_split_product<true, true>(E, E->V, np, E->H, np, E->A_part, mp, kp, np, 1);
-          if (rc) return rc; }
-        return gx_prepare(E, E->HHt, -1.0);
+        return gx_ao_w_products(E, bf);
     case 3:
-        if (kp > 512) {                                // (r5) the launches of gx_ao_subproblem's long form, with the decision taken from the all-reduced sums
-            const int64_t cnt4 = mp * kp / 4;
-            const int nblk = (int)((cnt4 + 255) / 256);
-            const int* stop = &E->state->inner_stop;
-            if (round > 0) hipLaunchKernelGGL(gx_decide_global_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)(E->xf64 + 1), E->state);
-            else hipLaunchKernelGGL(gx_rhs_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, (const float*)E->A_part, (const float*)W, (const float*)E->dualW,
-                                    E->gx_r, cnt4, (const DevState*)E->state);
-            NMFX_HIP(hipGetLastError());
-            if ((rc = gx_launch<true, false>(E, GX_STORE, E->gx_r, kp, E->Minv, kp, E->gx_d, kp, 0, mp, kp, kp, 1, nullptr, 0, nullptr, stop))) return rc;
-            hipLaunchKernelGGL(gx_prox_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, (const float*)E->gx_d, W, E->dualW, prox, (float)lam, cnt4, E->gx_nrm,
-                               (const DevState*)E->state, (const float*)E->A_part, E->gx_r);      // (leaves the next round's right-hand side)
-            hipLaunchKernelGGL(gx_gather_norms_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->xf64 + 1, (const DevState*)E->state);
-            NMFX_HIP(hipGetLastError());
-            return NMFX_OK;
-        }
-        if ((rc = nmfx_round_any(E, false, E->A_part, W, E->dualW, prox, (float)lam, round, round > 0 ? E->xf64 + 1 : nullptr))) return rc;
-        return nmfx_gather_round_norms(E, (int)(mp / 64), round);
+        return gx_ao_round(E, false, E->A_part, E->W[0], E->dualW, prox, (float)lam, round, true, E->xf64 + 1);
     case 4:
-        if (kp > 512) {
-            if (admm_iter > 0) hipLaunchKernelGGL(gx_decide_global_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)(E->xf64 + 1), E->state);
-            hipLaunchKernelGGL(gx_close_kernel, dim3(1), dim3(1), 0, E->stream, E->state, E->inner_hist + j * 2 + 1);
-            NMFX_HIP(hipGetLastError());
-        } else
-        if ((rc = nmfx_inner_finish(E, (int)(mp / 64), admm_iter, E->inner_hist + j * 2 + 1, E->xf64 + 1))) return rc;
-        if (bf) { ProfScope ps(E, "images");
-                  if ((rc = gxb_images_w(E, W))) return rc; }
-        return gx_objective_partial(E, bf);
+        if ((rc = gx_ao_finish(E, false, admm_iter, E->inner_hist + j * 2 + 1, E->xf64 + 1))) return rc;
+        return gx_ao_new_pair(E, bf);
     default:
         E->err = "generic AO-ADMM phase: 0 .. 4"; return NMFX_E_ARG;
     }
@@ -1838,51 +1854,73 @@ int gx_kl_objective_partial(nmfx_engine* E) {        // KL(V, W H) (utils.py:21-
     return nmfx_launch_obj_reduce(E, (mp / GX_T) * (np / GX_T), E->gx_part);
 }
 
-int gx_admm_buffers(nmfx_engine* E) {
+// ---- the KL iteration (ao_admm.py:71-101) in steps: nmfx_generic_aoadmm_kl_run runs them in a loop, nmfx_generic_aoadmm_kl_phase one or
+// two per call.  hside: X = H ([kp][np]), other factor W, data S = v_aux + dual_v; else X = W on the transposed data ----
+// the round behind its right-hand side product (xf32 / A_part): solve, prox and dual step, v_aux / dual_v from P = (other factor) x
+// (this round's aux, gx_d) (ao_admm.py:90-95), then the stop decision of the round -- or (decided: as for gx_ao_round) the rank's norm
+// sums of the round for the caller's all-reduce
+int gx_kl_round(nmfx_engine* E, bool hside, int prox, float lam, const double* decided) {
     int rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp;
-    if ((rc = gx_buffers(E, false))) return rc;
-    if ((rc = gx_alloc(E, &E->gx_r, std::max(mp, np) * kp))) return rc;
-    if ((rc = gx_alloc(E, &E->gx_w64, gx_w64_count(kp)))) return rc;
-    return gx_alloc(E, &E->gx_nrm, std::max(mp, np) * kp / 1024 * 4 + 64);
-}
-
-// one KL sub-problem (ao_admm.py:71-101): hside: X = H ([kp][np]), other factor W, data S = v_aux + dual_v; else X = W on the
-// transposed data.  G = the other factor's Gram matrix.
-int gx_ao_kl_subproblem(nmfx_engine* E, bool hside, const float* G, int prox, float lam, int admm_iter, int32_t* slot) {
-    int rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp, rows = hside ? kp : mp, cols = hside ? np : kp, cnt4 = rows * cols / 4;
+    const int64_t mp = E->mp, np = E->np, kp = E->kp, cnt4 = (hside ? kp * np : mp * kp) / 4;
+    const int nblk = (int)((cnt4 + 255) / 256);
+    const int* stop = &E->state->inner_stop;
     float* W = E->W[0];
     float* X = hside ? E->H : W;
     float* U = hside ? E->dualH : E->dualW;
-    if ((rc = gx_prepare(E, G, -1.0))) return rc;
-    ProfScope ps(E, hside ? "inner_h" : "inner_w");
-    const int nblk = (int)((cnt4 + 255) / 256);
-    const int* stop = &E->state->inner_stop;
-    for (int r = 0; r < admm_iter; ++r) {
-        // right-hand side product with the CURRENT S (ao_admm.py:85)
-        if (hside) rc = gx_split_product<false, false>(E, W, kp, E->S, np, E->xf32, kp, np, mp, 8, stop);
-        else rc = gx_split_product<true, true>(E, E->S, np, E->H, np, E->A_part, mp, kp, np, 1, stop);
-        if (rc) return rc;
-        hipLaunchKernelGGL(gx_rhs_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, hside ? (const float*)E->xf32 : (const float*)E->A_part,
-                           (const float*)X, (const float*)U, E->gx_r, cnt4, (const DevState*)E->state);
-        NMFX_HIP(hipGetLastError());
-        if (hside) rc = gx_launch<true, false>(E, GX_STORE, E->Minv, kp, E->gx_r, np, E->gx_d, np, 0, kp, np, kp, 1, nullptr, 0, nullptr, stop);
-        else rc = gx_launch<true, false>(E, GX_STORE, E->gx_r, kp, E->Minv, kp, E->gx_d, kp, 0, mp, kp, kp, 1, nullptr, 0, nullptr, stop);
-        if (rc) return rc;
-        hipLaunchKernelGGL(gx_prox_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, (const float*)E->gx_d, X, U, prox, lam, cnt4, E->gx_nrm,
-                           (const DevState*)E->state);
-        NMFX_HIP(hipGetLastError());
-        // v_aux, dual_v from P = (other factor) x (this round's aux) (ao_admm.py:90-95): the aux matrix is gx_d
-        if (hside) rc = gx_launch<true, false>(E, GX_VAUX, W, kp, E->gx_d, np, E->DV, np, 0, mp, np, kp, 1, E->V, np, nullptr, stop, E->S);
-        else rc = gx_launch<true, false>(E, GX_VAUX, E->gx_d, kp, E->H, np, E->DV, np, 0, mp, np, kp, 1, E->V, np, nullptr, stop, E->S);
-        if (rc) return rc;
-        hipLaunchKernelGGL(gx_decide_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->state);
-        NMFX_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(gx_close_kernel, dim3(1), dim3(1), 0, E->stream, E->state, slot);
+    hipLaunchKernelGGL(gx_rhs_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, hside ? (const float*)E->xf32 : (const float*)E->A_part,
+                       (const float*)X, (const float*)U, E->gx_r, cnt4, (const DevState*)E->state);
+    NMFX_HIP(hipGetLastError());
+    if (hside) rc = gx_launch<true, false>(E, GX_STORE, E->Minv, kp, E->gx_r, np, E->gx_d, np, 0, kp, np, kp, 1, nullptr, 0, nullptr, stop);
+    else rc = gx_launch<true, false>(E, GX_STORE, E->gx_r, kp, E->Minv, kp, E->gx_d, kp, 0, mp, kp, kp, 1, nullptr, 0, nullptr, stop);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gx_prox_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, (const float*)E->gx_d, X, U, prox, lam, cnt4, E->gx_nrm,
+                       (const DevState*)E->state);
+    NMFX_HIP(hipGetLastError());
+    if (hside) rc = gx_launch<true, false>(E, GX_VAUX, W, kp, E->gx_d, np, E->DV, np, 0, mp, np, kp, 1, E->V, np, nullptr, stop, E->S);
+    else rc = gx_launch<true, false>(E, GX_VAUX, E->gx_d, kp, E->H, np, E->DV, np, 0, mp, np, kp, 1, E->V, np, nullptr, stop, E->S);
+    if (rc) return rc;
+    if (decided) hipLaunchKernelGGL(gx_gather_norms_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->xf64 + 1, (const DevState*)E->state);
+    else hipLaunchKernelGGL(gx_decide_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->state);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
+}
+
+// right-hand side product of a round with the CURRENT S (ao_admm.py:85): W^T S -> xf32, or S H^T -> A_part
+int gx_kl_product(nmfx_engine* E, bool hside, const int* stop) {
+    const int64_t mp = E->mp, np = E->np, kp = E->kp;
+    if (hside) return gx_split_product<false, false>(E, E->W[0], kp, E->S, np, E->xf32, kp, np, mp, 8, stop);
+    return gx_split_product<true, true>(E, E->S, np, E->H, np, E->A_part, mp, kp, np, 1, stop);
+}
+
+int gx_kl_gram_tn(nmfx_engine* E) {                  // W^T W behind the k n part of the f32 exchange buffer
+    ProfScope ps(E, "gram_tn");
+    return gx_split_product<false, false>(E, E->W[0], E->kp, E->W[0], E->kp, E->xf32 + E->kp * E->np, E->kp, E->kp, E->mp, 64);
+}
+
+// inner-round bookkeeping of a sub-problem (decided: the decision of the last W round from the all-reduced sums first)
+int gx_kl_close(nmfx_engine* E, bool hside, int admm_iter, int64_t j, const double* decided) {
+    int rc;
+    if (decided && admm_iter > 0 && (rc = gx_decide_global(E, decided))) return rc;
+    hipLaunchKernelGGL(gx_close_kernel, dim3(1), dim3(1), 0, E->stream, E->state, E->inner_hist + j * 2 + (hside ? 0 : 1));
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+int gx_kl_w_prepare(nmfx_engine* E) {                // H H^T and its shifted inverse for the W side
+    int rc;
+    { ProfScope ps(E, "gram_nt");
+      if ((rc = gx_split_product<true, true>(E, E->H, E->np, E->H, E->np, E->HHt, E->kp, E->kp, E->np, 64))) return rc; }
+    return gx_prepare(E, E->HHt, -1.0);
+}
+
+int gx_ao_kl_subproblem(nmfx_engine* E, bool hside, int prox, float lam, int admm_iter, int64_t j) {
+    int rc;
+    ProfScope ps(E, hside ? "inner_h" : "inner_w");
+    for (int r = 0; r < admm_iter; ++r) {
+        if ((rc = gx_kl_product(E, hside, &E->state->inner_stop))) return rc;
+        if ((rc = gx_kl_round(E, hside, prox, lam, nullptr))) return rc;
+    }
+    return gx_kl_close(E, hside, admm_iter, j, nullptr);
 }
 
 // X = prox(aux, U), U += X - aux for one side of the ADMM state (admm.py:117-156, 321-322)
@@ -1922,20 +1960,14 @@ int nmfx_generic_aoadmm_kl_run(nmfx_engine* E, int prox_w, double lam_w, int pro
                                double tol1, double tol2, int64_t first, int64_t count) {
     int rc;
     if ((rc = gx_admm_buffers(E))) return rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp;
-    float* W = E->W[0];
-    float* xG = E->xf32 + kp * np;
     if (first == 0 && count > 0 && (rc = gx_kl_objective_partial(E))) return rc;   // obj[0] (ao_admm.py:256)
     for (int64_t j = first; j < first + count; ++j) {
-        hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
-                           E->state, E->obj_hist);
-        NMFX_HIP(hipGetLastError());
-        { ProfScope ps(E, "gram_tn");
-          if ((rc = gx_split_product<false, false>(E, W, kp, W, kp, xG, kp, kp, mp, 64))) return rc; }
-        if ((rc = gx_ao_kl_subproblem(E, true, xG, prox_h, (float)lam_h, admm_iter, E->inner_hist + j * 2))) return rc;
-        { ProfScope ps(E, "gram_nt");
-          if ((rc = gx_split_product<true, true>(E, E->H, np, E->H, np, E->HHt, kp, kp, np, 64))) return rc; }
-        if ((rc = gx_ao_kl_subproblem(E, false, E->HHt, prox_w, (float)lam_w, admm_iter, E->inner_hist + j * 2 + 1))) return rc;
+        if ((rc = gx_record(E, j, min_iter, tol1, tol2))) return rc;
+        if ((rc = gx_kl_gram_tn(E))) return rc;
+        if ((rc = gx_prepare(E, E->xf32 + E->kp * E->np, -1.0))) return rc;
+        if ((rc = gx_ao_kl_subproblem(E, true, prox_h, (float)lam_h, admm_iter, j))) return rc;
+        if ((rc = gx_kl_w_prepare(E))) return rc;
+        if ((rc = gx_ao_kl_subproblem(E, false, prox_w, (float)lam_w, admm_iter, j))) return rc;
         if ((rc = gx_kl_objective_partial(E))) return rc;
     }
     return NMFX_OK;
@@ -1956,69 +1988,33 @@ int nmfx_generic_aoadmm_kl_phase(nmfx_engine* E, int phase, int prox, double lam
                                  int64_t j, int round) {
     int rc;
     if ((rc = gx_admm_buffers(E))) return rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp;
-    float* W = E->W[0];
-    float* xG = E->xf32 + kp * np;
     const int* stop = &E->state->inner_stop;
-    const bool hside = phase <= 2;
-    const int64_t cnt4 = (hside ? kp * np : mp * kp) / 4;
-    const int nblk = (int)((cnt4 + 255) / 256);
-    float* X = hside ? E->H : W;
-    float* U = hside ? E->dualH : E->dualW;
     switch (phase) {
-    case 0:
+    case 0: {
         if (round == 0) {
             if (j == 0 && (rc = gx_kl_objective_partial(E))) return rc;            // obj[0] (ao_admm.py:256)
-            ProfScope ps(E, "gram_tn");
-            if ((rc = gx_split_product<false, false>(E, W, kp, W, kp, xG, kp, kp, mp, 64))) return rc;
+            if ((rc = gx_kl_gram_tn(E))) return rc;
         }
-        { ProfScope ps(E, "hphase");
-          return gx_split_product<false, false>(E, W, kp, E->S, np, E->xf32, kp, np, mp, 8, round > 0 ? stop : nullptr); }
-    case 3:
-        if (round > 0) {
-            hipLaunchKernelGGL(gx_decide_global_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)(E->xf64 + 1), E->state);
-            NMFX_HIP(hipGetLastError());
-        }
-        { ProfScope ps(E, "wphase");
-          if ((rc = gx_split_product<true, true>(E, E->S, np, E->H, np, E->A_part, mp, kp, np, 1, stop))) return rc; }
-        [[fallthrough]];
+        ProfScope ps(E, "hphase");
+        return gx_kl_product(E, true, round > 0 ? stop : nullptr); }
     case 1: {
-        if (phase == 1 && round == 0) {
-            hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
-                               E->state, E->obj_hist);
-            NMFX_HIP(hipGetLastError());
-            if ((rc = gx_prepare(E, xG, -1.0))) return rc;
+        if (round == 0) {
+            if ((rc = gx_record(E, j, min_iter, tol1, tol2))) return rc;
+            if ((rc = gx_prepare(E, E->xf32 + E->kp * E->np, -1.0))) return rc;
         }
-        ProfScope ps(E, hside ? "inner_h" : "inner_w");
-        hipLaunchKernelGGL(gx_rhs_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, hside ? (const float*)E->xf32 : (const float*)E->A_part,
-                           (const float*)X, (const float*)U, E->gx_r, cnt4, (const DevState*)E->state);
-        NMFX_HIP(hipGetLastError());
-        if (hside) rc = gx_launch<true, false>(E, GX_STORE, E->Minv, kp, E->gx_r, np, E->gx_d, np, 0, kp, np, kp, 1, nullptr, 0, nullptr, stop);
-        else rc = gx_launch<true, false>(E, GX_STORE, E->gx_r, kp, E->Minv, kp, E->gx_d, kp, 0, mp, kp, kp, 1, nullptr, 0, nullptr, stop);
-        if (rc) return rc;
-        hipLaunchKernelGGL(gx_prox_kernel, dim3((unsigned)nblk), dim3(256), 0, E->stream, (const float*)E->gx_d, X, U, prox, (float)lam, cnt4, E->gx_nrm,
-                           (const DevState*)E->state);
-        NMFX_HIP(hipGetLastError());
-        if (hside) rc = gx_launch<true, false>(E, GX_VAUX, W, kp, E->gx_d, np, E->DV, np, 0, mp, np, kp, 1, E->V, np, nullptr, stop, E->S);
-        else rc = gx_launch<true, false>(E, GX_VAUX, E->gx_d, kp, E->H, np, E->DV, np, 0, mp, np, kp, 1, E->V, np, nullptr, stop, E->S);
-        if (rc) return rc;
-        if (hside) hipLaunchKernelGGL(gx_decide_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->state);
-        else hipLaunchKernelGGL(gx_gather_norms_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_nrm, nblk, E->xf64 + 1, (const DevState*)E->state);
-        NMFX_HIP(hipGetLastError());
-        return NMFX_OK; }
+        ProfScope ps(E, "inner_h");
+        return gx_kl_round(E, true, prox, (float)lam, nullptr); }
     case 2:
-        hipLaunchKernelGGL(gx_close_kernel, dim3(1), dim3(1), 0, E->stream, E->state, E->inner_hist + j * 2);
-        NMFX_HIP(hipGetLastError());
-        { ProfScope ps(E, "gram_nt");
-          if ((rc = gx_split_product<true, true>(E, E->H, np, E->H, np, E->HHt, kp, kp, np, 64))) return rc; }
-        return gx_prepare(E, E->HHt, -1.0);
+        if ((rc = gx_kl_close(E, true, admm_iter, j, nullptr))) return rc;
+        return gx_kl_w_prepare(E);
+    case 3: {
+        if (round > 0 && (rc = gx_decide_global(E, E->xf64 + 1))) return rc;
+        { ProfScope ps(E, "wphase");
+          if ((rc = gx_kl_product(E, false, stop))) return rc; }
+        ProfScope ps(E, "inner_w");
+        return gx_kl_round(E, false, prox, (float)lam, E->xf64 + 1); }
     case 4:
-        if (admm_iter > 0) {
-            hipLaunchKernelGGL(gx_decide_global_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)(E->xf64 + 1), E->state);
-            NMFX_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(gx_close_kernel, dim3(1), dim3(1), 0, E->stream, E->state, E->inner_hist + j * 2 + 1);
-        NMFX_HIP(hipGetLastError());
+        if ((rc = gx_kl_close(E, false, admm_iter, j, E->xf64 + 1))) return rc;
         return gx_kl_objective_partial(E);
     default:
         E->err = "generic AO-ADMM-KL phase: 0 .. 4"; return NMFX_E_ARG;
@@ -2068,9 +2064,7 @@ static int gx_admm_update(nmfx_engine* E, const GxAdmm& c, double rho, int prox_
     int rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
     float* W = E->W[0];
-    hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, (const double*)E->xf64, (long long)j, (long long)min_iter, tol1, tol2,
-                       E->state, E->obj_hist);
-    NMFX_HIP(hipGetLastError());
+    if ((rc = gx_record(E, j, min_iter, tol1, tol2))) return rc;
     if ((rc = gx_prepare(E, c.xG, rho))) return rc;
     { ProfScope ps(E, "inner_h");
       const int64_t c4 = kp * np / 4;

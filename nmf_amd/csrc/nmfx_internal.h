@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 #include <map>
 #include <vector>
@@ -244,6 +245,22 @@ struct nmfx_engine {
 #define NMFX_STR(x) NMFX_STR2(x)
 #define NMFX_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
     E->err = std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" NMFX_STR(__LINE__) ")"; return NMFX_E_HIP; } } while (0)
+
+// a device buffer allocated (and zeroed) on first use
+template <typename T>
+inline int nmfx_lazy_alloc(nmfx_engine* E, T** p, int64_t count) {
+    if (*p) return NMFX_OK;
+    NMFX_HIP(hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T)));
+    NMFX_HIP(hipMemsetAsync(*p, 0, (size_t)count * sizeof(T), E->stream));
+    return NMFX_OK;
+}
+
+// an A/B knob of the environment: on unless set to 0.  A call site keeps the answer in a `static const` of its own: read once, on first use
+inline bool nmfx_knob_on(const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); }
+// the knobs of the KL-loss iterations on the split-bf16 kernels, shared by ADMM (kernels_admm.hip) and AO-ADMM (kernels_aoadmm.hip)
+inline bool nmfx_kl_bf16_on() { static const bool on = nmfx_knob_on("NMFX_KL_BF16"); return on; }
+inline bool nmfx_kl_gather_on() { static const bool on = nmfx_knob_on("NMFX_KL_GATHER"); return on; }
+inline bool nmfx_kl_fuse_on() { static const bool on = nmfx_knob_on("NMFX_KL_FUSE"); return on; }
 
 // ---- launch helpers implemented in the kernel translation units ---------
 // A_part[sp] = V(rows, cols of split sp) * H^T ; optionally the residual

@@ -11,8 +11,12 @@ return code and the text of nmfx_last_error.  The sections are run at k = 40 (pa
 call: MUR-KL in two calls, with a Euclidean iteration in between, the phase calls behind a run, IS then KL, beta with and
 without weights, ARD, fold-in, a precision switch, pair mode, a masked sparse handle; AO-ADMM (both losses) in two calls and
 through the row-sharded phase calls; ADMM-KL in two calls; ANLS with a change of the reported distance and through its phase
-calls.  The last sections make the refused calls: every compute entry point without V, without factors, with weights present,
-with ARD set, with NMFX_BETA, behind another solver family, with two refusals applying at once, and -- one at a time -- between
+calls.  Behind them (admm_step_sections) the ADMM family by the steps its runs and its row-sharded phase entry points share,
+also at k = 12 (pads to 16): ADMM with either loss in runs and phase calls, with every prox operator (l2n through a seeded
+operator, and once without it), AO-ADMM in exact f32, with prox 'l1inf', with the speculative W rounds (phase_w_fused /
+phase_w_repair), and the Euclidean AO-ADMM once at k = 520 on a 640 x 576 problem (more than 512 padded components).  The
+refusal sections make the refused calls: every compute entry point without V, without factors, with weights present, with ARD
+set, with NMFX_BETA, behind another solver family, with two refusals applying at once, and -- one at a time -- between
 the calls of a MUR-KL run and of an AO-ADMM run.
 
 Two builds that print the same lines keep and void the same things and refuse in the same order: the file is what a change of
@@ -53,11 +57,12 @@ def fold(lines):
         print(f"{name:<26} lines={len(sec):<4} {hashlib.sha256(''.join(x + chr(10) for x in sec).encode()).hexdigest()}")
 
 
-def make_inputs(k, seed):
+def make_inputs(k, seed, shape=(M, N), scale=1.0):
+    M, N = shape
     rng = np.random.default_rng(seed)
     v = rng.uniform(0.05, 1.0, (M, N)).astype(np.float32)
-    w0 = rng.uniform(0.1, 1.0, (M, k)).astype(np.float32).astype(np.float64)
-    h0 = rng.uniform(0.1, 1.0, (k, N)).astype(np.float32).astype(np.float64)
+    w0 = (scale * rng.uniform(0.1, 1.0, (M, k))).astype(np.float32).astype(np.float64)
+    h0 = (scale * rng.uniform(0.1, 1.0, (k, N))).astype(np.float32).astype(np.float64)
     om = (10.0 ** rng.uniform(-2.0, 2.0, (M, N))).astype(np.float32)
     om[rng.random((M, N)) < 0.1] = 0
     mask = rng.random((M, N)) < 0.7
@@ -102,7 +107,7 @@ def dense(name, k, v, w0, h0, body, **kw):
     from nmf_amd.engine import Engine
     if ONLY and ONLY not in name:
         return
-    with Engine(M, N, k) as eng:
+    with Engine(v.shape[0], v.shape[1], k) as eng:
         s = Section(f"{name} k={k}", eng, **kw)
         eng.upload_v(v)
         eng.set_factors(w0, h0)
@@ -219,24 +224,35 @@ def mur_sections(k, v, w0, h0, om, mask):
             s.step("anls_run", lambda: e.anls_run(0.0, 0.0, NEVER, 1e-3, 1e-3, 0, 1))
 
 
-def admm_family_sections(k, v, w0, h0):
+def admm_family_sections(k, v, w0, h0, f32=False, losses=("eu", "kl")):
+    """f32: the AO-ADMM two-calls and phases bodies only, behind set_precision('f32') (sections "<name>-f32"); one loss: those two
+    bodies of that loss only."""
     from nmf_amd import _lib as L
     T = (NEVER, 1e-3, 1e-3)
+    tag = "-f32" if f32 else ""
     for dist, dn in ((L.EU, "eu"), (L.KL, "kl")):
+        if dn not in losses:
+            continue
+
         def two_calls(s, e):
+            if f32:
+                s.step("set_precision f32", lambda: e.set_precision("f32"))
             s.step("run 0..1", lambda: e.aoadmm_run(dist, 1, 0.1, 1, 0.1, 5, *T, 0, 2))
             s.step("run 2..3", lambda: e.aoadmm_run(dist, 1, 0.1, 1, 0.1, 5, *T, 2, 2))
             s.step("finish 4", lambda: e.aoadmm_finish(*T, 4))
-        dense(f"aoadmm-{dn}/two-calls", k, v, w0, h0, two_calls)
+        dense(f"aoadmm-{dn}/two-calls{tag}", k, v, w0, h0, two_calls)
 
         def other_loss(s, e):
             s.step("run 0..1", lambda: e.aoadmm_run(dist, 1, 0.1, 1, 0.1, 5, *T, 0, 2))
             s.step("other loss 2", lambda: e.aoadmm_run(L.KL if dist == L.EU else L.EU, 1, 0.1, 1, 0.1, 5, *T, 2, 1))
             s.step("run 3..4", lambda: e.aoadmm_run(dist, 1, 0.1, 1, 0.1, 5, *T, 3, 2))
             s.step("finish 5", lambda: e.aoadmm_finish(*T, 5))
-        dense(f"aoadmm-{dn}/other-loss", k, v, w0, h0, other_loss)
+        if not f32 and len(losses) == 2:
+            dense(f"aoadmm-{dn}/other-loss", k, v, w0, h0, other_loss)
 
         def phases(s, e):
+            if f32:
+                s.step("set_precision f32", lambda: e.set_precision("f32"))
             s.step("run 0..1", lambda: e.aoadmm_run(dist, 1, 0.1, 1, 0.1, 5, *T, 0, 2))
             j = 2
             if dist == L.EU:
@@ -257,7 +273,9 @@ def admm_family_sections(k, v, w0, h0):
             s.step("run 3", lambda: e.aoadmm_run(dist, 1, 0.1, 1, 0.1, 5, *T, 3, 1))
             s.step("objective_partial", e.objective_partial)
             s.step("finish_b 4", lambda: e.mur_finish_b(*T, 4))
-        dense(f"aoadmm-{dn}/phases", k, v, w0, h0, phases)
+        dense(f"aoadmm-{dn}/phases{tag}", k, v, w0, h0, phases)
+    if f32 or len(losses) < 2:
+        return
 
     def admm_kl(s, e):
         s.step("kl run 0..1", lambda: e.admm_run(L.KL, 1.0, 1, 0.1, 1, 0.1, *T, 0, 2))
@@ -282,6 +300,65 @@ def admm_family_sections(k, v, w0, h0):
         s.step("objective_partial", e.objective_partial)
         s.step("finish_b 8", lambda: e.mur_finish_b(*T, 8))
     dense("anls", k, v, w0, h0, anls)
+
+
+def admm_step_sections(k, v, w0, h0):
+    """What the run loops and the row-sharded phase entry points of ADMM and AO-ADMM share, on the paths the sections above do not
+    reach: ADMM with either loss and every prox operator, exact-f32 runs, prox 'l1inf' inside AO-ADMM, the speculative W rounds."""
+    from nmf_amd import _lib as L
+    T = (NEVER, 1e-3, 1e-3)
+    NN, L1N, L2N, L1INF, L1INF_T = (L.PROX[p] for p in ("nn", "l1n", "l2n", "l1inf", "l1inf_transpose"))
+    rng = np.random.default_rng(7000 + k)
+    a = rng.standard_normal((k, k))
+    op = a @ a.T / k + np.eye(k)                     # symmetric positive definite: stands in for ((lambda T^T T + rho I) / rho)^-1
+
+    for dist, dn in ((L.EU, "eu"), (L.KL, "kl")):
+        for f32 in (False, True):
+            def admm(s, e):
+                run = lambda first, count: e.admm_run(dist, 1.0, L1N, 0.1, L1N, 0.1, *T, first, count)
+                if f32:
+                    s.step("set_precision f32", lambda: e.set_precision("f32"))
+                s.step("run 0..1", lambda: run(0, 2))
+                s.step("run 2..3", lambda: run(2, 2))
+                s.step("products 4", lambda: e.admm_phase_products(dist, 1.0, L1N, L1N, 4))
+                s.step("update 4", lambda: e.admm_phase_update(dist, 1.0, L1N, 0.1, L1N, 0.1, *T, 4))
+                s.step("run 5", lambda: run(5, 1))
+                s.step("finish 6", lambda: e.aoadmm_finish(*T, 6))
+            dense(f"admm/{dn}-steps" + ("-f32" if f32 else ""), k, v, w0, h0, admm)
+
+        def admm_prox(s, e):
+            s.step("l2n without operator", lambda: e.admm_run(dist, 1.0, L2N, 0.1, L1INF, 0.1, *T, 0, 2))
+            s.step("set_l2n_operator w", lambda: e.set_l2n_operator(0, op))
+            s.step("set_l2n_operator h", lambda: e.set_l2n_operator(1, op))
+            for pw, ph in ((L2N, L1INF), (L1INF_T, L2N), (L1N, L2N)):
+                s.step("set_factors", lambda: e.set_factors(w0, h0))
+                s.step(f"run 0..1 prox {pw},{ph}", lambda: e.admm_run(dist, 1.0, pw, 0.1, ph, 0.1, *T, 0, 2))
+                s.step(f"products 2 prox {pw},{ph}", lambda: e.admm_phase_products(dist, 1.0, pw, ph, 2))
+                s.step(f"update 2 prox {pw},{ph}", lambda: e.admm_phase_update(dist, 1.0, pw, 0.1, ph, 0.1, *T, 2))
+                s.step(f"run 3 prox {pw},{ph}", lambda: e.admm_run(dist, 1.0, pw, 0.1, ph, 0.1, *T, 3, 1))
+            s.step("finish 4", lambda: e.aoadmm_finish(*T, 4))
+        dense(f"admm-{dn}/prox", k, v, w0, h0, admm_prox)
+
+        def ao_l1inf(s, e):
+            for pw, ph in ((L1INF, L1N), (L1N, L1INF), (L1INF_T, L1N), (L1N, L1INF_T)):
+                s.step("set_factors", lambda: e.set_factors(w0, h0))
+                s.step(f"run 0..1 prox {pw},{ph}", lambda: e.aoadmm_run(dist, pw, 0.1, ph, 0.1, 4, *T, 0, 2))
+                s.step(f"run 2 prox {pw},{ph}", lambda: e.aoadmm_run(dist, pw, 0.1, ph, 0.1, 4, *T, 2, 1))
+                s.step("finish 3", lambda: e.aoadmm_finish(*T, 3))
+        dense(f"aoadmm-{dn}/l1inf", k, v, w0, h0, ao_l1inf)
+
+    def w_fused(s, e):
+        s.step("run 0..1", lambda: e.aoadmm_run(L.EU, 1, 0.1, 1, 0.1, 5, *T, 0, 2))
+        s.step("h_products 2", lambda: e.aoadmm_phase_h_products(2))
+        s.step("h_solve 2", lambda: e.aoadmm_phase_h_solve(1, 0.1, 5, *T, 2))
+        s.step("w_products 2", lambda: e.aoadmm_phase_w_products(*T, 2))
+        s.step("w_fused", lambda: e.aoadmm_phase_w_fused(1, 0.1, 5))
+        s.step("w_repair 2", lambda: e.aoadmm_phase_w_repair(1, 0.1, 5, 2))
+        s.step("run 3", lambda: e.aoadmm_run(L.EU, 1, 0.1, 1, 0.1, 5, *T, 3, 1))
+        s.step("finish 4", lambda: e.aoadmm_finish(*T, 4))
+    if k <= 128:
+        dense("aoadmm-eu/w-fused", k, v, w0, h0, w_fused)
+    admm_family_sections(k, v, w0, h0, f32=True)
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------
@@ -500,6 +577,17 @@ def main():
         admm_family_sections(k, v, w0, h0)
         refusal_sections(k, v, w0, h0, om)
         between_sections(k, v, w0, h0)
+    # (behind the sections above, whose lines they leave where they were) the ADMM family by its steps: also at a rank that pads to 16,
+    # and the Euclidean AO-ADMM once beyond 512 padded components, where its sub-problems take the rhs / solve / prox launches
+    for k in (12,) + RANKS:
+        v, w0, h0, om, mask = make_inputs(k, seed=5000 + k)
+        if k not in RANKS:
+            admm_family_sections(k, v, w0, h0)
+        admm_step_sections(k, v, w0, h0)
+    # (a start with W H at the data's scale: from the unscaled one the first sub-problem wipes H out and the next Gram system is singular)
+    v, w0, h0, om, mask = make_inputs(520, seed=5520, shape=(640, 576), scale=0.06)
+    admm_family_sections(520, v, w0, h0, losses=("eu",))
+    admm_family_sections(520, v, w0, h0, f32=True, losses=("eu",))
     if LINES is not None:
         fold(LINES)
 
