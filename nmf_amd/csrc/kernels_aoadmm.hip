@@ -33,9 +33,8 @@
 // ONE rank-1 FMA update to its patch.  The in-place Gauss-Jordan step
 //     a[p][p] <- 1/piv,  a[p][c] <- a[p][c]/piv,  a[i][p] <- -a[i][p]/piv,
 //     a[i][c] <- a[i][c] - a[i][p] a[p][c]/piv
-// is exactly  a[i][c] <- a[i][c] - cv[i] * rv[c]  with the published values adjusted to
-//     cv[p] = piv - 1   and   rv[p] = 1 + 1/piv      (rv[c] = a[p][c]/piv otherwise),
-// so there are no special cases in the update (the kernel is f64 issue bound).
+// is  a[i][c] <- a[i][c] - cv[i] * rv[c]  off row and column p, which are selected in as the values above.  (Folding them into the
+// update with cv[p] = piv - 1 and rv[p] = 1 + 1/piv is exact only on paper: the pivot entry then cancels to piv^2 eps.)
 template <int KP>
 __global__ __launch_bounds__((KP / 4) * (KP / 4) < 64 ? 64 : (KP / 4) * (KP / 4)) void ao_prepare_kernel(
     const float* __restrict__ src, int k, float* __restrict__ Minv, DevState* __restrict__ st,
@@ -72,9 +71,11 @@ __global__ __launch_bounds__((KP / 4) * (KP / 4) < 64 ? 64 : (KP / 4) * (KP / 4)
     }
     __syncthreads();
     const double rho = shrho;
+    // padded variables (index >= k) get a unit diagonal: with rho = 0 (ADMM: a plain Gram solve) their pivots would be 0; the
+    // padding off the diagonal is zero, so the logical block of the inverse does not depend on them
     if (active && ti == tj) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) a[r][r] += rho;
+        for (int r = 0; r < 4; ++r) a[r][r] += (4 * ti + r >= k) ? 1.0 : rho;
     }
     for (int p = 0; p < KP; ++p) {
         const int buf = p & 1, pg = p >> 2, pr = p & 3;
@@ -106,13 +107,19 @@ __global__ __launch_bounds__((KP / 4) * (KP / 4) < 64 ? 64 : (KP / 4) * (KP / 4)
         double rv[4], cv[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            rv[c] = (4 * tj + c == p) ? 1.0 + inv : rowr[buf][(4 * tj + c) & (KP - 1)] * inv;
-            cv[c] = (4 * ti + c == p) ? piv - 1.0 : colp[buf][(4 * ti + c) & (KP - 1)];
+            rv[c] = rowr[buf][(4 * tj + c) & (KP - 1)] * inv;
+            cv[c] = colp[buf][(4 * ti + c) & (KP - 1)];
         }
+        // row p and column p are written as what they are: the adjusted-pivot form piv - (piv - 1)(1 + 1/piv) of the pivot entry
+        // cancels, with an error of piv^2 eps relative (1e-4 for a pivot of 1e6)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) a[r][c] = fma(-cv[r], rv[c], a[r][c]);
+            for (int c = 0; c < 4; ++c) {
+                const bool prow = 4 * ti + r == p, pcol = 4 * tj + c == p;
+                const double upd = fma(-cv[r], rv[c], a[r][c]);
+                a[r][c] = prow ? (pcol ? inv : rv[c]) : (pcol ? -cv[r] * inv : upd);
+            }
     }
     if (active) {
 #pragma unroll

@@ -1510,7 +1510,7 @@ __global__ __launch_bounds__(256) void gx_bgj_init_kernel(const float* __restric
     __syncthreads();
     double rho = (((part[0] + part[1]) + part[2]) + part[3]) / (double)k;
     if (fixed_rho >= 0.0) rho = fixed_rho;
-    for (int c = tid; c < kp; c += 256) T[(int64_t)row * kp + c] = (double)G[(int64_t)row * kp + c] + (c == row ? rho : 0.0);
+    for (int c = tid; c < kp; c += 256) T[(int64_t)row * kp + c] = (double)G[(int64_t)row * kp + c] + (c == row ? (row >= k ? 1.0 : rho) : 0.0);   // (padded variables: unit diagonal, rho = 0 included)
     if (row == 0 && tid == 0) { st->rho = rho; st->inner_stop = 0; st->inner_count = 0; }
 }
 

@@ -46,7 +46,7 @@ template <int QSRC> __device__ __forceinline__ double bcast_row_f64(double v) {
 }
 // One scalar pivot of the in-wave 16 x 16 Gauss-Jordan (tile in the C/D layout: a[r] = D[q + 4r][c]).
 // Row P lives in the lanes with q == P & 3 (bcast_row brings it to every row of lanes), column P
-// in lane P of every row of lanes (row_share).  Same adjusted-pivot update as the scalar kernel.  A pivot that is not
+// in lane P of every row of lanes (row_share).  Same update as the scalar kernel.  A pivot that is not
 // positive (scipy cholesky would raise LinAlgError) is only NOTED in `ok` (no branch on the chain of 16 dependent pivots;
 // what follows it is garbage nobody uses).
 template <int P> __device__ __forceinline__ void gj16_pivot(f64x4& a, int c, int q, bool& ok) {
@@ -56,12 +56,15 @@ template <int P> __device__ __forceinline__ void gj16_pivot(f64x4& a, int c, int
     double inv = __builtin_amdgcn_rcp(piv);                             // + two Newton steps: full f64 accuracy
     inv = fma(fma(-piv, inv, 1.0), inv, inv);
     inv = fma(fma(-piv, inv, 1.0), inv, inv);
-    const double rv = (c == P) ? 1.0 + inv : rowp * inv;
+    // row P and column P are written as what they are (1/piv, D[P][c]/piv, -D[i][P]/piv).  The adjusted-pivot form of the update,
+    // piv - (piv - 1)(1 + 1/piv) for the pivot entry, cancels: its error is piv^2 eps relative, 1e-4 for a pivot of 1e6 (a Gram
+    // matrix of data in the hundreds) and total from 1e8 on
+    const double rs = rowp * inv;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const double colv = row_share_f64<P>(a[r]);                     // D[q + 4r][P]
-        const double cv = (q + 4 * r == P) ? piv - 1.0 : colv;
-        a[r] = fma(-cv, rv, a[r]);
+        const double upd = fma(-colv, rs, a[r]);
+        a[r] = (q + 4 * r == P) ? ((c == P) ? inv : rs) : ((c == P) ? -colv * inv : upd);
     }
 }
 
@@ -94,7 +97,7 @@ __device__ __forceinline__ void ao_prepare_body(
     // matrix is the KP x KP f64 block at src64 (row stride ld64), nothing is added to its diagonal, its f64 inverse goes to out64
     // [KP][KP]; a pivot <= 0 is the run's "not positive definite" unless soft_bad is given.
     // out64 != nullptr (ANLS, nnls_cinv_kernel): the f64 inverse of src + fixed_rho I goes to out64 [KP][KP] instead of the
-    // f32 one to Minv, padded variables (index >= k) get a unit diagonal, the solver state is left alone, and
+    // f32 one to Minv, the solver state is left alone, and
     // "not positive definite" or "too ill-conditioned for an explicit inverse" (max diag(inverse) x mean diag(matrix)
     // > 1e9) are reported in *soft_bad instead of stopping the run
     //
@@ -182,10 +185,10 @@ __device__ __forceinline__ void ao_prepare_body(
         for (int jb = 0; jb < NB; ++jb)
             if (jb == w) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) if (q + 4 * r == c) t[jb][r] += (out64 && 16 * w + c >= k) ? 1.0 : rho;
+                for (int r = 0; r < 4; ++r) if (q + 4 * r == c) t[jb][r] += (!src64 && 16 * w + c >= k) ? 1.0 : rho;      // (padded variables: unit diagonal, whatever rho is)
             }
     }
-    // the helper's job: invert the tile in `diag` with the adjusted-pivot update of the scalar kernel, leave it in dinv[buf]
+    // the helper's job: invert the tile in `diag` with the pivot update of the scalar kernel, leave it in dinv[buf]
     auto invert_diag = [&](int buf) {
         f64x4 a;
 #pragma unroll
