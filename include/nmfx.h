@@ -390,7 +390,11 @@ int nmfx_mur_finish_sharded(nmfx_handle_t h, int distance, int64_t min_iter, dou
  * Rayleigh-Ritz on `block` columns (0 = max(k + 16, 1.5 k)), stopped when
  * ||V^T u_i - s_i v_i|| <= tol * s_1 for i < k (tol <= 0: 1e-11) or after max_sweeps (<= 0: 4000).
  * u: m x k, s: k, vt: k x n (row-major, host).  sweeps / resid (may be NULL) report the sweeps
- * run and the largest relative residual reached, so the caller can tell a cap from convergence. */
+ * run and the largest relative residual reached, so the caller can tell a cap from convergence.
+ * All k columns of u and rows of vt are orthonormal: a triplet whose Ritz value is numerically zero
+ * (V of rank below k) comes back with s_i = 0 and unit vectors orthogonal to the others, and resid
+ * covers it too, so a block that lost rank is never reported as converged.  NMFX_E_ARG (with a
+ * message): k < 1, k > min(m, n), k > 192, a null u, s or vt; NMFX_E_STATE before nmfx_upload_v. */
 int nmfx_topk_svd(nmfx_handle_t h, int k, int block, double tol, int max_sweeps, uint64_t seed,
                   double* u, double* s, double* vt, int* sweeps, double* resid);
 

@@ -5,7 +5,9 @@
 // Method: block subspace iteration with Rayleigh-Ritz on an L-column block (L > k):
 //     Y = V Q;   Y^T Y = S Theta S^T;   U = Y S Theta^-1/2,  Qr = Q S,  sigma = sqrt(Theta)
 //     Z = V^T U; residual_i = || Z_i - sigma_i Qr_i ||;      Z^T Z = S' Theta' S'^T;  Q = Z S' Theta'^-1/2
-// until the residuals of the k leading triplets are below tol * sigma_i.  V stays in its
+// until the residuals of the k leading triplets are below tol * sigma_1.  A Ritz value at or below the floor gives a null
+// triplet (its column of U is zero); null triplets among the first k are completed to an orthonormal set before the call stops,
+// and the residual is then taken again over all k, so a block that lost rank is never reported as converged.  V stays in its
 // f32 device layout (exact in f64), all products accumulate in f64 on v_mfma_f64_16x16x4_f64,
 // the L x L eigenproblems run on the host (threshold Jacobi; they are nearly diagonal after
 // the first sweep).  Per sweep V is read twice; nothing else is larger than (m + n) x L.
@@ -273,6 +275,35 @@ void jacobi_eigh(int L, std::vector<double>& a, std::vector<double>& evec, std::
     evec.swap(v2);
 }
 
+// Each column j < k of X (row-major rows x L, `used` true rows) with dead[j] becomes a random unit vector orthogonal to the other
+// k - 1 columns: two Gram-Schmidt passes against them, a new draw if nothing is left of the first.
+void complete_columns(std::vector<double>& X, int64_t used, int L, int k, const std::vector<char>& dead, std::mt19937_64& gen)
+{
+    std::normal_distribution<double> nd(0.0, 1.0);
+    std::vector<double> c((size_t)used);
+    for (int j = 0; j < k; ++j) {
+        if (!dead[j]) continue;
+        for (int64_t r = 0; r < used; ++r) X[(size_t)r * L + j] = 0.0;
+        double nrm = 0.0;
+        for (int attempt = 0; attempt < 4; ++attempt) {
+            for (int64_t r = 0; r < used; ++r) c[(size_t)r] = nd(gen);
+            for (int pass = 0; pass < 2; ++pass)
+                for (int i = 0; i < k; ++i) {
+                    if (i == j) continue;
+                    double dot = 0.0;
+                    for (int64_t r = 0; r < used; ++r) dot += X[(size_t)r * L + i] * c[(size_t)r];
+                    for (int64_t r = 0; r < used; ++r) c[(size_t)r] -= dot * X[(size_t)r * L + i];
+                }
+            nrm = 0.0;
+            for (int64_t r = 0; r < used; ++r) nrm += c[(size_t)r] * c[(size_t)r];
+            nrm = std::sqrt(nrm);
+            if (nrm > 1e-8) break;
+        }
+        if (nrm > 0.0)
+            for (int64_t r = 0; r < used; ++r) X[(size_t)r * L + j] = c[(size_t)r] / nrm;
+    }
+}
+
 struct SvdWork {
     nmfx_engine* E; int L, NT;
     double *Q = nullptr, *Qr = nullptr, *Z = nullptr, *Y = nullptr, *U = nullptr, *part = nullptr, *T = nullptr,
@@ -411,6 +442,7 @@ int topk_svd(nmfx_engine* E, int k, double tol, int max_sweeps, uint64_t seed, d
         NMFX_HIP(hipStreamSynchronize(E->stream));
     }
     std::vector<double> theta, S, sigma(L), M((size_t)L * L), rpart, res(L, 0.0);
+    std::vector<char> dead(L, 0);                      // Ritz value at or below the floor: the column of U is zero
     if ((rc = orthonormalize<NT>(w, w.Q, w.Z, np, theta, S))) return rc;
     int sweep = 0;
     double worst = INFINITY;
@@ -426,14 +458,16 @@ int topk_svd(nmfx_engine* E, int k, double tol, int max_sweeps, uint64_t seed, d
             for (int j = 0; j < L; ++j) {
                 sigma[j] = theta[j] > 0.0 ? std::sqrt(theta[j]) : 0.0;
                 const double sc = theta[j] > floor_ && theta[j] > 0.0 ? 1.0 / sigma[j] : 0.0;
+                dead[j] = sc == 0.0;
                 for (int i = 0; i < L; ++i) M[(size_t)i * L + j] = S[(size_t)i * L + j] * sc;
             }
             if ((rc = rotate<NT>(w, w.Y, M, w.U, mp))) return rc;
             if ((rc = rotate<NT>(w, w.Q, S, w.Qr, np))) return rc;
         }
         // Z = V^T U; residuals of the Ritz triplets
-        if ((rc = launch_apply<NT>(w, true, w.U, w.Z))) return rc;
-        {
+        auto residuals = [&](bool all_k) -> int {
+            int r2;
+            if ((r2 = launch_apply<NT>(w, true, w.U, w.Z))) return r2;
             NMFX_HIP(hipMemcpyAsync(w.sig, sigma.data(), (size_t)L * 8, hipMemcpyHostToDevice, E->stream));
             int64_t rpc = 512; while (np % rpc) rpc >>= 1;
             const int64_t chunks = np / rpc;
@@ -442,18 +476,47 @@ int topk_svd(nmfx_engine* E, int k, double tol, int max_sweeps, uint64_t seed, d
             rpart.resize((size_t)chunks * L);
             NMFX_HIP(hipMemcpyAsync(rpart.data(), w.part, rpart.size() * 8, hipMemcpyDeviceToHost, E->stream));
             NMFX_HIP(hipStreamSynchronize(E->stream));
-            worst = 0.0;
+            double wst = 0.0;
             for (int j = 0; j < L; ++j) {
                 double s2 = 0.0;
                 for (int64_t c = 0; c < chunks; ++c) s2 += rpart[(size_t)c * L + j];
                 res[j] = std::sqrt(s2);
-                if (j < k && sigma[j] > 0.0) worst = std::max(worst, res[j] / sigma[0]);
+                if (j < k && (all_k || sigma[j] > 0.0)) wst = std::max(wst, sigma[0] > 0.0 ? res[j] / sigma[0] : 0.0);
+            }
+            worst = all_k ? std::max(worst, wst) : wst;
+            return NMFX_OK;
+        };
+        if ((rc = residuals(false))) return rc;
+        // Null triplets among the first k (V of rank below k, or a block that lost rank under the filter): before the call
+        // stops their columns of U and Qr become unit vectors orthogonal to the others, their values exact zeros, and the
+        // residual is taken again over all k.  For a V of rank below k these are singular triplets and the residual stays
+        // below tol; where the block lost rank the completed u_j has V^T u_j of the size of the missing singular value, the
+        // stop test fails, and Z = V^T U carries the fresh directions into the next block.
+        bool completed = false;
+        {
+            int ndead = 0;
+            for (int j = 0; j < k; ++j) ndead += dead[j];
+            if (ndead && (worst <= tol || sweep >= max_sweeps)) {
+                std::vector<double> hu((size_t)mp * L), hq((size_t)np * L);
+                NMFX_HIP(hipMemcpyAsync(hu.data(), w.U, hu.size() * 8, hipMemcpyDeviceToHost, E->stream));
+                NMFX_HIP(hipMemcpyAsync(hq.data(), w.Qr, hq.size() * 8, hipMemcpyDeviceToHost, E->stream));
+                NMFX_HIP(hipStreamSynchronize(E->stream));
+                std::mt19937_64 gen(seed ^ (0x9E3779B97F4A7C15ULL * (uint64_t)sweep));
+                complete_columns(hu, E->m, L, k, dead, gen);
+                complete_columns(hq, E->n, L, k, dead, gen);
+                for (int j = 0; j < k; ++j) if (dead[j]) sigma[j] = 0.0;
+                NMFX_HIP(hipMemcpyAsync(w.U, hu.data(), hu.size() * 8, hipMemcpyHostToDevice, E->stream));
+                NMFX_HIP(hipMemcpyAsync(w.Qr, hq.data(), hq.size() * 8, hipMemcpyHostToDevice, E->stream));
+                NMFX_HIP(hipStreamSynchronize(E->stream));     // (the host vectors go out of scope)
+                if ((rc = residuals(true))) return rc;
+                completed = true;
             }
         }
         if (worst <= tol || sweep >= max_sweeps) break;
         // next block.  Plain subspace iteration: Q = orth(Z) (= orth(A Qr), A = V^T V).  Its error
         // shrinks by (s_{L+1} / s_k)^2 per sweep, which is hopeless without a gap behind the k-th
-        // singular value (noise bulk, real data): from the fourth sweep on the block is therefore
+        // singular value (noise bulk, real data).  Sweeps 1 and 2 stay plain (`sweep < 3` below); the block
+        // built behind the third sweep, and every block after it, is therefore
         // passed through a Chebyshev polynomial of A that is small on [0, theta_L] (the block's
         // smallest Ritz value bounds the unwanted spectrum) and grows fast above it (Zhou & Saad's
         // filtered subspace iteration; scaled three-term recurrence, degree 10: the error then
@@ -473,7 +536,7 @@ int topk_svd(nmfx_engine* E, int k, double tol, int max_sweeps, uint64_t seed, d
             const double ratio = grow(a0) / std::max(grow(theta[k - 1]), 1.0);
             if (ratio > 1.0) degree = (int)std::min(10.0, std::floor(std::log(1e9) / std::log(ratio)));
         }
-        if (sweep < 3 || degree < 2 || !(cb > 1e-12 * a0) || !(a0 > 1.000001 * cb)) {
+        if (completed || sweep < 3 || degree < 2 || !(cb > 1e-12 * a0) || !(a0 > 1.000001 * cb)) {
             std::vector<double> th2, S2;
             if ((rc = orthonormalize<NT>(w, w.Z, w.Q, np, th2, S2))) return rc;
             std::swap(w.Q, w.Z);                       // orthonormalize leaves its result in its first argument
@@ -528,7 +591,7 @@ int topk_svd(nmfx_engine* E, int k, double tol, int max_sweeps, uint64_t seed, d
             std::swap(w.Q, w.Z);                       // ax == w.Z holds the new block
         }
     }
-    // polish U (orthonormal to rounding) and hand out the k leading triplets
+    // hand out the k leading triplets (null triplets were completed above; U is as orthonormal as the Ritz step leaves it)
     {
         std::vector<double> hu((size_t)mp * L), hq((size_t)np * L);
         NMFX_HIP(hipMemcpyAsync(hu.data(), w.U, hu.size() * 8, hipMemcpyDeviceToHost, E->stream));
@@ -552,7 +615,9 @@ extern "C" int nmfx_topk_svd(nmfx_handle_t E, int k, int block, double tol, int 
                              double* u, double* s, double* vt, int* sweeps, double* resid)
 {
     NMFX_DENSE_ONLY(E);
-    if (!E || !u || !s || !vt || k < 1) return NMFX_E_ARG;
+    if (!E) return NMFX_E_ARG;
+    if (!u || !s || !vt) { E->err = "topk_svd: u, s and vt must not be null"; return NMFX_E_ARG; }
+    if (k < 1) { E->err = "topk_svd: k must be at least 1"; return NMFX_E_ARG; }
     if (!E->have_v) { E->err = "upload V first"; return NMFX_E_STATE; }
     const int64_t lim = std::min(E->m, E->n);
     if (k > lim) { E->err = "topk_svd: k exceeds min(m, n)"; return NMFX_E_ARG; }

@@ -46,6 +46,8 @@ def _nndsvd_from_triplets(x, u, s, vt, rank, variant):
         rp, rn = np.maximum(row, 0), np.maximum(-row, 0)
         ncp, ncn = np.linalg.norm(cp), np.linalg.norm(cn)
         nrp, nrn = np.linalg.norm(rp), np.linalg.norm(rn)
+        if max(ncp * nrp, ncn * nrn) == 0 or s[c] == 0:
+            continue                                    # a null triplet, or one without a part on either side: a zero column, not 0 / 0
         if ncp * nrp >= ncn * nrn:
             scale = np.sqrt(s[c] * ncp * nrp)
             w[:, c], h[c, :] = scale / ncp * cp, scale / nrp * rp
