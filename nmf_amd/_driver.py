@@ -119,14 +119,26 @@ class Referee:
         return 0, -1, max_iter
 
 
-def drive(engine, run_batch, finish, max_iter, tol1, tol2, before_line=None, referee=None):
-    """run_batch(first, count) queues iterations; finish(done) completes the
+def say_objective(i, value, digits):
+    """The line the reference prints at the end of iteration i (nmf/mur.py:130)."""
+    utils.say('[{}]: {:.{}f}'.format(i, value, digits))
+
+
+def require_iterations(max_iter):
+    """The reference's loops with max_iter <= 0: `for i in range(0)` never binds i -> UnboundLocalError at mur.py:145.  (The
+    row-sharded drivers ask before their first collective: every rank raises, none is left waiting.)"""
+    if max_iter <= 0:
+        raise UnboundLocalError("local variable 'i' referenced before assignment")
+
+
+def drive(engine, run_batch, finish, max_iter, tol1, tol2, before_line=None, referee=None, batch=BATCH, prints=True):
+    """run_batch(first, count) queues iterations, `batch` of them between two host syncs; finish(done) completes the
     bookkeeping of the last one; before_line(i) may print what the reference
     prints inside iteration i before its objective line.  Returns (i, obj_history) like the reference
-    loops (nmf/mur.py:119-145): obj_history has i + 2 entries."""
-    if max_iter <= 0:
-        # reference: `for i in range(0)` never binds i -> UnboundLocalError at mur.py:145
-        raise UnboundLocalError("local variable 'i' referenced before assignment")
+    loops (nmf/mur.py:119-145): obj_history has i + 2 entries.  `prints=False` (the ranks of a row-sharded run other
+    than rank 0) keeps the `[i]: objective` lines, before_line and the convergence message to itself; history, stop
+    index and log records are those of a caller that prints."""
+    require_iterations(max_iter)
     digits = utils.tol_digits(tol1, tol2)
     history = []
     done = 0
@@ -135,13 +147,13 @@ def drive(engine, run_batch, finish, max_iter, tol1, tol2, before_line=None, ref
         _, _, n_obj = engine.state()
         for val in engine.objectives(len(history), n_obj - len(history)):
             history.append(np.float64(val))
-            if len(history) >= 2:
+            if len(history) >= 2 and prints:
                 if before_line is not None:
                     before_line(len(history) - 2)
-                utils.say('[{}]: {:.{}f}'.format(len(history) - 2, val, digits))
+                say_objective(len(history) - 2, val, digits)
 
     while done < max_iter and not rule:
-        count = min(BATCH, max_iter - done)
+        count = min(batch, max_iter - done)
         run_batch(done, count)
         done += count
         if done == max_iter:
@@ -162,7 +174,8 @@ def drive(engine, run_batch, finish, max_iter, tol1, tol2, before_line=None, ref
     if referee is not None:
         referee.final_rule = rule                    # (callers that need it: the device's flag was cleared by a walk)
     if rule:
-        utils.convergence_message(rule)
+        if prints:
+            utils.convergence_message(rule)
         logging.warning('Converged.')
         return stop_i, history[:stop_i + 2]
     logging.info('Max iteration reached.')

@@ -33,13 +33,18 @@ def l2n_operator(k, rho, lam):
     return np.linalg.inv((lam * t.T @ t + rho * np.eye(k)) / rho)
 
 
+def experiment_of(k, kw):
+    """The Experiment tuple of an admm run with the keyword arguments `kw` (admm's own, and dist.factorize's)."""
+    return Experiment('admm', k, kw['rho'], kw['distance_type'], kw['nndsvd_init'], kw['min_iter'], kw['max_iter'],
+                      kw['tol1'], kw['tol2'], kw['reg_w'][0], kw['reg_w'][1], kw['reg_h'][0], kw['reg_h'][1])
+
+
 def admm(v, k, *, rho=1, distance_type='eu', reg_w=(0, 'nn'), reg_h=(0, 'l2n'), min_iter=10,
          max_iter=100000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
          device=0, engine=None):
     """ADMM NMF.  rho: fixed penalty; reg_w / reg_h = (lambda, 'nn' | 'l1n' | 'l2n');
     other arguments as in the reference.  Returns Results(w, h, i, obj_history, experiment)."""
-    experiment = Experiment('admm', k, rho, distance_type, nndsvd_init, min_iter, max_iter, tol1, tol2,
-                            reg_w[0], reg_w[1], reg_h[0], reg_h[1])
+    experiment = experiment_of(k, locals())
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via admm.py:289
     sparse.reject(v, 'admm')

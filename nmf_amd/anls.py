@@ -21,11 +21,16 @@ from .engine import Engine
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h fcnnls')
 
 
+def experiment_of(k, kw):
+    """The Experiment tuple of an anls run with the keyword arguments `kw` (anls's own, and dist.factorize's)."""
+    return Experiment('anls', k, kw['distance_type'], kw['nndsvd_init'], kw['max_iter'], kw['tol1'], kw['tol2'],
+                      kw['lambda_w'], kw['lambda_h'], kw['use_fcnnls'])
+
+
 def anls(x, k, *, distance_type='eu', use_fcnnls=False, lambda_w=0, lambda_h=0, min_iter=10,
          max_iter=1000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
          device=0, engine=None):
-    experiment = Experiment('anls', k, distance_type, nndsvd_init, max_iter, tol1, tol2, lambda_w,
-                            lambda_h, use_fcnnls)
+    experiment = experiment_of(k, locals())
     if distance_type == 'is':
         raise ValueError("anls: distance_type='is' (Itakura-Saito) is a loss of mur only")
     if distance_type == 'beta':

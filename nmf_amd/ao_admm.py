@@ -43,13 +43,18 @@ def _prox_code(kind, on_device=False):
     raise TypeError('Unknown prox_type.')                       # nmf/ao_admm.py:198
 
 
+def experiment_of(k, kw):
+    """The Experiment tuple of an ao_admm run with the keyword arguments `kw` (ao_admm's own, and dist.factorize's)."""
+    return Experiment('ao_admm', k, kw['distance_type'], kw['nndsvd_init'], kw['min_iter'], kw['max_iter'], kw['admm_iter'],
+                      kw['tol1'], kw['tol2'], kw['reg_w'][0], kw['reg_w'][1], kw['reg_h'][0], kw['reg_h'][1])
+
+
 def ao_admm(v, k, *, distance_type='eu', reg_w=(0, 'nn'), reg_h=(0, 'l2n'), min_iter=10,
             max_iter=100000, admm_iter=10, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'),
             save_dir='./results/', device=0, engine=None):
     """AO-ADMM NMF.  reg_w / reg_h = (lambda, 'nn' | 'l1n'); other arguments as
     in the reference.  Returns Results(w, h, i, obj_history, experiment)."""
-    experiment = Experiment('ao_admm', k, distance_type, nndsvd_init, min_iter, max_iter, admm_iter,
-                            tol1, tol2, reg_w[0], reg_w[1], reg_h[0], reg_h[1])
+    experiment = experiment_of(k, locals())
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via ao_admm.py:256
     sparse.reject(v, 'ao_admm')

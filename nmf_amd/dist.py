@@ -1,27 +1,32 @@
-"""Row-sharded MUR over several GPUs of one node (one process per GPU).
+"""The four solvers over a matrix whose rows are sharded over the GPUs of one node (one process per GPU).
 
-Rank p holds the rows [r0, r1) of V and of W; H (k x n) and H H^T are
-replicated.  The W update is row-local (nmf/mur.py:29: row i of W depends only
-on row i of V).  The H update (nmf/mur.py:45) needs W^T V = sum_p W_p^T V_p and
-W^T W = sum_p W_p^T W_p: ONE sum-all-reduce per outer iteration of the packed
-f32 buffer [W^T V | W^T W] (k*n + k*k elements), followed on the same stream by
-the 64-byte f64 all-reduce of the objective partial (torch cannot coalesce two
-dtypes into one RCCL group).
-Every rank then applies the identical H update, so no broadcast is needed and
-the device-side stop flag agrees on all ranks.
+Rank p holds the rows [r0, r1) of V and of W; H (k x n) is replicated.  What couples the ranks is a sum over the row
+blocks -- W^T V and W^T W for the H update, the objective, the norms of AO-ADMM's `terminate` -- so an outer iteration
+is engine phases with sum-all-reduces of the engine's exchange buffers between them.  Every rank then does the same
+replicated work, so no broadcast is needed and the device-side stop flag agrees on all ranks.
 
-The collective is `torch.distributed.all_reduce` (backend "nccl" = RCCL over
-xGMI on the GPU box; "gloo" in the CPU tests, where a numpy stand-in engine
-from the test-suite replaces the HIP engine).  The loop below only talks to an
-object with phase_a / phase_b / finish_a / finish_b / state / objectives, so the
-sharding logic is the same code in both cases.
+The parts, in the order of the file:
+  TorchComm / NativeComm   the collectives: torch.distributed ("nccl" = RCCL over xGMI; "gloo" in the CPU tests), or
+                           RCCL behind the C ABI.  Each states what it can do (`scatters`, `async_all_reduce`, `stage`).
+  Shard                    what the drivers ask of a shard: `eng` (the engine: nmf_amd.engine.Engine, whose phase
+                           methods the drivers call by name; the test-suite's numpy stand-in implements the same names),
+                           the exchange buffers, and what the ranks must agree on before the first collective
+                           (negotiate, merge_objective, chunk_ranges, slice_info).  DeviceShard / NativeShard.
+  run_iterations           MUR's outer iteration in its three exchange forms; GraphedIterations / Runner replay the
+                           one-piece forms from a hipGraph.
+  *_sharded                one function per solver: ITS sequence of phases and collectives, written once, handed to
+                           _driver.drive (the outer loop of the single-GPU solvers) by _sharded_loop.
+  factorize                the reference's call surface, SPMD.
+
+The sequence of collectives of a run is fixed by these functions and by what negotiate() settled, never by probing an
+object for a method: tests/test_dist_sequence.py pins it.
 """
 import logging
 
 import numpy as np
 
 from . import utils
-from ._driver import Results
+from ._driver import Results, drive, require_iterations
 
 
 def row_range(m, rank, world):
@@ -35,6 +40,8 @@ class TorchComm:
     `stage_through_host=True` copies device tensors to the host, reduces them
     with a CPU backend (gloo) and copies back: slow, but lets several ranks
     share ONE GPU in tests where RCCL refuses duplicate devices."""
+    scatters = True             # reduce_scatter / all_gather: the "rsag" exchange form is open to this communicator
+    async_all_reduce = True     # all_reduce_async: the chunked exchange form is
 
     def __init__(self, group=None, stage_through_host=False):
         import inspect
@@ -131,29 +138,23 @@ class TorchComm:
         self.dist.barrier(group=self.group)
 
 
-class DeviceShard:
-    """HIP engine for one row shard, with exchange buffers allocated by torch so
-    that RCCL can reduce them in place, and running on torch's current stream so
-    the collective is ordered after phase A and before phase B."""
+class Shard:
+    """One rank's rows of V and W behind an engine, and what the drivers below ask of it beyond the engine's phase calls
+    (`shard.eng.<phase>`): the exchange buffers and everything that fixes the SEQUENCE of collectives.  The defaults are
+    those of a shard with nothing to settle: one exchange form, the objective partial in the f64 buffer."""
+    fused_w_rounds = False      # aoadmm_phase_w_fused / _repair: the W sub-problem of AO-ADMM with ONE exchange
 
     def __init__(self, v_local, k, w0_local, h0, device, shape=None, fill=None):
         """`v_local`: this rank's rows of V (host array) -- or None with `shape = (rows, n)` and `fill(engine)`, a callable
-        that hands the rows over on the device (Engine.upload_v_device), for shards that are produced there."""
-        import torch
+        that hands the rows over on the device (Engine.upload_v_device), for shards that are produced there.  The subclass's
+        `_make_buffers(device, n32, n64)` provides `xf32` / `xf64`."""
         from .engine import Engine
-        self.torch = torch
-        torch.cuda.set_device(device)
         rows, n = v_local.shape if v_local is not None else shape
         self.eng = Engine(rows, n, k, device=device)
-        n32, n64 = self.eng.exchange_sizes()
-        self.xf32 = torch.zeros(n32, dtype=torch.float32, device=f"cuda:{device}")
-        self.xf64 = torch.zeros(n64, dtype=torch.float64, device=f"cuda:{device}")
-        torch.cuda.synchronize()
         self._merged = False          # negotiate(comm) settles these two with the other ranks
         self._chunk_unit = 0
         self._negotiated = None
-        self.eng.set_exchange_buffers(self.xf32.data_ptr(), n32, self.xf64.data_ptr(), n64)
-        self.eng.set_stream(torch.cuda.current_stream().cuda_stream)
+        self._make_buffers(device, *self.eng.exchange_sizes())
         if v_local is not None:
             self.eng.upload_v(v_local)
         else:
@@ -162,6 +163,49 @@ class DeviceShard:
 
     def buffers(self):
         return self.xf32, self.xf64
+
+    def negotiate(self, comm):
+        """Agree with the other ranks of `comm` on what fixes the sequence of collectives.  Here: nothing to settle."""
+
+    def merge_objective(self):
+        """True when the objective partial of MUR-eu travels inside the f32 exchange buffer."""
+        return False
+
+    def chunk_ranges(self, dist_code, chunks):
+        """Column ranges of a phase A in `chunks` pieces, or None: no chunked phase A."""
+        return None
+
+    def slice_info(self, dist_code, world):
+        """(columns of H per rank, f32 exchange elements per rank) of the sliced phase B, or (0, 0): none."""
+        return 0, 0
+
+    def anls_set_distance(self, dist_code):
+        if dist_code != 0:
+            raise NotImplementedError("this shard type reports the Euclidean objective only")
+
+    def close(self):
+        pass
+
+
+class DeviceShard(Shard):
+    """HIP engine for one row shard, with exchange buffers allocated by torch so
+    that RCCL can reduce them in place, and running on torch's current stream so
+    the collective is ordered after phase A and before phase B."""
+    fused_w_rounds = True
+
+    def __init__(self, v_local, k, w0_local, h0, device, shape=None, fill=None):
+        import torch
+        self.torch = torch
+        torch.cuda.set_device(device)
+        super().__init__(v_local, k, w0_local, h0, device, shape, fill)
+
+    def _make_buffers(self, device, n32, n64):
+        torch = self.torch
+        self.xf32 = torch.zeros(n32, dtype=torch.float32, device=f"cuda:{device}")
+        self.xf64 = torch.zeros(n64, dtype=torch.float64, device=f"cuda:{device}")
+        torch.cuda.synchronize()
+        self.eng.set_exchange_buffers(self.xf32.data_ptr(), n32, self.xf64.data_ptr(), n64)
+        self.eng.set_stream(torch.cuda.current_stream().cuda_stream)
 
     def negotiate(self, comm):
         """Agree with the other ranks of `comm` on everything that fixes the SEQUENCE of collectives: whether the
@@ -175,15 +219,14 @@ class DeviceShard:
             return
         import os
         torch = self.torch
-        rank, world = getattr(comm, "rank", 0), getattr(comm, "world", 1)
         bf16 = 1 if self.eng.precision() == "bf16" else 0
         merge = 0
-        if os.environ.get("NMFX_DIST_MERGE", "1") != "0" and bf16 and world <= 64:
+        if os.environ.get("NMFX_DIST_MERGE", "1") != "0" and bf16 and comm.world <= 64:
             merge = 1
         unit = int(self.eng.mur_chunk_info(0)[0] or 0)
         offer = [merge, unit, bf16, -bf16]              # MIN over ranks: [all can merge, smallest unit, all bf16, -(any bf16)]
-        if world > 1:
-            staged = getattr(comm, "stage", False) or comm.dist.get_backend(comm.group) != "nccl"
+        if comm.world > 1:
+            staged = comm.stage or comm.dist.get_backend(comm.group) != "nccl"
             t = torch.tensor(offer, dtype=torch.int64, device="cpu" if staged else self.xf32.device)
             comm.dist.all_reduce(t, op=comm.dist.ReduceOp.MIN, group=comm.group)
             offer = [int(x) for x in t.tolist()]
@@ -193,7 +236,7 @@ class DeviceShard:
         self._merged = bool(offer[0])
         self._chunk_unit = offer[1]
         if self._merged:
-            self.eng.set_exchange_rank(rank, world)     # (cannot fail: every rank has just said it runs the split-bf16 epilogues)
+            self.eng.set_exchange_rank(comm.rank, comm.world)     # (cannot fail: every rank has just said it runs the split-bf16 epilogues)
         else:
             self.eng.set_exchange_rank(0, 0)
         self._negotiated = key
@@ -202,12 +245,6 @@ class DeviceShard:
         """True when the objective partial of MUR-eu travels inside the f32 exchange buffer (split-bf16 epilogues on EVERY rank, at
         most 64 ranks; NMFX_DIST_MERGE=0 keeps the separate f64 all-reduce).  Settled by negotiate()."""
         return bool(self._merged)
-
-    def phase_a(self, dist_code, lambda_w, j):
-        self.eng.mur_phase_a(dist_code, lambda_w, j)
-
-    def phase_b(self, dist_code, lambda_h, min_iter, tol1, tol2, j):
-        self.eng.mur_phase_b(dist_code, lambda_h, min_iter, tol1, tol2, j)
 
     def chunk_ranges(self, dist_code, chunks):
         """Column ranges [(c0, c1, first element, end element of the f32 exchange buffer)] of a phase A in `chunks` pieces,
@@ -230,96 +267,8 @@ class DeviceShard:
         where the engine has none for this loss / arithmetic / shape (nmfx_mur_slice_info)."""
         return self.eng.mur_slice_info(dist_code, world)
 
-    def phase_b_slice(self, dist_code, lambda_h, min_iter, tol1, tol2, j, c0, c1):
-        self.eng.mur_phase_b_slice(dist_code, lambda_h, min_iter, tol1, tol2, j, c0, c1)
-
-    def phase_b_rest(self, dist_code, c0, c1):
-        self.eng.mur_phase_b_rest(dist_code, c0, c1)
-
-    def phase_a_head(self, dist_code, lambda_w, j):
-        self.eng.mur_phase_a_head(dist_code, lambda_w, j)
-
-    def phase_a_cols(self, dist_code, c0, c1):
-        self.eng.mur_phase_a_cols(dist_code, c0, c1)
-
-    def finish_a(self, dist_code, j):
-        self.eng.mur_finish_a(dist_code, j)
-
-    def finish_b(self, min_iter, tol1, tol2, j):
-        self.eng.mur_finish_b(min_iter, tol1, tol2, j)
-
-    # AO-ADMM / ANLS phases: straight delegation to the engine
-    def ao_h_products(self, j):
-        self.eng.aoadmm_phase_h_products(j)
-
-    def ao_h_solve(self, prox_h, lam_h, admm_iter, min_iter, tol1, tol2, j):
-        self.eng.aoadmm_phase_h_solve(prox_h, lam_h, admm_iter, min_iter, tol1, tol2, j)
-
-    def ao_w_products(self, min_iter, tol1, tol2, j):
-        self.eng.aoadmm_phase_w_products(min_iter, tol1, tol2, j)
-
-    def ao_w_round(self, prox_w, lam_w, rnd):
-        self.eng.aoadmm_phase_w_round(prox_w, lam_w, rnd)
-
-    def ao_w_close(self, admm_iter, j):
-        self.eng.aoadmm_phase_w_close(admm_iter, j)
-
-    def ao_w_fused(self, prox_w, lam_w, admm_iter):
-        self.eng.aoadmm_phase_w_fused(prox_w, lam_w, admm_iter)
-
-    def ao_w_repair(self, prox_w, lam_w, admm_iter, j):
-        self.eng.aoadmm_phase_w_repair(prox_w, lam_w, admm_iter, j)
-
-    def ao_kl_h_products(self, j, rnd):
-        self.eng.aoadmm_kl_phase_h_products(j, rnd)
-
-    def ao_kl_h_round(self, prox_h, lam_h, rnd, min_iter, tol1, tol2, j):
-        self.eng.aoadmm_kl_phase_h_round(prox_h, lam_h, rnd, min_iter, tol1, tol2, j)
-
-    def ao_kl_h_close(self, admm_iter, min_iter, tol1, tol2, j):
-        self.eng.aoadmm_kl_phase_h_close(admm_iter, min_iter, tol1, tol2, j)
-
-    def ao_kl_w_round(self, prox_w, lam_w, rnd):
-        self.eng.aoadmm_kl_phase_w_round(prox_w, lam_w, rnd)
-
-    def ao_kl_w_close(self, admm_iter, j):
-        self.eng.aoadmm_kl_phase_w_close(admm_iter, j)
-
-    def admm_products(self, dist_code, rho, prox_w, prox_h, j):
-        self.eng.admm_phase_products(dist_code, rho, prox_w, prox_h, j)
-
-    def admm_update(self, dist_code, rho, prox_w, lam_w, prox_h, lam_h, min_iter, tol1, tol2, j):
-        self.eng.admm_phase_update(dist_code, rho, prox_w, lam_w, prox_h, lam_h, min_iter, tol1, tol2, j)
-
-    def set_l2n_operator(self, which, p):
-        self.eng.set_l2n_operator(which, p)
-
     def anls_set_distance(self, dist_code):
         self.eng.anls_set_distance(dist_code)
-
-    def objective_partial(self):
-        self.eng.objective_partial()
-
-    def anls_objective(self, j):
-        self.eng.anls_phase_objective(j)
-
-    def anls_w(self, lam_w, min_iter, tol1, tol2, j):
-        self.eng.anls_phase_w(lam_w, min_iter, tol1, tol2, j)
-
-    def anls_h(self, lam_h, j):
-        self.eng.anls_phase_h(lam_h, j)
-
-    def state(self):
-        return self.eng.state()
-
-    def objectives(self, first, count):
-        return self.eng.objectives(first, count)
-
-    def get_factors(self):
-        return self.eng.get_factors()
-
-    def synchronize(self):
-        self.eng.synchronize()
 
     def close(self):
         self.eng.close()
@@ -347,20 +296,11 @@ class NativeShard(DeviceShard):
     the engine's own stream, the sharded MUR loop as one C call (nmfx_mur_run_sharded) -- no torch tensor, stream or collective on
     the data path.  torch.distributed is only the launcher's means of handing rank 0's 128-byte RCCL id to the other ranks
     (`NativeComm.create`)."""
+    torch = None
+    __init__ = Shard.__init__
 
-    def __init__(self, v_local, k, w0_local, h0, device, shape=None, fill=None):
-        from .engine import Engine
-        self.torch = None
-        rows, n = v_local.shape if v_local is not None else shape
-        self.eng = Engine(rows, n, k, device=device)
-        n32, n64 = self.eng.exchange_sizes()
+    def _make_buffers(self, device, n32, n64):
         self.xf32, self.xf64 = ExRef(0, 0, n32), ExRef(1, 0, n64)
-        self._merged, self._chunk_unit, self._negotiated = False, 0, None
-        if v_local is not None:
-            self.eng.upload_v(v_local)
-        else:
-            fill(self.eng)
-        self.eng.set_factors(w0_local, h0)
 
     def negotiate(self, comm):
         key = (id(comm), self.eng.precision_epoch)     # (nmfx_set_precision voids the library's side as well)
@@ -375,6 +315,8 @@ class NativeShard(DeviceShard):
 class NativeComm:
     """The exchange of a NativeShard: nmfx_comm_* (RCCL through the C ABI) on the engine's stream."""
     stage = False
+    scatters = False            # (the library's own loop has the reduce-scatter / all-gather form: nmfx_comm_set_exchange)
+    async_all_reduce = True
 
     def __init__(self, shard, rank, world, uid):
         self.eng, self.rank, self.world = shard.eng, rank, world
@@ -405,17 +347,12 @@ class NativeComm:
         self.eng.comm_destroy()
 
 
-def _negotiate(shard, comm):
-    if comm is not None and getattr(shard, "negotiate", None) is not None:
-        shard.negotiate(comm)
-
-
 def _mur_buffers(shard, dist_code=None):
     """The exchange of one MUR iteration.  A device shard with the Euclidean loss carries its objective partial inside the f32
     buffer (nmfx_set_exchange_rank: every rank's partial as exact 16-bit digits in its own slot), so ONE all-reduce
     suffices; otherwise the f32 buffer and the head of the f64 buffer (its tail is the norm table of sharded AO-ADMM)."""
     x32, x64 = shard.buffers()
-    if dist_code == 0 and getattr(shard, "merge_objective", None) is not None and shard.merge_objective():
+    if dist_code == 0 and shard.merge_objective():
         return (x32,)
     return x32, x64[:8]
 
@@ -445,67 +382,67 @@ def exchange_mode():
 
 
 def _slice_plan(shard, comm, dist_code):
-    """(c0, c1, elems) of this rank's column slice for the reduce-scatter / all-gather exchange, or None (mode off, a shard or
-    communicator without it, or the engine has no sliced phase B for this run: every rank then takes the all-reduce -- the answer
+    """(c0, c1, elems) of this rank's column slice for the reduce-scatter / all-gather exchange, or None (mode off, a
+    communicator without it, or the shard has no sliced phase B for this run: every rank then takes the all-reduce -- the answer
     depends on the shape, the loss and what negotiate() settled, which are the same everywhere)."""
-    if exchange_mode() != "rsag" or getattr(shard, "slice_info", None) is None or not hasattr(comm, "reduce_scatter"):
+    if exchange_mode() != "rsag" or not comm.scatters:
         return None
-    world, rank = getattr(comm, "world", 1), getattr(comm, "rank", 0)
-    cols, elems = shard.slice_info(dist_code, world)
+    cols, elems = shard.slice_info(dist_code, comm.world)
     if not cols:
         return None
-    return rank * cols, (rank + 1) * cols, elems
+    return comm.rank * cols, (comm.rank + 1) * cols, elems
 
 
 def _iteration(shard, comm, bufs, plan, dist_code, lambda_w, lambda_h, min_iter, tol1, tol2, j):
     """One sharded outer iteration, exchange in one piece: all-reduce, or reduce-scatter . slice . all-gather . rest."""
-    shard.phase_a(dist_code, lambda_w, j)
+    eng = shard.eng
+    eng.mur_phase_a(dist_code, lambda_w, j)
     if plan is None:
         comm.all_reduce(*bufs)
-        shard.phase_b(dist_code, lambda_h, min_iter, tol1, tol2, j)
+        eng.mur_phase_b(dist_code, lambda_h, min_iter, tol1, tol2, j)
         return
     c0, c1, elems = plan
     x32 = bufs[0]
-    world = getattr(comm, "world", 1)
     comm.reduce_scatter(x32, elems)
-    comm.all_reduce(x32[world * elems:], *bufs[1:])               # W^T W, the objective digits (and the f64 partial where not merged)
-    shard.phase_b_slice(dist_code, lambda_h, min_iter, tol1, tol2, j, c0, c1)
+    comm.all_reduce(x32[comm.world * elems:], *bufs[1:])          # W^T W, the objective digits (and the f64 partial where not merged)
+    eng.mur_phase_b_slice(dist_code, lambda_h, min_iter, tol1, tol2, j, c0, c1)
     comm.all_gather(x32, elems)
-    shard.phase_b_rest(dist_code, c0, c1)
+    eng.mur_phase_b_rest(dist_code, c0, c1)
+
+
+def _chunked_iteration(shard, comm, bufs, ranges, dist_code, lambda_w, lambda_h, min_iter, tol1, tol2, j):
+    """One sharded outer iteration with phase A in column chunks, the all-reduce of each chunk running behind the next one."""
+    eng = shard.eng
+    x32 = bufs[0]
+    eng.mur_phase_a_head(dist_code, lambda_w, j)
+    pending = []
+    for c0, c1, e0, e1 in ranges:
+        eng.mur_phase_a_cols(dist_code, c0, c1)
+        pending.append(comm.all_reduce_async(x32[e0:e1]))
+    if len(bufs) > 1:                                            # (the objective partial when it is not inside the f32 buffer)
+        comm.all_reduce(*bufs[1:])
+    for work in pending:
+        if work is not None:
+            work.wait()
+    eng.mur_phase_b(dist_code, lambda_h, min_iter, tol1, tol2, j)
 
 
 def run_iterations(shard, comm, dist_code, lambda_w, lambda_h, min_iter, tol1, tol2, first, count, chunks=None):
-    """Queue `count` sharded outer iterations (no host sync)."""
-    _negotiate(shard, comm)
+    """Queue `count` sharded outer iterations (no host sync).  The exchange form is chosen once: reduce-scatter / all-gather
+    where asked for and available, else column chunks where asked for and available, else the all-reduce."""
+    shard.negotiate(comm)
     bufs = _mur_buffers(shard, dist_code)
     plan = _slice_plan(shard, comm, dist_code)
-    if plan is not None:
-        for j in range(first, first + count):
-            _iteration(shard, comm, bufs, plan, dist_code, lambda_w, lambda_h, min_iter, tol1, tol2, j)
-        return
-    chunks = _exchange_chunks() if chunks is None else chunks
     ranges = None
-    if chunks > 1 and dist_code == 0 and getattr(shard, "chunk_ranges", None) is not None and hasattr(comm, "all_reduce_async"):
-        ranges = shard.chunk_ranges(dist_code, chunks)
-    if ranges is None:
-        for j in range(first, first + count):
-            shard.phase_a(dist_code, lambda_w, j)
-            comm.all_reduce(*bufs)
-            shard.phase_b(dist_code, lambda_h, min_iter, tol1, tol2, j)
-        return
-    x32 = bufs[0]
+    if plan is None:
+        chunks = _exchange_chunks() if chunks is None else chunks
+        if chunks > 1 and dist_code == 0 and comm.async_all_reduce:
+            ranges = shard.chunk_ranges(dist_code, chunks)
     for j in range(first, first + count):
-        shard.phase_a_head(dist_code, lambda_w, j)
-        pending = []
-        for c0, c1, e0, e1 in ranges:
-            shard.phase_a_cols(dist_code, c0, c1)
-            pending.append(comm.all_reduce_async(x32[e0:e1]))
-        if len(bufs) > 1:                                            # (the objective partial when it is not inside the f32 buffer)
-            comm.all_reduce(*bufs[1:])
-        for work in pending:
-            if work is not None:
-                work.wait()
-        shard.phase_b(dist_code, lambda_h, min_iter, tol1, tol2, j)
+        if ranges is None:
+            _iteration(shard, comm, bufs, plan, dist_code, lambda_w, lambda_h, min_iter, tol1, tol2, j)
+        else:
+            _chunked_iteration(shard, comm, bufs, ranges, dist_code, lambda_w, lambda_h, min_iter, tol1, tol2, j)
 
 
 class GraphedIterations:
@@ -526,7 +463,7 @@ class GraphedIterations:
         self.shard, self.torch = shard, torch
         self.args = (dist_code, lambda_w, lambda_h, min_iter, tol1, tol2)
         self.graph = torch.cuda.CUDAGraph()
-        _negotiate(shard, comm)
+        shard.negotiate(comm)
         bufs = _mur_buffers(shard, dist_code)
         plan = _slice_plan(shard, comm, dist_code)
         side = torch.cuda.Stream()
@@ -563,25 +500,23 @@ class Runner:
         import os
         self.shard, self.comm = shard, comm
         self.args = (dist_code, lambda_w, lambda_h, min_iter, tol1, tol2)
-        self.native = isinstance(comm, NativeComm)
-        if self.native:
-            # the whole loop is one C call per batch (nmfx_mur_run_sharded); hipGraph replay is the library's business too
-            if graph is None:
-                graph = os.environ.get("NMFX_DIST_GRAPH", "0") == "1"
-            shard.negotiate(comm)
-            shard.eng.comm_set_exchange(1 if exchange_mode() == "rsag" else 0)
-            shard.eng.comm_set_graph(bool(graph) and max_iter >= 4)
-            self.want_graph, self.graph = False, None
-            self.mode = "native-hipgraph" if (graph and max_iter >= 4) else "native"
-            return
         if graph is None:
             # opt-in: capturing RCCL collectives of a multi-rank world cannot be rehearsed on a one-GPU
             # box, and the replay only removes launch gaps (5 % at 2048 rows per rank) -- the eager loop
             # is GPU-bound, not host-bound
             graph = os.environ.get("NMFX_DIST_GRAPH", "0") == "1"
-        capturable = isinstance(shard, DeviceShard) and not getattr(comm, "stage", True)
-        self.want_graph = bool(graph and capturable and max_iter >= 4)
+        graph = bool(graph) and max_iter >= 4
+        self.native = isinstance(comm, NativeComm)
         self.graph = None
+        if self.native:
+            # the whole loop is one C call per batch (nmfx_mur_run_sharded); hipGraph replay is the library's business too
+            shard.negotiate(comm)
+            shard.eng.comm_set_exchange(1 if exchange_mode() == "rsag" else 0)
+            shard.eng.comm_set_graph(graph)
+            self.want_graph = False
+            self.mode = "native-hipgraph" if graph else "native"
+            return
+        self.want_graph = graph and isinstance(shard, DeviceShard) and not comm.stage
         self.mode = "eager"
         if self.want_graph:
             shard.eng.reserve_objectives(max_iter + 2)     # the history must not move under the graph
@@ -598,7 +533,7 @@ class Runner:
     def _capture(self):
         self.want_graph = False
         try:
-            self.shard.synchronize()
+            self.shard.eng.synchronize()
             self.graph = GraphedIterations(self.shard, self.comm, *self.args)
             self.mode = "hipgraph"
         except Exception as exc:      # noqa: BLE001
@@ -640,75 +575,41 @@ def finish(shard, comm, dist_code, min_iter, tol1, tol2, done):
     if isinstance(comm, NativeComm):
         shard.eng.mur_finish_sharded(dist_code, min_iter, tol1, tol2, done)
         return
-    shard.finish_a(dist_code, done)
+    shard.eng.mur_finish_a(dist_code, done)
     comm.all_reduce(_mur_buffers(shard)[1])
-    shard.finish_b(min_iter, tol1, tol2, done)
+    shard.eng.mur_finish_b(min_iter, tol1, tol2, done)
+
+
+def _finish_run(shard, comm, min_iter, tol1, tol2, done):
+    """The closing step of AO-ADMM, ADMM and ANLS: the objective of the last pair of factors, summed over the ranks, recorded
+    and tested like every other entry of the history."""
+    shard.eng.objective_partial()
+    comm.all_reduce(shard.buffers()[1][:8])
+    shard.eng.mur_finish_b(min_iter, tol1, tol2, done)
+
+
+def _sharded_loop(shard, comm, queue, finish_run, *, max_iter, tol1, tol2, batch, experiment):
+    """The reference's outer loop (_driver.drive: obj_history, `[i]: objective` lines on rank 0, stop bookkeeping) around
+    `queue(first, count)`, which only queues device work and collectives, and `finish_run(done)`.  Returns Results whose `w`
+    is THIS rank's row block; h, i and obj_history are identical on every rank."""
+    require_iterations(max_iter)                       # (before any collective)
+    shard.negotiate(comm)
+    i, history = drive(shard.eng, queue, finish_run, max_iter, tol1, tol2, batch=batch, prints=comm.rank == 0)
+    w, h = shard.eng.get_factors()
+    return Results(w, h, i, history, experiment)
 
 
 def mur_sharded(shard, comm, *, distance_type='eu', min_iter=100, max_iter=100000, tol1=1e-5,
                 tol2=1e-5, lambda_w=0.0, lambda_h=0.0, batch=32, experiment=None, graph=None):
-    """The reference's MUR loop (nmf/mur.py:119-145) over a row-sharded V.
-    Returns Results whose `w` is THIS rank's row block; h, i and obj_history
-    are identical on every rank."""
+    """The reference's MUR loop (nmf/mur.py:119-145) over a row-sharded V: one exchange of [W^T V | W^T W | objective] per
+    outer iteration, in the form run_iterations chooses (or inside the library: NativeComm)."""
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')
-    if max_iter <= 0:
-        raise UnboundLocalError("local variable 'i' referenced before assignment")
+    require_iterations(max_iter)                       # (the Runner of a native communicator negotiates when it is made)
     code = 0 if distance_type == 'eu' else 1
-    digits = utils.tol_digits(tol1, tol2)
-    history, done, rule, stop_i = [], 0, 0, -1
     runner = Runner(shard, comm, code, lambda_w, lambda_h, min_iter, tol1, tol2, max_iter, graph=graph)
-    while done < max_iter and not rule:
-        count = min(batch, max_iter - done)
-        runner(done, count)
-        done += count
-        if done == max_iter:
-            finish(shard, comm, code, min_iter, tol1, tol2, done)
-        rule, stop_i, n_obj = shard.state()
-        for val in shard.objectives(len(history), n_obj - len(history)):
-            history.append(np.float64(val))
-            if len(history) >= 2 and comm.rank == 0:
-                utils.say('[{}]: {:.{}f}'.format(len(history) - 2, val, digits))
-    w, h = shard.get_factors()
-    if rule:
-        if comm.rank == 0:
-            utils.convergence_message(rule)
-        logging.warning('Converged.')
-        return Results(w, h, stop_i, history[:stop_i + 2], experiment)
-    return Results(w, h, max_iter - 1, history, experiment)
-
-
-def _sharded_loop(shard, comm, queue, finish_run, *, max_iter, tol1, tol2, batch, experiment):
-    """The reference's outer loop shape (obj_history, `[i]: objective` lines, stop bookkeeping)
-    around `queue(first, count)`, which only queues device work and collectives."""
-    _negotiate(shard, comm)
-    if max_iter <= 0:
-        raise UnboundLocalError("local variable 'i' referenced before assignment")
-    digits = utils.tol_digits(tol1, tol2)
-    history, done, rule, stop_i = [], 0, 0, -1
-    while done < max_iter and not rule:
-        count = min(batch, max_iter - done)
-        queue(done, count)
-        done += count
-        if done == max_iter:
-            finish_run(done)
-        rule, stop_i, n_obj = shard.state()
-        for val in shard.objectives(len(history), n_obj - len(history)):
-            history.append(np.float64(val))
-            if len(history) >= 2 and comm.rank == 0:
-                utils.say('[{}]: {:.{}f}'.format(len(history) - 2, val, digits))
-    w, h = shard.get_factors()
-    if rule:
-        if comm.rank == 0:
-            utils.convergence_message(rule)
-        logging.warning('Converged.')
-        return Results(w, h, stop_i, history[:stop_i + 2], experiment)
-    return Results(w, h, max_iter - 1, history, experiment)
-
-
-def _prox_code(kind):
-    from .ao_admm import _prox_code as single        # same codes and the reference's errors ('l2n': ValueError, 'l1inf*': LinAlgError)
-    return single(kind)
+    return _sharded_loop(shard, comm, runner, lambda done: finish(shard, comm, code, min_iter, tol1, tol2, done),
+                         max_iter=max_iter, tol1=tol1, tol2=tol2, batch=batch, experiment=experiment)
 
 
 MAX_FUSED_ROUNDS = 64         # rows of the norm table in the engine's f64 exchange buffer
@@ -729,66 +630,55 @@ def aoadmm_sharded(shard, comm, *, distance_type='eu', reg_w=(0, 'nn'), reg_h=(0
     INSIDE the inner rounds, so every round of the H sub-problem all-reduces [W^T S | W^T W] and every round of the W
     sub-problem its four norm sums; v_aux and dual_v (m x n) are rank-local rows.  Returns Results with THIS rank's rows
     of w."""
+    from .ao_admm import _prox_code          # same codes and the reference's errors ('l2n': ValueError, 'l1inf*': LinAlgError)
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')
     prox_h, prox_w = _prox_code(reg_h[1]), _prox_code(reg_w[1])     # H's regulariser is met first
+    eng = shard.eng
     x32, x64 = shard.buffers()
     norms = x64[1:5]
-    if distance_type == 'kl':
-        def queue_kl(first, count):
-            for j in range(first, first + count):
-                for rnd in range(admm_iter):
-                    shard.ao_kl_h_products(j, rnd)
-                    if rnd == 0:
-                        comm.all_reduce(x32, x64[:8])
-                    else:
-                        comm.all_reduce(x32)
-                    shard.ao_kl_h_round(prox_h, reg_h[0], rnd, min_iter, tol1, tol2, j)
-                shard.ao_kl_h_close(admm_iter, min_iter, tol1, tol2, j)
-                for rnd in range(admm_iter):
-                    shard.ao_kl_w_round(prox_w, reg_w[0], rnd)
-                    comm.all_reduce(norms)
-                shard.ao_kl_w_close(admm_iter, j)
-
-        def finish_kl(done):
-            shard.objective_partial()
-            comm.all_reduce(x64[:8])
-            shard.finish_b(min_iter, tol1, tol2, done)
-
-        return _sharded_loop(shard, comm, queue_kl, finish_kl, max_iter=max_iter, tol1=tol1, tol2=tol2,
-                             batch=batch, experiment=experiment)
     # ONE exchange for the whole W sub-problem where the shard can run its rounds speculatively (the HIP engine, for
     # 2 <= admm_iter <= 64): the [admm_iter x 4] table of norm sums.  `fused=False` keeps one exchange per round.
+    # (beyond 128 components the device composes the iteration from generic kernels -- r4 -- and exchanges the norm sums of
+    #  the W sub-problem round by round: the speculative fused rounds keep a k-wide panel on chip)
     if fused is None:
-        # (beyond 128 components the device composes the iteration from generic kernels -- r4 -- and exchanges the norm sums of
-        #  the W sub-problem round by round: the speculative fused rounds keep a k-wide panel on chip)
-        small_k = getattr(getattr(shard, "eng", None), "k", 0) <= 128
-        fused = hasattr(shard, "ao_w_fused") and 2 <= admm_iter <= MAX_FUSED_ROUNDS and small_k
+        fused = shard.fused_w_rounds and 2 <= admm_iter <= MAX_FUSED_ROUNDS and eng.k <= 128
     table = x64[8:8 + 4 * admm_iter] if fused else None
 
-    def queue(first, count):
+    def queue_kl(first, count):
         for j in range(first, first + count):
-            shard.ao_h_products(j)
+            for rnd in range(admm_iter):
+                eng.aoadmm_kl_phase_h_products(j, rnd)
+                if rnd == 0:
+                    comm.all_reduce(x32, x64[:8])
+                else:
+                    comm.all_reduce(x32)
+                eng.aoadmm_kl_phase_h_round(prox_h, reg_h[0], rnd, min_iter, tol1, tol2, j)
+            eng.aoadmm_kl_phase_h_close(admm_iter, min_iter, tol1, tol2, j)
+            for rnd in range(admm_iter):
+                eng.aoadmm_kl_phase_w_round(prox_w, reg_w[0], rnd)
+                comm.all_reduce(norms)
+            eng.aoadmm_kl_phase_w_close(admm_iter, j)
+
+    def queue_eu(first, count):
+        for j in range(first, first + count):
+            eng.aoadmm_phase_h_products(j)
             comm.all_reduce(x32, x64[:8])
-            shard.ao_h_solve(prox_h, reg_h[0], admm_iter, min_iter, tol1, tol2, j)
-            shard.ao_w_products(min_iter, tol1, tol2, j)
+            eng.aoadmm_phase_h_solve(prox_h, reg_h[0], admm_iter, min_iter, tol1, tol2, j)
+            eng.aoadmm_phase_w_products(min_iter, tol1, tol2, j)
             if fused:
-                shard.ao_w_fused(prox_w, reg_w[0], admm_iter)
+                eng.aoadmm_phase_w_fused(prox_w, reg_w[0], admm_iter)
                 comm.all_reduce(table)
-                shard.ao_w_repair(prox_w, reg_w[0], admm_iter, j)
+                eng.aoadmm_phase_w_repair(prox_w, reg_w[0], admm_iter, j)
             else:
                 for rnd in range(admm_iter):
-                    shard.ao_w_round(prox_w, reg_w[0], rnd)
+                    eng.aoadmm_phase_w_round(prox_w, reg_w[0], rnd)
                     comm.all_reduce(norms)
-                shard.ao_w_close(admm_iter, j)
+                eng.aoadmm_phase_w_close(admm_iter, j)
 
-    def finish_run(done):
-        shard.objective_partial()
-        comm.all_reduce(x64[:8])
-        shard.finish_b(min_iter, tol1, tol2, done)
-
-    return _sharded_loop(shard, comm, queue, finish_run, max_iter=max_iter, tol1=tol1, tol2=tol2,
-                         batch=batch, experiment=experiment)
+    return _sharded_loop(shard, comm, queue_kl if distance_type == 'kl' else queue_eu,
+                         lambda done: _finish_run(shard, comm, min_iter, tol1, tol2, done),
+                         max_iter=max_iter, tol1=tol1, tol2=tol2, batch=batch, experiment=experiment)
 
 
 def admm_sharded(shard, comm, *, rho=1, distance_type='eu', reg_w=(0, 'nn'), reg_h=(0, 'nn'), min_iter=10,
@@ -809,26 +699,21 @@ def admm_sharded(shard, comm, *, rho=1, distance_type='eu', reg_w=(0, 'nn'), reg
         raise NotImplementedError(f"prox '{reg_w[1]}' on W couples all rows and is not available row-sharded")
     code = 0 if distance_type == 'eu' else 1
     prox_h, prox_w = L.PROX[reg_h[1]], L.PROX[reg_w[1]]
-    k = shard.get_factors()[1].shape[0]
+    eng = shard.eng
     if reg_w[1] == 'l2n':
-        shard.set_l2n_operator(0, l2n_operator(k, rho, reg_w[0]))
+        eng.set_l2n_operator(0, l2n_operator(eng.k, rho, reg_w[0]))
     if reg_h[1] == 'l2n':
-        shard.set_l2n_operator(1, l2n_operator(k, rho, reg_h[0]))
+        eng.set_l2n_operator(1, l2n_operator(eng.k, rho, reg_h[0]))
     x32, x64 = shard.buffers()
 
     def queue(first, count):
         for j in range(first, first + count):
-            shard.admm_products(code, rho, prox_w, prox_h, j)
+            eng.admm_phase_products(code, rho, prox_w, prox_h, j)
             comm.all_reduce(x32, x64[:8])
-            shard.admm_update(code, rho, prox_w, reg_w[0], prox_h, reg_h[0], min_iter, tol1, tol2, j)
+            eng.admm_phase_update(code, rho, prox_w, reg_w[0], prox_h, reg_h[0], min_iter, tol1, tol2, j)
 
-    def finish_run(done):
-        shard.objective_partial()
-        comm.all_reduce(x64[:8])
-        shard.finish_b(min_iter, tol1, tol2, done)
-
-    return _sharded_loop(shard, comm, queue, finish_run, max_iter=max_iter, tol1=tol1, tol2=tol2,
-                         batch=batch, experiment=experiment)
+    return _sharded_loop(shard, comm, queue, lambda done: _finish_run(shard, comm, min_iter, tol1, tol2, done),
+                         max_iter=max_iter, tol1=tol1, tol2=tol2, batch=batch, experiment=experiment)
 
 
 def anls_sharded(shard, comm, *, distance_type='eu', lambda_w=0, lambda_h=0, min_iter=10, max_iter=1000, tol1=1e-3,
@@ -840,27 +725,20 @@ def anls_sharded(shard, comm, *, distance_type='eu', lambda_w=0, lambda_h=0, min
     the iteration are queued.  Returns Results with THIS rank's rows of w."""
     if distance_type not in ('eu', 'kl'):
         raise KeyError('Distance type unknown: use "kl" or "eu"')
-    if hasattr(shard, "anls_set_distance"):
-        shard.anls_set_distance(0 if distance_type == 'eu' else 1)
-    elif distance_type != 'eu':
-        raise NotImplementedError("this shard type reports the Euclidean objective only")
+    shard.anls_set_distance(0 if distance_type == 'eu' else 1)
+    eng = shard.eng
     x32, x64 = shard.buffers()
 
     def queue(first, count):
         for j in range(first, first + count):
-            shard.anls_objective(j)
+            eng.anls_phase_objective(j)
             comm.all_reduce(x64[:8])
-            shard.anls_w(lambda_w, min_iter, tol1, tol2, j)
+            eng.anls_phase_w(lambda_w, min_iter, tol1, tol2, j)
             comm.all_reduce(x32)
-            shard.anls_h(lambda_h, j)
+            eng.anls_phase_h(lambda_h, j)
 
-    def finish_run(done):
-        shard.objective_partial()
-        comm.all_reduce(x64[:8])
-        shard.finish_b(min_iter, tol1, tol2, done)
-
-    return _sharded_loop(shard, comm, queue, finish_run, max_iter=max_iter, tol1=tol1, tol2=tol2,
-                         batch=batch, experiment=experiment)
+    return _sharded_loop(shard, comm, queue, lambda done: _finish_run(shard, comm, min_iter, tol1, tol2, done),
+                         max_iter=max_iter, tol1=tol1, tol2=tol2, batch=batch, experiment=experiment)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -878,21 +756,6 @@ def _defaults(method):
     kw = {name: p.default for name, p in sig.parameters.items()
           if p.kind is p.KEYWORD_ONLY and name not in ('device', 'engine', 'save_dir', 'mask', 'weights', 'beta')}     # (no masked, weighted or beta-divergence sharded runs)
     return mod, kw
-
-
-def _experiment(mod, method, k, kw):
-    if method == 'mur':
-        return mod.Experiment('mur', k, kw['distance_type'], kw['nndsvd_init'], kw['max_iter'], kw['tol1'], kw['tol2'],
-                              kw['lambda_w'], kw['lambda_h'])
-    if method == 'anls':
-        return mod.Experiment('anls', k, kw['distance_type'], kw['nndsvd_init'], kw['max_iter'], kw['tol1'], kw['tol2'],
-                              kw['lambda_w'], kw['lambda_h'], kw['use_fcnnls'])
-    if method == 'admm':
-        return mod.Experiment('admm', k, kw['rho'], kw['distance_type'], kw['nndsvd_init'], kw['min_iter'], kw['max_iter'],
-                              kw['tol1'], kw['tol2'], kw['reg_w'][0], kw['reg_w'][1], kw['reg_h'][0], kw['reg_h'][1])
-    return mod.Experiment('ao_admm', k, kw['distance_type'], kw['nndsvd_init'], kw['min_iter'], kw['max_iter'],
-                          kw['admm_iter'], kw['tol1'], kw['tol2'], kw['reg_w'][0], kw['reg_w'][1], kw['reg_h'][0],
-                          kw['reg_h'][1])
 
 
 def init_process_group(backend=None):
@@ -957,7 +820,7 @@ def factorize(data, k, method='mur', *, gather=True, device=None, backend=None, 
     if unknown:
         raise TypeError(f"{method}() got an unexpected keyword argument '{sorted(unknown)[0]}'")
     kw.update(method_params)
-    experiment = _experiment(mod, method, k, kw)
+    experiment = mod.experiment_of(k, kw)
     m, n = data.shape
     if world > m:
         raise ValueError('more ranks than rows')
@@ -1020,8 +883,7 @@ def factorize(data, k, method='mur', *, gather=True, device=None, backend=None, 
                 w = np.concatenate([parts[p][:row_range(m, p, world)[1] - row_range(m, p, world)[0]].cpu().numpy()
                                     for p in range(world)])
     finally:
-        if hasattr(shard, "close"):
-            shard.close()
+        shard.close()
     return Results(w, res.h, res.i, res.obj_history, experiment)
 
 

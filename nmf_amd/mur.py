@@ -15,11 +15,17 @@ from . import masked
 from . import sparse
 from . import utils
 from . import weighted
-from ._driver import BATCH, NEVER, Referee, Results, run_loop
+from ._driver import BATCH, NEVER, Referee, Results, run_loop, say_objective
 from .engine import Engine
 
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h')
 BetaExperiment = namedtuple('Experiment', Experiment._fields + ('beta',))      # distance_type='beta' alone: one trailing field
+
+
+def experiment_of(k, kw):
+    """The Experiment tuple of a mur run with the keyword arguments `kw` (mur's own, and dist.factorize's)."""
+    return Experiment('mur', k, kw['distance_type'], kw['nndsvd_init'], kw['max_iter'], kw['tol1'], kw['tol2'],
+                      kw['lambda_w'], kw['lambda_h'])
 
 
 def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-5,
@@ -38,8 +44,7 @@ def mur(x, k, *, distance_type='kl', min_iter=100, max_iter=100000, tol1=1e-5, t
     1 <= k <= 256).  weights: None, or a dense real array Omega >= 0 of x's shape (boolean counts as 0 / 1): the fit is
     Sum omega * loss(x, wh) on the dense kernels with k <= 128; a cell with weight 0 is unknown and x is not read there
     (nmf_amd.weighted; not together with mask= or engine=).  Returns Results(w, h, i, obj_history, experiment) with float64 w, h."""
-    experiment = Experiment('mur', k, distance_type, nndsvd_init, max_iter, tol1, tol2,
-                            lambda_w, lambda_h)
+    experiment = experiment_of(k, locals())
     losses.check_loss(distance_type)
     dist = losses.CODES[distance_type]
     beta = losses.check_beta(distance_type, beta)
@@ -222,7 +227,7 @@ def mur_pair(x, k, params, *, min_iter=100, max_iter=100000, tol1=1e-5, tol2=1e-
             else:
                 i = max_iter - 1
             for it, val in enumerate(history[1:]):              # the lines the reference prints, problem by problem
-                utils.say('[{}]: {:.{}f}'.format(it, val, digits))
+                say_objective(it, val, digits)
             if rule:
                 utils.convergence_message(rule)
                 logging.warning('Converged.')

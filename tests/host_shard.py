@@ -1,16 +1,20 @@
 """numpy stand-in for the HIP engine of one row shard (TEST INFRASTRUCTURE).
 
-Implements the same phase_a / all-reduce / phase_b protocol as
-nmf_amd.dist.DeviceShard with the oracle's arithmetic on the local rows, so the
-sharding logic of nmf_amd/dist.py can be exercised with gloo on a CPU-only box."""
+A nmf_amd.dist.Shard that is its own engine (`shard.eng is shard`): it implements the phase methods of
+nmf_amd.engine.Engine that the sharded drivers call, under the Engine's names, with the oracle's arithmetic on the local
+rows, so the sharding logic of nmf_amd/dist.py can be exercised with gloo on a CPU-only box."""
 import numpy as np
 import torch
 
+from nmf_amd.dist import Shard
 from oracle import nmf_ref as R
 
 
-class HostShard:
+class HostShard(Shard):
+    fused_w_rounds = True
+
     def __init__(self, v_local, k, w0_local, h0):
+        self.eng = self
         self.v = np.asarray(v_local, dtype=np.float64)
         self.w = w0_local.copy()
         self.h = h0.copy()
@@ -34,7 +38,7 @@ class HostShard:
         t = np.where(np.isnan(t) | (t == np.inf), 0, t)
         return np.sum(t - self.v + wh)
 
-    def phase_a(self, kind, lambda_w, j):
+    def mur_phase_a(self, kind, lambda_w, j):
         if self.flag:
             return
         k, n = self.k, self.v.shape[1]
@@ -61,7 +65,7 @@ class HostShard:
             self.flag, self.stop_i = rule, j - 1
         return rule
 
-    def phase_b(self, kind, lambda_h, min_iter, tol1, tol2, j):
+    def mur_phase_b(self, kind, lambda_h, min_iter, tol1, tol2, j):
         if self.flag or self._record(min_iter, tol1, tol2, j):
             return
         k, n = self.k, self.v.shape[1]
@@ -76,12 +80,12 @@ class HostShard:
             c = self.h * b
             self.h = 2 * c / (d + np.sqrt(d ** 2 + 4 * lambda_h * c))
 
-    def finish_a(self, kind, j):
+    def mur_finish_a(self, kind, j):
         if not self.flag:
             self.x64.zero_()
             self.x64[0] = self._local_objective(kind)
 
-    def finish_b(self, min_iter, tol1, tol2, j):
+    def mur_finish_b(self, min_iter, tol1, tol2, j):
         if not self.flag:
             self._record(min_iter, tol1, tol2, j)
 
@@ -92,7 +96,7 @@ class HostShard:
             self.dual_h = np.zeros_like(self.h)
             self.inner = {}
 
-    def ao_h_products(self, j):
+    def aoadmm_phase_h_products(self, j):
         self._ao_init()
         if self.flag:
             return
@@ -109,7 +113,7 @@ class HostShard:
         d = aux - dual - (lam / rho if kind == 1 else 0.0)
         return np.where(d < 0, 0, d)
 
-    def ao_h_solve(self, prox_h, lam_h, admm_iter, min_iter, tol1, tol2, j):
+    def aoadmm_phase_h_solve(self, prox_h, lam_h, admm_iter, min_iter, tol1, tol2, j):
         import scipy.linalg as sla
         if self.flag or self._record(min_iter, tol1, tol2, j):
             return
@@ -130,7 +134,7 @@ class HostShard:
                 break
         self.inner[(j, 0)] = ran
 
-    def ao_w_products(self, min_iter, tol1, tol2, j):
+    def aoadmm_phase_w_products(self, min_iter, tol1, tol2, j):
         import scipy.linalg as sla
         if self.flag:
             return
@@ -140,7 +144,7 @@ class HostShard:
         self._b_w = self.h @ self.v.T                       # k x m_local
         self._w_stop, self._w_ran = False, 0
 
-    def ao_w_round(self, prox_w, lam_w, rnd):
+    def aoadmm_phase_w_round(self, prox_w, lam_w, rnd):
         import scipy.linalg as sla
         if self.flag:
             return
@@ -163,7 +167,7 @@ class HostShard:
         self.w, self.dual_w = new.T.copy(), dual.T.copy()
         self._w_ran = rnd + 1
 
-    def ao_w_close(self, admm_iter, j):
+    def aoadmm_phase_w_close(self, admm_iter, j):
         if not self.flag:
             self.inner[(j, 1)] = self._w_ran
 
@@ -182,7 +186,7 @@ class HostShard:
             wt, dt = new, dual
         return wt, dt
 
-    def ao_w_fused(self, prox_w, lam_w, admm_iter):
+    def aoadmm_phase_w_fused(self, prox_w, lam_w, admm_iter):
         if self.flag:
             return
         self._w_start = (self.w.T.copy(), self.dual_w.T.copy())
@@ -191,7 +195,7 @@ class HostShard:
         self.w, self.dual_w = wt.T.copy(), dt.T.copy()
         self.x64[8:8 + 4 * admm_iter] = torch.from_numpy(table.ravel())
 
-    def ao_w_repair(self, prox_w, lam_w, admm_iter, j):
+    def aoadmm_phase_w_repair(self, prox_w, lam_w, admm_iter, j):
         if self.flag:
             return
         table = self.x64[8:8 + 4 * admm_iter].numpy().reshape(admm_iter, 4)
@@ -216,7 +220,7 @@ class HostShard:
             self.v_aux = np.zeros_like(self.v)
             self.dual_v = np.zeros_like(self.v)
 
-    def ao_kl_h_products(self, j, rnd):
+    def aoadmm_kl_phase_h_products(self, j, rnd):
         self._ao_kl_init()
         if self.flag or (rnd > 0 and self._h_stop):
             return
@@ -230,7 +234,7 @@ class HostShard:
             self.x64[0] = self._local_objective(1)
             self._h_stop, self._h_ran = False, 0
 
-    def ao_kl_h_round(self, prox_h, lam_h, rnd, min_iter, tol1, tol2, j):
+    def aoadmm_kl_phase_h_round(self, prox_h, lam_h, rnd, min_iter, tol1, tol2, j):
         import scipy.linalg as sla
         if self.flag:
             return
@@ -255,7 +259,7 @@ class HostShard:
         self._h_ran = rnd + 1
         self._h_stop = bool(R.inner_stop(self.h, prev, aux, self.dual_h))
 
-    def ao_kl_h_close(self, admm_iter, min_iter, tol1, tol2, j):
+    def aoadmm_kl_phase_h_close(self, admm_iter, min_iter, tol1, tol2, j):
         import scipy.linalg as sla
         if self.flag:
             return
@@ -265,7 +269,7 @@ class HostShard:
         self._chol_w = sla.cholesky(g + self._rho_w * np.eye(self.k), lower=True)
         self._w_stop, self._w_ran = False, 0
 
-    def ao_kl_w_round(self, prox_w, lam_w, rnd):
+    def aoadmm_kl_phase_w_round(self, prox_w, lam_w, rnd):
         import scipy.linalg as sla
         if self.flag:
             return
@@ -293,7 +297,7 @@ class HostShard:
         self.w, self.dual_w = new.T.copy(), dual.T.copy()
         self._w_ran = rnd + 1
 
-    def ao_kl_w_close(self, admm_iter, j):
+    def aoadmm_kl_phase_w_close(self, admm_iter, j):
         if not self.flag:
             self.inner[(j, 1)] = self._w_ran
 
@@ -303,7 +307,7 @@ class HostShard:
             self.l2n = {}
         self.l2n[which] = np.asarray(p, dtype=np.float64)
 
-    def admm_products(self, kind, rho, prox_w, prox_h, j):
+    def admm_phase_products(self, kind, rho, prox_w, prox_h, j):
         if not hasattr(self, "w_aux"):
             self.w_aux, self.h_aux = self.w.copy(), self.h.copy()
             self.dual_w, self.dual_h = np.zeros_like(self.w), np.zeros_like(self.h)
@@ -327,7 +331,7 @@ class HostShard:
             return np.where(out < 0, 0, out)
         return R.prox(kind, aux, dual, rho=rho, lam=lam)
 
-    def admm_update(self, kind, rho, prox_w, lam_w, prox_h, lam_h, min_iter, tol1, tol2, j):
+    def admm_phase_update(self, kind, rho, prox_w, lam_w, prox_h, lam_h, min_iter, tol1, tol2, j):
         if self.flag or self._record(min_iter, tol1, tol2, j):
             return
         k, n = self.k, self.v.shape[1]
@@ -355,12 +359,12 @@ class HostShard:
     def anls_set_distance(self, kind):
         self.obj_kind = kind
 
-    def anls_objective(self, j):
+    def anls_phase_objective(self, j):
         if not self.flag:
             self.x64.zero_()
             self.x64[0] = self._local_objective(getattr(self, "obj_kind", 0))
 
-    def anls_w(self, lam_w, min_iter, tol1, tol2, j):
+    def anls_phase_w(self, lam_w, min_iter, tol1, tol2, j):
         if self.flag or self._record(min_iter, tol1, tol2, j):
             return
         k, n = self.k, self.v.shape[1]
@@ -370,7 +374,7 @@ class HostShard:
         x[:k * n] = (self.w.T @ self.v).ravel()
         x[k * n:k * n + k * k] = (self.w.T @ self.w).ravel()
 
-    def anls_h(self, lam_h, j):
+    def anls_phase_h(self, lam_h, j):
         if self.flag:
             return
         # the stacked problem of anls.py:34-47 from its normal equations (what the device solves):
@@ -396,7 +400,7 @@ class HostShard:
 
 class ChunkedHostShard(HostShard):
     """HostShard with the exchange buffer of the device's split-bf16 path -- [column][factor] -- and phase A in pieces
-    (phase_a_head / phase_a_cols, Euclidean loss), so that dist.run_iterations' chunked loop runs on the CPU."""
+    (mur_phase_a_head / mur_phase_a_cols, Euclidean loss), so that dist.run_iterations' chunked loop runs on the CPU."""
     unit = 8                                           # column granularity of the stand-in
 
     def chunk_ranges(self, kind, chunks):
@@ -410,7 +414,7 @@ class ChunkedHostShard(HostShard):
         total = self.x32.numel()
         return [(c0, c1, c0 * k, c1 * k if c1 < n else total) for c0, c1 in zip(edges[:-1], edges[1:])]
 
-    def phase_a_head(self, kind, lambda_w, j):
+    def mur_phase_a_head(self, kind, lambda_w, j):
         assert kind == 0
         self.cols_seen = []
         if self.flag:
@@ -420,7 +424,7 @@ class ChunkedHostShard(HostShard):
         self.w_new = R.mur_w_step("eu", self.v, self.w, self.h, self.w @ self.h, lambda_w)
         self.x32.zero_()
 
-    def phase_a_cols(self, kind, c0, c1):
+    def mur_phase_a_cols(self, kind, c0, c1):
         self.cols_seen.append((c0, c1))
         if self.flag:
             return
@@ -430,15 +434,15 @@ class ChunkedHostShard(HostShard):
         if c1 == n:
             x[k * n:k * n + k * k] = (self.w_new.T @ self.w_new).ravel()
 
-    def phase_a(self, kind, lambda_w, j):
+    def mur_phase_a(self, kind, lambda_w, j):
         if kind != 0:
-            return super().phase_a(kind, lambda_w, j)
-        self.phase_a_head(kind, lambda_w, j)
-        self.phase_a_cols(kind, 0, self.v.shape[1])
+            return super().mur_phase_a(kind, lambda_w, j)
+        self.mur_phase_a_head(kind, lambda_w, j)
+        self.mur_phase_a_cols(kind, 0, self.v.shape[1])
 
-    def phase_b(self, kind, lambda_h, min_iter, tol1, tol2, j):
+    def mur_phase_b(self, kind, lambda_h, min_iter, tol1, tol2, j):
         if kind != 0:
-            return super().phase_b(kind, lambda_h, min_iter, tol1, tol2, j)
+            return super().mur_phase_b(kind, lambda_h, min_iter, tol1, tol2, j)
         if self.flag or self._record(min_iter, tol1, tol2, j):
             return
         k, n = self.k, self.v.shape[1]
@@ -461,7 +465,7 @@ class SlicedHostShard(ChunkedHostShard):
         self.slices_seen = getattr(self, "slices_seen", [])
         return n // world, (n // world) * k
 
-    def phase_b_slice(self, kind, lambda_h, min_iter, tol1, tol2, j, c0, c1):
+    def mur_phase_b_slice(self, kind, lambda_h, min_iter, tol1, tol2, j, c0, c1):
         assert kind == 0
         self.slices_seen.append((c0, c1))
         self._stopped_now = bool(self.flag or self._record(min_iter, tol1, tol2, j))
@@ -478,7 +482,7 @@ class SlicedHostShard(ChunkedHostShard):
         self.h[:, c0:c1] = new
         x[c0 * k:c1 * k] = new.T.ravel()                 # what the all-gather sends
 
-    def phase_b_rest(self, kind, c0, c1):
+    def mur_phase_b_rest(self, kind, c0, c1):
         if self._stopped_now:
             return
         k, n = self.k, self.v.shape[1]
