@@ -498,6 +498,17 @@ int nmfx_anls_phase_objective(nmfx_handle_t h, int64_t j);
 int nmfx_anls_phase_w(nmfx_handle_t h, double lambda_w, int64_t min_iter, double tol1, double tol2, int64_t j);
 int nmfx_anls_phase_h(nmfx_handle_t h, double lambda_h, int64_t j);
 
+/* ---- HALS (hierarchical alternating least squares, Cichocki & Phan 2009) -- */
+/* The iteration of nmfx_anls_run with each exact NNLS solve replaced by `sweeps` (1 .. 16) projected Gauss-Seidel sweeps over
+ * the k components, started from the current row of W / column of H:
+ *     for j = 0 .. k-1:  if G[j][j] > 0:  x[j] = max(0, x[j] + (r[j] - sum_l G[j][l] x[l]) / G[j][j])
+ * on the same G = F^T F + 2 lambda I and r = F^T b.  Objective, stop rule and history as nmfx_anls_run; nmfx_anls_set_distance
+ * selects the recorded objective and nmfx_aoadmm_finish closes the run.  Dense handles without weights, k <= 128
+ * (NMFX_E_ARG otherwise, and for sweeps outside 1 .. 16, a negative lambda or a negative range).                        */
+int nmfx_hals_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
+                  int64_t min_iter, double tol1, double tol2,
+                  int64_t first, int64_t count);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Accumulated device time (HIP events on the handle's stream) and launch count
  * of a named kernel since the last reset; names: "wphase" "hphase" ...        */

@@ -115,6 +115,7 @@ SIGNATURES = {
     "nmfx_admm_phase_update": (_i32, [_vp, _i32, _dbl, _i32, _dbl, _i32, _dbl, _i64, _dbl, _dbl, _i64]),
     "nmfx_anls_set_distance": (_i32, [_vp, _i32]),
     "nmfx_anls_run": (_i32, [_vp, _dbl, _dbl, _i64, _dbl, _dbl, _i64, _i64]),
+    "nmfx_hals_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_get_diagnostics": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "nmfx_get_nnls_fallbacks": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "nmfx_get_inner_paths": (_i32, [_vp, C.POINTER(_i64)]),

@@ -45,7 +45,7 @@ static int preload_once(nmfx_engine* E) {
     std::lock_guard<std::mutex> lock(mu);
     if (done[E->device]) return NMFX_OK;
     if (nmfx_preload_bf16() || nmfx_preload_products() || nmfx_preload_mur() || nmfx_preload_kl() || nmfx_preload_phase() || nmfx_preload_aoadmm() ||
-        nmfx_preload_anls() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic() ||
+        nmfx_preload_anls() || nmfx_preload_hals() || nmfx_preload_svd() || nmfx_preload_prox() || nmfx_preload_generic() ||
         nmfx_preload_sparse()) {
         E->err = "loading the kernels onto the device failed"; return NMFX_E_HIP; }
     hipLaunchKernelGGL(nmfx_startup_kernel, dim3(1), dim3(1), 0, 0, (int*)nullptr);
@@ -153,7 +153,7 @@ int nmfx_enter(nmfx_engine* E, const nmfx_entry& a) {
 
 extern "C" {
 
-int nmfx_version(void) { return 370; }      // 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 380; }      // 380: HALS (nmfx_hals_run); 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;

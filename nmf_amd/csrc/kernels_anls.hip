@@ -635,7 +635,15 @@ static int anls_objective(nmfx_engine* E) {
     return NMFX_OK;
 }
 
-static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, double tol1, double tol2, int64_t j) {
+// The solve of a half-step on (G, diag_add, R), X in place: the exact NNLS of ANLS (sweeps = 0), or `sweeps` projected Gauss-Seidel
+// sweeps from the current X (HALS, kernels_hals.hip).  Everything around it -- products, Gram matrices, objective, stop rule -- is
+// written once, below, for both.
+static int half_solve(nmfx_engine* E, int sweeps, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                      int64_t nprob) {
+    return sweeps ? nmfx_hals_sweep(E, G, diag_add, R, X, sj, sc, nprob, sweeps) : nnls(E, G, diag_add, R, X, sj, sc, nprob);
+}
+
+static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, double tol1, double tol2, int64_t j, int sweeps = 0) {
     int rc;
     float* W = E->W[0];
     const int64_t kk = (int64_t)E->kp * E->kp;
@@ -647,11 +655,11 @@ static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, d
             if ((rc = nmfx_bf16_images_h(E, false))) return rc;
             if ((rc = nmfx_bf16_vht(E, false, 0, "wphase_noobj"))) return rc;
         }
-        E->derived.drop(NMFX_D_anls_a_ready);          // (used up: the NNLS below moves W)
+        E->derived.drop(NMFX_D_anls_a_ready);          // (used up: the solve below moves W)
         if (!byprod && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
         if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, kk, E->HHt))) return rc;
         if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->bf_wsplit, E->mp * E->kp, E->Asum))) return rc;
-        if ((rc = nnls(E, E->HHt, (float)(2.0 * lam_w), E->Asum, W, 1, E->kp, E->m))) return rc;
+        if ((rc = half_solve(E, sweeps, E->HHt, (float)(2.0 * lam_w), E->Asum, W, 1, E->kp, E->m))) return rc;
         if ((rc = nmfx_bf16_images_w(E, W, 0))) return rc;
         if ((rc = nmfx_bf16_vtw(E, false, "hphase"))) return rc;
         if (byprod) return nmfx_bf16_pack_t(E, E->G_part, nmfx_bf16_g_slabs(E), E->obj_count);
@@ -663,7 +671,7 @@ static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, d
     if ((rc = nmfx_launch_wphase(E, W, true, false))) return rc;
     if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
     if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum))) return rc;
-    if ((rc = nnls(E, E->HHt, (float)(2.0 * lam_w), E->Asum, W, 1, E->kp, E->m))) return rc;
+    if ((rc = half_solve(E, sweeps, E->HHt, (float)(2.0 * lam_w), E->Asum, W, 1, E->kp, E->m))) return rc;
     // ---- products for H: [W^T V | W^T W] ----
     const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
     if (!fuse_g && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
@@ -671,29 +679,31 @@ static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, d
     return nmfx_launch_pack(E);
 }
 
-static int anls_h(nmfx_engine* E, double lam_h) {
+static int anls_h(nmfx_engine* E, double lam_h, int sweeps = 0) {
     int rc;
     // ---- H: columns of H from G = W^T W + 2 lam_h I, r = (W^T V)[:, c]  (anls.py:34-47) ----
-    if ((rc = nnls(E, E->xf32 + (int64_t)E->kp * E->np, (float)(2.0 * lam_h), E->xf32, E->H, E->np, 1, E->n))) return rc;
+    if ((rc = half_solve(E, sweeps, E->xf32 + (int64_t)E->kp * E->np, (float)(2.0 * lam_h), E->xf32, E->H, E->np, 1, E->n))) return rc;
     // ---- objective (anls.py:118) ----
     return anls_objective(E);
 }
 
 static int anls_iteration(nmfx_engine* E, double lam_w, double lam_h, int64_t min_iter, double tol1, double tol2,
-                          int64_t j) {
+                          int64_t j, int sweeps = 0) {
     int rc;
     // objective of the current pair (filled by the previous pass) and the stop rule
     if ((rc = nmfx_launch_obj_reduce(E))) return rc;
-    if ((rc = anls_w_and_products(E, lam_w, min_iter, tol1, tol2, j))) return rc;
-    return anls_h(E, lam_h);
+    if ((rc = anls_w_and_products(E, lam_w, min_iter, tol1, tol2, j, sweeps))) return rc;
+    return anls_h(E, lam_h, sweeps);
 }
 
-// Every ANLS entry point: the guard, then the solver's own buffer.  Between ANLS calls the products of the fused objective pass
+// Every ANLS entry point (and HALS's, as a family of its own on the same products): the guard, then the solver's own buffer.
+// Between calls of one family the products of the fused objective pass
 // stay trusted (k <= 128; the generic loop beyond that keeps nothing); bad = a negative index, count or lambda
-static int anls_ready(nmfx_engine* E, int64_t first, int64_t count, bool bad, bool whole_run = false) {
+static int anls_ready(nmfx_engine* E, int64_t first, int64_t count, bool bad, bool whole_run = false, int family = NMFX_FAM_ANLS,
+                      const char* bad_text = "bad range or lambda") {
     if (!E) return NMFX_E_ARG;
-    nmfx_entry a = {NMFX_FAM_ANLS, first, count, E->kp <= 128 ? NMFX_D_anls_a_ready : NMFX_D_NONE, NMFX_D_himg_both | NMFX_D_kl_h_iter};
-    if (bad) a.bad = "bad range or lambda";
+    nmfx_entry a = {family, first, count, E->kp <= 128 ? NMFX_D_anls_a_ready : NMFX_D_NONE, NMFX_D_himg_both | NMFX_D_kl_h_iter};
+    if (bad) a.bad = bad_text;
     int rc = nmfx_enter(E, a); if (rc) return rc;
     if (!E->Asum && !(whole_run && E->kp > 128)) {     // (the summed V H^T; the generic loop beyond 128 components has its own scratch)
         NMFX_HIP(hipMalloc(reinterpret_cast<void**>(&E->Asum), (size_t)E->mp * E->kp * sizeof(float)));
@@ -745,6 +755,22 @@ extern "C" int nmfx_anls_run(nmfx_handle_t E, double lambda_w, double lambda_h, 
     if (first == 0 && count > 0 && (rc = anls_objective(E))) return rc;   // obj[0]
     for (int64_t j = first; j < first + count; ++j)
         if ((rc = anls_iteration(E, lambda_w, lambda_h, min_iter, tol1, tol2, j))) return rc;
+    return NMFX_OK;
+}
+
+// HALS: the iteration of nmfx_anls_run with `sweeps` Gauss-Seidel sweeps in place of each NNLS solve (include/nmfx.h)
+extern "C" int nmfx_hals_run(nmfx_handle_t E, double lambda_w, double lambda_h, int sweeps, int64_t min_iter, double tol1,
+                             double tol2, int64_t first, int64_t count) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    if (E->kp > 128) { E->err = nmfx_small_k_text("nmfx_hals_run"); return NMFX_E_ARG; }
+    const bool bad_sweeps = sweeps < 1 || sweeps > 16;
+    int rc = anls_ready(E, first, count, bad_sweeps || first < 0 || count < 0 || !(lambda_w >= 0) || !(lambda_h >= 0), true, NMFX_FAM_HALS,
+                        bad_sweeps ? "nmfx_hals_run: sweeps must be between 1 and 16" : "nmfx_hals_run: bad range or lambda");
+    if (rc) return rc;
+    if (first == 0 && count > 0 && (rc = anls_objective(E))) return rc;   // obj[0]
+    for (int64_t j = first; j < first + count; ++j)
+        if ((rc = anls_iteration(E, lambda_w, lambda_h, min_iter, tol1, tol2, j, sweeps))) return rc;
     return NMFX_OK;
 }
 

@@ -104,7 +104,8 @@ struct nmfx_derived {
 // What the run since nmfx_set_factors is: the solver family (one per set of factors, nmfx_enter), and for MUR the loss kind, the
 // W buffer that holds the iterate and whether two problems are stacked.  reset() is nmfx_set_factors'.
 enum { NMFX_FAM_NONE = 0, NMFX_FAM_MUR = 1, NMFX_FAM_AOADMM = 2, NMFX_FAM_ADMM = 3, NMFX_FAM_ANLS = 4,
-       NMFX_FAM_MUR_PAIR = 5 };                         // (asked of nmfx_enter only: family NMFX_FAM_MUR in pair mode)
+       NMFX_FAM_MUR_PAIR = 5,                           // (asked of nmfx_enter only: family NMFX_FAM_MUR in pair mode)
+       NMFX_FAM_HALS = 6 };                             // (ANLS's products and derived state; its own warm start: the values, not the support)
 enum { NMFX_LOSS_PLAIN = 0, NMFX_LOSS_IS = 1, NMFX_LOSS_BETA = 2 };      // MUR: Euclidean / KL, or a loss nmfx_objective_f64 has to refuse (and how it words that)
 struct nmfx_run {
     int family = NMFX_FAM_NONE;    // solver family that has run since nmfx_set_factors
@@ -453,6 +454,9 @@ int nmfx_preload_kl();
 int nmfx_preload_phase();
 int nmfx_preload_aoadmm();
 int nmfx_preload_anls();
+int nmfx_preload_hals();
+// kernels_hals.hip: `sweeps` projected Gauss-Seidel sweeps per problem on (G + diag_add I, R), X in place; strides as the NNLS launcher's
+int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps);
 int nmfx_preload_svd();
 int nmfx_preload_prox();
 

@@ -378,6 +378,12 @@ class Engine:
         self._ck(self.lib.nmfx_anls_run(self.h, float(lam_w), float(lam_h), int(min_iter), float(tol1),
                                         float(tol2), int(first), int(count)))
 
+    def hals_run(self, lam_w, lam_h, sweeps, min_iter, tol1, tol2, first, count):
+        """`count` HALS iterations from iteration `first`: the iteration of anls_run with `sweeps` projected Gauss-Seidel sweeps
+        in place of each NNLS solve (anls_set_distance selects the recorded objective, aoadmm_finish closes the run)."""
+        self._ck(self.lib.nmfx_hals_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
+                                        float(tol2), int(first), int(count)))
+
     # -- the f64 referee of the stop rule (include/nmfx.h) --------------------------------------
     def objective_f64(self):
         """1/2 ||V - W H||^2 of the current pair with product and sum in float64 on the device."""

@@ -5,7 +5,7 @@ from importlib import import_module
 
 from . import utils
 
-_METHODS = ('mur', 'anls', 'admm', 'ao_admm')
+_METHODS = ('mur', 'anls', 'admm', 'ao_admm', 'hals')
 
 
 class NMF:
@@ -32,7 +32,7 @@ class NMF:
 
     def factorize(self, method='mur', saving=False, **method_params):
         if method not in _METHODS:
-            raise Exception('Method not known. Choose one from: mur anls admm ao_admm')
+            raise Exception('Method not known. Choose one from: ' + ' '.join(_METHODS))
         solver = getattr(import_module('.' + method, __package__), method)
         self.results = solver(self.data, self.factors, **method_params)
         # README.md:22 promises nmf.w / nmf.h; the reference only sets .results
