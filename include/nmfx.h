@@ -509,6 +509,41 @@ int nmfx_hals_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
                   int64_t min_iter, double tol1, double tol2,
                   int64_t first, int64_t count);
 
+/* ---- stacked HALS (version 390) ------------------------------------------------------------------------------------------
+ * MANY least-squares factorizations of the same V in one pass over it: P problems sit side by side in the factor columns,
+ * W = [W_0 | W_1 | ...], H = [H_0; H_1; ...].  The V-sized products V H^T and W^T V of the stacked factors are the P problems'
+ * products, and with the Gram entries between different problems masked the Gauss-Seidel sweep over all components is P
+ * independent sweeps: problem p's iterates are those of nmfx_hals_run on a handle of its own.  Dense handles without weights,
+ * k <= 128 (NMFX_E_ARG otherwise, nothing launched).  A family of its own: hals, anls, mur and the stack do not continue
+ * each other without nmfx_set_factors.
+ *
+ * nmfx_hals_stack_set: problem p owns the components [o_p, o_p + k_p), o_p = sum_{q < p} k_q; every k_p >= 1 and their sum
+ * <= the handle's k (NMFX_E_ARG).  Components past the last problem belong to none: set them to zero, they stay zero.
+ * nprob = 0 clears the stack.  Call it after nmfx_set_factors and before the run (NMFX_E_STATE once a solver has run on the
+ * factors); the partition survives nmfx_set_factors, which starts every problem's stop state and history anew.
+ *
+ * nmfx_hals_stack_terms: out[nprob][2] = <V, W_p H_p> and ||W_p H_p||^2 of the current factors (the least-squares scale of
+ * a start is their quotient).
+ *
+ * nmfx_hals_stack_run / _finish: as nmfx_hals_run / nmfx_aoadmm_finish, with lambda_w[nprob], lambda_h[nprob].  The objective
+ * of problem p after j iterations, recorded at obj_p[j], is
+ *     1/2 ||V||^2 - sum_i sum_{c in p} W_ic (V H^T)_ic + 1/2 <(W^T W)_pp, (H H^T)_pp>
+ * with ||V||^2, both Gram blocks and both sums in f64 over the f32 factor values and the f32 product V H^T.  Each problem has
+ * its own stop rule (that of nmfx_hals_run, on obj_p) and keeps its iterate from its stop on while the others go on; no f64
+ * referee stands behind this objective (nmfx_set_stop_guard does not apply).  nmfx_get_state reports a stop once ALL problems
+ * have stopped.
+ *
+ * nmfx_hals_stack_get_state / _get_objectives / _get_factors: problem p's stop rule, stop index, number of recorded objectives;
+ * obj_p[first .. first + count); w (m x k_p) and hmat (k_p x n).                                                             */
+int nmfx_hals_stack_set(nmfx_handle_t h, int nprob, const int* k_p);
+int nmfx_hals_stack_terms(nmfx_handle_t h, double* out);
+int nmfx_hals_stack_run(nmfx_handle_t h, const double* lambda_w, const double* lambda_h, int sweeps,
+                        int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count);
+int nmfx_hals_stack_finish(nmfx_handle_t h, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
+int nmfx_hals_stack_get_state(nmfx_handle_t h, int p, int* stop_rule, int64_t* stop_i, int64_t* n_obj);
+int nmfx_hals_stack_get_objectives(nmfx_handle_t h, int p, int64_t first, int64_t count, double* out);
+int nmfx_hals_stack_get_factors(nmfx_handle_t h, int p, double* w, double* hmat);
+
 /* ---- measurement -------------------------------------------------------- */
 /* Accumulated device time (HIP events on the handle's stream) and launch count
  * of a named kernel since the last reset; names: "wphase" "hphase" ...        */

@@ -116,6 +116,13 @@ SIGNATURES = {
     "nmfx_anls_set_distance": (_i32, [_vp, _i32]),
     "nmfx_anls_run": (_i32, [_vp, _dbl, _dbl, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_hals_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
+    "nmfx_hals_stack_set": (_i32, [_vp, _i32, C.POINTER(_i32)]),
+    "nmfx_hals_stack_terms": (_i32, [_vp, _vp]),
+    "nmfx_hals_stack_run": (_i32, [_vp, _pd, _pd, _i32, _i64, _dbl, _dbl, _i64, _i64]),
+    "nmfx_hals_stack_finish": (_i32, [_vp, _i64, _dbl, _dbl, _i64]),
+    "nmfx_hals_stack_get_state": (_i32, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)]),
+    "nmfx_hals_stack_get_objectives": (_i32, [_vp, _i32, _i64, _i64, _vp]),
+    "nmfx_hals_stack_get_factors": (_i32, [_vp, _i32, _vp, _vp]),
     "nmfx_get_diagnostics": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "nmfx_get_nnls_fallbacks": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "nmfx_get_inner_paths": (_i32, [_vp, C.POINTER(_i64)]),

@@ -153,7 +153,7 @@ int nmfx_enter(nmfx_engine* E, const nmfx_entry& a) {
 
 extern "C" {
 
-int nmfx_version(void) { return 380; }      // 380: HALS (nmfx_hals_run); 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 390; }      // 390: stacked HALS (nmfx_hals_stack_*); 380: HALS (nmfx_hals_run); 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -290,7 +290,8 @@ int nmfx_destroy(nmfx_handle_t E) {
                     E->Wlo[0], E->Wlo[1], E->WThi, E->WTlo, E->Hhi, E->Hlo, E->HThi, E->HTlo, E->nrm_rounds, E->bkX, E->bkU,
                     E->nnls_ginv, E->nnls_todo, E->G_big, E->kl_part, E->Bt_chunk, E->gx_part, E->gx_d, E->gx_s, E->gx_r, E->gx_w64, E->gx_nrm, E->prox_keys, E->gx_nnls_work,
                     E->gxb_v[0], E->gxb_v[1], E->gxb_v[2], E->gxb_v[3], E->gxb_vt, E->gxb_q[0], E->gxb_q[1],
-                    E->kl_S[0], E->kl_S[1], E->kl_DV[0], E->kl_DV[1], E->sk[0].seg, E->sk[0].first, E->sk[0].cnt, E->sk[0].slabs, E->sk[1].seg, E->sk[1].first, E->sk[1].cnt, E->sk[1].slabs, E->minv_img, E->gx_gimg};
+                    E->kl_S[0], E->kl_S[1], E->kl_DV[0], E->kl_DV[1], E->sk[0].seg, E->sk[0].first, E->sk[0].cnt, E->sk[0].slabs, E->sk[1].seg, E->sk[1].first, E->sk[1].cnt, E->sk[1].slabs, E->minv_img, E->gx_gimg,
+                    E->stack_dev, E->stack_obj, E->stack_part};
     for (void* b : bufs) if (b) hipFree(b);
     if (E->own_stream) hipStreamDestroy(E->own_stream);
     delete E;
@@ -376,6 +377,7 @@ int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int6
     if (E->have_v) { int rc_ = nmfx_need_v(E); if (rc_) return rc_; }       // (rows of a V whose row-major copy was dropped)
     { int rc_ = copy_rows_in(E, E->V + row0 * E->np, host, dtype, ld, rows, "upload_v"); if (rc_) return rc_; }
     E->have_v = true;
+    E->stack_vv_ready = false;
     E->bf_ready = false;
     E->gxb_v_ready = false;
     E->gxb_vt_ready = false;
@@ -513,6 +515,7 @@ int nmfx_upload_v_device(nmfx_handle_t E, const void* dev, int dtype, int64_t ld
     } else { E->err = "upload_v_device: dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
     NMFX_HIP(hipStreamSynchronize(E->stream));
     E->have_v = true;
+    E->stack_vv_ready = false;
     E->bf_ready = false;
     E->gxb_v_ready = false;
     E->gxb_vt_ready = false;
@@ -562,6 +565,7 @@ int nmfx_set_factors(nmfx_handle_t E, const double* w, const double* hmat) {
     for (int i = 0; i < 10; ++i)
         if (zero[i]) NMFX_HIP(hipMemsetAsync(zero[i], 0, (size_t)zc[i] * 4, E->stream));
     hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, E->stream, E->state);
+    if ((rc = nmfx_hals_stack_reset(E))) return rc;
     E->have_f = true;
     E->bf_ready = false;
     E->derived.void_all_but(NMFX_D_NONE);

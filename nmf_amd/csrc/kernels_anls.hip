@@ -774,5 +774,194 @@ extern "C" int nmfx_hals_run(nmfx_handle_t E, double lambda_w, double lambda_h, 
     return NMFX_OK;
 }
 
+// ---- stacked HALS (include/nmfx.h, version 390) -----------------------------------------------------------------
+// P problems side by side in the factor columns: the V-sized products of the stacked factors are the P problems' products, and with
+// the Gram entries between different problems masked (kernels_hals.hip) the sweep over all components is P independent sweeps.
+// The products are ANLS's without the fused residual objective -- ||V - sum_p W_p H_p||^2 means nothing here; each problem's
+// objective comes from the products and f64 Gram blocks instead (nmfx_hals_stack_objective).
+static const char* const STACK_NONE_TEXT = "no stack is set on this handle (nmfx_hals_stack_set)";
+
+// what every nmfx_hals_stack_* compute entry point refuses, nothing launched; then the guard as a family of its own
+static int stack_ready(nmfx_engine* E, const char* who, int64_t first, int64_t count, const std::string& bad) {
+    if (E->kp > 128) { E->err = nmfx_small_k_text(who); return NMFX_E_ARG; }
+    if (E->stack_nprob <= 0) { E->err = std::string(who) + ": " + STACK_NONE_TEXT; return NMFX_E_STATE; }
+    int rc = anls_ready(E, first, count, !bad.empty(), true, NMFX_FAM_HALS_STACK, bad.c_str()); if (rc) return rc;
+    if ((rc = nmfx_hals_stack_alloc(E))) return rc;
+    if ((rc = nmfx_hals_stack_ensure_obj(E, (int64_t)E->stack_nprob * (first + count + 2)))) return rc;
+    return nmfx_hals_stack_vv(E);
+}
+
+// V H^T (slabs in A_part) and the H H^T slabs of the current H, no objective
+static int stack_w_products(nmfx_engine* E) {
+    int rc;
+    if (anls_bf16(E)) {
+        if ((rc = nmfx_bf16_prepare(E))) return rc;
+        if ((rc = nmfx_bf16_images_h(E, false))) return rc;
+        return nmfx_bf16_vht(E, false, 0, "wphase_noobj");
+    }
+    if ((rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
+    return nmfx_launch_wphase(E, E->W[0], true, false);
+}
+
+// ... summed: HHt and Asum, what the W half-step and the objective read
+static int stack_w_sums(nmfx_engine* E) {
+    int rc;
+    const int64_t kk = (int64_t)E->kp * E->kp;
+    if (!E->derived.anls_a_ready && (rc = stack_w_products(E))) return rc;
+    E->derived.anls_a_ready = true;
+    if (anls_bf16(E)) {
+        const bool byprod = E->kp == 64;
+        if (!byprod && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
+        if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, kk, E->HHt))) return rc;
+        return nmfx_launch_sum_partials(E, E->A_part, E->bf_wsplit, E->mp * E->kp, E->Asum);
+    }
+    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
+    return nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum);
+}
+
+static int stack_iteration(nmfx_engine* E, int sweeps, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    int rc;
+    float* W = E->W[0];
+    if ((rc = stack_w_sums(E))) return rc;
+    if ((rc = nmfx_hals_stack_objective(E, true, j, min_iter, tol1, tol2))) return rc;      // obj_p[j] + each problem's stop rule
+    E->derived.drop(NMFX_D_anls_a_ready);              // (used up: the sweep below moves W)
+    if ((rc = nmfx_hals_stack_sweep(E, E->HHt, 0, E->Asum, W, 1, E->kp, E->m, sweeps))) return rc;
+    if (anls_bf16(E)) {
+        const bool byprod = E->kp == 64;
+        if ((rc = nmfx_bf16_images_w(E, W, 0))) return rc;
+        if ((rc = nmfx_bf16_vtw(E, false, "hphase"))) return rc;
+        if (byprod) rc = nmfx_bf16_pack_t(E, E->G_part, nmfx_bf16_g_slabs(E), 0);
+        else if (!(rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) rc = nmfx_bf16_pack_t(E, E->G_part, E->gsplit, 0);
+        if (rc) return rc;
+    } else {
+        const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
+        if (!fuse_g && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
+        if ((rc = nmfx_launch_hphase(E, W, fuse_g))) return rc;
+        if ((rc = nmfx_launch_pack(E))) return rc;
+    }
+    if ((rc = nmfx_hals_stack_sweep(E, E->xf32 + (int64_t)E->kp * E->np, 1, E->xf32, E->H, E->np, 1, E->n, sweeps))) return rc;
+    if ((rc = stack_w_products(E))) return rc;         // the next iteration's right-hand sides, and what its objective is formed from
+    E->derived.anls_a_ready = true;
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_stack_set(nmfx_handle_t E, int nprob, const int* k_p) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    if (E->kp > 128) { E->err = nmfx_small_k_text("nmfx_hals_stack_set"); return NMFX_E_ARG; }
+    if (nprob < 0 || nprob > NMFX_STACK_MAX || (nprob > 0 && !k_p)) { E->err = "nmfx_hals_stack_set: 0 <= nprob <= 128 and their ranks"; return NMFX_E_ARG; }
+    int64_t total = 0;
+    for (int p = 0; p < nprob; ++p) {
+        if (k_p[p] < 1) { E->err = "nmfx_hals_stack_set: every problem needs k_p >= 1"; return NMFX_E_ARG; }
+        total += k_p[p];
+    }
+    if (total > E->k) { E->err = "nmfx_hals_stack_set: the problems' ranks add up to " + std::to_string(total) + ", more than the handle's k = " + std::to_string(E->k); return NMFX_E_ARG; }
+    if (E->run.family != NMFX_FAM_NONE) { E->err = "nmfx_hals_stack_set: a solver has run on this handle since nmfx_set_factors: set the factors, then the stack"; return NMFX_E_STATE; }
+    NMFX_HIP(hipSetDevice(E->device));
+    E->stack_nprob = nprob;
+    E->stack_off[0] = 0;
+    for (int p = 0; p < nprob; ++p) E->stack_off[p + 1] = E->stack_off[p] + k_p[p];
+    E->derived.drop(NMFX_D_anls_a_ready);
+    if (nprob == 0 && !E->stack_dev) return NMFX_OK;
+    return nmfx_hals_stack_config(E);
+}
+
+extern "C" int nmfx_hals_stack_terms(nmfx_handle_t E, double* out) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    int rc = stack_ready(E, "nmfx_hals_stack_terms", 0, 0, out ? "" : "nmfx_hals_stack_terms: out is NULL"); if (rc) return rc;
+    if ((rc = stack_w_sums(E))) return rc;
+    if ((rc = nmfx_hals_stack_objective(E, false, 0, 0, 0.0, 0.0))) return rc;
+    NMFX_HIP(hipMemcpyAsync(out, reinterpret_cast<const char*>(E->stack_dev) + offsetof(HalsStackDev, terms), (size_t)E->stack_nprob * 2 * sizeof(double),
+                            hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
+static std::string stack_run_bad(nmfx_engine* E, const double* lw, const double* lh, int sweeps, int64_t first, int64_t count) {
+    if (sweeps < 1 || sweeps > 16) return "nmfx_hals_stack_run: sweeps must be between 1 and 16";
+    if (first < 0 || count < 0 || !lw || !lh) return "nmfx_hals_stack_run: bad range or lambda";
+    for (int p = 0; p < E->stack_nprob; ++p)
+        if (!(lw[p] >= 0) || !(lh[p] >= 0)) return "nmfx_hals_stack_run: bad range or lambda";
+    return "";
+}
+
+extern "C" int nmfx_hals_stack_run(nmfx_handle_t E, const double* lambda_w, const double* lambda_h, int sweeps, int64_t min_iter, double tol1,
+                                   double tol2, int64_t first, int64_t count) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    int rc = stack_ready(E, "nmfx_hals_stack_run", first, count, stack_run_bad(E, lambda_w, lambda_h, sweeps, first, count)); if (rc) return rc;
+    if ((rc = nmfx_hals_stack_lambdas(E, lambda_w, lambda_h))) return rc;
+    for (int64_t j = first; j < first + count; ++j)
+        if ((rc = stack_iteration(E, sweeps, min_iter, tol1, tol2, j))) return rc;
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_stack_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    int rc = stack_ready(E, "nmfx_hals_stack_finish", iters_done, 1, iters_done < 0 ? "nmfx_hals_stack_finish: negative iteration count" : ""); if (rc) return rc;
+    if ((rc = stack_w_sums(E))) return rc;
+    return nmfx_hals_stack_objective(E, true, iters_done, min_iter, tol1, tol2);
+}
+
+static int stack_read(nmfx_engine* E, const char* who, int p, HalsStackDev* hs) {
+    if (E->stack_nprob <= 0 || !E->stack_dev) { E->err = std::string(who) + ": " + STACK_NONE_TEXT; return NMFX_E_STATE; }
+    if (p < 0 || p >= E->stack_nprob) { E->err = std::string(who) + ": no such problem in the stack"; return NMFX_E_ARG; }
+    NMFX_HIP(hipSetDevice(E->device));
+    NMFX_HIP(hipMemcpyAsync(hs, E->stack_dev, sizeof(HalsStackDev), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_stack_get_state(nmfx_handle_t E, int p, int* stop_rule, int64_t* stop_i, int64_t* n_obj) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    HalsStackDev hs;
+    int rc = stack_read(E, "nmfx_hals_stack_get_state", p, &hs); if (rc) return rc;
+    if (stop_rule) *stop_rule = hs.pflag[p];
+    if (stop_i) *stop_i = hs.pstop_i[p];
+    if (n_obj) *n_obj = hs.pn_obj[p];
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_stack_get_objectives(nmfx_handle_t E, int p, int64_t first, int64_t count, double* out) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    if (E->stack_nprob <= 0) { E->err = std::string("nmfx_hals_stack_get_objectives: ") + STACK_NONE_TEXT; return NMFX_E_STATE; }
+    const int64_t P = E->stack_nprob;
+    if (p < 0 || p >= P || !out || first < 0 || count < 0 || P * (first + count) > E->stack_obj_cap) { E->err = "nmfx_hals_stack_get_objectives: range"; return NMFX_E_ARG; }
+    if (count == 0) return NMFX_OK;
+    NMFX_HIP(hipSetDevice(E->device));
+    std::vector<double> tmp((size_t)(P * count));
+    NMFX_HIP(hipMemcpyAsync(tmp.data(), E->stack_obj + P * first, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    for (int64_t i = 0; i < count; ++i) out[i] = tmp[(size_t)(P * i + p)];
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_stack_get_factors(nmfx_handle_t E, int p, double* w, double* hmat) {
+    NMFX_DENSE_ONLY(E);
+    if (!E) return NMFX_E_ARG;
+    if (E->stack_nprob <= 0) { E->err = std::string("nmfx_hals_stack_get_factors: ") + STACK_NONE_TEXT; return NMFX_E_STATE; }
+    if (p < 0 || p >= E->stack_nprob) { E->err = "nmfx_hals_stack_get_factors: no such problem in the stack"; return NMFX_E_ARG; }
+    if (!E->have_f) { E->err = "nmfx_hals_stack_get_factors: set factors first"; return NMFX_E_STATE; }
+    NMFX_HIP(hipSetDevice(E->device));
+    const int o = E->stack_off[p], kq = E->stack_off[p + 1] - o;
+    if (w) {
+        std::vector<float> tmp((size_t)E->m * kq);
+        NMFX_HIP(hipMemcpy2DAsync(tmp.data(), (size_t)kq * 4, E->W[0] + o, (size_t)E->kp * 4, (size_t)kq * 4, (size_t)E->m, hipMemcpyDeviceToHost, E->stream));
+        NMFX_HIP(hipStreamSynchronize(E->stream));
+        for (size_t i = 0; i < tmp.size(); ++i) w[i] = (double)tmp[i];
+    }
+    if (hmat) {
+        std::vector<float> tmp((size_t)kq * E->n);
+        NMFX_HIP(hipMemcpy2DAsync(tmp.data(), (size_t)E->n * 4, E->H + (int64_t)o * E->np, (size_t)E->np * 4, (size_t)E->n * 4, (size_t)kq, hipMemcpyDeviceToHost, E->stream));
+        NMFX_HIP(hipStreamSynchronize(E->stream));
+        for (size_t i = 0; i < tmp.size(); ++i) hmat[i] = (double)tmp[i];
+    }
+    return NMFX_OK;
+}
+
 // (nmfx_create: forces this translation unit's code object onto the device under the library's start-up lock)
 int nmfx_preload_anls() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(nnls_bpp_reg128_kernel)) == hipSuccess ? 0 : -1; }

@@ -60,6 +60,25 @@ struct DevState {          // lives in device memory, written by kernels
     double stop_guard;
 };
 
+// Stacked HALS (nmfx_hals_stack_*, kernels_hals.hip): P problems side by side in the factor columns.  Lives in a device buffer of
+// the stack's own (DevState stays as the existing kernels know it); `flag` of DevState is set once every problem has stopped.
+#define NMFX_STACK_MAX 128
+struct HalsStackDev {
+    // -- configuration and stop state: written by nmfx_hals_stack_set, the stop state again by nmfx_set_factors --
+    int nprob;                         // 0: no stack
+    int pad0;
+    int off[NMFX_STACK_MAX + 1];       // problem p owns the components [off[p], off[p + 1])
+    unsigned char c2p[NMFX_STACK_MAX]; // component -> problem, 255: none (the tail past the last problem)
+    int pflag[NMFX_STACK_MAX];         // 0 running, 1 / 2 the rule that stopped problem p
+    long long pstop_i[NMFX_STACK_MAX];
+    long long pn_obj[NMFX_STACK_MAX];
+    // -- written by kernels --
+    float diag[2][NMFX_STACK_MAX];     // per component 2 lambda of its problem: [0] the W half-step (lambda_w), [1] the H half-step
+    double half_vv;                    // 1/2 ||V||^2
+    double terms[NMFX_STACK_MAX][2];   // <V, W_p H_p> and ||W_p H_p||^2 of the factors the last objective launch saw
+};
+#define NMFX_STACK_NONE 255
+
 struct ProfSlot { double ms = 0; int64_t n = 0; };
 
 // ---- what a handle derives from the current (W, H) and trusts in a later call -----------------------------------------------
@@ -105,7 +124,8 @@ struct nmfx_derived {
 // W buffer that holds the iterate and whether two problems are stacked.  reset() is nmfx_set_factors'.
 enum { NMFX_FAM_NONE = 0, NMFX_FAM_MUR = 1, NMFX_FAM_AOADMM = 2, NMFX_FAM_ADMM = 3, NMFX_FAM_ANLS = 4,
        NMFX_FAM_MUR_PAIR = 5,                           // (asked of nmfx_enter only: family NMFX_FAM_MUR in pair mode)
-       NMFX_FAM_HALS = 6 };                             // (ANLS's products and derived state; its own warm start: the values, not the support)
+       NMFX_FAM_HALS = 6,                               // (ANLS's products and derived state; its own warm start: the values, not the support)
+       NMFX_FAM_HALS_STACK = 7 };                       // (nmfx_hals_stack_*: HALS on problems stacked in the factor columns; its own stop state and history)
 enum { NMFX_LOSS_PLAIN = 0, NMFX_LOSS_IS = 1, NMFX_LOSS_BETA = 2 };      // MUR: Euclidean / KL, or a loss nmfx_objective_f64 has to refuse (and how it words that)
 struct nmfx_run {
     int family = NMFX_FAM_NONE;    // solver family that has run since nmfx_set_factors
@@ -234,6 +254,14 @@ struct nmfx_engine {
     double* ard_sums = nullptr;    // [W row blocks + H column chunks][kp] f64 partial column sums of W / row sums of H
     double* ard_lam = nullptr;     // [kp] the relevances lambda_k, then [1] the penalty phi c Sum (1 + log lambda_k)
     float* ard_pen = nullptr;      // [kp] phi / lambda_k, what the update kernels add to their denominators (0 for k >= K)
+    // stacked HALS (nmfx_hals_stack_*): host mirror of the partition, the device state, the objective history obj[P j + p] and the
+    // f64 partials of the objective (column sums of W o A per row slab | Gram slabs of W and of H | their sums)
+    int stack_nprob = 0;
+    int stack_off[NMFX_STACK_MAX + 1] = {0};
+    HalsStackDev* stack_dev = nullptr;
+    double* stack_obj = nullptr; int64_t stack_obj_cap = 0;
+    double* stack_part = nullptr;
+    bool stack_vv_ready = false;   // half_vv is that of the current V
     struct nmfx_sparse* sp = nullptr;   // a sparse handle (nmfx_create_csr): CSR / CSC of V, H^T, Grams (kernels_sparse.hip); MUR only
     // profiling
     bool prof = false;
@@ -457,6 +485,17 @@ int nmfx_preload_anls();
 int nmfx_preload_hals();
 // kernels_hals.hip: `sweeps` projected Gauss-Seidel sweeps per problem on (G + diag_add I, R), X in place; strides as the NNLS launcher's
 int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps);
+// ... and the stacked form (nmfx_hals_stack_*): G masked to the problems' diagonal blocks while it is staged, 2 lambda_p per component
+// (side 0: lambda_w, 1: lambda_h), the components of a stopped problem left as they are
+int nmfx_hals_stack_sweep(nmfx_engine* E, const float* G, int side, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps);
+int nmfx_hals_stack_alloc(nmfx_engine* E);                     // the device state and the partial buffers, on first use
+int nmfx_hals_stack_config(nmfx_engine* E);                    // stack_nprob / stack_off -> device, stop state cleared
+int nmfx_hals_stack_reset(nmfx_engine* E);                     // nmfx_set_factors: the per-problem stop state back to "running"
+int nmfx_hals_stack_lambdas(nmfx_engine* E, const double* lambda_w, const double* lambda_h);
+int nmfx_hals_stack_vv(nmfx_engine* E);                        // half_vv of the current V, once per upload
+int nmfx_hals_stack_ensure_obj(nmfx_engine* E, int64_t need);
+// obj_p = half_vv - sum_{c in p} sum_i W_ic Asum_ic + 1/2 <(W^T W)_pp, (H H^T)_pp> in f64; record: obj[P j + p] and the stop rule
+int nmfx_hals_stack_objective(nmfx_engine* E, bool record, int64_t j, int64_t min_iter, double tol1, double tol2);
 int nmfx_preload_svd();
 int nmfx_preload_prox();
 

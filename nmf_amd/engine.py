@@ -384,6 +384,46 @@ class Engine:
         self._ck(self.lib.nmfx_hals_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
                                         float(tol2), int(first), int(count)))
 
+    # -- stacked HALS: many problems side by side in the factor columns (include/nmfx.h) ---------
+    def hals_stack_set(self, ks):
+        """Problem p owns the components [sum(ks[:p]), sum(ks[:p + 1])); () clears the stack.  After set_factors, before the run."""
+        ks = [int(k) for k in ks]
+        self._ck(self.lib.nmfx_hals_stack_set(self.h, len(ks), (C.c_int * max(1, len(ks)))(*ks)))
+        self.stack_ks = ks
+
+    def hals_stack_terms(self):
+        """[P, 2] float64: <V, W_p H_p> and ||W_p H_p||^2 of the current factors."""
+        out = np.zeros((len(self.stack_ks), 2), dtype=np.float64)
+        self._ck(self.lib.nmfx_hals_stack_terms(self.h, _ptr(out)))
+        return out
+
+    def hals_stack_run(self, lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count):
+        n = len(lambda_w)
+        lw = (C.c_double * n)(*[float(v) for v in lambda_w])
+        lh = (C.c_double * n)(*[float(v) for v in lambda_h])
+        self._ck(self.lib.nmfx_hals_stack_run(self.h, lw, lh, int(sweeps), int(min_iter), float(tol1), float(tol2), int(first), int(count)))
+
+    def hals_stack_finish(self, min_iter, tol1, tol2, done):
+        self._ck(self.lib.nmfx_hals_stack_finish(self.h, int(min_iter), float(tol1), float(tol2), int(done)))
+
+    def hals_stack_state(self, p):
+        a, b, c = C.c_int(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.nmfx_hals_stack_get_state(self.h, int(p), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def hals_stack_objectives(self, p, first, count):
+        out = np.zeros(max(0, int(count)), dtype=np.float64)
+        if count > 0:
+            self._ck(self.lib.nmfx_hals_stack_get_objectives(self.h, int(p), int(first), int(count), _ptr(out)))
+        return out
+
+    def hals_stack_get_factors(self, p):
+        k_p = self.stack_ks[p]
+        w = np.empty((self.m, k_p), dtype=np.float64)
+        h = np.empty((k_p, self.n), dtype=np.float64)
+        self._ck(self.lib.nmfx_hals_stack_get_factors(self.h, int(p), _ptr(w), _ptr(h)))
+        return w, h
+
     # -- the f64 referee of the stop rule (include/nmfx.h) --------------------------------------
     def objective_f64(self):
         """1/2 ||V - W H||^2 of the current pair with product and sum in float64 on the device."""

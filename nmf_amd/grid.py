@@ -29,7 +29,7 @@ from . import losses
 from . import utils
 from ._driver import Referee
 
-_METHODS = ('mur', 'anls', 'admm', 'ao_admm')
+_METHODS = ('mur', 'anls', 'admm', 'ao_admm', 'hals')
 
 
 def factorize_grid(data, method='mur', *, features, lambda_w=(0.0,), lambda_h=(0.0,), rho=(1,),
@@ -67,13 +67,15 @@ def factorize_grid(data, method='mur', *, features, lambda_w=(0.0,), lambda_h=(0
     pairs = _pairable(method, common) and os.environ.get("NMFX_GRID_PAIR", "1") != "0"
     if pairs:
         return _mur_eu_grid_in_pairs(data, solver, features, lambda_w, lambda_h, save_dir, device, common)
+    if method == 'hals':
+        return _hals_grid_in_stacks(data, solver, features, lambda_w, lambda_h, save_dir, device, common)
     for k in features:
         with Engine(data.shape[0], data.shape[1], k, device=device) as eng:
             eng.upload_v(data)
             combos = product(rho, lambda_w, lambda_h) if method == 'admm' else product((None,), lambda_w, lambda_h)
             for r, lw, lh in combos:
                 kw = dict(common)
-                if method in ('mur', 'anls'):
+                if method in ('mur', 'anls', 'hals'):
                     kw.update(lambda_w=lw, lambda_h=lh)
                 else:
                     kw.update(reg_w=(lw, prox_w), reg_h=(lh, prox_h))
@@ -164,6 +166,80 @@ def _mur_eu_grid_in_pairs(data, solver, features, lambda_w, lambda_h, save_dir, 
             if save_dir is not None:                           # after every run, like the sequential loop: a late failure keeps the earlier files
                 for q in done_now:
                     _save(data, combos[q][0], out[q], save_dir)
+    finally:
+        if big is not None:
+            big.close()
+        for eng in singles.values():
+            eng.close()
+    return [(dict(features=k, lambda_w=lw, lambda_h=lh), res) for (k, lw, lh), res in zip(combos, out)]
+
+
+def _hals_stacks(combos, limit):
+    """The combinations packed greedily, in order, into runs of consecutive indices whose ranks add up to at most `limit`."""
+    stacks, cur, total = [], [], 0
+    for i, (k, _, _) in enumerate(combos):
+        if cur and total + k > limit:
+            stacks.append(cur)
+            cur, total = [], 0
+        cur.append(i)
+        total += k
+    if cur:
+        stacks.append(cur)
+    return stacks
+
+
+def _hals_grid_in_stacks(data, solver, features, lambda_w, lambda_h, save_dir, device, common):
+    """HALS: the combinations are packed greedily, in the legacy driver's order, into stacks of at most 128 components, and each
+    stack is ONE run over V (nmf_amd.hals.hals_stack on a k = 128 engine that stays resident for the whole grid).  RNG consumption
+    and the (params, Results) list are those of the sequential calls.  A stack runs on its own recorded objective without a float64
+    referee: a stack with a combination that stopped early where a single run would have been refereed (hals_stack.last_would_arm) is run
+    again singly from the saved RNG state; singly run too are all combinations with distance_type='kl' (a stack records the Euclidean
+    objective only) and with NMFX_GRID_PAIR=0."""
+    from .hals import MAX_K, _check, hals_stack
+    defaults = {name: par.default for name, par in inspect.signature(solver).parameters.items() if par.default is not inspect.Parameter.empty}
+    combos = [(k, lw, lh) for k in features for lw, lh in product(lambda_w, lambda_h)]
+    sweeps = common.get('sweeps', defaults['sweeps'])
+    distance_type = common.get('distance_type', defaults['distance_type'])
+    for k, lw, lh in combos:                                   # every refusal of hals, before any engine exists
+        _check(data, k, distance_type, sweeps, lw, lh)
+    stacking = distance_type == 'eu' and os.environ.get("NMFX_GRID_PAIR", "1") != "0"
+    stack_kw = {key: val for key, val in common.items() if key not in ('distance_type', 'save_dir')}
+    out = [None] * len(combos)
+    singles = {}
+
+    def run_single(i):
+        k, lw, lh = combos[i]
+        if k not in singles:
+            singles[k] = Engine(data.shape[0], data.shape[1], k, device=device)
+            singles[k].upload_v(data)
+        return solver(data, k, device=device, engine=singles[k], lambda_w=lw, lambda_h=lh, **common)
+
+    big = None
+    try:
+        stacks = _hals_stacks(combos, MAX_K) if stacking else [[i] for i in range(len(combos))]
+        if any(len(st) > 1 for st in stacks):
+            big = Engine(data.shape[0], data.shape[1], MAX_K, device=device)
+            big.upload_v(data)
+        max_iter = common.get('max_iter', defaults['max_iter'])
+        for st in stacks:
+            if len(st) == 1:
+                out[st[0]] = run_single(st[0])
+            else:
+                rng_state = np.random.get_state()
+                held = io.StringIO()                           # (a stack that is run again singly below must not print twice)
+                with contextlib.redirect_stdout(held):
+                    res = hals_stack(data, [dict(k=combos[i][0], lambda_w=combos[i][1], lambda_h=combos[i][2]) for i in st],
+                                     engine=big, device=device, **stack_kw)
+                if any(r.i < max_iter - 1 and arm for r, arm in zip(res, hals_stack.last_would_arm)):
+                    np.random.set_state(rng_state)
+                    res = [run_single(i) for i in st]
+                else:
+                    sys.stdout.write(held.getvalue())
+                for q, i in enumerate(st):
+                    out[i] = res[q]
+            if save_dir is not None:
+                for i in st:
+                    _save(data, combos[i][0], out[i], save_dir)
     finally:
         if big is not None:
             big.close()

@@ -12,7 +12,11 @@ clamp is an exact zero.  Defaults, start, printed lines, stop rule, its float64 
 
 `rescale_start`: before the first iteration both start factors are multiplied by sqrt(alpha), alpha = <V, W0 H0> / ||W0 H0||^2,
 the least-squares optimal scale of the start.  A start scaled far above V (uniform or |randn| factors) makes the very
-first W sweep clamp most of W to zero, and the run then needs many iterations to recover."""
+first W sweep clamp most of W to zero, and the run then needs many iterations to recover.
+
+`hals_stack` runs many Euclidean problems on the same data side by side in the factor columns of one engine: one pair of
+passes over V per iteration for all of them."""
+import logging
 import math
 import numbers
 from collections import namedtuple
@@ -22,7 +26,7 @@ import numpy as np
 from . import _lib as L
 from . import sparse
 from . import utils
-from ._driver import NEVER, Referee, Results, drive
+from ._driver import BATCH, NEVER, Referee, Results, drive, require_iterations, say_objective
 from .engine import Engine
 
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h sweeps')
@@ -64,6 +68,134 @@ def _check(x, k, distance_type, sweeps, lambda_w, lambda_h):
     for name, lam in (('lambda_w', lambda_w), ('lambda_h', lambda_h)):
         if not lam >= 0:
             raise ValueError(f'hals: {name} must be non-negative (got {name} = {lam!r})')
+
+
+_STACK_KEYS = ('k', 'lambda_w', 'lambda_h')
+
+
+def _check_stack(x, problems, sweeps):
+    """Every refusal of hals_stack, before any device work and before any RNG draw.  Returns [(k, lambda_w, lambda_h)]."""
+    sparse.reject(x, 'hals_stack')
+    try:
+        problems = list(problems)
+    except TypeError:
+        raise ValueError(f'hals_stack: problems must be a non-empty sequence of dicts (got {problems!r})') from None
+    if not problems:
+        raise ValueError('hals_stack: problems is empty: it takes at least one dict with the key k')
+    out = []
+    for p, prob in enumerate(problems):
+        if not isinstance(prob, dict):
+            raise ValueError(f'hals_stack: problem {p} is not a dict (got {prob!r})')
+        unknown = sorted(set(prob) - set(_STACK_KEYS), key=str)
+        if unknown:
+            raise ValueError(f'hals_stack: problem {p} has the unknown key {unknown[0]!r} (known: k, lambda_w, lambda_h)')
+        if 'k' not in prob:
+            raise ValueError(f'hals_stack: problem {p} has no k')
+        k = prob['k']
+        if not isinstance(k, numbers.Integral) or isinstance(k, bool) or k < 1:
+            raise ValueError(f'hals_stack: problem {p} needs an integer k >= 1 (got k = {k!r})')
+        lams = []
+        for name in ('lambda_w', 'lambda_h'):
+            lam = prob.get(name, 0)
+            if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not lam >= 0:
+                raise ValueError(f'hals_stack: problem {p}: {name} must be non-negative (got {name} = {lam!r})')
+            lams.append(lam)
+        out.append((int(k), lams[0], lams[1]))
+    total = sum(k for k, _, _ in out)
+    if total > MAX_K:
+        raise ValueError(f'hals_stack: the problems hold {total} components together; a stack takes at most {MAX_K}')
+    if not isinstance(sweeps, numbers.Integral) or isinstance(sweeps, bool) or not 1 <= sweeps <= MAX_SWEEPS:
+        raise ValueError(f'hals_stack: sweeps must be an integer between 1 and {MAX_SWEEPS} (got sweeps = {sweeps!r})')
+    return out
+
+
+def hals_stack(x, problems, *, sweeps=1, rescale_start=True, min_iter=10, max_iter=1000, tol1=1e-3, tol2=1e-3,
+               nndsvd_init=(True, 'zero'), device=0, engine=None):
+    """MANY Euclidean HALS factorizations of the same data in one pass over it per half-iteration: `problems` is a
+    non-empty sequence of dicts with `k` and optionally `lambda_w`, `lambda_h` (default 0), 1 <= k_p, sum of the k_p <= 128.
+    Returns [Results], one per problem in order; problem p's result is what
+    `hals(x, k_p, lambda_w=.., lambda_h=.., sweeps=.., rescale_start=.., distance_type='eu', ...)` defines from the same
+    start: the problems draw from the global numpy RNG in problem order as consecutive `hals` calls would, each start is
+    scaled by its own sqrt(alpha_p) (`hals_stack.last_alpha`), and history, stop rule and the iterate kept at a stop are per
+    problem -- a problem that has stopped keeps its iterate while the others go on.  The lines `hals` prints come problem
+    by problem after the run.
+
+    The problems sit side by side in the factor columns of one engine (nmfx_hals_stack_*): the two products with V per
+    iteration serve all of them, and the Gram entries between different problems are masked in the sweep.
+
+    The stop rule runs on the stack's own recorded objective,
+        1/2 ||V||^2 - <W_p, V H_p^T> + 1/2 <W_p^T W_p, H_p H_p^T>
+    (float32 product V H^T, everything else float64).  It carries more rounding than the residual objective `hals` records
+    (a difference of large terms near an exact fit), and no float64 Referee stands behind it: a single `hals` run may stop
+    at another index where the decrease per iteration is near tol2.  `hals_stack.last_would_arm` holds, per problem,
+    `Referee.would_arm(history_p, tol2)`: True says a single run would have been refereed there.
+
+    `engine`: an Engine with k >= the sum of the k_p that already holds x (nmf_amd.grid keeps a k = 128 one resident)."""
+    probs = _check_stack(x, problems, sweeps)
+    require_iterations(max_iter)
+    ks = [k for k, _, _ in probs]
+    lws = [float(lw) for _, lw, _ in probs]
+    lhs = [float(lh) for _, _, lh in probs]
+    total = sum(ks)
+    inits = [utils.initial_factors(x, k, nndsvd_init, uniform=True, defer_device=True) for k in ks]     # RNG order: problem by problem
+    m, n = x.shape
+    if engine is not None and (engine.m, engine.n) == (m, n) and total <= engine.k <= MAX_K:
+        scope_k = engine.k
+    else:
+        scope_k = total
+    with Engine.for_data(x, scope_k, device=device, engine=engine) as eng:
+        def stacked(scale):
+            w0, h0 = np.zeros((m, eng.k)), np.zeros((eng.k, n))
+            o = 0
+            for p, k in enumerate(ks):
+                w0[:, o:o + k] = np.asarray(starts[p][0], dtype=np.float64) * scale[p]
+                h0[o:o + k] = np.asarray(starts[p][1], dtype=np.float64) * scale[p]
+                o += k
+            return w0, h0
+        starts = [utils.device_initial_factors(eng, x, k, nndsvd_init, inits[p]) for p, k in enumerate(ks)]
+        scale = [1.0] * len(ks)
+        eng.set_factors(*stacked(scale))
+        eng.hals_stack_set(ks)
+        alphas = [None] * len(ks)
+        if rescale_start:
+            for p, (dot, whwh) in enumerate(eng.hals_stack_terms()):
+                if whwh > 0:
+                    alphas[p] = dot / whwh
+                    if alphas[p] > 0 and math.isfinite(alphas[p]):
+                        scale[p] = math.sqrt(alphas[p])
+            eng.set_factors(*stacked(scale))
+        hals_stack.last_alpha = alphas
+        logging.info('Entering Main Loop.')
+        done, rules = 0, [0] * len(ks)
+        while done < max_iter and not all(rules):
+            count = min(BATCH, max_iter - done)
+            eng.hals_stack_run(lws, lhs, sweeps, min_iter, tol1, tol2, done, count)
+            done += count
+            if done == max_iter:
+                eng.hals_stack_finish(min_iter, tol1, tol2, done)
+            rules = [eng.hals_stack_state(p)[0] for p in range(len(ks))]
+        out, arm = [], []
+        digits = utils.tol_digits(tol1, tol2)
+        for p, k in enumerate(ks):
+            rule, stop_i, n_obj = eng.hals_stack_state(p)
+            history = [np.float64(v) for v in eng.hals_stack_objectives(p, 0, n_obj)]
+            w, h = eng.hals_stack_get_factors(p)
+            if rule:
+                i, history = stop_i, history[:stop_i + 2]
+            else:
+                i = max_iter - 1
+            for it, val in enumerate(history[1:]):              # the lines hals prints, problem by problem
+                say_objective(it, val, digits)
+            if rule:
+                utils.convergence_message(rule)
+                logging.warning('Converged.')
+            else:
+                logging.info('Max iteration reached.')
+            arm.append(Referee.would_arm(history, tol2))
+            experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, probs[p][1], probs[p][2], sweeps)
+            out.append(Results(w=w, h=h, i=i, obj_history=history, experiment=experiment))
+        hals_stack.last_would_arm = arm
+    return out
 
 
 def hals(x, k, *, distance_type='eu', sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10,
