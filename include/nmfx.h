@@ -164,8 +164,10 @@ int nmfx_get_relevance(nmfx_handle_t h, double* lambda_out /* k */);
  * On a sparse handle these entry points keep their meaning and the iteration contract of a dense handle, with the same
  * layouts of W and H: nmfx_set_factors, nmfx_get_factors, nmfx_mur_run, nmfx_mur_finish, nmfx_get_state,
  * nmfx_get_objectives, nmfx_objective_f64, nmfx_set_stop_guard, nmfx_resume, nmfx_synchronize, nmfx_set_stream
- * (and nmfx_reset_stream, nmfx_destroy, nmfx_last_error, nmfx_get_note).  The objective is recorded in f64 from the
- * non-zeros plus k x k terms ("Sparse V").  Every other entry point returns NMFX_E_ARG and launches nothing. */
+ * (and nmfx_reset_stream, nmfx_destroy, nmfx_last_error, nmfx_get_note; from version 391 nmfx_profile_enable,
+ * nmfx_profile_get and nmfx_profile_reset, which count the sp_* scopes, and nmfx_hals_sparse_run / _finish on an unmasked
+ * handle with k <= 128).  The objective is recorded in f64 from the non-zeros plus k x k terms ("Sparse V").
+ * Every other entry point returns NMFX_E_ARG and launches nothing. */
 int nmfx_create_csr(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k, int64_t nnz);
 int nmfx_upload_csr(nmfx_handle_t h, const int64_t* row_ptr, const int32_t* col_idx, const void* values, int dtype);
 /* Masked V (version 320).  on = 1: the stored entries are the OBSERVED set M -- stored zeros included -- and every other
@@ -509,7 +511,25 @@ int nmfx_hals_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
                   int64_t min_iter, double tol1, double tol2,
                   int64_t first, int64_t count);
 
-/* ---- stacked HALS (version 390) ------------------------------------------------------------------------------------------
+/* ---- HALS on sparse handles (version 391) ----------------------------------------------------------------------------------
+ * The outer iteration of nmfx_hals_run on an unmasked nmfx_create_csr handle with k <= 128: the W half-step, then the H
+ * half-step, each `sweeps` sweeps per row of W / column of H on G = the other factor's Gram + 2 lambda I and r summed from
+ * the non-zeros; V is never densified.  One launch per half-step gathers r and runs the sweep (plus one for the rows longer
+ * than a piece); the H half-step also sums <h_c, r_c> in f64, so the Euclidean objective of the new pair,
+ *     1/2 [ ||X||^2 - 2 Sum_c <h_c, W^T x_c> + <W^T W, H H^T> ]      (everything in f64 over the f32 factors),
+ * costs no third pass over the non-zeros.  nmfx_hals_sparse_run records obj[0] when first == 0 and obj[j + 1] at the end of
+ * iteration j, where the stop rule for loop index j is evaluated; once it has fired the later iterations of the call do
+ * nothing and the factors are the pair the last recorded objective belongs to.  nmfx_hals_sparse_finish records
+ * obj[iters_done] only where it does not exist yet.  Two runs give the same bits.
+ * NMFX_E_ARG with a message, nothing launched: a dense handle, a masked handle, k padded to 256, sweeps outside 1 .. 16, a
+ * negative lambda or range.  The run is of the HALS family: on a sparse handle neither nmfx_mur_run nor nmfx_hals_sparse_run
+ * continues the other's run without nmfx_set_factors (NMFX_E_STATE).  nmfx_hals_run itself stays dense-only.             */
+int nmfx_hals_sparse_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
+                         int64_t min_iter, double tol1, double tol2,
+                         int64_t first, int64_t count);
+int nmfx_hals_sparse_finish(nmfx_handle_t h, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
+
+/* ---- stacked HALS (version 390)------------------------------------------------------------------------------------------
  * MANY least-squares factorizations of the same V in one pass over it: P problems sit side by side in the factor columns,
  * W = [W_0 | W_1 | ...], H = [H_0; H_1; ...].  The V-sized products V H^T and W^T V of the stacked factors are the P problems'
  * products, and with the Gram entries between different problems masked the Gauss-Seidel sweep over all components is P

@@ -153,7 +153,7 @@ int nmfx_enter(nmfx_engine* E, const nmfx_entry& a) {
 
 extern "C" {
 
-int nmfx_version(void) { return 390; }      // 390: stacked HALS (nmfx_hals_stack_*); 380: HALS (nmfx_hals_run); 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 391; }      // 391: HALS on sparse handles (nmfx_hals_sparse_run, nmfx_hals_sparse_finish); 390: stacked HALS (nmfx_hals_stack_*); 380: HALS (nmfx_hals_run); 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;
@@ -1027,7 +1027,7 @@ int nmfx_foldin_finish(nmfx_handle_t E, int distance, int64_t min_iter, double t
     return nmfx_finish_b(E, min_iter, tol1, tol2, iters_done);
 }
 
-// ---- profiling -------------------------------------------------------------
+// ---- profiling (scopes and counts on dense and sparse handles alike; nmfx_profile_repeat is dense-only) -----
 static void drain_profile(nmfx_engine* E) {
     if (E->prof_pending.empty()) return;
     hipStreamSynchronize(E->stream);
@@ -1043,7 +1043,6 @@ static void drain_profile(nmfx_engine* E) {
 }
 
 int nmfx_profile_enable(nmfx_handle_t E, int on) {
-    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     drain_profile(E);
     E->prof = on != 0;
@@ -1051,7 +1050,6 @@ int nmfx_profile_enable(nmfx_handle_t E, int on) {
 }
 
 int nmfx_profile_get(nmfx_handle_t E, const char* name, double* total_ms, int64_t* launches) {
-    NMFX_NOT_SPARSE(E);
     if (!E || !name) return NMFX_E_ARG;
     drain_profile(E);
     auto it = E->prof_slots.find(name);
@@ -1112,7 +1110,6 @@ int nmfx_profile_repeat(nmfx_handle_t E, const char* which, int distance, int re
 }
 
 int nmfx_profile_reset(nmfx_handle_t E) {
-    NMFX_NOT_SPARSE(E);
     if (!E) return NMFX_E_ARG;
     drain_profile(E);
     E->prof_slots.clear();

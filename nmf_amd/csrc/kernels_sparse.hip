@@ -1,4 +1,4 @@
-// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.
+// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.  (HALS on the same handle: the last section.)
 //
 // Layout.  Both factors are row-major along their long dimension: W [m][kp] (double buffered, E->W) and H^T [n][kp]
 // (nmfx_sparse::Ht), kp in {4, 8, 16, 32, 64, 128, 256}.  V is held twice: CSR (the W phase walks rows of V and gathers
@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #define SP_CHUNK 256          // non-zeros per unit: longer rows are split into pieces
 #define SP_WAVES 8            // waves per block of the phase kernels
@@ -50,6 +51,8 @@ struct SpSide {               // one orientation of V: 0 = CSR (W phase), 1 = CS
     SpUnit* units = nullptr; int64_t nunits = 0;
     SpLong* longs = nullptr; int64_t nlong = 0;
     float* slab = nullptr;    // [pieces][kp] ([pieces][2 kp] on a masked handle)
+    double* slab64 = nullptr; // [pieces][kp] in f64: the pieces' right-hand sides of the sparse HALS H phase (allocated at first use)
+    int64_t npieces = 0;
     int nblk = 1;             // blocks of the phase kernel (a fixed stride over the units)
 };
 
@@ -65,6 +68,7 @@ struct nmfx_sparse {
     double* stat_part = nullptr;           // [slabs][kp * kp + kp]
     double* obj_part = nullptr;            // [blocks]
     int obj_cap = 0;
+    double* hals_part = nullptr;           // sparse HALS: [blocks of the H phase | blocks of its fix-up] partials of Sum_nz x wh (allocated at first use)
     bool masked = false;      // the stored entries are the observed set (nmfx_set_masked)
 };
 
@@ -464,10 +468,10 @@ void nmfx_sparse_free(nmfx_engine* E) {
     nmfx_sparse* S = E->sp;
     if (!S) return;
     void* bufs[] = {S->Ht, S->g64[0], S->g64[1], S->gf[0], S->gf[1], S->cs64[0], S->cs64[1], S->csf[0], S->csf[1],
-                    S->stat_part, S->obj_part};
+                    S->stat_part, S->obj_part, S->hals_part};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& sd : S->side) {
-        void* sb[] = {sd.idx, sd.val, sd.units, sd.longs, sd.slab};
+        void* sb[] = {sd.idx, sd.val, sd.units, sd.longs, sd.slab, sd.slab64};
         for (void* b : sb) if (b) hipFree(b);
     }
     delete S;
@@ -489,8 +493,9 @@ static int build_side(nmfx_engine* E, SpSide& sd, const int64_t* ptr) {
             units.push_back({(long long)(b + (int64_t)p * SP_CHUNK), (int)r, (int)std::min<int64_t>(SP_CHUNK, len - (int64_t)p * SP_CHUNK), slot + p, 0});
         slot += np;
     }
-    for (void* b : {(void*)sd.units, (void*)sd.longs, (void*)sd.slab}) if (b) hipFree(b);
-    sd.units = nullptr; sd.longs = nullptr; sd.slab = nullptr;
+    for (void* b : {(void*)sd.units, (void*)sd.longs, (void*)sd.slab, (void*)sd.slab64}) if (b) hipFree(b);
+    sd.units = nullptr; sd.longs = nullptr; sd.slab = nullptr; sd.slab64 = nullptr;
+    sd.npieces = slot;
     sd.nunits = (int64_t)units.size(); sd.nlong = (int64_t)longs.size();
     int rc;
     if ((rc = sp_alloc(E, &sd.units, sd.nunits))) return rc;
@@ -712,14 +717,14 @@ int nmfx_sparse_mur_finish(nmfx_engine* E, int distance, int64_t min_iter, doubl
     return launch_objective(E, distance, E->xf64, true, done, min_iter, tol1, tol2);
 }
 
-// After the stop rule has fired, the launches behind it in the batch did nothing: the current W is the one of the pair at
-// the stop (W[(stop_i + 1) & 1]), whose Gram is still in g64[0].
+// After the stop rule has fired, the launches behind it in the batch did nothing: the current W of a MUR run is the one of
+// the pair at the stop (W[(stop_i + 1) & 1]), whose Gram is still in g64[0].
 static int sync_wsel(nmfx_engine* E) {
     NMFX_HIP(hipSetDevice(E->device));
     DevState hs;
     NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
-    if (hs.flag) E->run.wsel = (int)((hs.stop_i + 1) & 1);
+    if (hs.flag && !E->run.w_in_place) E->run.wsel = (int)((hs.stop_i + 1) & 1);      // (sparse HALS updates W[0] in place)
     return NMFX_OK;
 }
 
@@ -790,6 +795,314 @@ int nmfx_sparse_get_factors(nmfx_engine* E, double* w, double* hmat) {
             for (int64_t j = 0; j < n; ++j) hmat[c * n + j] = (double)t[(size_t)(j * kp + c)];
     }
     return NMFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// HALS on sparse V (nmfx_hals_sparse_run)
+// ---------------------------------------------------------------------------------------------------------------------
+// A half-step is, per owned row x of the factor being updated (a row of W, or a row of H^T = a column of H),
+//     r = Sum_nz v * gathered row of the other factor,    G = the other factor's Gram + 2 lambda I,
+// and `sweeps` projected Gauss-Seidel sweeps of kernels_hals.hip on (G, r) from x.  The wave that gathered r runs the sweep:
+// after sp_sum_groups every group of G = KP / 4 lanes holds r and x as float4 per lane (variable j: lane j / 4 of its group,
+// component j % 4), and the sweep stays in that layout -- all groups run it redundantly on the same bits.  The residual
+// g = r - G x is formed once, row l of the LDS copy of G (= column l) against x_l broadcast from its lane; step j takes
+//     delta = max(-x_j, g_j / G_jj) from variable j's lane (v_readlane),  x_j += delta,  g -= delta G[j][:]
+// (the lane keeps -x_j, the lower bound of its step).  No wh, no butterfly per non-zero.  Loop bounds are wave-uniform
+// (ceil(k / 4) lanes, sweeps, the unit index); padded components are written as exact zeros; a component with G_jj = 0
+// keeps its value.  A piece of a long row stores its partial r in the slab; sp_hals_fixup_kernel adds the pieces in piece
+// order and runs the same sweep.
+//
+// CROSS (the H phase): r_c = W_new^T x_c is summed in f64 (products of f32 values are exact there) and rounded to f32 for
+// the sweep only; after the sweep the wave adds <h_new_c, r_c> in f64 to its block's partial.  Summed over the columns that
+// is Sum_nz x wh of the new pair, the one term of the Euclidean objective that needs the non-zeros: no third pass over them.
+template <int KP>
+__device__ __forceinline__ void sp_hals_stage(float* gs, const float* __restrict__ Gf, float diag_add, int k) {
+    for (int i = threadIdx.x * 4; i < KP * KP; i += 64 * SP_WAVES * 4) {
+        float4 v = *reinterpret_cast<const float4*>(Gf + i);
+        const int row = i / KP, col = i % KP;
+        if (row < k) {
+            v.x += (col == row) ? diag_add : 0.f; v.y += (col + 1 == row) ? diag_add : 0.f;
+            v.z += (col + 2 == row) ? diag_add : 0.f; v.w += (col + 3 == row) ? diag_add : 0.f;
+        }
+        *reinterpret_cast<float4*>(gs + i) = v;
+    }
+    __syncthreads();
+}
+
+// The sweeps of one owned row.  x: the row (this lane's four components), g: in r, out the kept residual; on return x is the
+// new row (padding 0, dead components as they were).
+template <int KP>
+__device__ __forceinline__ void sp_hals_sweep(const float* gs, const float (&inv)[4], const bool (&live)[4], float (&x)[4],
+                                              float (&g)[4], int k, int sweeps, int lig)
+{
+    const int nl = (k + 3) >> 2;                        // lanes of a group that hold a variable
+    const float* grow = gs + lig * 4;
+    float nx[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) nx[t] = live[t] ? -x[t] : 0.f;      // 0 with inv = 0 where G_jj = 0 or beyond k: a step of 0
+    for (int l4 = 0; l4 < nl; ++l4) {
+        float4 c[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) c[t] = *reinterpret_cast<const float4*>(grow + (4 * l4 + t) * KP);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t]), l4));
+            g[0] = fmaf(-c[t].x, xl, g[0]); g[1] = fmaf(-c[t].y, xl, g[1]);
+            g[2] = fmaf(-c[t].z, xl, g[2]); g[3] = fmaf(-c[t].w, xl, g[3]);
+        }
+    }
+    for (int s = 0; s < sweeps; ++s) {
+        for (int l4 = 0; l4 < nl; ++l4) {
+            float4 c[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) c[t] = *reinterpret_cast<const float4*>(grow + (4 * l4 + t) * KP);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float cand = fmaxf(nx[t], g[t] * inv[t]);
+                const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), l4));
+                nx[t] = (lig == l4) ? nx[t] - d : nx[t];           // (d = -x_j: an exact zero)
+                g[0] = fmaf(-c[t].x, d, g[0]); g[1] = fmaf(-c[t].y, d, g[1]);
+                g[2] = fmaf(-c[t].z, d, g[2]); g[3] = fmaf(-c[t].w, d, g[3]);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) x[t] = lig * 4 + t >= k ? 0.f : live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0)
+}
+
+// this lane's reciprocals of the diagonal of the staged G
+template <int KP>
+__device__ __forceinline__ void sp_hals_diag(const float* gs, int k, int lig, float (&inv)[4], bool (&live)[4]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = lig * 4 + t;
+        const float gd = gs[j * KP + j];
+        live[t] = j < k && gd > 0.f;
+        inv[t] = live[t] ? 1.f / gd : 0.f;
+    }
+}
+
+// One owned row with its summed right-hand side r (R = double on the CROSS side): the sweep, the row written by group 0, and
+// on the CROSS side the row's <x_new, r> in f64 (returned on every lane of group 0; added by lane 0).
+template <int KP, bool CROSS, typename R>
+__device__ __forceinline__ double sp_hals_row(const float* gs, const float (&inv)[4], const bool (&live)[4], const R (&r)[4],
+                                              float* row, int k, int sweeps, int lig, int grp)
+{
+    constexpr int G = KP / 4;
+    const float4 x4 = *reinterpret_cast<const float4*>(row + lig * 4);
+    float x[4] = {x4.x, x4.y, x4.z, x4.w};
+    float g[4] = {(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
+    sp_hals_sweep<KP>(gs, inv, live, x, g, k, sweeps, lig);
+    if (grp == 0) *reinterpret_cast<float4*>(row + lig * 4) = make_float4(x[0], x[1], x[2], x[3]);
+    double cross = 0.0;
+    if constexpr (CROSS) {
+        cross = fma((double)x[0], (double)r[0], fma((double)x[1], (double)r[1], fma((double)x[2], (double)r[2], (double)x[3] * (double)r[3])));
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) cross += __shfl_xor(cross, off, 64);
+    }
+    return cross;
+}
+
+// the waves' objective sums -> the block's partial (every thread of the block calls)
+__device__ __forceinline__ void sp_hals_block_partial(double objacc, double* ob, double* __restrict__ out) {
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) ob[tid >> 6] = objacc;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int w = 0; w < SP_WAVES; ++w) s += ob[w];
+        *out = s;
+    }
+}
+
+//   Own [rows][KP]: the factor being updated, in place (a row is owned by one wave; the gathers read the other factor only);
+//   Other [*][KP]: the factor gathered per non-zero; Gf: its Gram (KP x KP f32), diag_add = (float)(2 lambda);
+//   slab: the pieces' partial r, f32 (W phase) or f64 (CROSS); obj_part[blockIdx.x]: the block's Sum <x_new, r> (CROSS).
+template <int KP, bool CROSS>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_phase_kernel(
+    const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
+    const float* __restrict__ Other, float* Own, const float* __restrict__ Gf, float diag_add, void* __restrict__ slab,
+    double* __restrict__ obj_part, int k, int sweeps, const int* flag)
+{
+    if (*flag) return;
+    constexpr int G = KP / 4, NG = 64 / G;
+    using R = typename std::conditional<CROSS, double, float>::type;
+    __shared__ __attribute__((aligned(16))) float gs[KP * KP];
+    __shared__ double ob[SP_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
+    sp_hals_stage<KP>(gs, Gf, diag_add, k);
+    float inv[4]; bool live[4];
+    sp_hals_diag<KP>(gs, k, lig, inv, live);
+    double objacc = 0.0;
+    for (int64_t u = (int64_t)blockIdx.x * SP_WAVES + wave; u < nunits; u += (int64_t)gridDim.x * SP_WAVES) {
+        const SpUnit U = units[u];
+        R acc[4] = {0, 0, 0, 0};
+        const long long end = U.beg + U.len;
+        for (long long e0 = U.beg + grp; e0 < end; e0 += 4 * NG) {
+            int c[4]; float x[4]; float4 h[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const long long e = e0 + (long long)t * NG;
+                const bool ok = e < end;
+                c[t] = ok ? idx[e] : 0;
+                x[t] = ok ? val[e] : 0.f;               // (a slot past the unit's end gathers row 0 with weight 0)
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) h[t] = *reinterpret_cast<const float4*>(Other + (int64_t)c[t] * KP + lig * 4);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if constexpr (CROSS) {
+                    const double xv = x[t];
+                    acc[0] = fma(xv, (double)h[t].x, acc[0]); acc[1] = fma(xv, (double)h[t].y, acc[1]);
+                    acc[2] = fma(xv, (double)h[t].z, acc[2]); acc[3] = fma(xv, (double)h[t].w, acc[3]);
+                } else {
+                    acc[0] = fmaf(x[t], h[t].x, acc[0]); acc[1] = fmaf(x[t], h[t].y, acc[1]);
+                    acc[2] = fmaf(x[t], h[t].z, acc[2]); acc[3] = fmaf(x[t], h[t].w, acc[3]);
+                }
+            }
+        }
+#pragma unroll
+        for (int off = G; off < 64; off <<= 1) {        // the groups' sums: every lane ends with the same bits
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] += __shfl_xor(acc[t], off, 64);
+        }
+        if (U.slot >= 0) {                              // (wave-uniform)
+            if (grp == 0) {
+                R* p = static_cast<R*>(slab) + (int64_t)U.slot * KP + lig * 4;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) p[t] = acc[t];
+            }
+            continue;
+        }
+        const double cross = sp_hals_row<KP, CROSS, R>(gs, inv, live, acc, Own + (int64_t)U.row * KP, k, sweeps, lig, grp);
+        if (lane == 0) objacc += cross;
+    }
+    if constexpr (CROSS) sp_hals_block_partial(objacc, ob, obj_part + blockIdx.x);
+}
+
+// Rows split into pieces: the pieces' partial r added in piece order (every group adds all of them: the same bits), then the
+// sweep of a whole row; CROSS: the long columns' <h_new, r> into this launch's own slots obj_part[blockIdx.x].
+template <int KP, bool CROSS>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_fixup_kernel(
+    const SpLong* __restrict__ longs, int64_t nlong, const void* __restrict__ slab, float* Own, const float* __restrict__ Gf,
+    float diag_add, double* __restrict__ obj_part, int k, int sweeps, const int* flag)
+{
+    if (*flag) return;
+    constexpr int G = KP / 4;
+    using R = typename std::conditional<CROSS, double, float>::type;
+    __shared__ __attribute__((aligned(16))) float gs[KP * KP];
+    __shared__ double ob[SP_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
+    sp_hals_stage<KP>(gs, Gf, diag_add, k);
+    float inv[4]; bool live[4];
+    sp_hals_diag<KP>(gs, k, lig, inv, live);
+    double objacc = 0.0;
+    for (int64_t l = (int64_t)blockIdx.x * SP_WAVES + wave; l < nlong; l += (int64_t)gridDim.x * SP_WAVES) {
+        const SpLong L = longs[l];
+        R acc[4] = {0, 0, 0, 0};
+        for (int p = 0; p < L.npieces; ++p) {
+            const R* s = static_cast<const R*>(slab) + (int64_t)(L.slot0 + p) * KP + lig * 4;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] += s[t];
+        }
+        const double cross = sp_hals_row<KP, CROSS, R>(gs, inv, live, acc, Own + (int64_t)L.row * KP, k, sweeps, lig, grp);
+        if (lane == 0) objacc += cross;
+    }
+    if constexpr (CROSS) sp_hals_block_partial(objacc, ob, obj_part + blockIdx.x);
+}
+
+// one half-step: side 0 the W phase (own W, gather H^T, Gram 1), side 1 the H phase (own H^T, gather W, Gram 0, CROSS).
+// *nparts: the objective partials the H phase left in hals_part.
+template <int KP, bool CROSS>
+static int launch_hals_phase(nmfx_engine* E, float* Own, const float* Other, float diag_add, int sweeps, int* nparts) {
+    nmfx_sparse* S = E->sp;
+    constexpr int side = CROSS ? 1 : 0;
+    SpSide& sd = S->side[side];
+    const int* flag = &E->state->flag;
+    void* slab = CROSS ? (void*)sd.slab64 : (void*)sd.slab;
+    hipLaunchKernelGGL((sp_hals_phase_kernel<KP, CROSS>), dim3(sd.nblk), dim3(64 * SP_WAVES), 0, E->stream, (const SpUnit*)sd.units,
+                       sd.nunits, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, (const float*)S->gf[1 - side], diag_add,
+                       slab, S->hals_part, E->k, sweeps, flag);
+    NMFX_HIP(hipGetLastError());
+    int nb = 0;
+    if (sd.nlong) {
+        nb = (int)std::min<int64_t>(4 * E->ncu, (sd.nlong + SP_WAVES - 1) / SP_WAVES);
+        hipLaunchKernelGGL((sp_hals_fixup_kernel<KP, CROSS>), dim3(nb), dim3(64 * SP_WAVES), 0, E->stream, (const SpLong*)sd.longs,
+                           sd.nlong, (const void*)slab, Own, (const float*)S->gf[1 - side], diag_add, S->hals_part + sd.nblk, E->k,
+                           sweeps, flag);
+        NMFX_HIP(hipGetLastError());
+    }
+    if (nparts) *nparts = sd.nblk + nb;
+    return NMFX_OK;
+}
+
+// Iteration j: W phase, stats(W), H phase, stats(H), then obj[j + 1] of the new pair and the stop rule for loop index j.
+// Two passes over the non-zeros.  Once the rule has fired every later launch returns at once: the pair stays the one the
+// last recorded objective belongs to.
+template <int KP>
+static int sp_hals_iteration(nmfx_engine* E, double lw, double lh, int sweeps, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    nmfx_sparse* S = E->sp;
+    const int* flag = &E->state->flag;
+    float* W = E->W[0];
+    int rc, nparts = 0;
+    { ProfScope ps(E, "sp_hals_wphase");
+      if ((rc = launch_hals_phase<KP, false>(E, W, S->Ht, (float)(2.0 * lw), sweeps, nullptr))) return rc; }
+    { ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<KP>(E, W, E->m, 0, flag))) return rc; }
+    { ProfScope ps(E, "sp_hals_hphase");
+      if ((rc = launch_hals_phase<KP, true>(E, S->Ht, W, (float)(2.0 * lh), sweeps, &nparts))) return rc; }
+    { ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<KP>(E, S->Ht, E->n, 1, flag))) return rc; }
+    hipLaunchKernelGGL((sp_objective_kernel<false, false>), dim3(1), dim3(256), 0, E->stream, (const double*)S->hals_part, nparts,
+                       (const double*)S->g64[0], (const double*)S->g64[1], (const double*)S->cs64[0], (const double*)S->cs64[1],
+                       E->kp, S->x2, E->xf64, 1, (long long)(j + 1), (long long)min_iter, tol1, tol2, E->state, E->obj_hist);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+// what both entry points refuse, nothing launched; then the guard (family HALS: on a sparse handle neither MUR nor HALS
+// continues the other's run without nmfx_set_factors) and the buffers of first use
+static int sp_hals_ready(nmfx_engine* E, const char* who, int sweeps, double lw, double lh, int64_t first, int64_t count) {
+    if (!E) return NMFX_E_ARG;
+    if (!E->sp) { E->err = std::string(who) + ": needs a sparse handle (nmfx_create_csr); a dense handle runs nmfx_hals_run"; return NMFX_E_ARG; }
+    if (E->sp->masked) { E->err = std::string(who) + ": not available on a masked handle (nmfx_set_masked): masked handles run MUR only"; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = nmfx_small_k_text(who); return NMFX_E_ARG; }
+    nmfx_entry a = {NMFX_FAM_HALS, first, count, NMFX_D_NONE, NMFX_D_NONE};
+    if (sweeps < 1 || sweeps > 16) a.bad = std::string(who) + ": sweeps must be between 1 and 16";
+    else if (first < 0 || count < 0 || !(lw >= 0) || !(lh >= 0)) a.bad = std::string(who) + ": bad range or lambda";
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    E->run.in_place();
+    nmfx_sparse* S = E->sp;
+    if ((rc = nmfx_lazy_alloc(E, &S->hals_part, (int64_t)8 * E->ncu + 64))) return rc;
+    return nmfx_lazy_alloc(E, &S->side[1].slab64, std::max<int64_t>(1, S->side[1].npieces * E->kp));
+}
+
+extern "C" int nmfx_hals_sparse_run(nmfx_handle_t E, double lambda_w, double lambda_h, int sweeps, int64_t min_iter, double tol1,
+                                    double tol2, int64_t first, int64_t count) {
+    int rc = sp_hals_ready(E, "nmfx_hals_sparse_run", sweeps, lambda_w, lambda_h, first, count); if (rc) return rc;
+    if (first == 0 && count > 0) {                     // obj[0]: one objective-only pass over the start
+        if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+        if ((rc = launch_objective(E, NMFX_EU, E->xf64, true, 0, min_iter, tol1, tol2))) return rc;
+    }
+    for (int64_t j = first; j < first + count && !rc; ++j) {
+#define SP_IT(KP) sp_hals_iteration<KP>(E, lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, j)
+        switch (E->kp) { case 4: rc = SP_IT(4); break; case 8: rc = SP_IT(8); break; case 16: rc = SP_IT(16); break;
+                         case 32: rc = SP_IT(32); break; case 64: rc = SP_IT(64); break; default: rc = SP_IT(128); break; }
+#undef SP_IT
+    }
+    return rc;
+}
+
+// Every iteration has recorded the objective of the pair it left: there is something to record only where obj[iters_done]
+// does not exist yet (no iteration has run).
+extern "C" int nmfx_hals_sparse_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
+    int rc = sp_hals_ready(E, "nmfx_hals_sparse_finish", 1, 0.0, 0.0, iters_done, 0); if (rc) return rc;
+    DevState hs;
+    NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    if (hs.flag || hs.n_obj > iters_done) return NMFX_OK;
+    if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+    return launch_objective(E, NMFX_EU, E->xf64, true, iters_done, min_iter, tol1, tol2);
 }
 
 int nmfx_preload_sparse() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(sp_stats_reduce_kernel)) == hipSuccess ? 0 : -1; }

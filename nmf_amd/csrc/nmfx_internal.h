@@ -262,7 +262,7 @@ struct nmfx_engine {
     double* stack_obj = nullptr; int64_t stack_obj_cap = 0;
     double* stack_part = nullptr;
     bool stack_vv_ready = false;   // half_vv is that of the current V
-    struct nmfx_sparse* sp = nullptr;   // a sparse handle (nmfx_create_csr): CSR / CSC of V, H^T, Grams (kernels_sparse.hip); MUR only
+    struct nmfx_sparse* sp = nullptr;   // a sparse handle (nmfx_create_csr): CSR / CSC of V, H^T, Grams (kernels_sparse.hip); MUR, and HALS on an unmasked handle
     // profiling
     bool prof = false;
     std::map<std::string, ProfSlot> prof_slots;

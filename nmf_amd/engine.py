@@ -50,7 +50,7 @@ class Engine:
     @classmethod
     def for_sparse(cls, x, k, device=0, masked=False):
         """A fresh engine on sparse `x` (canonical CSR from nmf_amd.sparse.normalise), uploaded through nmfx_create_csr /
-        nmfx_upload_csr.  Runs MUR only (include/nmfx.h); usable as a context manager like any Engine.  masked=True: `x`
+        nmfx_upload_csr.  Runs MUR and, unmasked with k <= 128, sparse HALS (include/nmfx.h); usable as a context manager like any Engine.  masked=True: `x`
         holds the observed entries (nmf_amd.masked.observed) and nmfx_set_masked is called before the upload."""
         from . import sparse
         row_ptr, col_idx, values = sparse.arrays(x)
@@ -383,6 +383,15 @@ class Engine:
         in place of each NNLS solve (anls_set_distance selects the recorded objective, aoadmm_finish closes the run)."""
         self._ck(self.lib.nmfx_hals_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
                                         float(tol2), int(first), int(count)))
+
+    def hals_sparse_run(self, lam_w, lam_h, sweeps, min_iter, tol1, tol2, first, count):
+        """`count` HALS iterations from iteration `first` on a sparse engine (for_sparse, unmasked, k <= 128): iteration j
+        records obj[j + 1] and evaluates the stop rule for loop index j (include/nmfx.h)."""
+        self._ck(self.lib.nmfx_hals_sparse_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
+                                               float(tol2), int(first), int(count)))
+
+    def hals_sparse_finish(self, min_iter, tol1, tol2, done):
+        self._ck(self.lib.nmfx_hals_sparse_finish(self.h, int(min_iter), float(tol1), float(tol2), int(done)))
 
     # -- stacked HALS: many problems side by side in the factor columns (include/nmfx.h) ---------
     def hals_stack_set(self, ks):

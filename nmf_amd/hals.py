@@ -14,6 +14,9 @@ clamp is an exact zero.  Defaults, start, printed lines, stop rule, its float64 
 the least-squares optimal scale of the start.  A start scaled far above V (uniform or |randn| factors) makes the very
 first W sweep clamp most of W to zero, and the run then needs many iterations to recover.
 
+`hals_sparse` is the same iteration on scipy.sparse input: the right-hand sides are gathered from the non-zeros and swept in
+the same launch (csrc/kernels_sparse.hip); `hals` itself takes dense data only.
+
 `hals_stack` runs many Euclidean problems on the same data side by side in the factor columns of one engine: one pair of
 passes over V per iteration for all of them."""
 import logging
@@ -222,5 +225,49 @@ def hals(x, k, *, distance_type='eu', sweeps=1, rescale_start=True, lambda_w=0, 
             lambda first, count: eng.hals_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
             lambda done: eng.aoadmm_finish(NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
             max_iter, tol1, tol2, referee=referee)
+        w, h = eng.get_factors()
+    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def _check_sparse(x, k, sweeps, lambda_w, lambda_h):
+    """Every refusal of hals_sparse but the one of the stored values, before any device work and before any RNG draw."""
+    if not sparse.is_sparse(x):
+        raise TypeError('hals_sparse: x must be a scipy.sparse matrix; use hals')
+    if not isinstance(k, numbers.Integral) or isinstance(k, bool) or k < 1 or k > MAX_K:
+        raise ValueError(f'hals_sparse: supports 1 <= k <= {MAX_K} components (got k = {k!r})')
+    if not isinstance(sweeps, numbers.Integral) or isinstance(sweeps, bool) or not 1 <= sweeps <= MAX_SWEEPS:
+        raise ValueError(f'hals_sparse: sweeps must be an integer between 1 and {MAX_SWEEPS} (got sweeps = {sweeps!r})')
+    for name, lam in (('lambda_w', lambda_w), ('lambda_h', lambda_h)):
+        if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not lam >= 0:
+            raise ValueError(f'hals_sparse: {name} must be non-negative (got {name} = {lam!r})')
+
+
+def hals_sparse(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10, max_iter=1000, tol1=1e-3,
+                tol2=1e-3, nndsvd_init=(True, 'zero'), device=0):
+    """HALS on scipy.sparse input (any format; canonicalised by sparse.normalise, never densified, never modified),
+    1 <= k <= 128: the outer iteration of `hals` on x.toarray() -- the W half-step, then the H half-step, each `sweeps`
+    projected Gauss-Seidel sweeps with an exact-zero clamp on G = F^T F + 2 lambda I, r = F^T b; a component with
+    G_jj = 0 keeps its value -- with r gathered from the non-zeros (csrc/kernels_sparse.hip).  Start, RNG
+    draws, `rescale_start`, printed lines, stop rule and history are those of `hals`; the recorded objective is the Euclidean
+    one, evaluated in float64 from the non-zeros plus k x k terms, so no float64 referee stands behind the stop rule.
+    Returns Results with the Experiment of `hals` (distance_type 'eu')."""
+    experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
+    _check_sparse(x, k, sweeps, lambda_w, lambda_h)
+    try:
+        xs = sparse.normalise(x, k)
+    except ValueError as e:
+        raise ValueError(f'hals_sparse: {e}') from None
+    w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
+    with Engine.for_sparse(xs, k, device=device) as eng:
+        alpha = start_scale(eng, w0, h0) if rescale_start else None
+        if alpha is not None and alpha > 0 and math.isfinite(alpha):
+            w0, h0 = np.asarray(w0, dtype=np.float64) * math.sqrt(alpha), np.asarray(h0, dtype=np.float64) * math.sqrt(alpha)
+        hals_sparse.last_alpha = alpha
+        eng.set_factors(w0, h0)
+        i, history = drive(
+            eng,
+            lambda first, count: eng.hals_sparse_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
+            lambda done: eng.hals_sparse_finish(min_iter, tol1, tol2, done),
+            max_iter, tol1, tol2, referee=None)
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)

@@ -3,6 +3,7 @@
 import os
 from importlib import import_module
 
+from . import sparse
 from . import utils
 
 _METHODS = ('mur', 'anls', 'admm', 'ao_admm', 'hals')
@@ -34,6 +35,8 @@ class NMF:
         if method not in _METHODS:
             raise Exception('Method not known. Choose one from: ' + ' '.join(_METHODS))
         solver = getattr(import_module('.' + method, __package__), method)
+        if method == 'hals' and sparse.is_sparse(self.data):       # (hals itself takes dense data only)
+            solver = import_module('.hals', __package__).hals_sparse
         self.results = solver(self.data, self.factors, **method_params)
         # README.md:22 promises nmf.w / nmf.h; the reference only sets .results
         self.w, self.h = self.results.w, self.results.h
