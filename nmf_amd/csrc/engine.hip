@@ -339,6 +339,21 @@ int nmfx_synchronize(nmfx_handle_t E) {
     return NMFX_OK;
 }
 
+// f64 rows in device memory (row stride lds) -> f32 rows of a padded [..][np] device matrix.  One row per grid.y entry: at
+// most CVT_MAX_ROWS rows per launch (grid.y ends at 65535), every launch checked.  Both upload paths convert through here.
+static const int64_t CVT_MAX_ROWS = 32768;
+static hipError_t cvt_f64_rows(nmfx_engine* E, const double* src, int64_t lds, float* dst, int64_t rows) {
+    for (int64_t r = 0; r < rows; r += CVT_MAX_ROWS) {
+        const int64_t cnt = std::min<int64_t>(CVT_MAX_ROWS, rows - r);
+        dim3 grid((unsigned)((E->n + 255) / 256), (unsigned)cnt);
+        hipLaunchKernelGGL(cvt_f64_rows_kernel, grid, dim3(256), 0, E->stream, src + r * lds, lds, E->n,
+                           dst + r * E->np, E->np, cnt);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // rows of a host matrix (row stride ld, dtype NMFX_F32 / NMFX_F64) into rows of a padded [..][np] f32 device matrix
 static int copy_rows_in(nmfx_engine* E, float* dst, const void* host, int dtype, int64_t ld, int64_t rows, const char* who) {
     if (dtype == NMFX_F32) {
@@ -354,12 +369,9 @@ static int copy_rows_in(nmfx_engine* E, float* dst, const void* host, int dtype,
             const int64_t cnt = std::min(chunk, rows - r);
             hipError_t e = hipMemcpy2DAsync(stage, (size_t)E->n * 8, src + r * ld, (size_t)ld * 8,
                                             (size_t)E->n * 8, (size_t)cnt, hipMemcpyHostToDevice, E->stream);
-            if (e != hipSuccess) { hipFree(stage); E->err = hipGetErrorString(e); return NMFX_E_HIP; }
-            dim3 grid((unsigned)((E->n + 255) / 256), (unsigned)cnt);
-            hipLaunchKernelGGL(cvt_f64_rows_kernel, grid, dim3(256), 0, E->stream, stage, E->n, E->n,
-                               dst + r * E->np, E->np, cnt);
-            e = hipStreamSynchronize(E->stream);
-            if (e != hipSuccess) { hipFree(stage); E->err = hipGetErrorString(e); return NMFX_E_HIP; }
+            if (e == hipSuccess) e = cvt_f64_rows(E, stage, E->n, dst + r * E->np, cnt);
+            if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
+            if (e != hipSuccess) { hipFree(stage); E->err = std::string(who) + ": " + hipGetErrorString(e); return NMFX_E_HIP; }
         }
         hipFree(stage);
     } else { E->err = std::string(who) + ": dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
@@ -371,6 +383,7 @@ int nmfx_upload_v(nmfx_handle_t E, const void* host, int dtype, int64_t ld, int6
     if (!E) return NMFX_E_ARG;
     if (!host || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
         E->err = "upload_v: bad row range or leading dimension"; return NMFX_E_ARG; }
+    if (dtype != NMFX_F32 && dtype != NMFX_F64) { E->err = "upload_v: dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
     E->derived.drop(NMFX_D_anls_a_ready);              // (products with V)
     NMFX_HIP(hipSetDevice(E->device));
     if (rows == 0) return NMFX_OK;
@@ -496,6 +509,7 @@ int nmfx_upload_v_device(nmfx_handle_t E, const void* dev, int dtype, int64_t ld
     if (!E) return NMFX_E_ARG;
     if (!dev || row0 < 0 || rows < 0 || row0 + rows > E->m || ld < E->n) {
         E->err = "upload_v_device: bad row range or leading dimension"; return NMFX_E_ARG; }
+    if (dtype != NMFX_F32 && dtype != NMFX_F64) { E->err = "upload_v_device: dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
     E->derived.drop(NMFX_D_anls_a_ready);
     NMFX_HIP(hipSetDevice(E->device));
     if (rows == 0) return NMFX_OK;
@@ -505,13 +519,7 @@ int nmfx_upload_v_device(nmfx_handle_t E, const void* dev, int dtype, int64_t ld
         NMFX_HIP(hipMemcpy2DAsync(dst, (size_t)E->np * 4, dev, (size_t)ld * 4, (size_t)E->n * 4,
                                   (size_t)rows, hipMemcpyDeviceToDevice, E->stream));
     } else if (dtype == NMFX_F64) {
-        for (int64_t r = 0; r < rows; r += 32768) {          // (grid.y limit)
-            const int64_t cnt = std::min<int64_t>(32768, rows - r);
-            dim3 grid((unsigned)((E->n + 255) / 256), (unsigned)cnt);
-            hipLaunchKernelGGL(cvt_f64_rows_kernel, grid, dim3(256), 0, E->stream,
-                               static_cast<const double*>(dev) + r * ld, ld, E->n, dst + r * E->np, E->np, cnt);
-        }
-        NMFX_HIP(hipGetLastError());
+        NMFX_HIP(cvt_f64_rows(E, static_cast<const double*>(dev), ld, dst, rows));
     } else { E->err = "upload_v_device: dtype must be NMFX_F32 or NMFX_F64"; return NMFX_E_ARG; }
     NMFX_HIP(hipStreamSynchronize(E->stream));
     E->have_v = true;

@@ -11,6 +11,28 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _row_block(a, n, what):
+    """(array, dtype code, ld) of a block of rows for nmfx_upload_v / nmfx_upload_weights: float32 or float64 (anything else is
+    converted to float64), unit column stride, rows `ld` >= n elements apart.  A view that meets this is passed as it is; any
+    other (Fortran order, reversed or broadcast rows, rows that overlap such as a sliding window) is copied.  A single row
+    goes with ld = n, whatever its row stride says."""
+    a = np.asarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    if a.ndim != 2 or a.shape[1] != n:
+        raise ValueError(f"{what} has the wrong shape")
+    rows, item = a.shape[0], a.itemsize
+    if rows <= 1:
+        if n > 1 and a.strides[1] != item:
+            a = np.ascontiguousarray(a)
+        ld = n
+    else:
+        if not ((n == 1 or a.strides[1] == item) and a.strides[0] % item == 0 and a.strides[0] >= n * item):
+            a = np.ascontiguousarray(a)
+        ld = a.strides[0] // item
+    return a, (L.F32 if a.dtype == np.float32 else L.F64), ld
+
+
 class Engine:
     """One device-resident factorisation problem: V (or a row shard of it), W, H
     and all scratch live in HBM for the lifetime of the object."""
@@ -117,16 +139,8 @@ class Engine:
 
     # -- data --------------------------------------------------------------
     def upload_v(self, v, row0=0):
-        v = np.asarray(v)
-        if v.dtype not in (np.float32, np.float64):
-            v = v.astype(np.float64)
-        if v.ndim != 2 or v.shape[1] != self.n:
-            raise ValueError("V block has the wrong shape")
-        if not (v.strides[1] == v.itemsize and v.strides[0] % v.itemsize == 0 and v.strides[0] > 0):
-            v = np.ascontiguousarray(v)
-        ld = v.strides[0] // v.itemsize
-        self._ck(self.lib.nmfx_upload_v(self.h, _ptr(v), L.F32 if v.dtype == np.float32 else L.F64,
-                                        ld, int(row0), v.shape[0]))
+        v, code, ld = _row_block(v, self.n, "V block")
+        self._ck(self.lib.nmfx_upload_v(self.h, _ptr(v), code, ld, int(row0), v.shape[0]))
 
     def upload_v_device(self, ptr, rows, row0=0, dtype=np.float32, ld=None):
         """Rows [row0, row0 + rows) of V from device memory of this GPU (`ptr` = a raw device
@@ -139,16 +153,8 @@ class Engine:
     def upload_weights(self, weights, row0=0):
         """Per-entry weights for rows [row0, row0 + rows) of V (dense handle, k <= 128; rows never uploaded weigh 0).
         While present, mur_run / mur_finish run the weighted update and the other solvers refuse (include/nmfx.h)."""
-        v = np.asarray(weights)
-        if v.dtype not in (np.float32, np.float64):
-            v = v.astype(np.float64)
-        if v.ndim != 2 or v.shape[1] != self.n:
-            raise ValueError("weights block has the wrong shape")
-        if not (v.strides[1] == v.itemsize and v.strides[0] % v.itemsize == 0 and v.strides[0] > 0):
-            v = np.ascontiguousarray(v)
-        ld = v.strides[0] // v.itemsize
-        self._ck(self.lib.nmfx_upload_weights(self.h, _ptr(v), L.F32 if v.dtype == np.float32 else L.F64,
-                                              ld, int(row0), v.shape[0]))
+        v, code, ld = _row_block(weights, self.n, "weights block")
+        self._ck(self.lib.nmfx_upload_weights(self.h, _ptr(v), code, ld, int(row0), v.shape[0]))
 
     def clear_weights(self):
         self._ck(self.lib.nmfx_clear_weights(self.h))
