@@ -195,3 +195,19 @@ def run_loop(engine, run, run_head, finish, finish_head, min_iter, max_iter, tol
         lambda first, count: run(*run_head, min_iter, tol1, tol2, first, count),
         lambda done: finish(*finish_head, NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
         max_iter, tol1, tol2, referee=referee)
+
+
+def run_least_squares(solver, engine, run, run_head, distance_type, min_iter, max_iter, tol1, tol2):
+    """The tail of an anls / hals run: `run` is the engine's anls_run / hals_run, `run_head` its arguments in front of
+    (min_iter, tol1, tol2, first, count).  With the Euclidean objective the stop rule is refereed in float64 near the stop
+    (Referee); `solver.last_referee` holds the referee, or None, before the loop runs.  A referee that walked has taken the
+    stop rule over: the closing bookkeeping then leaves the device's rule off.  Returns (drive's (i, obj_history), referee)."""
+    referee = None
+    if distance_type == 'eu':
+        referee = Referee(engine, lambda i: run(*run_head, NEVER, tol1, tol2, i, 1), min_iter, tol1, tol2)
+    solver.last_referee = referee
+    return drive(
+        engine,
+        lambda first, count: run(*run_head, min_iter, tol1, tol2, first, count),
+        lambda done: engine.aoadmm_finish(NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
+        max_iter, tol1, tol2, referee=referee), referee

@@ -15,7 +15,7 @@ from collections import namedtuple
 from . import _lib as L
 from . import sparse
 from . import utils
-from ._driver import Referee, Results, drive
+from ._driver import Results, run_least_squares
 from .engine import Engine
 
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h fcnnls')
@@ -27,33 +27,31 @@ def experiment_of(k, kw):
                       kw['lambda_w'], kw['lambda_h'], kw['use_fcnnls'])
 
 
+def loss_code(solver, distance_type):
+    """The library code of 'eu' / 'kl', the objectives the least-squares solvers (`solver`: 'anls', 'hals') report; the
+    losses of mur and unknown names are refused."""
+    if distance_type == 'is':
+        raise ValueError(f"{solver}: distance_type='is' (Itakura-Saito) is a loss of mur only")
+    if distance_type == 'beta':
+        raise ValueError(f"{solver}: distance_type='beta' (the beta-divergence) is a loss of mur only")
+    if distance_type not in ('eu', 'kl'):
+        raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via anls.py:108
+    return L.EU if distance_type == 'eu' else L.KL
+
+
 def anls(x, k, *, distance_type='eu', use_fcnnls=False, lambda_w=0, lambda_h=0, min_iter=10,
          max_iter=1000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
          device=0, engine=None):
     experiment = experiment_of(k, locals())
-    if distance_type == 'is':
-        raise ValueError("anls: distance_type='is' (Itakura-Saito) is a loss of mur only")
-    if distance_type == 'beta':
-        raise ValueError("anls: distance_type='beta' (the beta-divergence) is a loss of mur only")
-    if distance_type not in ('eu', 'kl'):
-        raise KeyError('Distance type unknown: use "kl" or "eu"')   # nmf/utils.py:31 via anls.py:108
+    dist = loss_code('anls', distance_type)
     sparse.reject(x, 'anls')
-    dist = L.EU if distance_type == 'eu' else L.KL
     init = utils.initial_factors(x, k, nndsvd_init, uniform=True, defer_device=True)
     with Engine.for_data(x, k, device=device, engine=engine) as eng:
         w0, h0 = utils.device_initial_factors(eng, x, k, nndsvd_init, init)
         eng.set_factors(w0, h0)
         eng.anls_set_distance(dist)
-        NEVER = 10 ** 15
-        referee = None
-        if distance_type == 'eu':                   # the stop rule refereed in float64 near the stop (nmf_amd._driver.Referee)
-            referee = Referee(eng, lambda i: eng.anls_run(lambda_w, lambda_h, NEVER, tol1, tol2, i, 1), min_iter, tol1, tol2)
-        anls.last_referee = referee
-        i, history = drive(
-            eng,
-            lambda first, count: eng.anls_run(lambda_w, lambda_h, min_iter, tol1, tol2, first, count),
-            lambda done: eng.aoadmm_finish(NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=referee)
+        (i, history), _ = run_least_squares(anls, eng, eng.anls_run, (lambda_w, lambda_h), distance_type,
+                                            min_iter, max_iter, tol1, tol2)
         w, h = eng.get_factors()
         evicted, capped = eng.diagnostics()
     if capped:                    # (the reference's FCNNLS prints 'Not converged.' there, nmf/fcnnls.py:118)

@@ -643,40 +643,62 @@ static int half_solve(nmfx_engine* E, int sweeps, const float* G, float diag_add
     return sweeps ? nmfx_hals_sweep(E, G, diag_add, R, X, sj, sc, nprob, sweeps) : nnls(E, G, diag_add, R, X, sj, sc, nprob);
 }
 
-static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, double tol1, double tol2, int64_t j, int sweeps = 0) {
+// ---- the half-step products, written once for ANLS, HALS and stacked HALS.  Each step only launches. ----
+// anls_a_ready says "A_part and the H H^T slabs are those of the current (W, H)":
+//   set by      the fused objective pass of anls_objective (split-bf16 only), and by the stack after ls_w_products (both modes);
+//   consumed by the next W half-step of the same family, which then skips ls_w_products (ANLS / HALS: split-bf16 only -- the
+//               exact-f32 iteration always launches them), and by the stack's terms / finish;
+//   dropped by  whoever moves W or H: the half-step right before its solve, anls_objective, nmfx_anls_set_distance,
+//               nmfx_hals_stack_set, the uploads and nmfx_set_factors, and nmfx_enter for a call of another family (engine.hip).
+
+// W-side products of the current H, no objective: V H^T (slabs in A_part) and, where they are a by-product, the H H^T slabs
+static int ls_w_products(nmfx_engine* E) {
+    int rc;
+    if (anls_bf16(E)) {
+        if ((rc = nmfx_bf16_prepare(E))) return rc;
+        if ((rc = nmfx_bf16_images_h(E, false))) return rc;
+        return nmfx_bf16_vht(E, false, 0, "wphase_noobj");
+    }
+    if ((rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
+    return nmfx_launch_wphase(E, E->W[0], true, false);
+}
+
+// ... summed: HHt and Asum, what the W half-step (and the stack's objective) read
+static int ls_w_sums(nmfx_engine* E) {
+    int rc;
+    const bool bf = anls_bf16(E), byprod = bf && E->kp == 64;              // split-bf16, kp = 64: H H^T as a by-product of V H^T
+    if (bf && !byprod && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
+    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, (int64_t)E->kp * E->kp, E->HHt))) return rc;
+    return nmfx_launch_sum_partials(E, E->A_part, bf ? E->bf_wsplit : E->wsplit, E->mp * E->kp, E->Asum);
+}
+
+// H-side products of the new W: [W^T V | W^T W] packed into xf32; `slot`: the objective partials nmfx_bf16_pack_t steps over
+static int ls_h_products(nmfx_engine* E, int64_t slot) {
     int rc;
     float* W = E->W[0];
-    const int64_t kk = (int64_t)E->kp * E->kp;
-    if ((rc = nmfx_finish_b(E, min_iter, tol1, tol2, j))) return rc;      // obj[j] + stop rule
-    if (anls_bf16(E)) {     // the same steps with the products on the split-bf16 kernels (kp = 64 / 128)
-        const bool byprod = E->kp == 64;                                   // Gram matrices as by-products
-        if ((rc = nmfx_bf16_prepare(E))) return rc;
-        if (!E->derived.anls_a_ready) {                                            // (else: A_part and the H H^T slabs come from the objective pass)
-            if ((rc = nmfx_bf16_images_h(E, false))) return rc;
-            if ((rc = nmfx_bf16_vht(E, false, 0, "wphase_noobj"))) return rc;
-        }
-        E->derived.drop(NMFX_D_anls_a_ready);          // (used up: the solve below moves W)
-        if (!byprod && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-        if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, kk, E->HHt))) return rc;
-        if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->bf_wsplit, E->mp * E->kp, E->Asum))) return rc;
-        if ((rc = half_solve(E, sweeps, E->HHt, (float)(2.0 * lam_w), E->Asum, W, 1, E->kp, E->m))) return rc;
+    if (anls_bf16(E)) {
+        const bool byprod = E->kp == 64;               // W^T W as a by-product of W^T V
         if ((rc = nmfx_bf16_images_w(E, W, 0))) return rc;
         if ((rc = nmfx_bf16_vtw(E, false, "hphase"))) return rc;
-        if (byprod) return nmfx_bf16_pack_t(E, E->G_part, nmfx_bf16_g_slabs(E), E->obj_count);
-        if ((rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
-        return nmfx_bf16_pack_t(E, E->G_part, E->gsplit, E->obj_count);
+        if (!byprod && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
+        return nmfx_bf16_pack_t(E, E->G_part, byprod ? nmfx_bf16_g_slabs(E) : E->gsplit, slot);
     }
-    // ---- W: rows of W from G = H H^T + 2 lam_w I, r = (V H^T)[i, :]  (anls.py:18-31) ----
-    if ((rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-    if ((rc = nmfx_launch_wphase(E, W, true, false))) return rc;
-    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
-    if ((rc = nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum))) return rc;
-    if ((rc = half_solve(E, sweeps, E->HHt, (float)(2.0 * lam_w), E->Asum, W, 1, E->kp, E->m))) return rc;
-    // ---- products for H: [W^T V | W^T W] ----
     const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
     if (!fuse_g && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
     if ((rc = nmfx_launch_hphase(E, W, fuse_g))) return rc;
     return nmfx_launch_pack(E);
+}
+
+// obj[j] + stop rule, then rows of W from G = H H^T + 2 lam_w I, r = (V H^T)[i, :]  (anls.py:18-31), then the products for H
+static int anls_w_and_products(nmfx_engine* E, double lam_w, int64_t min_iter, double tol1, double tol2, int64_t j, int sweeps = 0) {
+    int rc;
+    if ((rc = nmfx_finish_b(E, min_iter, tol1, tol2, j))) return rc;
+    const bool left = anls_bf16(E) && E->derived.anls_a_ready;             // the fused objective pass left A_part and the H H^T slabs
+    if ((rc = left ? nmfx_bf16_prepare(E) : ls_w_products(E))) return rc;
+    E->derived.drop(NMFX_D_anls_a_ready);              // (used up: the solve below moves W)
+    if ((rc = ls_w_sums(E))) return rc;
+    if ((rc = half_solve(E, sweeps, E->HHt, (float)(2.0 * lam_w), E->Asum, E->W[0], 1, E->kp, E->m))) return rc;
+    return ls_h_products(E, E->obj_count);
 }
 
 static int anls_h(nmfx_engine* E, double lam_h, int sweeps = 0) {
@@ -764,10 +786,8 @@ extern "C" int nmfx_hals_run(nmfx_handle_t E, double lambda_w, double lambda_h, 
     NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
     if (E->kp > 128) { E->err = nmfx_small_k_text("nmfx_hals_run"); return NMFX_E_ARG; }
-    const bool bad_sweeps = sweeps < 1 || sweeps > 16;
-    int rc = anls_ready(E, first, count, bad_sweeps || first < 0 || count < 0 || !(lambda_w >= 0) || !(lambda_h >= 0), true, NMFX_FAM_HALS,
-                        bad_sweeps ? "nmfx_hals_run: sweeps must be between 1 and 16" : "nmfx_hals_run: bad range or lambda");
-    if (rc) return rc;
+    const std::string bad = nmfx_hals_args_bad("nmfx_hals_run", sweeps, first, count, &lambda_w, &lambda_h);
+    int rc = anls_ready(E, first, count, !bad.empty(), true, NMFX_FAM_HALS, bad.c_str()); if (rc) return rc;
     if (first == 0 && count > 0 && (rc = anls_objective(E))) return rc;   // obj[0]
     for (int64_t j = first; j < first + count; ++j)
         if ((rc = anls_iteration(E, lambda_w, lambda_h, min_iter, tol1, tol2, j, sweeps))) return rc;
@@ -791,56 +811,23 @@ static int stack_ready(nmfx_engine* E, const char* who, int64_t first, int64_t c
     return nmfx_hals_stack_vv(E);
 }
 
-// V H^T (slabs in A_part) and the H H^T slabs of the current H, no objective
-static int stack_w_products(nmfx_engine* E) {
-    int rc;
-    if (anls_bf16(E)) {
-        if ((rc = nmfx_bf16_prepare(E))) return rc;
-        if ((rc = nmfx_bf16_images_h(E, false))) return rc;
-        return nmfx_bf16_vht(E, false, 0, "wphase_noobj");
-    }
-    if ((rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-    return nmfx_launch_wphase(E, E->W[0], true, false);
-}
-
-// ... summed: HHt and Asum, what the W half-step and the objective read
+// HHt and Asum of the current (W, H), from products that are launched only where none are left
 static int stack_w_sums(nmfx_engine* E) {
     int rc;
-    const int64_t kk = (int64_t)E->kp * E->kp;
-    if (!E->derived.anls_a_ready && (rc = stack_w_products(E))) return rc;
+    if (!E->derived.anls_a_ready && (rc = ls_w_products(E))) return rc;
     E->derived.anls_a_ready = true;
-    if (anls_bf16(E)) {
-        const bool byprod = E->kp == 64;
-        if (!byprod && (rc = nmfx_launch_gram_nt(E, E->H, E->np, E->np, E->HHt_part, E->gsplit))) return rc;
-        if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, byprod ? nmfx_bf16_hht_slabs(E) : E->gsplit, kk, E->HHt))) return rc;
-        return nmfx_launch_sum_partials(E, E->A_part, E->bf_wsplit, E->mp * E->kp, E->Asum);
-    }
-    if ((rc = nmfx_launch_sum_partials(E, E->HHt_part, E->gsplit, kk, E->HHt))) return rc;
-    return nmfx_launch_sum_partials(E, E->A_part, E->wsplit, E->mp * E->kp, E->Asum);
+    return ls_w_sums(E);
 }
 
 static int stack_iteration(nmfx_engine* E, int sweeps, int64_t min_iter, double tol1, double tol2, int64_t j) {
     int rc;
-    float* W = E->W[0];
     if ((rc = stack_w_sums(E))) return rc;
     if ((rc = nmfx_hals_stack_objective(E, true, j, min_iter, tol1, tol2))) return rc;      // obj_p[j] + each problem's stop rule
     E->derived.drop(NMFX_D_anls_a_ready);              // (used up: the sweep below moves W)
-    if ((rc = nmfx_hals_stack_sweep(E, E->HHt, 0, E->Asum, W, 1, E->kp, E->m, sweeps))) return rc;
-    if (anls_bf16(E)) {
-        const bool byprod = E->kp == 64;
-        if ((rc = nmfx_bf16_images_w(E, W, 0))) return rc;
-        if ((rc = nmfx_bf16_vtw(E, false, "hphase"))) return rc;
-        if (byprod) rc = nmfx_bf16_pack_t(E, E->G_part, nmfx_bf16_g_slabs(E), 0);
-        else if (!(rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) rc = nmfx_bf16_pack_t(E, E->G_part, E->gsplit, 0);
-        if (rc) return rc;
-    } else {
-        const bool fuse_g = nmfx_hphase_can_fuse_gram(E);
-        if (!fuse_g && (rc = nmfx_launch_gram_tn(E, W, E->mp, E->G_part, E->gsplit))) return rc;
-        if ((rc = nmfx_launch_hphase(E, W, fuse_g))) return rc;
-        if ((rc = nmfx_launch_pack(E))) return rc;
-    }
-    if ((rc = nmfx_hals_stack_sweep(E, E->xf32 + (int64_t)E->kp * E->np, 1, E->xf32, E->H, E->np, 1, E->n, sweeps))) return rc;
-    if ((rc = stack_w_products(E))) return rc;         // the next iteration's right-hand sides, and what its objective is formed from
+    if ((rc = nmfx_hals_sweep(E, E->HHt, 0.f, E->Asum, E->W[0], 1, E->kp, E->m, sweeps, 0))) return rc;
+    if ((rc = ls_h_products(E, 0))) return rc;
+    if ((rc = nmfx_hals_sweep(E, E->xf32 + (int64_t)E->kp * E->np, 0.f, E->xf32, E->H, E->np, 1, E->n, sweeps, 1))) return rc;
+    if ((rc = ls_w_products(E))) return rc;            // the next iteration's right-hand sides, and what its objective is formed from
     E->derived.anls_a_ready = true;
     return NMFX_OK;
 }
@@ -878,19 +865,13 @@ extern "C" int nmfx_hals_stack_terms(nmfx_handle_t E, double* out) {
     return NMFX_OK;
 }
 
-static std::string stack_run_bad(nmfx_engine* E, const double* lw, const double* lh, int sweeps, int64_t first, int64_t count) {
-    if (sweeps < 1 || sweeps > 16) return "nmfx_hals_stack_run: sweeps must be between 1 and 16";
-    if (first < 0 || count < 0 || !lw || !lh) return "nmfx_hals_stack_run: bad range or lambda";
-    for (int p = 0; p < E->stack_nprob; ++p)
-        if (!(lw[p] >= 0) || !(lh[p] >= 0)) return "nmfx_hals_stack_run: bad range or lambda";
-    return "";
-}
-
 extern "C" int nmfx_hals_stack_run(nmfx_handle_t E, const double* lambda_w, const double* lambda_h, int sweeps, int64_t min_iter, double tol1,
                                    double tol2, int64_t first, int64_t count) {
     NMFX_DENSE_ONLY(E);
     if (!E) return NMFX_E_ARG;
-    int rc = stack_ready(E, "nmfx_hals_stack_run", first, count, stack_run_bad(E, lambda_w, lambda_h, sweeps, first, count)); if (rc) return rc;
+    int rc = stack_ready(E, "nmfx_hals_stack_run", first, count,
+                         nmfx_hals_args_bad("nmfx_hals_stack_run", sweeps, first, count, lambda_w, lambda_h, E->stack_nprob));
+    if (rc) return rc;
     if ((rc = nmfx_hals_stack_lambdas(E, lambda_w, lambda_h))) return rc;
     for (int64_t j = first; j < first + count; ++j)
         if ((rc = stack_iteration(E, sweeps, min_iter, tol1, tol2, j))) return rc;

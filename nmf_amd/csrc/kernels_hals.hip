@@ -140,9 +140,9 @@ __global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_sweep_kernel(
     }
 }
 
-template <int KP, bool STACK = false>
+template <int KP, bool STACK>
 static int launch_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                             int64_t nprob, int sweeps, int side = 0) {
+                             int64_t nprob, int sweeps, int side) {
     int rc;
     const size_t shm = (size_t)KP * KP * sizeof(float);
     auto kern = hals_sweep_kernel<KP, STACK>;
@@ -156,33 +156,28 @@ static int launch_hals_sweep(nmfx_engine* E, const float* G, float diag_add, con
     return NMFX_OK;
 }
 
-// Same arguments and stride conventions as the NNLS launcher of kernels_anls.hip (W: sj = 1, sc = kp; H: sj = np, sc = 1).
-int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                    int64_t nprob, int sweeps) {
-    ProfScope ps(E, "hals_sweep");
-    if (nprob <= 0) return NMFX_OK;
+// the one kp dispatch of the sweep, plain and stacked
+template <bool STACK>
+static int hals_sweep_kp(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                         int64_t nprob, int sweeps, int side) {
     switch (E->kp) {
-        case 16: return launch_hals_sweep<16>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 32: return launch_hals_sweep<32>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 64: return launch_hals_sweep<64>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 128: return launch_hals_sweep<128>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 16: return launch_hals_sweep<16, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
+        case 32: return launch_hals_sweep<32, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
+        case 64: return launch_hals_sweep<64, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
+        case 128: return launch_hals_sweep<128, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
     }
-    E->err = nmfx_small_k_text("hals_sweep");
+    E->err = nmfx_small_k_text(STACK ? "hals_stack_sweep" : "hals_sweep");
     return NMFX_E_ARG;
 }
 
-int nmfx_hals_stack_sweep(nmfx_engine* E, const float* G, int side, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob,
-                          int sweeps) {
+// Same arguments and stride conventions as the NNLS launcher of kernels_anls.hip (W: sj = 1, sc = kp; H: sj = np, sc = 1).
+// stack_side >= 0: the stacked form (nmfx_internal.h); its diagonal comes from the stack's own lambdas, not from diag_add.
+int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                    int64_t nprob, int sweeps, int stack_side) {
     ProfScope ps(E, "hals_sweep");
     if (nprob <= 0) return NMFX_OK;
-    switch (E->kp) {
-        case 16: return launch_hals_sweep<16, true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, side);
-        case 32: return launch_hals_sweep<32, true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, side);
-        case 64: return launch_hals_sweep<64, true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, side);
-        case 128: return launch_hals_sweep<128, true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, side);
-    }
-    E->err = nmfx_small_k_text("hals_stack_sweep");
-    return NMFX_E_ARG;
+    return stack_side < 0 ? hals_sweep_kp<false>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, 0)
+                          : hals_sweep_kp<true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, stack_side);
 }
 
 // ---- the stack's state and objective ------------------------------------------------------------------------------------------

@@ -1068,8 +1068,7 @@ static int sp_hals_ready(nmfx_engine* E, const char* who, int sweeps, double lw,
     if (E->sp->masked) { E->err = std::string(who) + ": not available on a masked handle (nmfx_set_masked): masked handles run MUR only"; return NMFX_E_ARG; }
     if (E->kp > 128) { E->err = nmfx_small_k_text(who); return NMFX_E_ARG; }
     nmfx_entry a = {NMFX_FAM_HALS, first, count, NMFX_D_NONE, NMFX_D_NONE};
-    if (sweeps < 1 || sweeps > 16) a.bad = std::string(who) + ": sweeps must be between 1 and 16";
-    else if (first < 0 || count < 0 || !(lw >= 0) || !(lh >= 0)) a.bad = std::string(who) + ": bad range or lambda";
+    a.bad = nmfx_hals_args_bad(who, sweeps, first, count, &lw, &lh);
     int rc = nmfx_enter(E, a); if (rc) return rc;
     E->run.in_place();
     nmfx_sparse* S = E->sp;

@@ -416,6 +416,14 @@ inline int nmfx_small_k_only(nmfx_engine* E, const char* what) {
     E->err = nmfx_small_k_text(what);
     return NMFX_E_ARG;
 }
+// What every HALS run refuses in its arguments, worded for nmfx_entry::bad ("": nothing): sweeps outside 1..16 first, then a
+// negative range or a lambda that is not >= 0 (nlam pairs: one per problem of a stack; a NULL array is refused too)
+inline std::string nmfx_hals_args_bad(const char* who, int sweeps, int64_t first, int64_t count, const double* lw, const double* lh, int nlam = 1) {
+    if (sweeps < 1 || sweeps > 16) return std::string(who) + ": sweeps must be between 1 and 16";
+    bool bad = first < 0 || count < 0 || !lw || !lh;
+    for (int p = 0; !bad && p < nlam; ++p) bad = !(lw[p] >= 0) || !(lh[p] >= 0);
+    return bad ? std::string(who) + ": bad range or lambda" : std::string();
+}
 int nmfx_ensure_inner_capacity(nmfx_engine* E, int64_t need);
 
 // AO-ADMM / ADMM building blocks (kernels_aoadmm.hip)
@@ -484,10 +492,10 @@ int nmfx_preload_aoadmm();
 int nmfx_preload_anls();
 int nmfx_preload_hals();
 // kernels_hals.hip: `sweeps` projected Gauss-Seidel sweeps per problem on (G + diag_add I, R), X in place; strides as the NNLS launcher's
-int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps);
-// ... and the stacked form (nmfx_hals_stack_*): G masked to the problems' diagonal blocks while it is staged, 2 lambda_p per component
-// (side 0: lambda_w, 1: lambda_h), the components of a stopped problem left as they are
-int nmfx_hals_stack_sweep(nmfx_engine* E, const float* G, int side, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps);
+// stack_side >= 0 is the stacked form (nmfx_hals_stack_*): G masked to the problems' diagonal blocks while it is staged, 2 lambda_p per
+// component in place of diag_add (side 0: lambda_w, 1: lambda_h), the components of a stopped problem left as they are
+int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps,
+                    int stack_side = -1);
 int nmfx_hals_stack_alloc(nmfx_engine* E);                     // the device state and the partial buffers, on first use
 int nmfx_hals_stack_config(nmfx_engine* E);                    // stack_nprob / stack_off -> device, stop state cleared
 int nmfx_hals_stack_reset(nmfx_engine* E);                     // nmfx_set_factors: the per-problem stop state back to "running"

@@ -195,13 +195,13 @@ def _hals_grid_in_stacks(data, solver, features, lambda_w, lambda_h, save_dir, d
     referee: a stack with a combination that stopped early where a single run would have been refereed (hals_stack.last_would_arm) is run
     again singly from the saved RNG state; singly run too are all combinations with distance_type='kl' (a stack records the Euclidean
     objective only) and with NMFX_GRID_PAIR=0."""
-    from .hals import MAX_K, _check, hals_stack
+    from .hals import MAX_K, check_hals, hals_stack
     defaults = {name: par.default for name, par in inspect.signature(solver).parameters.items() if par.default is not inspect.Parameter.empty}
     combos = [(k, lw, lh) for k in features for lw, lh in product(lambda_w, lambda_h)]
     sweeps = common.get('sweeps', defaults['sweeps'])
     distance_type = common.get('distance_type', defaults['distance_type'])
     for k, lw, lh in combos:                                   # every refusal of hals, before any engine exists
-        _check(data, k, distance_type, sweeps, lw, lh)
+        check_hals(data, k, distance_type, sweeps, lw, lh)
     stacking = distance_type == 'eu' and os.environ.get("NMFX_GRID_PAIR", "1") != "0"
     stack_kw = {key: val for key, val in common.items() if key not in ('distance_type', 'save_dir')}
     out = [None] * len(combos)

@@ -26,10 +26,10 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib as L
 from . import sparse
 from . import utils
-from ._driver import BATCH, NEVER, Referee, Results, drive, require_iterations, say_objective
+from ._driver import BATCH, Referee, Results, drive, require_iterations, say_objective, run_least_squares
+from .anls import loss_code
 from .engine import Engine
 
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h sweeps')
@@ -55,22 +55,46 @@ def start_scale(eng, w0, h0):
     return (half_vv + 0.5 * whwh - eng.objective_f64()) / whwh
 
 
-def _check(x, k, distance_type, sweeps, lambda_w, lambda_h):
-    """Every refusal of hals, before any device work."""
-    if distance_type == 'is':
-        raise ValueError("hals: distance_type='is' (Itakura-Saito) is a loss of mur only")
-    if distance_type == 'beta':
-        raise ValueError("hals: distance_type='beta' (the beta-divergence) is a loss of mur only")
-    if distance_type not in ('eu', 'kl'):
-        raise KeyError('Distance type unknown: use "kl" or "eu"')   # as anls
-    sparse.reject(x, 'hals')
-    if not isinstance(k, numbers.Integral) or isinstance(k, bool) or k < 1 or k > MAX_K:
-        raise ValueError(f'hals: supports 1 <= k <= {MAX_K} components (got k = {k!r})')
-    if not isinstance(sweeps, numbers.Integral) or isinstance(sweeps, bool) or not 1 <= sweeps <= MAX_SWEEPS:
-        raise ValueError(f'hals: sweeps must be an integer between 1 and {MAX_SWEEPS} (got sweeps = {sweeps!r})')
+def scaled_start(alpha, w0, h0):
+    """The start (w0, h0) times sqrt(alpha), in float64, where alpha (start_scale's, or None) is positive and finite; the start
+    as it is otherwise."""
+    if alpha is None or not (alpha > 0 and math.isfinite(alpha)):
+        return w0, h0
+    return np.asarray(w0, dtype=np.float64) * math.sqrt(alpha), np.asarray(h0, dtype=np.float64) * math.sqrt(alpha)
+
+
+def _is_count(value, most=None):
+    return isinstance(value, numbers.Integral) and not isinstance(value, bool) and value >= 1 and (most is None or value <= most)
+
+
+_ABSENT = object()
+
+
+def check_args(who, *, k=_ABSENT, sweeps=_ABSENT, lambda_w=_ABSENT, lambda_h=_ABSENT, real_lambdas, problem=None):
+    """The HALS rules for k, sweeps and a lambda, stated once, in the order k, sweeps, lambda_w, lambda_h; what is not given is
+    not checked.  `who` is the front end's name.  `problem`: the index of a problem of a stack, whose k has no bound of its own
+    (the stack's total has).  `real_lambdas` is inherited: hals_stack and hals_sparse refuse a bool or a non-Real lambda, hals
+    takes whatever answers `lam >= 0` with something true (True, for one)."""
+    at = who if problem is None else f'{who}: problem {problem}'
+    if k is not _ABSENT and not _is_count(k, MAX_K if problem is None else None):
+        if problem is None:
+            raise ValueError(f'{who}: supports 1 <= k <= {MAX_K} components (got k = {k!r})')
+        raise ValueError(f'{at} needs an integer k >= 1 (got k = {k!r})')
+    if sweeps is not _ABSENT and not _is_count(sweeps, MAX_SWEEPS):
+        raise ValueError(f'{who}: sweeps must be an integer between 1 and {MAX_SWEEPS} (got sweeps = {sweeps!r})')
     for name, lam in (('lambda_w', lambda_w), ('lambda_h', lambda_h)):
-        if not lam >= 0:
-            raise ValueError(f'hals: {name} must be non-negative (got {name} = {lam!r})')
+        if lam is _ABSENT:
+            continue
+        if (real_lambdas and (isinstance(lam, bool) or not isinstance(lam, numbers.Real))) or not lam >= 0:
+            raise ValueError(f'{at}: {name} must be non-negative (got {name} = {lam!r})')
+
+
+def check_hals(x, k, distance_type, sweeps, lambda_w, lambda_h):
+    """Every refusal of hals, before any device work (nmf_amd.grid asks for a whole grid first).  Returns the loss's library code."""
+    dist = loss_code('hals', distance_type)
+    sparse.reject(x, 'hals')
+    check_args('hals', k=k, sweeps=sweeps, lambda_w=lambda_w, lambda_h=lambda_h, real_lambdas=False)
+    return dist
 
 
 _STACK_KEYS = ('k', 'lambda_w', 'lambda_h')
@@ -94,21 +118,13 @@ def _check_stack(x, problems, sweeps):
             raise ValueError(f'hals_stack: problem {p} has the unknown key {unknown[0]!r} (known: k, lambda_w, lambda_h)')
         if 'k' not in prob:
             raise ValueError(f'hals_stack: problem {p} has no k')
-        k = prob['k']
-        if not isinstance(k, numbers.Integral) or isinstance(k, bool) or k < 1:
-            raise ValueError(f'hals_stack: problem {p} needs an integer k >= 1 (got k = {k!r})')
-        lams = []
-        for name in ('lambda_w', 'lambda_h'):
-            lam = prob.get(name, 0)
-            if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not lam >= 0:
-                raise ValueError(f'hals_stack: problem {p}: {name} must be non-negative (got {name} = {lam!r})')
-            lams.append(lam)
-        out.append((int(k), lams[0], lams[1]))
+        k, lw, lh = prob['k'], prob.get('lambda_w', 0), prob.get('lambda_h', 0)
+        check_args('hals_stack', k=k, lambda_w=lw, lambda_h=lh, real_lambdas=True, problem=p)
+        out.append((int(k), lw, lh))
     total = sum(k for k, _, _ in out)
     if total > MAX_K:
         raise ValueError(f'hals_stack: the problems hold {total} components together; a stack takes at most {MAX_K}')
-    if not isinstance(sweeps, numbers.Integral) or isinstance(sweeps, bool) or not 1 <= sweeps <= MAX_SWEEPS:
-        raise ValueError(f'hals_stack: sweeps must be an integer between 1 and {MAX_SWEEPS} (got sweeps = {sweeps!r})')
+    check_args('hals_stack', sweeps=sweeps, real_lambdas=True)
     return out
 
 
@@ -147,26 +163,20 @@ def hals_stack(x, problems, *, sweeps=1, rescale_start=True, min_iter=10, max_it
     else:
         scope_k = total
     with Engine.for_data(x, scope_k, device=device, engine=engine) as eng:
-        def stacked(scale):
+        def stacked(alphas):
             w0, h0 = np.zeros((m, eng.k)), np.zeros((eng.k, n))
             o = 0
             for p, k in enumerate(ks):
-                w0[:, o:o + k] = np.asarray(starts[p][0], dtype=np.float64) * scale[p]
-                h0[o:o + k] = np.asarray(starts[p][1], dtype=np.float64) * scale[p]
+                w0[:, o:o + k], h0[o:o + k] = scaled_start(alphas[p], *starts[p])
                 o += k
             return w0, h0
         starts = [utils.device_initial_factors(eng, x, k, nndsvd_init, inits[p]) for p, k in enumerate(ks)]
-        scale = [1.0] * len(ks)
-        eng.set_factors(*stacked(scale))
-        eng.hals_stack_set(ks)
         alphas = [None] * len(ks)
+        eng.set_factors(*stacked(alphas))
+        eng.hals_stack_set(ks)
         if rescale_start:
-            for p, (dot, whwh) in enumerate(eng.hals_stack_terms()):
-                if whwh > 0:
-                    alphas[p] = dot / whwh
-                    if alphas[p] > 0 and math.isfinite(alphas[p]):
-                        scale[p] = math.sqrt(alphas[p])
-            eng.set_factors(*stacked(scale))
+            alphas = [dot / whwh if whwh > 0 else None for dot, whwh in eng.hals_stack_terms()]
+            eng.set_factors(*stacked(alphas))
         hals_stack.last_alpha = alphas
         logging.info('Entering Main Loop.')
         done, rules = 0, [0] * len(ks)
@@ -205,26 +215,16 @@ def hals(x, k, *, distance_type='eu', sweeps=1, rescale_start=True, lambda_w=0, 
          max_iter=1000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
          device=0, engine=None):
     experiment = Experiment('hals', k, distance_type, nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
-    _check(x, k, distance_type, sweeps, lambda_w, lambda_h)
-    dist = L.EU if distance_type == 'eu' else L.KL
+    dist = check_hals(x, k, distance_type, sweeps, lambda_w, lambda_h)
     init = utils.initial_factors(x, k, nndsvd_init, uniform=True, defer_device=True)
     with Engine.for_data(x, k, device=device, engine=engine) as eng:
         w0, h0 = utils.device_initial_factors(eng, x, k, nndsvd_init, init)
         alpha = start_scale(eng, w0, h0) if rescale_start else None
-        if alpha is not None and alpha > 0 and math.isfinite(alpha):
-            w0, h0 = np.asarray(w0, dtype=np.float64) * math.sqrt(alpha), np.asarray(h0, dtype=np.float64) * math.sqrt(alpha)
         hals.last_alpha = alpha
-        eng.set_factors(w0, h0)
+        eng.set_factors(*scaled_start(alpha, w0, h0))
         eng.anls_set_distance(dist)
-        referee = None
-        if distance_type == 'eu':                   # the stop rule refereed in float64 near the stop (nmf_amd._driver.Referee)
-            referee = Referee(eng, lambda i: eng.hals_run(lambda_w, lambda_h, sweeps, NEVER, tol1, tol2, i, 1), min_iter, tol1, tol2)
-        hals.last_referee = referee
-        i, history = drive(
-            eng,
-            lambda first, count: eng.hals_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
-            lambda done: eng.aoadmm_finish(NEVER if referee is not None and referee.walked else min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=referee)
+        (i, history), _ = run_least_squares(hals, eng, eng.hals_run, (lambda_w, lambda_h, sweeps), distance_type,
+                                            min_iter, max_iter, tol1, tol2)
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
 
@@ -233,13 +233,7 @@ def _check_sparse(x, k, sweeps, lambda_w, lambda_h):
     """Every refusal of hals_sparse but the one of the stored values, before any device work and before any RNG draw."""
     if not sparse.is_sparse(x):
         raise TypeError('hals_sparse: x must be a scipy.sparse matrix; use hals')
-    if not isinstance(k, numbers.Integral) or isinstance(k, bool) or k < 1 or k > MAX_K:
-        raise ValueError(f'hals_sparse: supports 1 <= k <= {MAX_K} components (got k = {k!r})')
-    if not isinstance(sweeps, numbers.Integral) or isinstance(sweeps, bool) or not 1 <= sweeps <= MAX_SWEEPS:
-        raise ValueError(f'hals_sparse: sweeps must be an integer between 1 and {MAX_SWEEPS} (got sweeps = {sweeps!r})')
-    for name, lam in (('lambda_w', lambda_w), ('lambda_h', lambda_h)):
-        if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not lam >= 0:
-            raise ValueError(f'hals_sparse: {name} must be non-negative (got {name} = {lam!r})')
+    check_args('hals_sparse', k=k, sweeps=sweeps, lambda_w=lambda_w, lambda_h=lambda_h, real_lambdas=True)
 
 
 def hals_sparse(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10, max_iter=1000, tol1=1e-3,
@@ -260,10 +254,8 @@ def hals_sparse(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, m
     w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
     with Engine.for_sparse(xs, k, device=device) as eng:
         alpha = start_scale(eng, w0, h0) if rescale_start else None
-        if alpha is not None and alpha > 0 and math.isfinite(alpha):
-            w0, h0 = np.asarray(w0, dtype=np.float64) * math.sqrt(alpha), np.asarray(h0, dtype=np.float64) * math.sqrt(alpha)
         hals_sparse.last_alpha = alpha
-        eng.set_factors(w0, h0)
+        eng.set_factors(*scaled_start(alpha, w0, h0))
         i, history = drive(
             eng,
             lambda first, count: eng.hals_sparse_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),

@@ -17,7 +17,11 @@ operator, and once without it), AO-ADMM in exact f32, with prox 'l1inf', with th
 phase_w_repair), and the Euclidean AO-ADMM once at k = 520 on a 640 x 576 problem (more than 512 padded components).  The
 refusal sections make the refused calls: every compute entry point without V, without factors, with weights present, with ARD
 set, with NMFX_BETA, behind another solver family, with two refusals applying at once, and -- one at a time -- between
-the calls of a MUR-KL run and of an AO-ADMM run.
+the calls of a MUR-KL run and of an AO-ADMM run.  Last (hals_sections) the least-squares family behind ANLS: HALS runs at
+sweeps 1 and 3 in both arithmetic modes with a change of the reported distance; stacked HALS at k = 40 and k = 100 (a stack that
+fills the handle and one of ranks 3, 5, 8 that leaves components unowned) through set, terms, runs with differing lambdas, finish
+and the per-problem getters; sparse HALS; and the hals entry points refused: without V, without a stack, behind another family,
+with j < 0, sweeps = 0, sweeps = 17, a negative lambda.
 
 Two builds that print the same lines keep and void the same things and refuse in the same order: the file is what a change of
 the host code between the ABI and the kernels that is meant to change nothing is checked against.  The script uses
@@ -565,6 +569,124 @@ def between_sections(k, v, w0, h0):
     dense("between/aoadmm", k, v, w0, h0, ao_run)
 
 
+# ---- the least-squares family behind ANLS: HALS, stacked HALS, sparse HALS ---------------------------------------------------------
+def hals_sections(k, v, w0, h0):
+    """HALS runs in both arithmetic modes with a change of the reported distance; stacks at this rank (one with ranks that leave
+    components unowned) through set / terms / runs with differing lambdas / finish and the per-problem getters; sparse HALS;
+    and what the hals entry points refuse."""
+    import scipy.sparse as sp
+    from nmf_amd import _lib as L
+    from nmf_amd import sparse
+    from nmf_amd.engine import Engine
+    T = (NEVER, 1e-3, 1e-3)
+    for f32 in (False, True):
+        tag = "-f32" if f32 else ""
+        for sweeps in (1, 3):
+            def run(s, e):
+                if f32:
+                    s.step("set_precision f32", lambda: e.set_precision("f32"))
+                s.step("run 0..1", lambda: e.hals_run(0.0, 0.01, sweeps, *T, 0, 2))
+                s.step("set_distance kl", lambda: e.anls_set_distance(L.KL))
+                s.step("run 2..3", lambda: e.hals_run(0.0, 0.01, sweeps, *T, 2, 2))
+                s.step("set_distance eu", lambda: e.anls_set_distance(L.EU))
+                s.step("run 4", lambda: e.hals_run(0.02, 0.0, 4 - sweeps, *T, 4, 1))
+                s.step("run 5..6", lambda: e.hals_run(0.0, 0.01, sweeps, *T, 5, 2))
+                s.step("finish 7", lambda: e.aoadmm_finish(*T, 7))
+            dense(f"hals/s{sweeps}{tag}", k, v, w0, h0, run)
+
+        for name, ks in (("hals_stack/part", (3, 5, 8)), ("hals_stack/full", (k // 4, k // 2, k - k // 4 - k // 2))):
+            def stack(s, e):
+                P = range(len(ks))
+                lam = lambda a: [a * (p + 1) for p in P]
+
+                def problems(label):
+                    for p in P:
+                        rule, stop_i, n_obj = e.hals_stack_state(p)
+                        wp, hp = e.hals_stack_get_factors(p)
+                        s.line(f"  {label} p={p}", f"W={sha(wp)} H={sha(hp)} obj={sha(e.hals_stack_objectives(p, 0, n_obj))} "
+                                                    f"n={n_obj} rule={rule} stop_i={stop_i}")
+                if f32:
+                    s.step("set_precision f32", lambda: e.set_precision("f32"))
+                s.step("set", lambda: e.hals_stack_set(ks))
+                s.step("terms", lambda: s.line("  terms", sha(e.hals_stack_terms())))
+                s.step("run 0..1", lambda: e.hals_stack_run(lam(0.0), lam(0.01), 1, *T, 0, 2))
+                problems("run 0..1")
+                s.step("run 2..3", lambda: e.hals_stack_run(lam(0.02), lam(0.0), 3, *T, 2, 2))
+                problems("run 2..3")
+                s.step("terms", lambda: s.line("  terms", sha(e.hals_stack_terms())))
+                s.step("run 4..7 rule on", lambda: e.hals_stack_run(lam(0.02), lam(0.0), 1, 0, 1e-3, 1e-3 * 10.0 ** 6, 4, 4))
+                problems("run 4..7")
+                s.step("finish 8", lambda: e.hals_stack_finish(*T, 8))
+                problems("finish 8")
+            if k <= 128:
+                dense(f"{name}{tag}", k, v, w0, h0, stack)
+
+    if k <= 128 and not (ONLY and ONLY not in "hals_sparse"):
+        x = sp.csr_matrix(np.where(np.random.default_rng(9000 + k).random(v.shape) < 0.3, v, 0).astype(np.float64))
+        with Engine.for_sparse(sparse.normalise(x, k), k) as e:
+            s = Section(f"hals_sparse k={k}", e)
+            e.set_factors(w0, h0)
+            s.step("run 0..1", lambda: e.hals_sparse_run(0.0, 0.01, 1, *T, 0, 2))
+            s.step("run 2..3", lambda: e.hals_sparse_run(0.02, 0.0, 3, *T, 2, 2))
+            s.step("finish 4", lambda: e.hals_sparse_finish(*T, 4))
+            s.step("hals_run on it", lambda: e.hals_run(0.0, 0.0, 1, *T, 4, 1))
+            hals_refusals(s, L.require_gpu(), e.h, "sparse", ("hals_sparse_run", "hals_sparse_finish"), accepted_ok=False)
+
+    if ONLY and ONLY not in "refusals":
+        return
+    lib = L.require_gpu()
+    stack_calls = ("hals_stack_terms", "hals_stack_run", "hals_stack_finish")
+    dense_calls = ("hals_run",) + stack_calls + ("hals_sparse_run", "hals_sparse_finish")
+    with Engine(M, N, k) as e:
+        s = Section(f"refusals/hals k={k}", e)
+        hals_refusals(s, lib, e.h, "no V", dense_calls)
+        e.upload_v(v)
+        e.set_factors(w0, h0)
+        hals_refusals(s, lib, e.h, "no stack", dense_calls, accepted_ok=False)
+        if k > 128:
+            return
+        s.step("set", lambda: e.hals_stack_set((3, 5, 8)))
+        hals_refusals(s, lib, e.h, "stack set", stack_calls, accepted_ok=False)
+        s.step("set_factors", lambda: e.set_factors(w0, h0))
+        s.step("kl run 0..1", lambda: e.mur_run(L.KL, 0.01, 0.02, NEVER, 1e-5, 1e-5, 0, 2))
+        s.step("set behind mur", lambda: e.hals_stack_set((3, 5, 8)))
+        hals_refusals(s, lib, e.h, "behind mur", dense_calls)
+        s.step("set_factors", lambda: e.set_factors(w0, h0))
+        s.step("stack run 0", lambda: e.hals_stack_run([0.0] * 3, [0.0] * 3, 1, *T, 0, 1))
+        hals_refusals(s, lib, e.h, "behind the stack", ("hals_run",))
+        refuse(s, lib, e.h, ["mur", "ao", "admm", "anls"], L.EU, 1, "behind the stack")
+        s.step("set_factors", lambda: e.set_factors(w0, h0))
+        s.step("hals run 0", lambda: e.hals_run(0.0, 0.0, 1, *T, 0, 1))
+        hals_refusals(s, lib, e.h, "behind hals", stack_calls)
+        refuse(s, lib, e.h, ["mur", "ao", "admm", "anls"], L.EU, 1, "behind hals")
+        hals_refusals(s, lib, e.h, "hals", ("hals_run",), accepted_ok=False)
+
+
+def hals_refusals(s, lib, h, tag, names, accepted_ok=True):
+    """The hals entry points `names` as raw ABI calls: as they should be called (accepted_ok=False: that call is left out, the
+    handle would take it), then with j < 0, sweeps = 0 (terms: out = NULL), sweeps = 17, a negative lambda, no lambdas, and with two
+    of these at once.  An entry point that does not take the argument in question accepts the call; the line says so."""
+    T = (NEVER, 0.0, 0.0)
+    out = (C.c_double * 256)()
+    lam = lambda a: (C.c_double * 128)(*([a] * 128))
+    table = {
+        "hals_run": lambda j, sw, a: lib.nmfx_hals_run(h, a, 0.0, sw, *T, j, 1),
+        "hals_sparse_run": lambda j, sw, a: lib.nmfx_hals_sparse_run(h, 0.0, a, sw, *T, j, 1),
+        "hals_sparse_finish": lambda j, sw, a: lib.nmfx_hals_sparse_finish(h, *T, j),
+        "hals_stack_terms": lambda j, sw, a: lib.nmfx_hals_stack_terms(h, out if sw else None),
+        "hals_stack_run": lambda j, sw, a: lib.nmfx_hals_stack_run(h, lam(0.0), lam(a) if a > -1 else None, sw, *T, j, 1),
+        "hals_stack_finish": lambda j, sw, a: lib.nmfx_hals_stack_finish(h, *T, j),
+    }
+    cases = (("", 1, 1, 0.0), ("j<0", -1, 1, 0.0), ("sweeps=0", 1, 0, 0.0), ("sweeps=17", 1, 17, 0.0), ("lambda<0", 1, 1, -0.5),
+             ("lambda NULL", 1, 1, -2.0), ("sweeps=0, j<0", -1, 0, 0.0), ("sweeps=17, lambda<0", 1, 17, -0.5), ("j<0, lambda<0", -1, 1, -0.5))
+    for name in names:
+        for what, j, sw, a in cases:
+            if what or accepted_ok:
+                s.line(f"{tag} {name} {what}".rstrip(), refused(lib, h, table[name](j, sw, a)))
+    st = s.eng.state()
+    s.line(f"{tag} state", f"rule={st[0]} n_obj={st[2]}")
+
+
 def main():
     global LINES
     if "--fold" in sys.argv:
@@ -588,6 +710,10 @@ def main():
     v, w0, h0, om, mask = make_inputs(520, seed=5520, shape=(640, 576), scale=0.06)
     admm_family_sections(520, v, w0, h0, losses=("eu",))
     admm_family_sections(520, v, w0, h0, f32=True, losses=("eu",))
+    # (behind everything above) HALS on the products of ANLS: runs, stacks, sparse input, refusals
+    for k in RANKS:
+        v, w0, h0, om, mask = make_inputs(k, seed=5000 + k)
+        hals_sections(k, v, w0, h0)
     if LINES is not None:
         fold(LINES)
 

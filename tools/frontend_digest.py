@@ -1,4 +1,4 @@
-"""Digest of what the MUR front ends return through the public API: one SHA-256 per call.
+"""Digest of what the MUR and least-squares front ends return through the public API: one SHA-256 per call.
 
     python tools/frontend_digest.py > digest.txt
 
@@ -9,12 +9,17 @@ case runs twice: max_iter=5, where nothing stops, and min_iter=2, max_iter=200, 
 tested index and the history is trimmed.  The cases are dense 'eu' (one on negative data), 'kl', 'is' and 'beta' at
 beta = -1, 0.5, 2.5, each of them with weights=, mask= with 'eu', 'kl', 'is', scipy.sparse x with 'eu', 'kl', mur_pair,
 mur_ard and transform for all four losses, with and without weights= and h0=, on three shapes at which the padding arms
-differ; the NNDSVD starts run on the middle shape.  An exception is hashed as its class and message.
+differ; the NNDSVD starts run on the middle shape.  An exception is hashed as its class and message.  Behind them the
+least-squares part, on the same shapes with the same two stops: anls and hals with 'eu' and 'kl', hals with sweeps=2,
+rescale_start=False and lambdas, hals_sparse, hals_stack with three problems, factorize_grid(x, 'hals') on a 2 x 2 grid and
+NMF(x, k).factorize('hals') on dense and sparse x; there the hash also covers last_alpha, last_would_arm and the referee's
+walked / confirmed / final_rule.
 
 Two commits that print the same lines hand the library the same inputs in the same order and return what it computed
 unchanged: the file is what a change of the Python in front of the kernels that is meant to change nothing is checked
-against.  The script imports nmf_amd.mur.mur, mur_pair, nmf_amd.ard.mur_ard and nmf_amd.transform.transform only, so it
-runs unmodified in a checkout of another commit; all cases run in one process."""
+against.  The script imports nmf_amd.mur.mur, mur_pair, nmf_amd.ard.mur_ard, nmf_amd.transform.transform, nmf_amd.anls.anls,
+nmf_amd.hals.hals, hals_sparse, hals_stack, nmf_amd.grid.factorize_grid and nmf_amd.nmf.NMF only, so it runs unmodified in a
+checkout of another commit; all cases run in one process."""
 import contextlib
 import hashlib
 import io
@@ -88,6 +93,54 @@ def cases(m, n, k, nndsvd):
     return out
 
 
+def ls_cases(m, n, k, nndsvd):
+    """The least-squares part: (name, call, x, positional arguments, keywords, diagnostics); `diagnostics()` is what the front
+    end left on itself (last_alpha, last_would_arm, the referee's counters), hashed with the result."""
+    from nmf_amd.anls import anls
+    from nmf_amd.grid import factorize_grid
+    from nmf_amd.hals import hals, hals_sparse, hals_stack
+    from nmf_amd.nmf import NMF
+    x, om, mask, w, h0 = make_inputs(m, n, k, seed=4000 + k)
+    xs = sp.csr_matrix(np.where(mask, x, 0.0))
+    stack = [dict(k=max(1, k // 4)), dict(k=max(1, k // 2), lambda_w=0.05), dict(k=max(1, k // 8), lambda_w=0.01, lambda_h=0.1)]
+
+    def referee(fn):
+        r = getattr(fn, 'last_referee', None)
+        return None if r is None else (r.walked, r.confirmed, r.final_rule)
+
+    def grid(x, ks, **kw):
+        return [r for _, r in factorize_grid(x, 'hals', features=ks, lambda_w=(0.0, 0.05), lambda_h=(0.02,), **kw)]
+
+    def nmf_hals(x, k, **kw):
+        nmf = NMF(x, k)
+        nmf.factorize('hals', **kw)
+        return nmf.results
+    of_hals = lambda: (getattr(hals, 'last_alpha', None), referee(hals))
+    of_sparse = lambda: getattr(hals_sparse, 'last_alpha', None)
+    of_stack = lambda: (getattr(hals_stack, 'last_alpha', None), getattr(hals_stack, 'last_would_arm', None))
+    out = []
+    if nndsvd:
+        out += [('anls eu', anls, x, (k,), {}, lambda: referee(anls)),
+                ('hals eu', hals, x, (k,), {}, of_hals),
+                ('hals_sparse', hals_sparse, xs, (k,), {}, of_sparse),
+                ('hals_stack', hals_stack, x, (stack,), {}, of_stack)]
+        return [('nndsvd ' + name, fn, xx, args, kw, diag) for name, fn, xx, args, kw, diag in out]
+    rand = dict(nndsvd_init=(False, 'zero'))
+    for loss in ('eu', 'kl'):
+        out.append((f'anls {loss}', anls, x, (k,), dict(rand, distance_type=loss, lambda_h=0.05), lambda: referee(anls)))
+        out.append((f'hals {loss}', hals, x, (k,), dict(rand, distance_type=loss, lambda_w=0.05), of_hals))
+    out.append(('hals sweeps=2', hals, x, (k,), dict(rand, sweeps=2), of_hals))
+    out.append(('hals no rescale', hals, x, (k,), dict(rand, rescale_start=False, lambda_w=0.02, lambda_h=0.05), of_hals))
+    out.append(('hals_sparse', hals_sparse, xs, (k,), dict(rand, lambda_h=0.05), of_sparse))
+    out.append(('hals_sparse sweeps=2', hals_sparse, xs, (k,), dict(rand, sweeps=2, rescale_start=False), of_sparse))
+    out.append(('hals_stack', hals_stack, x, (stack,), dict(rand), of_stack))
+    out.append(('hals_stack sweeps=2', hals_stack, x, (stack,), dict(rand, sweeps=2, rescale_start=False), of_stack))
+    out.append(('grid hals', grid, x, ((max(1, k // 2), k),), dict(rand), lambda: (of_hals(), of_stack())))
+    out.append(('NMF hals', nmf_hals, x, (k,), dict(rand), of_hals))
+    out.append(('NMF hals sparse', nmf_hals, xs, (k,), dict(rand), of_sparse))
+    return out
+
+
 def as_bytes(v):
     if sp.issparse(v):
         return v.data.tobytes() + v.indices.tobytes() + v.indptr.tobytes()
@@ -96,7 +149,7 @@ def as_bytes(v):
     return repr(v).encode()
 
 
-def digest(fn, x, args, kw, seed):
+def digest(fn, x, args, kw, seed, diagnostics=None):
     """One call on a private copy of x, everything observable hashed."""
     x = x.copy()
     np.random.seed(seed)
@@ -110,6 +163,8 @@ def digest(fn, x, args, kw, seed):
     except Exception as e:  # noqa: BLE001  (a refusal is an outcome like any other)
         parts, note = [type(e).__name__.encode(), str(e).encode()], f'{type(e).__name__}: {e}'
     parts += [printed.getvalue().encode(), as_bytes(x), np.random.get_state()[1].tobytes()]
+    if diagnostics is not None:
+        parts.append(repr(diagnostics()).encode())
     sha = hashlib.sha256()
     for p in parts:
         sha.update(len(p).to_bytes(8, 'little') + p)
@@ -122,6 +177,12 @@ def main():
             for c, (name, fn, x, args, kw) in enumerate(cases(m, n, k, nndsvd)):
                 for s, (stop, stop_kw) in enumerate(STOPS):
                     sha, note = digest(fn, x, args, {**kw, **stop_kw}, seed=100 * c + s)
+                    print(f'{name:<22} {m}x{n} k={k} {stop:<4}  {sha}  {note}', flush=True)
+    for nndsvd, shapes in ((False, SHAPES), (True, [NNDSVD_SHAPE])):             # (behind the lines above, which stay where they were)
+        for m, n, k in shapes:
+            for c, (name, fn, x, args, kw, diag) in enumerate(ls_cases(m, n, k, nndsvd)):
+                for s, (stop, stop_kw) in enumerate(STOPS):
+                    sha, note = digest(fn, x, args, {**kw, **stop_kw}, seed=100 * c + s, diagnostics=diag)
                     print(f'{name:<22} {m}x{n} k={k} {stop:<4}  {sha}  {note}', flush=True)
 
 
