@@ -166,7 +166,7 @@ int nmfx_get_relevance(nmfx_handle_t h, double* lambda_out /* k */);
  * nmfx_get_objectives, nmfx_objective_f64, nmfx_set_stop_guard, nmfx_resume, nmfx_synchronize, nmfx_set_stream
  * (and nmfx_reset_stream, nmfx_destroy, nmfx_last_error, nmfx_get_note; from version 391 nmfx_profile_enable,
  * nmfx_profile_get and nmfx_profile_reset, which count the sp_* scopes, and nmfx_hals_sparse_run / _finish on an unmasked
- * handle with k <= 128).  The objective is recorded in f64 from the non-zeros plus k x k terms ("Sparse V").
+ * handle with k <= 128; from version 392 nmfx_hals_masked_run / _finish on a masked handle with k <= 64).  The objective is recorded in f64 from the non-zeros plus k x k terms ("Sparse V").
  * Every other entry point returns NMFX_E_ARG and launches nothing. */
 int nmfx_create_csr(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k, int64_t nnz);
 int nmfx_upload_csr(nmfx_handle_t h, const int64_t* row_ptr, const int32_t* col_idx, const void* values, int dtype);
@@ -528,6 +528,24 @@ int nmfx_hals_sparse_run(nmfx_handle_t h, double lambda_w, double lambda_h, int 
                          int64_t min_iter, double tol1, double tol2,
                          int64_t first, int64_t count);
 int nmfx_hals_sparse_finish(nmfx_handle_t h, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
+
+/* ---- HALS on masked handles (version 392) ----------------------------------------------------------------------------------
+ * The same outer iteration on a masked handle (nmfx_set_masked) with k <= 64: only the stored entries are part of the fit,
+ * so every row of W / column of H is swept on a system of its own,
+ *     G = Sum_{e in Omega} f_e f_e^T + 2 lambda I,    r = Sum_{e in Omega} v_e f_e,
+ * Omega the observed set of that row or column and f_e the gathered row of the other factor (for the H half-step the W just
+ * updated).  A stored zero is data: it adds to G and not to r.  A component with G_jj = 0 keeps its value (with lambda = 0:
+ * every component of a row with no observed entry, and a dead component).  One launch per half-step forms G and r on the f32
+ * MFMA pipe and sweeps (plus one for the rows longer than a piece); a third pass sums the recorded objective
+ * 1/2 Sum_Omega (v - wh)^2 per entry in f64.  Records, stop rule, the flag and nmfx_hals_masked_finish as the
+ * nmfx_hals_sparse_* pair.  Two runs give the same bits.
+ * NMFX_E_ARG with a message, nothing launched: a dense handle, an unmasked handle ("masked handle"), k padded beyond 64,
+ * sweeps outside 1 .. 16, a negative lambda or range.  HALS family: NMFX_E_STATE when continuing another solver's run
+ * without nmfx_set_factors.  nmfx_hals_sparse_* and nmfx_hals_run go on refusing masked handles.                          */
+int nmfx_hals_masked_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
+                         int64_t min_iter, double tol1, double tol2,
+                         int64_t first, int64_t count);
+int nmfx_hals_masked_finish(nmfx_handle_t h, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
 
 /* ---- stacked HALS (version 390)------------------------------------------------------------------------------------------
  * MANY least-squares factorizations of the same V in one pass over it: P problems sit side by side in the factor columns,

@@ -1,4 +1,4 @@
-// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.  (HALS on the same handle: the last section.)
+// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.  (HALS on the same handle: the last two sections.)
 //
 // Layout.  Both factors are row-major along their long dimension: W [m][kp] (double buffered, E->W) and H^T [n][kp]
 // (nmfx_sparse::Ht), kp in {4, 8, 16, 32, 64, 128, 256}.  V is held twice: CSR (the W phase walks rows of V and gathers
@@ -42,7 +42,7 @@
 #define SP_WAVES 8            // waves per block of the phase kernels
 
 struct SpUnit { long long beg; int row; int len; int slot; int pad; };   // slot -1: a whole row; else the piece's slab row
-struct SpLong { int row; int slot0; int npieces; int pad; };            // a row split into pieces [slot0, slot0 + npieces)
+struct SpLong { int row; int slot0; int npieces; int unit0; };          // a row split into pieces [slot0, slot0 + npieces): the units [unit0, unit0 + npieces)
 
 struct SpSide {               // one orientation of V: 0 = CSR (W phase), 1 = CSC (H phase)
     int64_t rows = 0;
@@ -488,7 +488,7 @@ static int build_side(nmfx_engine* E, SpSide& sd, const int64_t* ptr) {
         const int64_t b = ptr[r], len = ptr[r + 1] - ptr[r];
         if (len <= SP_CHUNK) { units.push_back({(long long)b, (int)r, (int)len, -1, 0}); continue; }
         const int np = (int)((len + SP_CHUNK - 1) / SP_CHUNK);
-        longs.push_back({(int)r, slot, np, 0});
+        longs.push_back({(int)r, slot, np, (int)units.size()});
         for (int p = 0; p < np; ++p)
             units.push_back({(long long)(b + (int64_t)p * SP_CHUNK), (int)r, (int)std::min<int64_t>(SP_CHUNK, len - (int64_t)p * SP_CHUNK), slot + p, 0});
         slot += np;
@@ -1096,6 +1096,299 @@ extern "C" int nmfx_hals_sparse_run(nmfx_handle_t E, double lambda_w, double lam
 // does not exist yet (no iteration has run).
 extern "C" int nmfx_hals_sparse_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
     int rc = sp_hals_ready(E, "nmfx_hals_sparse_finish", 1, 0.0, 0.0, iters_done, 0); if (rc) return rc;
+    DevState hs;
+    NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    if (hs.flag || hs.n_obj > iters_done) return NMFX_OK;
+    if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+    return launch_objective(E, NMFX_EU, E->xf64, true, iters_done, min_iter, tol1, tol2);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// HALS on a masked handle (nmfx_hals_masked_run)
+// ---------------------------------------------------------------------------------------------------------------------
+// With entries missing the owned rows no longer share one Gram matrix: row i of W sees only the columns observed in that row,
+//     G = Sum_{e in Omega} f_e f_e^T + 2 lambda I,    r = Sum_{e in Omega} v_e f_e      (f_e: the gathered row of the other factor)
+// and a half-step is the sweep of sp_hals_row on every row's own (G, r).  One wave forms G on the f32 MFMA pipe
+// (v_mfma_f32_16x16x4_f32, exact f32): a step takes four observed entries, lane l holds NB = max(1, KP / 16) consecutive
+// components NB (l & 15) + b of entry l >> 4 (one load of NB floats), and operand b against operand b' accumulates the 16 x 16
+// block of G whose rows are the components NB i + b and columns NB j + b' -- a permutation of G that is undone when the block
+// is written to LDS.  Only b <= b' is computed (NB (NB + 1) / 2 accumulators of 4 VGPRs: 10 at KP = 64) and mirrored on the
+// way out; the diagonal blocks are symmetric bit for bit (the same products in the same order).  KP = 4 and 8 use one block
+// with the lanes past KP holding zeros.  A slot past the row's end holds zero operands (not only a zero value).  r is summed
+// with plain FMAs next to it, per entry slot, and the four slots are added by a fixed butterfly.
+//
+// G (then 2 lambda on the diagonal of the first k components, in f32) and r go to a wave-private LDS region of KP x KP + KP
+// floats and the wave runs the sweep of sparse HALS on it, unchanged.  The unit loop has a different trip count per wave, so
+// there is no block barrier in it: the hand-off between the lanes of one wave is ordered by a wavefront-scope fence.
+//
+// Rows longer than a piece (SP_CHUNK entries): the phase kernel skips piece units, and sp_mhals_long_kernel takes one
+// workgroup per long row (a blockIdx-strided loop: block-uniform, so block barriers are legal there).  Wave w sums the pieces
+// w, w + MW, ... in registers and writes its [G | r] to an LDS region of its own; the block adds the regions in wave order,
+// and wave 0 sweeps.  No slab of k^2 floats per piece, no atomics: two runs give the same bits.
+template <int KP> struct MhCfg {
+    static constexpr int NB = KP >= 16 ? KP / 16 : 1;          // 16-wide operand blocks
+    static constexpr int NACC = NB * (NB + 1) / 2;             // blocks on and above the diagonal
+    static constexpr int MW = KP >= 64 ? 4 : 8;                // waves per block: (KP^2 + KP) floats of LDS each (65 KiB at KP = 64)
+    static constexpr int REGION = KP * KP + KP;                // [G | r]
+};
+typedef float mh_f4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void mh_wave_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// [G | r] of the entries [beg, beg + len) of one row, added to acc / racc (this lane's share: the header).  Blocks of 16
+// entries (four MFMA steps), software-pipelined: while block b is multiplied, the rows of block b + 1 and the indices and
+// values of block b + 2 are in flight (a gather is two dependent loads, and 40 MFMAs do not cover both).
+template <int KP>
+__device__ __forceinline__ void mh_accumulate(long long beg, int len, const int32_t* __restrict__ idx, const float* __restrict__ val,
+                                              const float* __restrict__ Other, mh_f4 (&acc)[MhCfg<KP>::NACC], float (&racc)[MhCfg<KP>::NB], int lane)
+{
+    constexpr int NB = MhCfg<KP>::NB;
+    const int slot = lane >> 4, c0 = NB * (lane & 15);
+    const bool holds = c0 < KP;                                 // (KP = 4, 8: the lanes past KP hold zeros)
+    const long long end = beg + len;
+    if (len <= 0) return;
+    // indices and values of the block at e0; a slot past the end reads nothing: row 0 with value 0
+    auto load_cx = [&](long long e0, int (&c)[4], float (&x)[4]) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const long long e = e0 + 4 * t + slot;
+            const bool ok = e < end;
+            c[t] = ok ? idx[e] : 0;
+            x[t] = ok ? val[e] : 0.f;
+        }
+    };
+    auto load_f = [&](const int (&c)[4], float (&f)[4][NB]) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float* src = Other + (int64_t)c[t] * KP + (holds ? c0 : 0);
+            if constexpr (NB == 4) {
+                const float4 v = *reinterpret_cast<const float4*>(src);
+                f[t][0] = v.x; f[t][1] = v.y; f[t][2] = v.z; f[t][3] = v.w;
+            } else if constexpr (NB == 2) {
+                const float2 v = *reinterpret_cast<const float2*>(src);
+                f[t][0] = v.x; f[t][1] = v.y;
+            } else {
+                f[t][0] = *src;
+            }
+        }
+    };
+    auto multiply = [&](long long e0, float (&f)[4][NB], const float (&x)[4]) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool ok = e0 + 4 * t + slot < end;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                f[t][b] = (ok && holds) ? f[t][b] : 0.f;        // a slot past the end gathered row 0: a zero operand
+                racc[b] = fmaf(x[t], f[t][b], racc[b]);
+            }
+            int a = 0;
+#pragma unroll
+            for (int ba = 0; ba < NB; ++ba) {
+#pragma unroll
+                for (int bb = ba; bb < NB; ++bb, ++a) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[t][ba], f[t][bb], acc[a], 0, 0, 0);
+            }
+        }
+    };
+    int cA[4], cB[4], cC[4], cD[4]; float xA[4], xB[4], xC[4], xD[4]; float fA[4][NB], fB[4][NB];
+    load_cx(beg, cA, xA);
+    load_f(cA, fA);
+    load_cx(beg + 16, cB, xB);
+    for (long long e0 = beg; e0 < end; e0 += 32) {             // (wave-uniform bounds)
+        load_f(cB, fB);
+        load_cx(e0 + 32, cC, xC);
+        multiply(e0, fA, xA);
+        if (e0 + 16 >= end) break;
+        load_f(cC, fA);
+        load_cx(e0 + 48, cD, xD);
+        multiply(e0 + 16, fB, xB);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { xA[t] = xC[t]; cB[t] = cD[t]; xB[t] = xD[t]; }
+    }
+}
+
+// This lane's share of [G | r] into the LDS region, mirrored; r after the butterfly over the four entry slots.  Every element
+// of the region is written by exactly one lane.
+template <int KP>
+__device__ __forceinline__ void mh_deposit(float* gs, const mh_f4 (&acc)[MhCfg<KP>::NACC], const float (&racc)[MhCfg<KP>::NB], int lane) {
+    constexpr int NB = MhCfg<KP>::NB;
+    const int j = lane & 15, i0 = 4 * (lane >> 4);
+    int a = 0;
+#pragma unroll
+    for (int ba = 0; ba < NB; ++ba) {
+#pragma unroll
+        for (int bb = ba; bb < NB; ++bb, ++a) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int row = NB * (i0 + v) + ba, col = NB * j + bb;
+                if (row < KP && col < KP) {
+                    const float g = acc[a][v];
+                    gs[row * KP + col] = g;
+                    if (ba != bb) gs[col * KP + row] = g;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        float r = racc[b];
+        r += __shfl_xor(r, 16, 64);
+        r += __shfl_xor(r, 32, 64);
+        const int c = NB * j + b;
+        if (lane < 16 && c < KP) gs[KP * KP + c] = r;
+    }
+}
+
+// The region holds the row's summed [G | r]: 2 lambda on the diagonal of the first k components, then the sweep of sparse
+// HALS from the row's current values; group 0 writes the row in place.  Called by every lane of ONE wave.
+template <int KP>
+__device__ __forceinline__ void mh_sweep_row(float* gs, float diag_add, float* row, int k, int sweeps, int lane) {
+    constexpr int G = KP / 4;
+    const int lig = lane % G, grp = lane / G;
+    mh_wave_fence();
+    if (lane < k) gs[lane * KP + lane] += diag_add;             // (k <= KP <= 64)
+    mh_wave_fence();
+    float inv[4]; bool live[4];
+    sp_hals_diag<KP>(gs, k, lig, inv, live);
+    const float4 r4 = *reinterpret_cast<const float4*>(gs + KP * KP + lig * 4);
+    const float r[4] = {r4.x, r4.y, r4.z, r4.w};
+    sp_hals_row<KP, false, float>(gs, inv, live, r, row, k, sweeps, lig, grp);
+    mh_wave_fence();                                            // (the next row's [G | r] overwrites the region)
+}
+
+//   Own [rows][KP]: the factor being updated, in place (a row is owned by one wave; the gathers read the other factor only);
+//   Other [*][KP]: the factor gathered per observed entry; diag_add = (float)(2 lambda).
+template <int KP>
+__global__ __launch_bounds__(64 * MhCfg<KP>::MW) void sp_mhals_phase_kernel(
+    const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
+    const float* __restrict__ Other, float* Own, float diag_add, int k, int sweeps, const int* flag)
+{
+    if (*flag) return;
+    constexpr int MW = MhCfg<KP>::MW, NB = MhCfg<KP>::NB, NACC = MhCfg<KP>::NACC;
+    __shared__ __attribute__((aligned(16))) float lds[MW * MhCfg<KP>::REGION];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* gs = lds + wave * MhCfg<KP>::REGION;
+    for (int64_t u = (int64_t)blockIdx.x * MW + wave; u < nunits; u += (int64_t)gridDim.x * MW) {      // (no block barrier in here)
+        const SpUnit U = units[u];
+        if (U.slot >= 0) continue;                              // a piece of a long row: sp_mhals_long_kernel (wave-uniform)
+        mh_f4 acc[NACC]; float racc[NB];
+#pragma unroll
+        for (int a = 0; a < NACC; ++a) acc[a] = mh_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < NB; ++b) racc[b] = 0.f;
+        mh_accumulate<KP>(U.beg, U.len, idx, val, Other, acc, racc, lane);
+        mh_deposit<KP>(gs, acc, racc, lane);
+        mh_sweep_row<KP>(gs, diag_add, Own + (int64_t)U.row * KP, k, sweeps, lane);
+    }
+}
+
+// One workgroup per long row; the pieces of row l are the units [unit0, unit0 + npieces).
+template <int KP>
+__global__ __launch_bounds__(64 * MhCfg<KP>::MW) void sp_mhals_long_kernel(
+    const SpLong* __restrict__ longs, int64_t nlong, const SpUnit* __restrict__ units, const int32_t* __restrict__ idx,
+    const float* __restrict__ val, const float* __restrict__ Other, float* Own, float diag_add, int k, int sweeps, const int* flag)
+{
+    if (*flag) return;
+    constexpr int MW = MhCfg<KP>::MW, NB = MhCfg<KP>::NB, NACC = MhCfg<KP>::NACC;
+    constexpr int REGION = MhCfg<KP>::REGION;
+    __shared__ __attribute__((aligned(16))) float gs[MW * REGION];      // region w: wave w's partial [G | r]; their sum lands in region 0
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t l = blockIdx.x; l < nlong; l += gridDim.x) {   // (block-uniform: the barriers below are reached by every wave)
+        const SpLong L = longs[l];
+        mh_f4 acc[NACC]; float racc[NB];
+#pragma unroll
+        for (int a = 0; a < NACC; ++a) acc[a] = mh_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < NB; ++b) racc[b] = 0.f;
+        for (int p = wave; p < L.npieces; p += MW) {
+            const SpUnit U = units[(int64_t)L.unit0 + p];
+            mh_accumulate<KP>(U.beg, U.len, idx, val, Other, acc, racc, lane);
+        }
+        mh_deposit<KP>(gs + wave * REGION, acc, racc, lane);
+        __syncthreads();
+        for (int i = threadIdx.x; i < REGION; i += 64 * MW) {   // the waves' partial sums, added in wave order
+            float sum = gs[i];
+#pragma unroll
+            for (int w = 1; w < MW; ++w) sum += gs[w * REGION + i];
+            gs[i] = sum;
+        }
+        __syncthreads();
+        if (wave == 0) mh_sweep_row<KP>(gs, diag_add, Own + (int64_t)L.row * KP, k, sweeps, lane);
+        __syncthreads();                                        // (the next row's deposit overwrites the region)
+    }
+}
+
+// one half-step: side 0 the W phase (own W, gather H^T), side 1 the H phase (own H^T, gather W)
+template <int KP>
+static int launch_mhals_phase(nmfx_engine* E, int side, float* Own, const float* Other, float diag_add, int sweeps) {
+    SpSide& sd = E->sp->side[side];
+    constexpr int MW = MhCfg<KP>::MW;
+    const int* flag = &E->state->flag;
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)(32 / MW) * E->ncu, (sd.nunits + MW - 1) / MW));
+    hipLaunchKernelGGL((sp_mhals_phase_kernel<KP>), dim3(nb), dim3(64 * MW), 0, E->stream, (const SpUnit*)sd.units, sd.nunits,
+                       (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, diag_add, E->k, sweeps, flag);
+    NMFX_HIP(hipGetLastError());
+    if (sd.nlong) {
+        const int nl = (int)std::min<int64_t>(4 * E->ncu, sd.nlong);
+        hipLaunchKernelGGL((sp_mhals_long_kernel<KP>), dim3(nl), dim3(64 * MW), 0, E->stream, (const SpLong*)sd.longs, sd.nlong,
+                           (const SpUnit*)sd.units, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, diag_add, E->k, sweeps, flag);
+        NMFX_HIP(hipGetLastError());
+    }
+    return NMFX_OK;
+}
+
+// Iteration j: W phase, H phase, the masked objective pass over the observed entries (f64 per entry), then obj[j + 1] of the
+// new pair and the stop rule for loop index j.  No Gram and no stats passes.  Once the rule has fired every launch returns at once.
+template <int KP>
+static int sp_mhals_iteration(nmfx_engine* E, double lw, double lh, int sweeps, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    nmfx_sparse* S = E->sp;
+    float* W = E->W[0];
+    int rc;
+    { ProfScope ps(E, "sp_mhals_wphase");
+      if ((rc = launch_mhals_phase<KP>(E, 0, W, S->Ht, (float)(2.0 * lw), sweeps))) return rc; }
+    { ProfScope ps(E, "sp_mhals_hphase");
+      if ((rc = launch_mhals_phase<KP>(E, 1, S->Ht, W, (float)(2.0 * lh), sweeps))) return rc; }
+    { ProfScope ps(E, "sp_mhals_objective");
+      if ((rc = sp_objective_pass<KP>(E, NMFX_EU, W, &E->state->flag))) return rc;
+      if ((rc = launch_objective(E, NMFX_EU, E->xf64, true, j + 1, min_iter, tol1, tol2))) return rc; }
+    return NMFX_OK;
+}
+
+// what both entry points refuse, nothing launched; then the guard (family HALS)
+static int sp_mhals_ready(nmfx_engine* E, const char* who, int sweeps, double lw, double lh, int64_t first, int64_t count) {
+    if (!E) return NMFX_E_ARG;
+    if (!E->sp) { E->err = std::string(who) + ": needs a sparse handle (nmfx_create_csr) made masked (nmfx_set_masked)"; return NMFX_E_ARG; }
+    if (!E->sp->masked) { E->err = std::string(who) + ": needs a masked handle (nmfx_set_masked); an unmasked sparse handle runs nmfx_hals_sparse_run"; return NMFX_E_ARG; }
+    if (E->kp > 64) { E->err = std::string(who) + ": not available with more than 64 components in this build"; return NMFX_E_ARG; }
+    nmfx_entry a = {NMFX_FAM_HALS, first, count, NMFX_D_NONE, NMFX_D_NONE};
+    a.bad = nmfx_hals_args_bad(who, sweeps, first, count, &lw, &lh);
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    E->run.in_place();
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_masked_run(nmfx_handle_t E, double lambda_w, double lambda_h, int sweeps, int64_t min_iter, double tol1,
+                                    double tol2, int64_t first, int64_t count) {
+    int rc = sp_mhals_ready(E, "nmfx_hals_masked_run", sweeps, lambda_w, lambda_h, first, count); if (rc) return rc;
+    if (first == 0 && count > 0) {                     // obj[0]: one objective-only pass over the start
+        if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+        if ((rc = launch_objective(E, NMFX_EU, E->xf64, true, 0, min_iter, tol1, tol2))) return rc;
+    }
+    for (int64_t j = first; j < first + count && !rc; ++j) {
+#define SP_IT(KP) sp_mhals_iteration<KP>(E, lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, j)
+        switch (E->kp) { case 4: rc = SP_IT(4); break; case 8: rc = SP_IT(8); break; case 16: rc = SP_IT(16); break;
+                         case 32: rc = SP_IT(32); break; default: rc = SP_IT(64); break; }
+#undef SP_IT
+    }
+    return rc;
+}
+
+// as nmfx_hals_sparse_finish: something to record only where obj[iters_done] does not exist yet
+extern "C" int nmfx_hals_masked_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
+    int rc = sp_mhals_ready(E, "nmfx_hals_masked_finish", 1, 0.0, 0.0, iters_done, 0); if (rc) return rc;
     DevState hs;
     NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));

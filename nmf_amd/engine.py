@@ -72,7 +72,7 @@ class Engine:
     @classmethod
     def for_sparse(cls, x, k, device=0, masked=False):
         """A fresh engine on sparse `x` (canonical CSR from nmf_amd.sparse.normalise), uploaded through nmfx_create_csr /
-        nmfx_upload_csr.  Runs MUR and, unmasked with k <= 128, sparse HALS (include/nmfx.h); usable as a context manager like any Engine.  masked=True: `x`
+        nmfx_upload_csr.  Runs MUR and, unmasked with k <= 128, sparse HALS, masked with k <= 64, masked HALS (include/nmfx.h); usable as a context manager like any Engine.  masked=True: `x`
         holds the observed entries (nmf_amd.masked.observed) and nmfx_set_masked is called before the upload."""
         from . import sparse
         row_ptr, col_idx, values = sparse.arrays(x)
@@ -398,6 +398,15 @@ class Engine:
 
     def hals_sparse_finish(self, min_iter, tol1, tol2, done):
         self._ck(self.lib.nmfx_hals_sparse_finish(self.h, int(min_iter), float(tol1), float(tol2), int(done)))
+
+    def hals_masked_run(self, lam_w, lam_h, sweeps, min_iter, tol1, tol2, first, count):
+        """`count` HALS iterations from iteration `first` on a masked engine (for_sparse(masked=True), k <= 64): every row of W /
+        column of H is swept on the Gram matrix of its own observed entries; records and stop rule as hals_sparse_run."""
+        self._ck(self.lib.nmfx_hals_masked_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
+                                               float(tol2), int(first), int(count)))
+
+    def hals_masked_finish(self, min_iter, tol1, tol2, done):
+        self._ck(self.lib.nmfx_hals_masked_finish(self.h, int(min_iter), float(tol1), float(tol2), int(done)))
 
     # -- stacked HALS: many problems side by side in the factor columns (include/nmfx.h) ---------
     def hals_stack_set(self, ks):

@@ -18,7 +18,17 @@ first W sweep clamp most of W to zero, and the run then needs many iterations to
 the same launch (csrc/kernels_sparse.hip); `hals` itself takes dense data only.
 
 `hals_stack` runs many Euclidean problems on the same data side by side in the factor columns of one engine: one pair of
-passes over V per iteration for all of them."""
+passes over V per iteration for all of them.
+
+`hals_masked` fits only the observed entries of V.  With entries missing the rows no longer share one Gram
+matrix: each owned row (a row of W, or a column of H) is swept on its own system over its observed set Omega,
+
+    G = Sum_{e in Omega} f_e f_e^T + 2 lambda I        r = Sum_{e in Omega} v_e f_e
+
+where F is the other factor (for the H half-step the W just updated) and f_e its row at entry e: `sweeps` passes of the sweep
+above, the clamp an exact zero.  A component with G_jj = 0 keeps its value -- with lambda = 0 that is every component of a
+row with no observed entry, and a dead component.  An observed zero is data: it adds to G and not to r.  Values of x outside
+the mask are never read (NaN is fine there).  With an all-ones mask this is `hals(x, k, distance_type='eu')`."""
 import logging
 import math
 import numbers
@@ -26,6 +36,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import masked
 from . import sparse
 from . import utils
 from ._driver import BATCH, Referee, Results, drive, require_iterations, say_objective, run_least_squares
@@ -35,6 +46,7 @@ from .engine import Engine
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h sweeps')
 
 MAX_K = 128
+MAX_K_MASKED = 64            # hals_masked: a k x k Gram per row, formed in registers and swept from LDS
 MAX_SWEEPS = 16
 
 
@@ -70,15 +82,15 @@ def _is_count(value, most=None):
 _ABSENT = object()
 
 
-def check_args(who, *, k=_ABSENT, sweeps=_ABSENT, lambda_w=_ABSENT, lambda_h=_ABSENT, real_lambdas, problem=None):
+def check_args(who, *, k=_ABSENT, sweeps=_ABSENT, lambda_w=_ABSENT, lambda_h=_ABSENT, real_lambdas, problem=None, most=MAX_K):
     """The HALS rules for k, sweeps and a lambda, stated once, in the order k, sweeps, lambda_w, lambda_h; what is not given is
     not checked.  `who` is the front end's name.  `problem`: the index of a problem of a stack, whose k has no bound of its own
-    (the stack's total has).  `real_lambdas` is inherited: hals_stack and hals_sparse refuse a bool or a non-Real lambda, hals
+    (the stack's total has); `most`: the front end's largest k.  `real_lambdas` is inherited: hals_stack and hals_sparse refuse a bool or a non-Real lambda, hals
     takes whatever answers `lam >= 0` with something true (True, for one)."""
     at = who if problem is None else f'{who}: problem {problem}'
-    if k is not _ABSENT and not _is_count(k, MAX_K if problem is None else None):
+    if k is not _ABSENT and not _is_count(k, most if problem is None else None):
         if problem is None:
-            raise ValueError(f'{who}: supports 1 <= k <= {MAX_K} components (got k = {k!r})')
+            raise ValueError(f'{who}: supports 1 <= k <= {most} components (got k = {k!r})')
         raise ValueError(f'{at} needs an integer k >= 1 (got k = {k!r})')
     if sweeps is not _ABSENT and not _is_count(sweeps, MAX_SWEEPS):
         raise ValueError(f'{who}: sweeps must be an integer between 1 and {MAX_SWEEPS} (got sweeps = {sweeps!r})')
@@ -260,6 +272,55 @@ def hals_sparse(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, m
             eng,
             lambda first, count: eng.hals_sparse_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
             lambda done: eng.hals_sparse_finish(min_iter, tol1, tol2, done),
+            max_iter, tol1, tol2, referee=None)
+        w, h = eng.get_factors()
+    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def masked_start_scale(eng, w0, h0):
+    """The least-squares scale of the start over the observed set, alpha = <v, q>_Omega / Sum_Omega q^2 with q = w0 h0, for the
+    observed entries a masked engine holds; None unless Sum_Omega q^2 > 0.  The masked objective of (s w0, h0) is the parabola
+    1/2 Sum v^2 - s <v, q> + 1/2 s^2 Sum q^2, so three float64 objective passes on the device, a, b, c at s = 0, 1, 2, give
+    e = c - 2 b + a = Sum q^2 and d = a - b + e / 2 = <v, q>.  Leaves (w0, h0) set on the engine."""
+    w64 = np.asarray(w0, dtype=np.float64)
+    h64 = np.asarray(h0, dtype=np.float64)
+    eng.set_factors(np.zeros_like(w64), np.zeros_like(h64))
+    a = eng.objective_f64()
+    eng.set_factors(2.0 * w64, h64)                    # (doubling is exact in float32: the device holds 2 (float) w0)
+    c = eng.objective_f64()
+    eng.set_factors(w0, h0)
+    b = eng.objective_f64()
+    e = c - 2.0 * b + a
+    if not e > 0:
+        return None
+    return (a - b + 0.5 * e) / e
+
+
+def hals_masked(x, k, mask, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10, max_iter=1000, tol1=1e-3,
+                tol2=1e-3, nndsvd_init=(True, 'zero'), device=0):
+    """HALS on the observed entries of `x` only, 1 <= k <= 64 (the module docstring's definition; csrc/kernels_sparse.hip,
+    DESIGN.md 4.14).  `x` and `mask` follow nmf_amd.masked.observed: dense or scipy.sparse `x`, a boolean, 0 / 1 or sparse
+    `mask` of the same shape; neither is modified and `x` is never read outside the mask.  Every refusal comes before any
+    device work and before any RNG draw.  Start, RNG draws, printed lines, stop rule and history are those of `hals_sparse` on
+    masked.observed(x, mask, k); `rescale_start` multiplies both start factors by sqrt(alpha) of `masked_start_scale`
+    (`hals_masked.last_alpha`).  The recorded objective is 1/2 Sum_Omega (x - wh)^2 summed per entry in float64
+    (nmf_amd.masked.objective), so no float64 referee stands behind the stop rule.  Returns Results with the Experiment of
+    `hals` (distance_type 'eu')."""
+    experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
+    check_args('hals_masked', k=k, sweeps=sweeps, lambda_w=lambda_w, lambda_h=lambda_h, real_lambdas=True, most=MAX_K_MASKED)
+    try:
+        xs = masked.observed(x, mask, k)
+    except (ValueError, TypeError) as e:
+        raise type(e)(f'hals_masked: {e}') from None
+    w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
+    with Engine.for_sparse(xs, k, device=device, masked=True) as eng:
+        alpha = masked_start_scale(eng, w0, h0) if rescale_start else None
+        hals_masked.last_alpha = alpha
+        eng.set_factors(*scaled_start(alpha, w0, h0))
+        i, history = drive(
+            eng,
+            lambda first, count: eng.hals_masked_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
+            lambda done: eng.hals_masked_finish(min_iter, tol1, tol2, done),
             max_iter, tol1, tol2, referee=None)
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)

@@ -35,7 +35,10 @@ class NMF:
         if method not in _METHODS:
             raise Exception('Method not known. Choose one from: ' + ' '.join(_METHODS))
         solver = getattr(import_module('.' + method, __package__), method)
-        if method == 'hals' and sparse.is_sparse(self.data):       # (hals itself takes dense data only)
+        if method == 'hals' and 'mask' in method_params:           # (hals_masked takes dense or sparse data)
+            masked = import_module('.hals', __package__).hals_masked
+            solver = lambda data, factors, mask, **kw: masked(data, factors, mask, **kw)
+        elif method == 'hals' and sparse.is_sparse(self.data):     # (hals itself takes dense data only)
             solver = import_module('.hals', __package__).hals_sparse
         self.results = solver(self.data, self.factors, **method_params)
         # README.md:22 promises nmf.w / nmf.h; the reference only sets .results
