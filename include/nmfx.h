@@ -166,7 +166,8 @@ int nmfx_get_relevance(nmfx_handle_t h, double* lambda_out /* k */);
  * nmfx_get_objectives, nmfx_objective_f64, nmfx_set_stop_guard, nmfx_resume, nmfx_synchronize, nmfx_set_stream
  * (and nmfx_reset_stream, nmfx_destroy, nmfx_last_error, nmfx_get_note; from version 391 nmfx_profile_enable,
  * nmfx_profile_get and nmfx_profile_reset, which count the sp_* scopes, and nmfx_hals_sparse_run / _finish on an unmasked
- * handle with k <= 128; from version 392 nmfx_hals_masked_run / _finish on a masked handle with k <= 64).  The objective is recorded in f64 from the non-zeros plus k x k terms ("Sparse V").
+ * handle with k <= 128; from version 392 nmfx_hals_masked_run / _finish on a masked handle with k <= 64; from version 393 nmfx_hals_foldin_run and
+ * nmfx_hals_foldin_get_sweeps on either).  The objective is recorded in f64 from the non-zeros plus k x k terms ("Sparse V").
  * Every other entry point returns NMFX_E_ARG and launches nothing. */
 int nmfx_create_csr(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k, int64_t nnz);
 int nmfx_upload_csr(nmfx_handle_t h, const int64_t* row_ptr, const int32_t* col_idx, const void* values, int dtype);
@@ -546,6 +547,26 @@ int nmfx_hals_masked_run(nmfx_handle_t h, double lambda_w, double lambda_h, int 
                          int64_t min_iter, double tol1, double tol2,
                          int64_t first, int64_t count);
 int nmfx_hals_masked_finish(nmfx_handle_t h, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
+
+/* ---- HALS fold-in (version 393) -------------------------------------------------------------------------------------------
+ * Least-squares H for the handle's V against a fixed W: the handle is an nmfx_create_csr handle of the NEW data with the
+ * factors set (nmfx_set_factors(w, h0)), unmasked with k <= 128 or masked (nmfx_set_masked) with k <= 64.  W is never touched.
+ * With W fixed a column's system depends on V and W only -- G = W^T W + 2 lambda_h I and r_c = W^T v_c, or on a masked handle
+ * the column's own G_c = Sum_Omega w_e w_e^T + 2 lambda_h I and r_c = Sum_Omega v_e w_e -- so it is formed once (one gather of
+ * V) and the projected Gauss-Seidel sweeps of the HALS H half-step run on it in place, column by column, from h0[:, c]:
+ * after sweep s, d_s is the largest step |delta_j| of that sweep and xmax_s the largest component after it; the column stops
+ * after the first s with d_s <= tol xmax_s (d_s = 0 included), or after max_sweeps.  The kept residual r - G x is formed anew
+ * before the sweeps 17, 33, ...  With tol = 0 and max_sweeps = s <= 16 the result is, bit for bit, the H half-step of
+ * nmfx_hals_sparse_run / nmfx_hals_masked_run with sweeps = s from the same (W, H).  Padded components are exact zeros, a
+ * component with G_jj = 0 keeps its value, no atomics: two runs give the same bits.
+ * nmfx_hals_foldin_run records obj[0] of the start and obj[1] of the result (nmfx_get_objectives; the objective its family
+ * records, at lambda_w = 0), and the stop rule of the outer loop never fires.  HALS family (NMFX_E_STATE when continuing
+ * another solver's run without nmfx_set_factors); the H-side statistics of an unmasked handle are current again on return.
+ * NMFX_E_ARG with a message, nothing launched: a dense handle, a masked handle with k padded beyond 64, k padded beyond 128, a
+ * NaN or negative tol or tol >= 1, max_sweeps outside 1 .. 10000, a lambda_h that is not >= 0.
+ * nmfx_hals_foldin_get_sweeps: out[n] = the sweeps each column took; NMFX_E_STATE if no solve has run since the factors were set. */
+int nmfx_hals_foldin_run(nmfx_handle_t h, double lambda_h, double tol, int max_sweeps);
+int nmfx_hals_foldin_get_sweeps(nmfx_handle_t h, int32_t* out /* n */);
 
 /* ---- stacked HALS (version 390)------------------------------------------------------------------------------------------
  * MANY least-squares factorizations of the same V in one pass over it: P problems sit side by side in the factor columns,

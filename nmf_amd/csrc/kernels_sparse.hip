@@ -1,4 +1,4 @@
-// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.  (HALS on the same handle: the last two sections.)
+// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.  (HALS and its fold-in on the same handle: the last three sections.)
 //
 // Layout.  Both factors are row-major along their long dimension: W [m][kp] (double buffered, E->W) and H^T [n][kp]
 // (nmfx_sparse::Ht), kp in {4, 8, 16, 32, 64, 128, 256}.  V is held twice: CSR (the W phase walks rows of V and gathers
@@ -70,6 +70,8 @@ struct nmfx_sparse {
     int obj_cap = 0;
     double* hals_part = nullptr;           // sparse HALS: [blocks of the H phase | blocks of its fix-up] partials of Sum_nz x wh (allocated at first use)
     bool masked = false;      // the stored entries are the observed set (nmfx_set_masked)
+    int32_t* foldin_sweeps = nullptr;      // HALS fold-in: [n] sweeps each column of H took (allocated at first use)
+    bool foldin_done = false;              // ... of a solve that has run since nmfx_set_factors
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -468,7 +470,7 @@ void nmfx_sparse_free(nmfx_engine* E) {
     nmfx_sparse* S = E->sp;
     if (!S) return;
     void* bufs[] = {S->Ht, S->g64[0], S->g64[1], S->gf[0], S->gf[1], S->cs64[0], S->cs64[1], S->csf[0], S->csf[1],
-                    S->stat_part, S->obj_part, S->hals_part};
+                    S->stat_part, S->obj_part, S->hals_part, S->foldin_sweeps};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& sd : S->side) {
         void* sb[] = {sd.idx, sd.val, sd.units, sd.longs, sd.slab, sd.slab64};
@@ -770,6 +772,7 @@ int nmfx_sparse_set_factors(nmfx_engine* E, const double* w, const double* hmat)
     E->have_f = true;
     E->derived.void_all_but(NMFX_D_NONE);
     E->run.reset();
+    E->sp->foldin_done = false;
     int rc;
     if (!E->sp->masked && (rc = stats_both(E))) return rc;
     NMFX_HIP(hipStreamSynchronize(E->stream));
@@ -870,6 +873,73 @@ __device__ __forceinline__ void sp_hals_sweep(const float* gs, const float (&inv
     for (int t = 0; t < 4; ++t) x[t] = lig * 4 + t >= k ? 0.f : live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0)
 }
 
+// The solve of one owned row (HALS fold-in): the sweeps of sp_hals_sweep -- the same layout and the same step,
+// so a count <= 16 leaves the bits of sp_hals_sweep with that count -- until a sweep moves no component by more than tol times
+// the largest component, or max_sweeps.  d comes from v_readlane and is wave-uniform: the sweep keeps a running max |d|; the
+// largest component is one butterfly over the group's lanes (every group holds the same bits); the test and the exit are
+// wave-uniform and the loop is bounded by max_sweeps.  The kept residual is formed anew from r (reload: g <- r) before the
+// sweeps 17, 33, ...: the most a half-step ever carries it.  Returns the number of sweeps run.
+template <int KP, typename RL>
+__device__ __forceinline__ int sp_hals_solve(const float* gs, const float (&inv)[4], const bool (&live)[4], float (&x)[4],
+                                             float (&g)[4], int k, float tol, int max_sweeps, int lig, RL reload)
+{
+    constexpr int G = KP / 4;
+    const int nl = (k + 3) >> 2;
+    const float* grow = gs + lig * 4;
+    float nx[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) nx[t] = live[t] ? -x[t] : 0.f;
+    auto residual = [&]() {                             // g -= G x
+        for (int l4 = 0; l4 < nl; ++l4) {
+            float4 c[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) c[t] = *reinterpret_cast<const float4*>(grow + (4 * l4 + t) * KP);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t]), l4));
+                g[0] = fmaf(-c[t].x, xl, g[0]); g[1] = fmaf(-c[t].y, xl, g[1]);
+                g[2] = fmaf(-c[t].z, xl, g[2]); g[3] = fmaf(-c[t].w, xl, g[3]);
+            }
+        }
+    };
+    residual();
+    int s = 0;
+    for (;;) {
+        float dmax = 0.f;
+        for (int l4 = 0; l4 < nl; ++l4) {
+            float4 c[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) c[t] = *reinterpret_cast<const float4*>(grow + (4 * l4 + t) * KP);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const float cand = fmaxf(nx[t], g[t] * inv[t]);
+                const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), l4));
+                dmax = fmaxf(dmax, fabsf(d));
+                nx[t] = (lig == l4) ? nx[t] - d : nx[t];
+                g[0] = fmaf(-c[t].x, d, g[0]); g[1] = fmaf(-c[t].y, d, g[1]);
+                g[2] = fmaf(-c[t].z, d, g[2]); g[3] = fmaf(-c[t].w, d, g[3]);
+            }
+        }
+        ++s;
+        float xmax = 0.f;                               // (a dead component keeps its value and counts; padding does not)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) xmax = fmaxf(xmax, live[t] ? 0.f - nx[t] : lig * 4 + t < k ? x[t] : 0.f);
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) xmax = fmaxf(xmax, __shfl_xor(xmax, off, 64));
+        xmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xmax)));
+        if (dmax <= tol * xmax || s >= max_sweeps) break;
+        if ((s & 15) == 0) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) x[t] = live[t] ? 0.f - nx[t] : x[t];
+            reload(g);
+            residual();
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) x[t] = lig * 4 + t >= k ? 0.f : live[t] ? 0.f - nx[t] : x[t];
+    return s;
+}
+
 // this lane's reciprocals of the diagonal of the staged G
 template <int KP>
 __device__ __forceinline__ void sp_hals_diag(const float* gs, int k, int lig, float (&inv)[4], bool (&live)[4]) {
@@ -884,15 +954,31 @@ __device__ __forceinline__ void sp_hals_diag(const float* gs, int k, int lig, fl
 
 // One owned row with its summed right-hand side r (R = double on the CROSS side): the sweep, the row written by group 0, and
 // on the CROSS side the row's <x_new, r> in f64 (returned on every lane of group 0; added by lane 0).
-template <int KP, bool CROSS, typename R>
+// SOLVE (fold-in): sp_hals_solve in place of the sweep, with `sweeps` its cap; lane 0 writes the row's sweep count to *count.
+// rlds: where the row's r stays in LDS for the solve's refresh (masked HALS), or nullptr: r stays in this lane's registers.
+template <int KP, bool CROSS, typename R, bool SOLVE = false>
 __device__ __forceinline__ double sp_hals_row(const float* gs, const float (&inv)[4], const bool (&live)[4], const R (&r)[4],
-                                              float* row, int k, int sweeps, int lig, int grp)
+                                              float* row, int k, int sweeps, int lig, int grp, float tol = 0.f,
+                                              int32_t* count = nullptr, const float* rlds = nullptr)
 {
     constexpr int G = KP / 4;
     const float4 x4 = *reinterpret_cast<const float4*>(row + lig * 4);
     float x[4] = {x4.x, x4.y, x4.z, x4.w};
     float g[4] = {(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
-    sp_hals_sweep<KP>(gs, inv, live, x, g, k, sweeps, lig);
+    if constexpr (SOLVE) {
+        const int s = sp_hals_solve<KP>(gs, inv, live, x, g, k, tol, sweeps, lig, [&](float (&gg)[4]) {
+            if (rlds) {
+                const float4 r4 = *reinterpret_cast<const float4*>(rlds + lig * 4);
+                gg[0] = r4.x; gg[1] = r4.y; gg[2] = r4.z; gg[3] = r4.w;
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) gg[t] = (float)r[t];
+            }
+        });
+        if (grp == 0 && lig == 0) *count = s;
+    } else {
+        sp_hals_sweep<KP>(gs, inv, live, x, g, k, sweeps, lig);
+    }
     if (grp == 0) *reinterpret_cast<float4*>(row + lig * 4) = make_float4(x[0], x[1], x[2], x[3]);
     double cross = 0.0;
     if constexpr (CROSS) {
@@ -918,11 +1004,14 @@ __device__ __forceinline__ void sp_hals_block_partial(double objacc, double* ob,
 //   Own [rows][KP]: the factor being updated, in place (a row is owned by one wave; the gathers read the other factor only);
 //   Other [*][KP]: the factor gathered per non-zero; Gf: its Gram (KP x KP f32), diag_add = (float)(2 lambda);
 //   slab: the pieces' partial r, f32 (W phase) or f64 (CROSS); obj_part[blockIdx.x]: the block's Sum <x_new, r> (CROSS).
-template <int KP, bool CROSS>
+//   SOLVE (fold-in): every row is swept to the stop rule of sp_hals_solve (tol; `sweeps` is the cap) and leaves its count in
+//   counts[row].  The waves' trip counts then differ by more than the gather length: the only block barriers are the staging
+//   one before the unit loop and the partial reduction behind it.
+template <int KP, bool CROSS, bool SOLVE = false>
 __global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_phase_kernel(
     const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
     const float* __restrict__ Other, float* Own, const float* __restrict__ Gf, float diag_add, void* __restrict__ slab,
-    double* __restrict__ obj_part, int k, int sweeps, const int* flag)
+    double* __restrict__ obj_part, int k, int sweeps, const int* flag, float tol = 0.f, int32_t* __restrict__ counts = nullptr)
 {
     if (*flag) return;
     constexpr int G = KP / 4, NG = 64 / G;
@@ -974,7 +1063,8 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_phase_kernel(
             }
             continue;
         }
-        const double cross = sp_hals_row<KP, CROSS, R>(gs, inv, live, acc, Own + (int64_t)U.row * KP, k, sweeps, lig, grp);
+        const double cross = sp_hals_row<KP, CROSS, R, SOLVE>(gs, inv, live, acc, Own + (int64_t)U.row * KP, k, sweeps, lig, grp, tol,
+                                                              SOLVE ? counts + U.row : nullptr);
         if (lane == 0) objacc += cross;
     }
     if constexpr (CROSS) sp_hals_block_partial(objacc, ob, obj_part + blockIdx.x);
@@ -982,10 +1072,11 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_phase_kernel(
 
 // Rows split into pieces: the pieces' partial r added in piece order (every group adds all of them: the same bits), then the
 // sweep of a whole row; CROSS: the long columns' <h_new, r> into this launch's own slots obj_part[blockIdx.x].
-template <int KP, bool CROSS>
+template <int KP, bool CROSS, bool SOLVE = false>
 __global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_fixup_kernel(
     const SpLong* __restrict__ longs, int64_t nlong, const void* __restrict__ slab, float* Own, const float* __restrict__ Gf,
-    float diag_add, double* __restrict__ obj_part, int k, int sweeps, const int* flag)
+    float diag_add, double* __restrict__ obj_part, int k, int sweeps, const int* flag, float tol = 0.f,
+    int32_t* __restrict__ counts = nullptr)
 {
     if (*flag) return;
     constexpr int G = KP / 4;
@@ -1005,31 +1096,34 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_fixup_kernel(
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] += s[t];
         }
-        const double cross = sp_hals_row<KP, CROSS, R>(gs, inv, live, acc, Own + (int64_t)L.row * KP, k, sweeps, lig, grp);
+        const double cross = sp_hals_row<KP, CROSS, R, SOLVE>(gs, inv, live, acc, Own + (int64_t)L.row * KP, k, sweeps, lig, grp, tol,
+                                                              SOLVE ? counts + L.row : nullptr);
         if (lane == 0) objacc += cross;
     }
     if constexpr (CROSS) sp_hals_block_partial(objacc, ob, obj_part + blockIdx.x);
 }
 
 // one half-step: side 0 the W phase (own W, gather H^T, Gram 1), side 1 the H phase (own H^T, gather W, Gram 0, CROSS).
-// *nparts: the objective partials the H phase left in hals_part.
-template <int KP, bool CROSS>
-static int launch_hals_phase(nmfx_engine* E, float* Own, const float* Other, float diag_add, int sweeps, int* nparts) {
+// *nparts: the objective partials the H phase left in hals_part.  SOLVE: the fold-in solve (sweeps: its cap; tol; the counts
+// into foldin_sweeps).
+template <int KP, bool CROSS, bool SOLVE = false>
+static int launch_hals_phase(nmfx_engine* E, float* Own, const float* Other, float diag_add, int sweeps, int* nparts, float tol = 0.f) {
     nmfx_sparse* S = E->sp;
     constexpr int side = CROSS ? 1 : 0;
     SpSide& sd = S->side[side];
     const int* flag = &E->state->flag;
     void* slab = CROSS ? (void*)sd.slab64 : (void*)sd.slab;
-    hipLaunchKernelGGL((sp_hals_phase_kernel<KP, CROSS>), dim3(sd.nblk), dim3(64 * SP_WAVES), 0, E->stream, (const SpUnit*)sd.units,
+    int32_t* counts = SOLVE ? S->foldin_sweeps : nullptr;
+    hipLaunchKernelGGL((sp_hals_phase_kernel<KP, CROSS, SOLVE>), dim3(sd.nblk), dim3(64 * SP_WAVES), 0, E->stream, (const SpUnit*)sd.units,
                        sd.nunits, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, (const float*)S->gf[1 - side], diag_add,
-                       slab, S->hals_part, E->k, sweeps, flag);
+                       slab, S->hals_part, E->k, sweeps, flag, tol, counts);
     NMFX_HIP(hipGetLastError());
     int nb = 0;
     if (sd.nlong) {
         nb = (int)std::min<int64_t>(4 * E->ncu, (sd.nlong + SP_WAVES - 1) / SP_WAVES);
-        hipLaunchKernelGGL((sp_hals_fixup_kernel<KP, CROSS>), dim3(nb), dim3(64 * SP_WAVES), 0, E->stream, (const SpLong*)sd.longs,
+        hipLaunchKernelGGL((sp_hals_fixup_kernel<KP, CROSS, SOLVE>), dim3(nb), dim3(64 * SP_WAVES), 0, E->stream, (const SpLong*)sd.longs,
                            sd.nlong, (const void*)slab, Own, (const float*)S->gf[1 - side], diag_add, S->hals_part + sd.nblk, E->k,
-                           sweeps, flag);
+                           sweeps, flag, tol, counts);
         NMFX_HIP(hipGetLastError());
     }
     if (nparts) *nparts = sd.nblk + nb;
@@ -1244,8 +1338,10 @@ __device__ __forceinline__ void mh_deposit(float* gs, const mh_f4 (&acc)[MhCfg<K
 
 // The region holds the row's summed [G | r]: 2 lambda on the diagonal of the first k components, then the sweep of sparse
 // HALS from the row's current values; group 0 writes the row in place.  Called by every lane of ONE wave.
-template <int KP>
-__device__ __forceinline__ void mh_sweep_row(float* gs, float diag_add, float* row, int k, int sweeps, int lane) {
+// SOLVE (fold-in): the solve of sp_hals_row on the region, whose r (at gs + KP KP) stays in place for the refresh; the count to *count.
+template <int KP, bool SOLVE = false>
+__device__ __forceinline__ void mh_sweep_row(float* gs, float diag_add, float* row, int k, int sweeps, int lane, float tol = 0.f,
+                                             int32_t* count = nullptr) {
     constexpr int G = KP / 4;
     const int lig = lane % G, grp = lane / G;
     mh_wave_fence();
@@ -1255,16 +1351,18 @@ __device__ __forceinline__ void mh_sweep_row(float* gs, float diag_add, float* r
     sp_hals_diag<KP>(gs, k, lig, inv, live);
     const float4 r4 = *reinterpret_cast<const float4*>(gs + KP * KP + lig * 4);
     const float r[4] = {r4.x, r4.y, r4.z, r4.w};
-    sp_hals_row<KP, false, float>(gs, inv, live, r, row, k, sweeps, lig, grp);
+    sp_hals_row<KP, false, float, SOLVE>(gs, inv, live, r, row, k, sweeps, lig, grp, tol, count, SOLVE ? gs + KP * KP : nullptr);
     mh_wave_fence();                                            // (the next row's [G | r] overwrites the region)
 }
 
 //   Own [rows][KP]: the factor being updated, in place (a row is owned by one wave; the gathers read the other factor only);
 //   Other [*][KP]: the factor gathered per observed entry; diag_add = (float)(2 lambda).
-template <int KP>
+//   SOLVE (fold-in): each row's [G | r] is formed once and swept in place to the stop rule (tol; `sweeps` is the cap); its count to counts[row].
+template <int KP, bool SOLVE = false>
 __global__ __launch_bounds__(64 * MhCfg<KP>::MW) void sp_mhals_phase_kernel(
     const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
-    const float* __restrict__ Other, float* Own, float diag_add, int k, int sweeps, const int* flag)
+    const float* __restrict__ Other, float* Own, float diag_add, int k, int sweeps, const int* flag, float tol = 0.f,
+    int32_t* __restrict__ counts = nullptr)
 {
     if (*flag) return;
     constexpr int MW = MhCfg<KP>::MW, NB = MhCfg<KP>::NB, NACC = MhCfg<KP>::NACC;
@@ -1281,15 +1379,16 @@ __global__ __launch_bounds__(64 * MhCfg<KP>::MW) void sp_mhals_phase_kernel(
         for (int b = 0; b < NB; ++b) racc[b] = 0.f;
         mh_accumulate<KP>(U.beg, U.len, idx, val, Other, acc, racc, lane);
         mh_deposit<KP>(gs, acc, racc, lane);
-        mh_sweep_row<KP>(gs, diag_add, Own + (int64_t)U.row * KP, k, sweeps, lane);
+        mh_sweep_row<KP, SOLVE>(gs, diag_add, Own + (int64_t)U.row * KP, k, sweeps, lane, tol, SOLVE ? counts + U.row : nullptr);
     }
 }
 
 // One workgroup per long row; the pieces of row l are the units [unit0, unit0 + npieces).
-template <int KP>
+template <int KP, bool SOLVE = false>
 __global__ __launch_bounds__(64 * MhCfg<KP>::MW) void sp_mhals_long_kernel(
     const SpLong* __restrict__ longs, int64_t nlong, const SpUnit* __restrict__ units, const int32_t* __restrict__ idx,
-    const float* __restrict__ val, const float* __restrict__ Other, float* Own, float diag_add, int k, int sweeps, const int* flag)
+    const float* __restrict__ val, const float* __restrict__ Other, float* Own, float diag_add, int k, int sweeps, const int* flag,
+    float tol = 0.f, int32_t* __restrict__ counts = nullptr)
 {
     if (*flag) return;
     constexpr int MW = MhCfg<KP>::MW, NB = MhCfg<KP>::NB, NACC = MhCfg<KP>::NACC;
@@ -1316,25 +1415,28 @@ __global__ __launch_bounds__(64 * MhCfg<KP>::MW) void sp_mhals_long_kernel(
             gs[i] = sum;
         }
         __syncthreads();
-        if (wave == 0) mh_sweep_row<KP>(gs, diag_add, Own + (int64_t)L.row * KP, k, sweeps, lane);
+        if (wave == 0) mh_sweep_row<KP, SOLVE>(gs, diag_add, Own + (int64_t)L.row * KP, k, sweeps, lane, tol, SOLVE ? counts + L.row : nullptr);
         __syncthreads();                                        // (the next row's deposit overwrites the region)
     }
 }
 
 // one half-step: side 0 the W phase (own W, gather H^T), side 1 the H phase (own H^T, gather W)
-template <int KP>
-static int launch_mhals_phase(nmfx_engine* E, int side, float* Own, const float* Other, float diag_add, int sweeps) {
+// SOLVE: the fold-in solve (sweeps: its cap; tol; the counts into foldin_sweeps)
+template <int KP, bool SOLVE = false>
+static int launch_mhals_phase(nmfx_engine* E, int side, float* Own, const float* Other, float diag_add, int sweeps, float tol = 0.f) {
     SpSide& sd = E->sp->side[side];
     constexpr int MW = MhCfg<KP>::MW;
     const int* flag = &E->state->flag;
+    int32_t* counts = SOLVE ? E->sp->foldin_sweeps : nullptr;
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)(32 / MW) * E->ncu, (sd.nunits + MW - 1) / MW));
-    hipLaunchKernelGGL((sp_mhals_phase_kernel<KP>), dim3(nb), dim3(64 * MW), 0, E->stream, (const SpUnit*)sd.units, sd.nunits,
-                       (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, diag_add, E->k, sweeps, flag);
+    hipLaunchKernelGGL((sp_mhals_phase_kernel<KP, SOLVE>), dim3(nb), dim3(64 * MW), 0, E->stream, (const SpUnit*)sd.units, sd.nunits,
+                       (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, diag_add, E->k, sweeps, flag, tol, counts);
     NMFX_HIP(hipGetLastError());
     if (sd.nlong) {
         const int nl = (int)std::min<int64_t>(4 * E->ncu, sd.nlong);
-        hipLaunchKernelGGL((sp_mhals_long_kernel<KP>), dim3(nl), dim3(64 * MW), 0, E->stream, (const SpLong*)sd.longs, sd.nlong,
-                           (const SpUnit*)sd.units, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, diag_add, E->k, sweeps, flag);
+        hipLaunchKernelGGL((sp_mhals_long_kernel<KP, SOLVE>), dim3(nl), dim3(64 * MW), 0, E->stream, (const SpLong*)sd.longs, sd.nlong,
+                           (const SpUnit*)sd.units, (const int32_t*)sd.idx, (const float*)sd.val, Other, Own, diag_add, E->k, sweeps, flag,
+                           tol, counts);
         NMFX_HIP(hipGetLastError());
     }
     return NMFX_OK;
@@ -1395,6 +1497,82 @@ extern "C" int nmfx_hals_masked_finish(nmfx_handle_t E, int64_t min_iter, double
     if (hs.flag || hs.n_obj > iters_done) return NMFX_OK;
     if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
     return launch_objective(E, NMFX_EU, E->xf64, true, iters_done, min_iter, tol1, tol2);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// HALS fold-in (nmfx_hals_foldin_run)
+// ---------------------------------------------------------------------------------------------------------------------
+// H for the handle's V against the W that was set, W never touched.  With W fixed a column's system depends on V and W only:
+// the H-side kernels of the two families above form it once (one gather; on a masked handle the column's own Gram) and
+// sp_hals_solve sweeps it in place until the column's stop rule or the cap.  obj[0] is the start's objective and obj[1] the
+// result's, each as its family records it: an objective-only pass (both on a masked handle), and on an unmasked handle the
+// solve's own Sum <h_c, r_c> with the Gram of the new H for obj[1].  The stop rule of the outer loop never fires here.
+#define SP_FOLDIN_NEVER ((int64_t)1 << 40)
+
+template <int KP>
+static int sp_foldin_solve(nmfx_engine* E, double lh, float tol, int max_sweeps) {
+    nmfx_sparse* S = E->sp;
+    const int* flag = &E->state->flag;
+    int rc, nparts = 0;
+    { ProfScope ps(E, "sp_hals_foldin");
+      if ((rc = launch_hals_phase<KP, true, true>(E, S->Ht, E->W[0], (float)(2.0 * lh), max_sweeps, &nparts, tol))) return rc; }
+    { ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<KP>(E, S->Ht, E->n, 1, flag))) return rc; }
+    hipLaunchKernelGGL((sp_objective_kernel<false, false>), dim3(1), dim3(256), 0, E->stream, (const double*)S->hals_part, nparts,
+                       (const double*)S->g64[0], (const double*)S->g64[1], (const double*)S->cs64[0], (const double*)S->cs64[1],
+                       E->kp, S->x2, E->xf64, 1, 1LL, (long long)SP_FOLDIN_NEVER, 0.0, 0.0, E->state, E->obj_hist);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+template <int KP>
+static int sp_mfoldin_solve(nmfx_engine* E, double lh, float tol, int max_sweeps) {
+    int rc;
+    { ProfScope ps(E, "sp_mhals_foldin");
+      if ((rc = launch_mhals_phase<KP, true>(E, 1, E->sp->Ht, E->W[0], (float)(2.0 * lh), max_sweeps, tol))) return rc; }
+    { ProfScope ps(E, "sp_mhals_objective");
+      if ((rc = sp_objective_pass<KP>(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+      if ((rc = launch_objective(E, NMFX_EU, E->xf64, true, 1, SP_FOLDIN_NEVER, 0.0, 0.0))) return rc; }
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_foldin_run(nmfx_handle_t E, double lambda_h, double tol, int max_sweeps) {
+    const char* who = "nmfx_hals_foldin_run";
+    if (!E) return NMFX_E_ARG;
+    if (!E->sp) { E->err = std::string(who) + ": needs a sparse handle (nmfx_create_csr), masked or not; a dense handle runs nmfx_foldin_run"; return NMFX_E_ARG; }
+    nmfx_sparse* S = E->sp;
+    if (S->masked && E->kp > 64) { E->err = std::string(who) + ": not available on a masked handle with more than 64 components in this build"; return NMFX_E_ARG; }
+    if (E->kp > 128) { E->err = nmfx_small_k_text(who); return NMFX_E_ARG; }
+    nmfx_entry a = {NMFX_FAM_HALS, 0, 0, NMFX_D_NONE, NMFX_D_NONE};      // (reads W, H and the Grams of nmfx_set_factors; derives nothing that outlives the call)
+    if (!(tol >= 0.0 && tol < 1.0)) a.bad = std::string(who) + ": tol must be at least 0 and below 1";
+    else if (max_sweeps < 1 || max_sweeps > 10000) a.bad = std::string(who) + ": max_sweeps must be between 1 and 10000";
+    else if (!(lambda_h >= 0)) a.bad = std::string(who) + ": bad lambda";
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    E->run.in_place();
+    if ((rc = nmfx_lazy_alloc(E, &S->foldin_sweeps, std::max<int64_t>(1, E->n)))) return rc;
+    if (!S->masked) {
+        if ((rc = nmfx_lazy_alloc(E, &S->hals_part, (int64_t)8 * E->ncu + 64))) return rc;
+        if ((rc = nmfx_lazy_alloc(E, &S->side[1].slab64, std::max<int64_t>(1, S->side[1].npieces * E->kp)))) return rc;
+    }
+    if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+    if ((rc = launch_objective(E, NMFX_EU, E->xf64, true, 0, SP_FOLDIN_NEVER, 0.0, 0.0))) return rc;
+    const float tolf = (float)tol;
+#define SP_FI(KP) (S->masked ? sp_mfoldin_solve<(KP) <= 64 ? (KP) : 64>(E, lambda_h, tolf, max_sweeps) : sp_foldin_solve<KP>(E, lambda_h, tolf, max_sweeps))
+    switch (E->kp) { case 4: rc = SP_FI(4); break; case 8: rc = SP_FI(8); break; case 16: rc = SP_FI(16); break;
+                     case 32: rc = SP_FI(32); break; case 64: rc = SP_FI(64); break; default: rc = SP_FI(128); break; }
+#undef SP_FI
+    if (rc) return rc;
+    S->foldin_done = true;
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_foldin_get_sweeps(nmfx_handle_t E, int32_t* out) {
+    if (!E || !out) return NMFX_E_ARG;
+    if (!E->sp || !E->sp->foldin_done) { E->err = "nmfx_hals_foldin_get_sweeps: no nmfx_hals_foldin_run since the factors were set"; return NMFX_E_STATE; }
+    NMFX_HIP(hipSetDevice(E->device));
+    NMFX_HIP(hipMemcpyAsync(out, E->sp->foldin_sweeps, (size_t)E->n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
 }
 
 int nmfx_preload_sparse() { hipFuncAttributes a; return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(sp_stats_reduce_kernel)) == hipSuccess ? 0 : -1; }

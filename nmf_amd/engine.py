@@ -72,7 +72,7 @@ class Engine:
     @classmethod
     def for_sparse(cls, x, k, device=0, masked=False):
         """A fresh engine on sparse `x` (canonical CSR from nmf_amd.sparse.normalise), uploaded through nmfx_create_csr /
-        nmfx_upload_csr.  Runs MUR and, unmasked with k <= 128, sparse HALS, masked with k <= 64, masked HALS (include/nmfx.h); usable as a context manager like any Engine.  masked=True: `x`
+        nmfx_upload_csr.  Runs MUR and, unmasked with k <= 128, sparse HALS, masked with k <= 64, masked HALS, and on either the HALS fold-in (include/nmfx.h); usable as a context manager like any Engine.  masked=True: `x`
         holds the observed entries (nmf_amd.masked.observed) and nmfx_set_masked is called before the upload."""
         from . import sparse
         row_ptr, col_idx, values = sparse.arrays(x)
@@ -409,6 +409,17 @@ class Engine:
         self._ck(self.lib.nmfx_hals_masked_finish(self.h, int(min_iter), float(tol1), float(tol2), int(done)))
 
     # -- stacked HALS: many problems side by side in the factor columns (include/nmfx.h) ---------
+    def hals_foldin_run(self, lam_h, tol, max_sweeps):
+        """Least-squares H against the fixed W that was set, on a sparse handle (unmasked k <= 128, masked k <= 64): every column's
+        system is formed once and swept in place to its stop rule (include/nmfx.h); records obj[0] of the start and obj[1]."""
+        self._ck(self.lib.nmfx_hals_foldin_run(self.h, float(lam_h), float(tol), int(max_sweeps)))
+
+    def hals_foldin_sweeps(self):
+        """The sweeps each column took in the last hals_foldin_run: int32, length n."""
+        out = np.empty(self.n, dtype=np.int32)
+        self._ck(self.lib.nmfx_hals_foldin_get_sweeps(self.h, _ptr(out)))
+        return out
+
     def hals_stack_set(self, ks):
         """Problem p owns the components [sum(ks[:p]), sum(ks[:p + 1])); () clears the stack.  After set_factors, before the run."""
         ks = [int(k) for k in ks]

@@ -28,7 +28,10 @@ matrix: each owned row (a row of W, or a column of H) is swept on its own system
 where F is the other factor (for the H half-step the W just updated) and f_e its row at entry e: `sweeps` passes of the sweep
 above, the clamp an exact zero.  A component with G_jj = 0 keeps its value -- with lambda = 0 that is every component of a
 row with no observed entry, and a dead component.  An observed zero is data: it adds to G and not to r.  Values of x outside
-the mask are never read (NaN is fine there).  With an all-ones mask this is `hals(x, k, distance_type='eu')`."""
+the mask are never read (NaN is fine there).  With an all-ones mask this is `hals(x, k, distance_type='eu')`.
+
+`hals_transform` is the least-squares fold-in of such fits: H for new sparse or masked data against a fixed
+W.  With W fixed a column's (G, r) never changes, so it is formed once and swept to convergence in place."""
 import logging
 import math
 import numbers
@@ -275,6 +278,72 @@ def hals_sparse(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, m
             max_iter, tol1, tol2, referee=None)
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+HalsTransformResults = namedtuple('HalsTransformResults', 'h sweeps obj_history experiment')
+TransformExperiment = namedtuple('Experiment', 'method components tol max_sweeps lambda_h')
+MAX_SOLVE_SWEEPS = 10000
+
+
+def _check_transform_factor(name, a, shape=None):
+    """A factor the caller hands to hals_transform: 2-D, real, finite, >= 0 (and of `shape`); a float64 copy."""
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError(f'hals_transform: {name} must be 2-D (got {a.ndim}-D)')
+    if a.dtype == object or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)
+                                 or np.issubdtype(a.dtype, np.bool_)):
+        raise ValueError(f'hals_transform: {name} must be a real array')
+    if shape is not None and tuple(a.shape) != tuple(shape):
+        raise ValueError(f'hals_transform: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}')
+    a = np.array(a, dtype=np.float64)
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f'hals_transform: {name} has an entry that is NaN or infinite')
+    if a.size and np.min(a) < 0:
+        raise ValueError(f'hals_transform: {name} has a negative entry')
+    return a
+
+
+def hals_transform(x_new, w, mask=None, *, h0=None, lambda_h=0, tol=1e-4, max_sweeps=200, device=0):
+    """Least-squares fold-in: H for new data `x_new` (m x n) against the fixed dictionary `w` (m x k, real, finite, >= 0).
+
+    Without `mask`, `x_new` is scipy.sparse under the rules of `hals_sparse`, 1 <= k <= 128; with `mask`, `x_new` and `mask`
+    follow nmf_amd.masked.observed as in `hals_masked`, 1 <= k <= 64.  Nothing of the caller's is modified.  With W fixed a
+    column's system depends on x_new and W only (G = W^T W + 2 lambda_h I, r_c = W^T x_c; masked: the sums over the column's
+    observed entries), so it is formed once and solved in place (csrc/kernels_sparse.hip): projected
+    Gauss-Seidel sweeps from h0[:, c] (`h0`: k x n, real, finite, >= 0; default all zeros -- no RNG draw in any case) until,
+    after sweep s, the largest step of that sweep is at most `tol` times the largest component, or `max_sweeps`.  The
+    defaults are scikit-learn's for its cd solver.  Returns HalsTransformResults: h float64 k x n; sweeps int32, the sweeps
+    each column took; obj_history = [objective(w, h0), objective(w, h)] as `hals_sparse` / `hals_masked` record it;
+    experiment ('hals_transform', k, tol, max_sweeps, lambda_h).  Every refusal comes before any device work."""
+    if mask is None and not sparse.is_sparse(x_new):
+        raise TypeError("hals_transform: dense x_new needs mask=; without a mask x_new must be a scipy.sparse matrix "
+                        "(dense data without a mask: nmf_amd.transform.transform(x_new, w, distance_type='eu'))")
+    w64 = _check_transform_factor('w', w)
+    k = w64.shape[1]
+    most = MAX_K if mask is None else MAX_K_MASKED
+    if not 1 <= k <= most:
+        raise ValueError(f'hals_transform: supports 1 <= k <= {most} components{"" if mask is None else " with a mask"} (w has {k} columns)')
+    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not 0 <= tol < 1:
+        raise ValueError(f'hals_transform: tol must be a real number with 0 <= tol < 1 (got tol = {tol!r})')
+    if not _is_count(max_sweeps, MAX_SOLVE_SWEEPS):
+        raise ValueError(f'hals_transform: max_sweeps must be an integer between 1 and {MAX_SOLVE_SWEEPS} (got max_sweeps = {max_sweeps!r})')
+    check_args('hals_transform', lambda_h=lambda_h, real_lambdas=True)
+    try:
+        xs = sparse.normalise(x_new, k) if mask is None else masked.observed(x_new, mask, k)
+    except (ValueError, TypeError) as e:
+        raise type(e)(f'hals_transform: {e}') from None
+    m, n = xs.shape
+    if w64.shape[0] != m:
+        raise ValueError(f'hals_transform: w has {w64.shape[0]} rows, x_new has {m}')
+    h64 = np.zeros((k, n)) if h0 is None else _check_transform_factor('h0', h0, (k, n))
+    experiment = TransformExperiment('hals_transform', k, tol, max_sweeps, lambda_h)
+    with Engine.for_sparse(xs, k, device=device, masked=mask is not None) as eng:
+        eng.set_factors(w64, h64)
+        eng.hals_foldin_run(lambda_h, tol, max_sweeps)
+        _, h = eng.get_factors()
+        sweeps = eng.hals_foldin_sweeps()
+        history = [np.float64(v) for v in eng.objectives(0, 2)]
+    return HalsTransformResults(h=h, sweeps=sweeps, obj_history=history, experiment=experiment)
 
 
 def masked_start_scale(eng, w0, h0):

@@ -50,9 +50,12 @@ class NMF:
     def transform(self, data, **kw):
         """H for new `data` against the dictionary self.w of the last factorize (nmf_amd.transform.transform): returns
         TransformResults(h, i, obj_history, experiment).  distance_type, and beta with it, default to what that factorize
-        used; every keyword of transform may be given."""
+        used; every keyword of transform may be given.  Sparse `data`, or a mask= among the keywords, goes to the least-squares
+        fold-in nmf_amd.hals.hals_transform instead, with the keywords as they are (HalsTransformResults)."""
         if self.results is None or self.w is None:
             raise RuntimeError('NMF.transform needs a dictionary: call factorize first')
+        if sparse.is_sparse(data) or 'mask' in kw:
+            return import_module('.hals', __package__).hals_transform(data, self.w, **kw)
         from .transform import transform
         exp = self.results.experiment
         if 'distance_type' not in kw:

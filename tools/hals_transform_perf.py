@@ -1,0 +1,113 @@
+"""Time one HALS fold-in solve (nmfx_hals_foldin_run at the defaults tol = 1e-4, max_sweeps = 200) beside one H phase of the
+fit it follows, on the same handle.
+
+    python tools/hals_transform_perf.py --kind masked --m 16384 --n 8192 --density 0.10 --k 64
+    python tools/hals_transform_perf.py --table > profiles/hals_transform_perf.txt
+
+Inputs are the seeded random CSR of tools/sparse_perf.py (--kind masked: its stored entries are the observed set), the matrices
+of profiles/sparse_hals_perf.txt and profiles/masked_hals_perf.txt.  W comes from --fit-iters HALS iterations from the seeded,
+rescaled |randn| start on that handle; the fold-in then starts from h0 = 0 against that W.  One JSON line per case:
+  foldin_ms: device time of one nmfx_hals_foldin_run (two objective records included), best of --reps, device events;
+  foldin_solve_ms: the solve's own scope (sp_hals_foldin / sp_mhals_foldin) of a profiled run (nmfx_profile_get);
+  sweeps_mean, sweeps_max, at_cap: over the columns of that run;
+  hphase_ms: one sp_hals_hphase / sp_mhals_hphase scope of a profiled HALS iteration (sweeps = 1) on the same handle."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ.setdefault("NMF_AMD_QUIET", "1")
+
+import numpy as np
+
+from sparse_perf import make_csr
+
+NEVER = 10 ** 12
+TABLE = [["--kind", "sparse", "--m", "16384", "--n", "8192", "--k", "64", "--density", d] for d in ("0.001", "0.01", "0.05")]
+TABLE += [["--kind", "sparse", "--m", "16384", "--n", "8192", "--k", "64", "--density", "0.01", "--powerlaw", "1.0"],
+          ["--kind", "sparse", "--m", "1048576", "--n", "131072", "--k", "32", "--density", "0.0001"]]
+TABLE += [["--kind", "masked", "--m", "16384", "--n", "8192", "--k", "64", "--density", d] for d in ("0.01", "0.10", "0.50")]
+TABLE += [["--kind", "masked", "--m", "1048576", "--n", "131072", "--k", "32", "--density", "0.0001"]]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=("sparse", "masked"), default="sparse")
+    ap.add_argument("--m", type=int, default=16384)
+    ap.add_argument("--n", type=int, default=8192)
+    ap.add_argument("--density", type=float, default=0.01)
+    ap.add_argument("--k", type=int, default=64)
+    ap.add_argument("--powerlaw", type=float, default=0.0, help="row-length exponent (0: uniform rows)")
+    ap.add_argument("--fit-iters", type=int, default=10)
+    ap.add_argument("--tol", type=float, default=1e-4)
+    ap.add_argument("--max-sweeps", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--table", action="store_true", help="every matrix of the two HALS tables, one process each")
+    a = ap.parse_args()
+    if a.table:
+        for row in TABLE:
+            subprocess.run([sys.executable, os.path.abspath(__file__), *row], check=True)
+        return
+
+    import torch
+    from nmf_amd import sparse
+    from nmf_amd.engine import Engine
+    from nmf_amd.hals import masked_start_scale, start_scale
+    masked = a.kind == "masked"
+    x = sparse.normalise(make_csr(a.m, a.n, a.density, a.seed, a.powerlaw), a.k)
+    rs = np.random.RandomState(a.seed)
+    w0 = np.abs(rs.randn(a.m, a.k))
+    h0 = np.abs(rs.randn(a.k, a.n))
+    zeros = np.zeros((a.k, a.n))
+    stream = torch.cuda.current_stream().cuda_stream
+    scope = "sp_mhals" if masked else "sp_hals"
+    with Engine.for_sparse(x, a.k, masked=masked) as eng:
+        eng.set_stream(stream)
+        fit = eng.hals_masked_run if masked else eng.hals_sparse_run
+        alpha = (masked_start_scale if masked else start_scale)(eng, w0, h0)
+        eng.set_factors(w0 * np.sqrt(alpha), h0 * np.sqrt(alpha))
+        fit(0.0, 0.0, 1, NEVER, 1e-30, 1e-30, 0, a.fit_iters)
+        # -- one H phase of the fit, profiled ---------------------------------------------------------------------------------
+        eng.profile_reset()
+        eng.profile_enable(True)
+        fit(0.0, 0.0, 1, NEVER, 1e-30, 1e-30, a.fit_iters, 3)
+        eng.synchronize()
+        t, cnt = eng.profile_get(scope + "_hphase")
+        hphase_ms = t / cnt
+        eng.profile_enable(False)
+        w, _ = eng.get_factors()
+        # -- the fold-in against that W from h0 = 0 ---------------------------------------------------------------------------
+        ms = []
+        for _ in range(a.reps + 1):                       # (the first round warms up)
+            eng.set_factors(w, zeros)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            eng.hals_foldin_run(0.0, a.tol, a.max_sweeps)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        sweeps = eng.hals_foldin_sweeps()
+        obj = eng.objectives(0, 2)
+        eng.set_factors(w, zeros)
+        eng.profile_reset()
+        eng.profile_enable(True)
+        eng.hals_foldin_run(0.0, a.tol, a.max_sweeps)
+        eng.synchronize()
+        solve_ms = eng.profile_get(scope + "_foldin")[0]
+        eng.profile_enable(False)
+        eng.reset_stream()
+    lens = np.diff(x.tocsc().indptr)
+    out = {"kind": a.kind, "m": a.m, "n": a.n, "k": a.k, "density": a.density, "powerlaw": a.powerlaw, "nnz": int(x.nnz),
+           "max_col_nnz": int(lens.max()), "tol": a.tol, "max_sweeps": a.max_sweeps, "fit_iters": a.fit_iters,
+           "foldin_ms": round(min(ms[1:]), 4), "foldin_solve_ms": round(solve_ms, 4), "hphase_ms": round(hphase_ms, 4),
+           "solve_over_hphase": round(solve_ms / hphase_ms, 3), "sweeps_mean": round(float(sweeps.mean()), 2),
+           "sweeps_max": int(sweeps.max()), "at_cap": int((sweeps == a.max_sweeps).sum()),
+           "obj_start": float(obj[0]), "obj_folded": float(obj[1])}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
