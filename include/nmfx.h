@@ -568,6 +568,27 @@ int nmfx_hals_masked_finish(nmfx_handle_t h, int64_t min_iter, double tol1, doub
 int nmfx_hals_foldin_run(nmfx_handle_t h, double lambda_h, double tol, int max_sweeps);
 int nmfx_hals_foldin_get_sweeps(nmfx_handle_t h, int32_t* out /* n */);
 
+/* ---- dense HALS fold-in (version 394) ------------------------------------------------------------------------------------
+ * The same solve for DENSE new data: the handle is an nmfx_create handle of the new data without weights, k <= 128, with the
+ * factors set (nmfx_set_factors(w, h0)).  W is never touched.  Every column shares G = W^T W + 2 lambda_h I and r_c is column c
+ * of W^T V: the products of the H half-step of nmfx_hals_run, formed ONCE in the handle's arithmetic mode (one pass over V);
+ * then every column is swept in place from h0[:, c] under the stop rule above (d_s <= tol xmax_s, or max_sweeps; the kept
+ * residual formed anew before the sweeps 17, 33, ...) -- k x n work that never reads V again.  With tol = 0 and
+ * max_sweeps = s <= 16 the result is, bit for bit, the H half-step of nmfx_hals_run with sweeps = s from the same (W, H).
+ * Padded components are exact zeros, a component with G_jj = 0 keeps its value, no atomics: two runs give the same bits.
+ * nmfx_hals_foldin_dense_run records obj[0] of the start and obj[1] of the result (nmfx_get_objectives), each 1/2 ||V - W H||^2
+ * with product and sum in f64: the quantity nmfx_objective_f64 returns, bit for bit.  nmfx_get_state reports 2 objectives and the
+ * stop rule of the outer loop never fires.  HALS family (NMFX_E_STATE when continuing another solver's run without
+ * nmfx_set_factors).  On a handle whose stop rule has already fired (an nmfx_hals_run that stopped, no nmfx_set_factors since)
+ * the call launches but moves nothing, as every solver does there: the iterate stays, nothing is recorded, and the counts are
+ * not those of a solve.
+ * NMFX_E_ARG with a message, nothing launched: a sparse handle, a handle with per-entry weights, k padded beyond 128, a NaN or
+ * negative tol or tol >= 1, max_sweeps outside 1 .. 10000, a lambda_h that is not >= 0.
+ * nmfx_hals_foldin_dense_get_sweeps: out[n] = the sweeps each column took; NMFX_E_STATE if no dense fold-in has run since the
+ * factors were set.  nmfx_hals_foldin_run / nmfx_hals_foldin_get_sweeps are as they were: sparse handles only. */
+int nmfx_hals_foldin_dense_run(nmfx_handle_t h, double lambda_h, double tol, int max_sweeps);
+int nmfx_hals_foldin_dense_get_sweeps(nmfx_handle_t h, int32_t* out /* n */);
+
 /* ---- stacked HALS (version 390)------------------------------------------------------------------------------------------
  * MANY least-squares factorizations of the same V in one pass over it: P problems sit side by side in the factor columns,
  * W = [W_0 | W_1 | ...], H = [H_0; H_1; ...].  The V-sized products V H^T and W^T V of the stacked factors are the P problems'

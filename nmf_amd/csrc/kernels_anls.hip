@@ -794,6 +794,44 @@ extern "C" int nmfx_hals_run(nmfx_handle_t E, double lambda_w, double lambda_h, 
     return NMFX_OK;
 }
 
+// ---- dense HALS fold-in (include/nmfx.h, version 394) -----------------------------------------------------------
+// H for the handle's V against the W that was set, W never touched.  Every column shares G = W^T W + 2 lambda_h I and its
+// right-hand side is a column of W^T V: the products of the H half-step, formed once (ls_h_products, in the handle's arithmetic
+// mode), then nmfx_hals_solve sweeps every column in place to its stop rule or the cap -- k x n work that never reads V again.
+// obj[0] is the start's objective and obj[1] the result's, both the f64 quantity of nmfx_objective_f64; the outer stop rule never fires.
+extern "C" int nmfx_hals_foldin_dense_run(nmfx_handle_t E, double lambda_h, double tol, int max_sweeps) {
+    const char* who = "nmfx_hals_foldin_dense_run";
+    if (!E) return NMFX_E_ARG;
+    if (E->sp) { E->err = std::string(who) + ": needs a dense handle (nmfx_create); a sparse handle, masked or not, runs nmfx_hals_foldin_run"; return NMFX_E_ARG; }
+    NMFX_DENSE_ONLY(E);
+    if (E->kp > 128) { E->err = nmfx_small_k_text(who); return NMFX_E_ARG; }
+    nmfx_entry a = {NMFX_FAM_HALS, 0, 0, NMFX_D_NONE, NMFX_D_himg_both | NMFX_D_kl_h_iter};      // (as anls_ready: the images of H are voided at entry, a refused call included; nothing is kept)
+    if (!(tol >= 0.0 && tol < 1.0)) a.bad = std::string(who) + ": tol must be at least 0 and below 1";
+    else if (max_sweeps < 1 || max_sweeps > 10000) a.bad = std::string(who) + ": max_sweeps must be between 1 and 10000";
+    else if (!(lambda_h >= 0)) a.bad = std::string(who) + ": bad lambda";
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    E->run.in_place();
+    E->run.foldin_dense_done = false;
+    if ((rc = nmfx_lazy_alloc(E, &E->foldin_dense_sweeps, std::max<int64_t>(1, E->n)))) return rc;
+    if ((rc = nmfx_objective_f64_record(E, 0))) return rc;                                  // obj[0]
+    if (anls_bf16(E) && (rc = nmfx_bf16_prepare(E))) return rc;
+    if ((rc = ls_h_products(E, 0))) return rc;                                              // [W^T V | W^T W] in xf32, as anls_h reads it
+    if ((rc = nmfx_hals_solve(E, E->xf32 + (int64_t)E->kp * E->np, (float)(2.0 * lambda_h), E->xf32, E->H, E->np, 1, E->n, (float)tol,
+                              max_sweeps, E->foldin_dense_sweeps))) return rc;
+    if ((rc = nmfx_objective_f64_record(E, 1))) return rc;                                  // obj[1]
+    E->run.foldin_dense_done = true;
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_foldin_dense_get_sweeps(nmfx_handle_t E, int32_t* out) {
+    if (!E || !out) return NMFX_E_ARG;
+    if (E->sp || !E->run.foldin_dense_done) { E->err = "nmfx_hals_foldin_dense_get_sweeps: no nmfx_hals_foldin_dense_run since the factors were set"; return NMFX_E_STATE; }
+    NMFX_HIP(hipSetDevice(E->device));
+    NMFX_HIP(hipMemcpyAsync(out, E->foldin_dense_sweeps, (size_t)E->n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
 // ---- stacked HALS (include/nmfx.h, version 390) -----------------------------------------------------------------
 // P problems side by side in the factor columns: the V-sized products of the stacked factors are the P problems' products, and with
 // the Gram entries between different problems masked (kernels_hals.hip) the sweep over all components is P independent sweeps.

@@ -2387,6 +2387,22 @@ int nmfx_generic_anls_phase(nmfx_engine* E, int phase, double lam, int64_t min_i
     return gx_nnls(E, xG, 2.0 * lam, xB, E->H, np, 1, E->n);
 }
 
+// 1/2 ||V - W H||^2 of the current pair in f64 (product and sum), left on the device at *out: written once, for nmfx_objective_f64
+// and for the objectives the dense HALS fold-in records
+static int gx_objective64(nmfx_engine* E, const double** out) {
+    int rc;
+    if ((rc = nmfx_need_v(E))) return rc;
+    const int64_t mp = E->mp, np = E->np, kp = E->kp, nblk = (mp / GX_T) * (np / GX_T);
+    if ((rc = gx_alloc(E, &E->gx_part, nblk + 64))) return rc;
+    const float* W = E->W[E->run.wsel];
+    hipLaunchKernelGGL(gx_resid64_kernel, dim3((unsigned)(np / GX_T), (unsigned)(mp / GX_T)), dim3(256), 0, E->stream, W, kp, (const float*)E->H, np, kp,
+                       (const float*)E->V, np, E->gx_part);
+    hipLaunchKernelGGL(gx_sum64_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_part, nblk, E->gx_part + nblk);
+    NMFX_HIP(hipGetLastError());
+    *out = E->gx_part + nblk;
+    return NMFX_OK;
+}
+
 // The Euclidean objective of the CURRENT pair (W as nmfx_get_factors would return it, H) evaluated entirely in float64 on the
 // device: the referee of the stop rule near the stop (see gx_resid64_kernel).  Synchronises.  Any k.
 extern "C" int nmfx_objective_f64(nmfx_handle_t E, double* out) {
@@ -2398,16 +2414,21 @@ extern "C" int nmfx_objective_f64(nmfx_handle_t E, double* out) {
     if (!E->have_v || !E->have_f) { E->err = "upload V and set factors first"; return NMFX_E_STATE; }
     NMFX_HIP(hipSetDevice(E->device));
     int rc;
-    if ((rc = nmfx_need_v(E))) return rc;
-    const int64_t mp = E->mp, np = E->np, kp = E->kp, nblk = (mp / GX_T) * (np / GX_T);
-    if ((rc = gx_alloc(E, &E->gx_part, nblk + 64))) return rc;
-    const float* W = E->W[E->run.wsel];
-    hipLaunchKernelGGL(gx_resid64_kernel, dim3((unsigned)(np / GX_T), (unsigned)(mp / GX_T)), dim3(256), 0, E->stream, W, kp, (const float*)E->H, np, kp,
-                       (const float*)E->V, np, E->gx_part);
-    hipLaunchKernelGGL(gx_sum64_kernel, dim3(1), dim3(256), 0, E->stream, (const double*)E->gx_part, nblk, E->gx_part + nblk);
-    NMFX_HIP(hipGetLastError());
-    NMFX_HIP(hipMemcpyAsync(out, E->gx_part + nblk, sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    const double* dev = nullptr;
+    if ((rc = gx_objective64(E, &dev))) return rc;
+    NMFX_HIP(hipMemcpyAsync(out, dev, sizeof(double), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
+// ... recorded as obj[j] on the device, no stop rule (the dense HALS fold-in, nmfx_hals_foldin_dense_run)
+int nmfx_objective_f64_record(nmfx_engine* E, int64_t j) {
+    ProfScope ps(E, "objective_f64");
+    int rc;
+    const double* dev = nullptr;
+    if ((rc = gx_objective64(E, &dev))) return rc;
+    hipLaunchKernelGGL(gx_record_kernel, dim3(1), dim3(1), 0, E->stream, dev, (long long)j, (long long)1 << 40, 0.0, 0.0, E->state, E->obj_hist);
+    NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }
 

@@ -175,9 +175,166 @@ static int hals_sweep_kp(nmfx_engine* E, const float* G, float diag_add, const f
 int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
                     int64_t nprob, int sweeps, int stack_side) {
     ProfScope ps(E, "hals_sweep");
+    ProfScope side(E, sc == 1 ? "hals_sweep_h" : "hals_sweep_w");          // (the same launch under its side's name: tools/hals_transform_perf.py --dense)
     if (nprob <= 0) return NMFX_OK;
     return stack_side < 0 ? hals_sweep_kp<false>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, 0)
                           : hals_sweep_kp<true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, stack_side);
+}
+
+// ---- the per-column solve of the dense fold-in (nmfx_hals_foldin_dense_run) ---------------------------------------
+// The layout, the staging and the step of hals_sweep_kernel -- a column that runs s <= 16 sweeps leaves the bits of the sweep kernel
+// with sweeps = s -- with the stop rule of sp_hals_solve (kernels_sparse.hip) per column: after sweep s, d_s is the running max |delta|
+// of the sweep (delta comes from v_readlane and is wave-uniform) and xmax_s the largest component (a dead component keeps its value
+// and counts, padding does not; reduced over the wave, made uniform by v_readfirstlane); the column stops after the first s with
+// d_s <= tol xmax_s, or at max_sweeps.  Before the sweeps 17, 33, ... the kept residual is formed anew: r is reloaded from R and the
+// mat-vec redone.  Lane 0 writes the column's sweep count.  Behind the staging barrier there is no block barrier (the trip counts
+// differ per wave); every loop bound and every exit is wave-uniform and the sweep loop is bounded by max_sweeps; the waves take
+// the columns at a static stride: no atomics, two runs give the same bits.
+template <int KP>
+__global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_solve_kernel(
+    const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
+    int64_t sj, int64_t sc, int64_t nprob, int k, float tol, int max_sweeps, int32_t* __restrict__ counts,
+    const DevState* __restrict__ st)
+{
+    if (st->flag) return;                               // (the stop rule has fired: the iterate stays, as in hals_sweep_kernel)
+    constexpr int NV = KP <= 64 ? 1 : KP / 64;          // variables per lane
+    constexpr int NW = NMFX_HALS_WAVES;
+    extern __shared__ __attribute__((aligned(16))) float hals_g[];      // G + diag_add I, [KP][KP]
+    for (int i4 = threadIdx.x; i4 < KP * KP / 4; i4 += 64 * NW) {
+        float4 v = *reinterpret_cast<const float4*>(G + 4 * (int64_t)i4);
+        const int row = (4 * i4) / KP, col = (4 * i4) % KP;
+        v.x += (col == row) ? diag_add : 0.f; v.y += (col + 1 == row) ? diag_add : 0.f;
+        v.z += (col + 2 == row) ? diag_add : 0.f; v.w += (col + 3 == row) ? diag_add : 0.f;
+        *reinterpret_cast<float4*>(hals_g + 4 * i4) = v;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int at[NV]; bool valid[NV], live[NV]; float inv[NV];
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+        const int idx = lane + 64 * t;
+        valid[t] = idx < k;
+        at[t] = idx < KP ? idx : KP - 1;                // (lanes beyond KP at kp = 16 / 32: any address inside the row; their values are unused)
+        const float gd = hals_g[at[t] * KP + at[t]];
+        live[t] = valid[t] && gd > 0.f;
+        inv[t] = live[t] ? 1.f / gd : 0.f;
+    }
+    for (int64_t c = (int64_t)blockIdx.x * NW + wave; c < nprob; c += (int64_t)gridDim.x * NW) {      // (wave-uniform)
+        float x[NV], g[NV], nx[NV];
+#pragma unroll
+        for (int t = 0; t < NV; ++t) {
+            const int64_t off = (int64_t)at[t] * sj + c * sc;
+            x[t] = valid[t] ? X[off] : 0.f;
+            g[t] = valid[t] ? R[off] : 0.f;
+            nx[t] = live[t] ? -x[t] : 0.f;
+        }
+        auto matvec = [&](int t2, int l, const float (&col)[NV]) {
+            const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t2]), l));
+#pragma unroll
+            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], xl, g[t]);
+        };
+        float dmax;                                     // the running max |delta| of the sweep (wave-uniform)
+        auto step = [&](int t2, int j, const float (&col)[NV]) {
+            const float cand = fmaxf(nx[t2], g[t2] * inv[t2]);
+            const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), j));
+            dmax = fmaxf(dmax, fabsf(d));
+            nx[t2] = (lane == j) ? nx[t2] - d : nx[t2];          // (d = -x_j: an exact zero)
+#pragma unroll
+            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], d, g[t]);
+        };
+        // g -= G x, four rows at a time as in hals_sweep_kernel
+        auto residual = [&]() {
+#pragma unroll
+            for (int t2 = 0; t2 < NV; ++t2) {
+                const int lim = k - 64 * t2 < 64 ? k - 64 * t2 : 64;
+                int l = 0;
+                for (; l + 4 <= lim; l += 4) {
+                    float c0[NV], c1[NV], c2[NV], c3[NV];
+                    hals_row<KP, NV>(hals_g, 64 * t2 + l, at, c0); hals_row<KP, NV>(hals_g, 64 * t2 + l + 1, at, c1);
+                    hals_row<KP, NV>(hals_g, 64 * t2 + l + 2, at, c2); hals_row<KP, NV>(hals_g, 64 * t2 + l + 3, at, c3);
+                    matvec(t2, l, c0); matvec(t2, l + 1, c1); matvec(t2, l + 2, c2); matvec(t2, l + 3, c3);
+                }
+                for (; l < lim; ++l) {
+                    float c0[NV];
+                    hals_row<KP, NV>(hals_g, 64 * t2 + l, at, c0);
+                    matvec(t2, l, c0);
+                }
+            }
+        };
+        residual();
+        int s = 0;
+        for (;;) {                                      // (bounded by max_sweeps)
+            dmax = 0.f;
+#pragma unroll
+            for (int t2 = 0; t2 < NV; ++t2) {
+                const int lim = k - 64 * t2 < 64 ? k - 64 * t2 : 64;
+                int j = 0;
+                for (; j + 4 <= lim; j += 4) {
+                    float c0[NV], c1[NV], c2[NV], c3[NV];
+                    hals_row<KP, NV>(hals_g, 64 * t2 + j, at, c0); hals_row<KP, NV>(hals_g, 64 * t2 + j + 1, at, c1);
+                    hals_row<KP, NV>(hals_g, 64 * t2 + j + 2, at, c2); hals_row<KP, NV>(hals_g, 64 * t2 + j + 3, at, c3);
+                    step(t2, j, c0); step(t2, j + 1, c1); step(t2, j + 2, c2); step(t2, j + 3, c3);
+                }
+                for (; j < lim; ++j) {
+                    float c0[NV];
+                    hals_row<KP, NV>(hals_g, 64 * t2 + j, at, c0);
+                    step(t2, j, c0);
+                }
+            }
+            ++s;
+            float xmax = 0.f;                           // (a dead component keeps its value and counts; padding holds x = 0)
+#pragma unroll
+            for (int t = 0; t < NV; ++t) xmax = fmaxf(xmax, live[t] ? 0.f - nx[t] : x[t]);
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) xmax = fmaxf(xmax, __shfl_xor(xmax, off, 64));
+            xmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xmax)));
+            const float dm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dmax)));
+            if (dm <= tol * xmax || s >= max_sweeps) break;
+            if ((s & 15) == 0) {                        // the kept residual anew: r from global memory, the mat-vec again
+#pragma unroll
+                for (int t = 0; t < NV; ++t) {
+                    x[t] = live[t] ? 0.f - nx[t] : x[t];
+                    g[t] = valid[t] ? R[(int64_t)at[t] * sj + c * sc] : 0.f;
+                }
+                residual();
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NV; ++t)
+            if (lane + 64 * t < KP) X[(int64_t)at[t] * sj + c * sc] = live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0; invalid lanes hold x = 0)
+        if (lane == 0) counts[c] = s;
+    }
+}
+
+template <int KP>
+static int launch_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                             int64_t nprob, float tol, int max_sweeps, int32_t* counts) {
+    int rc;
+    const size_t shm = (size_t)KP * KP * sizeof(float);
+    auto kern = hals_solve_kernel<KP>;
+    if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm))) return rc;
+    const int64_t blocks_needed = (nprob + NMFX_HALS_WAVES - 1) / NMFX_HALS_WAVES;
+    const int64_t round = (int64_t)E->ncu * NMFX_HALS_BLOCKS_PER_CU;
+    const unsigned grid = (unsigned)(blocks_needed < round ? blocks_needed : round);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NMFX_HALS_WAVES), shm, E->stream, G, diag_add, R, X, sj, sc, nprob, E->k, tol,
+                       max_sweeps, counts, E->state);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+// the one kp dispatch of the solve; arguments and strides as nmfx_hals_sweep, counts: [nprob]
+int nmfx_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                    int64_t nprob, float tol, int max_sweeps, int32_t* counts) {
+    ProfScope ps(E, "hals_solve");
+    if (nprob <= 0) return NMFX_OK;
+    switch (E->kp) {
+        case 16: return launch_hals_solve<16>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
+        case 32: return launch_hals_solve<32>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
+        case 64: return launch_hals_solve<64>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
+        case 128: return launch_hals_solve<128>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
+    }
+    E->err = nmfx_small_k_text("hals_solve");
+    return NMFX_E_ARG;
 }
 
 // ---- the stack's state and objective ------------------------------------------------------------------------------------------

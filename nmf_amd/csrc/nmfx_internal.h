@@ -135,6 +135,7 @@ struct nmfx_run {
     bool fused_pack = false;       // inside nmfx_mur_run (single GPU): no pack launch, h_update reads the slabs
     bool w_in_place = false;       // the solver updates W[0] in place (all but MUR, which ping-pongs)
     int wsel = 0;                  // W buffer holding the current iterate
+    bool foldin_dense_done = false;   // nmfx_hals_foldin_dense_run has run since nmfx_set_factors: foldin_dense_sweeps holds its counts
     void reset() { *this = nmfx_run(); }
     void in_place() { wsel = 0; w_in_place = true; }                         // AO-ADMM, ADMM, ANLS
     void ping_pong(int64_t j) { wsel = (int)((j + 1) & 1); w_in_place = false; }   // MUR: iteration j leaves W_{j+1} in the other buffer
@@ -262,6 +263,7 @@ struct nmfx_engine {
     double* stack_obj = nullptr; int64_t stack_obj_cap = 0;
     double* stack_part = nullptr;
     bool stack_vv_ready = false;   // half_vv is that of the current V
+    int32_t* foldin_dense_sweeps = nullptr;   // dense HALS fold-in (nmfx_hals_foldin_dense_run): [n] sweeps each column of H took (allocated at first use)
     struct nmfx_sparse* sp = nullptr;   // a sparse handle (nmfx_create_csr): CSR / CSC of V, H^T, Grams (kernels_sparse.hip); MUR, and HALS on an unmasked handle
     // profiling
     bool prof = false;
@@ -496,6 +498,12 @@ int nmfx_preload_hals();
 // component in place of diag_add (side 0: lambda_w, 1: lambda_h), the components of a stopped problem left as they are
 int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps,
                     int stack_side = -1);
+// the per-column solve of the dense fold-in: the sweeps of nmfx_hals_sweep until a sweep moves no component by more than tol times the
+// largest one, or max_sweeps; counts[nprob]: the sweeps each problem took
+int nmfx_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, float tol,
+                    int max_sweeps, int32_t* counts);
+// kernels_generic.hip: obj[j] = the f64 objective of nmfx_objective_f64 for the current pair, by its kernels, recorded without a stop rule
+int nmfx_objective_f64_record(nmfx_engine* E, int64_t j);
 int nmfx_hals_stack_alloc(nmfx_engine* E);                     // the device state and the partial buffers, on first use
 int nmfx_hals_stack_config(nmfx_engine* E);                    // stack_nprob / stack_off -> device, stop state cleared
 int nmfx_hals_stack_reset(nmfx_engine* E);                     // nmfx_set_factors: the per-problem stop state back to "running"

@@ -420,6 +420,18 @@ class Engine:
         self._ck(self.lib.nmfx_hals_foldin_get_sweeps(self.h, _ptr(out)))
         return out
 
+    def hals_foldin_dense_run(self, lam_h, tol, max_sweeps):
+        """Least-squares H against the fixed W that was set, on a dense handle without weights, k <= 128: one product pass over
+        V (the H half-step's [W^T V | W^T W]), then every column swept in place to its stop rule (include/nmfx.h); records
+        obj[0] of the start and obj[1] of the result, both the quantity objective_f64 returns."""
+        self._ck(self.lib.nmfx_hals_foldin_dense_run(self.h, float(lam_h), float(tol), int(max_sweeps)))
+
+    def hals_foldin_dense_sweeps(self):
+        """The sweeps each column took in the last hals_foldin_dense_run: int32, length n."""
+        out = np.empty(self.n, dtype=np.int32)
+        self._ck(self.lib.nmfx_hals_foldin_dense_get_sweeps(self.h, _ptr(out)))
+        return out
+
     def hals_stack_set(self, ks):
         """Problem p owns the components [sum(ks[:p]), sum(ks[:p + 1])); () clears the stack.  After set_factors, before the run."""
         ks = [int(k) for k in ks]

@@ -31,7 +31,9 @@ row with no observed entry, and a dead component.  An observed zero is data: it 
 the mask are never read (NaN is fine there).  With an all-ones mask this is `hals(x, k, distance_type='eu')`.
 
 `hals_transform` is the least-squares fold-in of such fits: H for new sparse or masked data against a fixed
-W.  With W fixed a column's (G, r) never changes, so it is formed once and swept to convergence in place."""
+W.  With W fixed a column's (G, r) never changes, so it is formed once and swept to convergence in place.
+`hals_transform_dense` is the same fold-in for dense new data: all columns share one Gram matrix and the
+right-hand sides are the H half-step's own product, so it costs one pass over the data and k x n work behind it."""
 import logging
 import math
 import numbers
@@ -39,6 +41,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import losses
 from . import masked
 from . import sparse
 from . import utils
@@ -285,21 +288,21 @@ TransformExperiment = namedtuple('Experiment', 'method components tol max_sweeps
 MAX_SOLVE_SWEEPS = 10000
 
 
-def _check_transform_factor(name, a, shape=None):
-    """A factor the caller hands to hals_transform: 2-D, real, finite, >= 0 (and of `shape`); a float64 copy."""
+def _check_transform_factor(name, a, shape=None, who='hals_transform'):
+    """A factor the caller hands to hals_transform (or to `who`): 2-D, real, finite, >= 0 (and of `shape`); a float64 copy."""
     a = np.asarray(a)
     if a.ndim != 2:
-        raise ValueError(f'hals_transform: {name} must be 2-D (got {a.ndim}-D)')
+        raise ValueError(f'{who}: {name} must be 2-D (got {a.ndim}-D)')
     if a.dtype == object or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)
                                  or np.issubdtype(a.dtype, np.bool_)):
-        raise ValueError(f'hals_transform: {name} must be a real array')
+        raise ValueError(f'{who}: {name} must be a real array')
     if shape is not None and tuple(a.shape) != tuple(shape):
-        raise ValueError(f'hals_transform: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}')
+        raise ValueError(f'{who}: {name} has shape {tuple(a.shape)}, expected {tuple(shape)}')
     a = np.array(a, dtype=np.float64)
     if not np.all(np.isfinite(a)):
-        raise ValueError(f'hals_transform: {name} has an entry that is NaN or infinite')
+        raise ValueError(f'{who}: {name} has an entry that is NaN or infinite')
     if a.size and np.min(a) < 0:
-        raise ValueError(f'hals_transform: {name} has a negative entry')
+        raise ValueError(f'{who}: {name} has a negative entry')
     return a
 
 
@@ -342,6 +345,54 @@ def hals_transform(x_new, w, mask=None, *, h0=None, lambda_h=0, tol=1e-4, max_sw
         eng.hals_foldin_run(lambda_h, tol, max_sweeps)
         _, h = eng.get_factors()
         sweeps = eng.hals_foldin_sweeps()
+        history = [np.float64(v) for v in eng.objectives(0, 2)]
+    return HalsTransformResults(h=h, sweeps=sweeps, obj_history=history, experiment=experiment)
+
+
+def hals_transform_dense(x_new, w, *, h0=None, lambda_h=0, tol=1e-4, max_sweeps=200, device=0):
+    """Least-squares fold-in for DENSE new data: H for `x_new` (m x n, dense, real, finite and >= 0 in float32; a zero is data
+    and nothing is lifted) against the fixed dictionary `w` (m x k, real, finite, >= 0), 1 <= k <= 128 -- the minimiser the H
+    half-step of `hals` works towards, where `transform(x_new, w, distance_type='eu')` takes multiplicative steps.
+
+    Every column shares G = W^T W + 2 lambda_h I and its right-hand side is a column of W^T x_new: the products of the H
+    half-step of `hals`, formed once in the engine's arithmetic mode -- ONE pass over x_new -- and then every column is solved
+    in place by the sweeps and under the stop rule of `hals_transform` (`h0`, `tol`, `max_sweeps`, `lambda_h` as there; h0
+    defaults to all zeros and no RNG draw is made in any case): k x n work that never reads x_new again
+    (csrc/kernels_hals.hip, hals_solve_kernel).  Returns HalsTransformResults: h float64 k x n; sweeps
+    int32, the sweeps each column took; obj_history = [objective(w, h0), objective(w, h)], each 1/2 ||x_new - w h||^2 in
+    float64 on the device (Engine.objective_f64); experiment ('hals_transform', k, tol, max_sweeps, lambda_h).  There is no
+    mask= (sparse or masked data: `hals_transform`).  Every refusal comes before any device work."""
+    who = 'hals_transform_dense'
+    if sparse.is_sparse(x_new):
+        raise TypeError(f'{who}: x_new must be a dense array; scipy.sparse data (or dense data with mask=) goes to '
+                        'nmf_amd.hals.hals_transform')
+    xa = np.asarray(x_new)
+    if xa.ndim != 2:
+        raise ValueError(f'{who}: x_new must be 2-D (got {xa.ndim}-D)')
+    w64 = _check_transform_factor('w', w, who=who)
+    m, n = xa.shape
+    k = w64.shape[1]
+    if w64.shape[0] != m:
+        raise ValueError(f'{who}: w has {w64.shape[0]} rows, x_new has {m}')
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f'{who}: supports 1 <= k <= {MAX_K} components (w has {k} columns)')
+    if m < 1 or n < 1:
+        raise ValueError(f'{who}: x_new is empty')
+    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not 0 <= tol < 1:
+        raise ValueError(f'{who}: tol must be a real number with 0 <= tol < 1 (got tol = {tol!r})')
+    if not _is_count(max_sweeps, MAX_SOLVE_SWEEPS):
+        raise ValueError(f'{who}: max_sweeps must be an integer between 1 and {MAX_SOLVE_SWEEPS} (got max_sweeps = {max_sweeps!r})')
+    check_args(who, lambda_h=lambda_h, real_lambdas=True)
+    h64 = np.zeros((k, n)) if h0 is None else _check_transform_factor('h0', h0, (k, n), who=who)
+    if not losses.is_real(xa):
+        raise ValueError(f'{who}: x_new must be a real array')
+    losses.check_f32_image(xa, 'eu', None, label=who)
+    experiment = TransformExperiment('hals_transform', k, tol, max_sweeps, lambda_h)
+    with Engine.for_data(xa, k, device=device) as eng:
+        eng.set_factors(w64, h64)
+        eng.hals_foldin_dense_run(lambda_h, tol, max_sweeps)
+        _, h = eng.get_factors()
+        sweeps = eng.hals_foldin_dense_sweeps()
         history = [np.float64(v) for v in eng.objectives(0, 2)]
     return HalsTransformResults(h=h, sweeps=sweeps, obj_history=history, experiment=experiment)
 

@@ -51,11 +51,19 @@ class NMF:
         """H for new `data` against the dictionary self.w of the last factorize (nmf_amd.transform.transform): returns
         TransformResults(h, i, obj_history, experiment).  distance_type, and beta with it, default to what that factorize
         used; every keyword of transform may be given.  Sparse `data`, or a mask= among the keywords, goes to the least-squares
-        fold-in nmf_amd.hals.hals_transform instead, with the keywords as they are (HalsTransformResults)."""
+        fold-in nmf_amd.hals.hals_transform instead, with the keywords as they are (HalsTransformResults).
+        solver='hals' asks for the least-squares fold-in on dense data too: nmf_amd.hals.hals_transform_dense with the other
+        keywords as they are (sparse data or mask=: hals_transform, as without it); solver='mur', the default, is everything
+        above.  Any other solver is a ValueError."""
+        solver = kw.pop('solver', 'mur')
+        if not (isinstance(solver, str) and solver in ('mur', 'hals')):
+            raise ValueError(f"NMF.transform: solver must be 'mur' or 'hals' (got {solver!r})")
         if self.results is None or self.w is None:
             raise RuntimeError('NMF.transform needs a dictionary: call factorize first')
         if sparse.is_sparse(data) or 'mask' in kw:
             return import_module('.hals', __package__).hals_transform(data, self.w, **kw)
+        if solver == 'hals':
+            return import_module('.hals', __package__).hals_transform_dense(data, self.w, **kw)
         from .transform import transform
         exp = self.results.experiment
         if 'distance_type' not in kw:
