@@ -298,7 +298,19 @@ int nmfx_mur_phase_b_rest(nmfx_handle_t h, int distance, int64_t c0, int64_t c1)
  * column sums of W), f64 part = [objective partial, 4 inner-loop norm sums (sharded AO-ADMM, round by round), 3 spare,
  * 64 x 4 norm sums of the speculative rounds (nmfx_aoadmm_phase_w_fused)].  Sizes in
  * elements.  The caller may supply its own device allocations (e.g. torch
- * tensors, so that torch.distributed can all-reduce them in place).           */
+ * tensors, so that torch.distributed can all-reduce them in place).
+ * Layout of the f32 part after nmfx_mur_phase_a (kp, n_pad: nmfx_mur_chunk_info), offsets in elements:
+ *   [0, kp n_pad)   the product.  Euclidean loss on the split-bf16 path (k padded to 64 / 128, nmfx_get_precision = 1):
+ *                   [column][factor], element c * kp + f (nmfx_mur_phase_a_cols, nmfx_mur_phase_b_slice rely on it: a column
+ *                   range is contiguous).  Everything else -- KL on that path, the exact-f32 kernels, k > 128 -- :
+ *                   [factor][column], element f * n_pad + c.  Padded rows and columns are zero.
+ *   kp n_pad        Euclidean: W^T W, [kp][kp].  KL with k <= 128: the kp column sums of W (what follows them up to kp kp is
+ *                   unspecified).  KL with k > 128: the column sums lie behind the Gram slot, at kp n_pad + kp kp.
+ *   kp n_pad + kp kp + kp    the tail of nmfx_set_exchange_rank: slot r = 4 floats, the 16-bit digits of rank r's objective
+ *                   partial, least significant first; phase A writes the slots [0, world) -- its own digits, +0.0 elsewhere.
+ * Phase A writes every element phase B reads, and so does nmfx_mur_finish_a for nmfx_mur_finish_b (f64 part [0]): neither buffer
+ * needs to be zeroed by the caller, and what a phase does not write (f64 [1, 8) in MUR, tail slots from `world` on, the ranges of
+ * other ranks after a reduce-scatter) is never read.  tests/test_gpu_shard_step.py fills all of it with NaN.            */
 int nmfx_exchange_sizes(nmfx_handle_t h, int64_t* n_f32, int64_t* n_f64);
 /* Stream-capture support for the caller-driven loop.  The phase calls only queue launches on the
  * handle's stream, so a caller may capture  phase_a(j=0) . all-reduce . phase_b(j=0) .

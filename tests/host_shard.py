@@ -29,6 +29,14 @@ class HostShard(Shard):
     def buffers(self):
         return self.x32, self.x64
 
+    def set_factors(self, w_local, h):
+        """A new start on the same rows of V, as nmfx_set_factors: the history and the stop flag are cleared."""
+        self.w = np.array(w_local, dtype=np.float64)
+        self.h = np.array(h, dtype=np.float64)
+        self.obj = []
+        self.flag, self.stop_i = 0, -1
+        self.w_new = None
+
     def _local_objective(self, kind):
         wh = self.w @ self.h
         if kind == 0:
