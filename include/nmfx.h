@@ -601,6 +601,32 @@ int nmfx_hals_foldin_get_sweeps(nmfx_handle_t h, int32_t* out /* n */);
 int nmfx_hals_foldin_dense_run(nmfx_handle_t h, double lambda_h, double tol, int max_sweeps);
 int nmfx_hals_foldin_dense_get_sweeps(nmfx_handle_t h, int32_t* out /* n */);
 
+/* ---- MUR fold-in on sparse and masked handles (version 395) ---------------------------------------------------------------
+ * H for the handle's V against a fixed W under the loss of sparse / masked MUR: the handle is an nmfx_create_csr handle of the
+ * NEW data, masked (nmfx_set_masked) or not, with the factors set (nmfx_set_factors(w, h0)), any k the handle takes (k <= 256).
+ * W is never written; H is updated in place.  With W fixed the columns of H are independent problems: column c repeats the H
+ * half-step of nmfx_mur_run on this handle -- entries e = (i_e, x_e) the column's non-zeros, or its observed cells on a masked
+ * handle, w_e row i_e of W, q_e = <w_e, h>, lambda = lambda_h --
+ *     unmasked NMFX_EU   h' = h a / (h G + lambda h + 1e-9)              a = Sum x_e w_e,  G = W^T W
+ *     unmasked NMFX_KL   h' = 2 h a / (s + sqrt(s^2 + 4 lambda h a))     a = Sum x_e / (q_e + 1e-9) w_e,  s = colsum W
+ *     masked NMFX_EU     h' = h a / (d + lambda h + 1e-9)                a = Sum x_e w_e,  d = Sum q_e w_e
+ *     masked NMFX_KL     h' = 2 h a / (d + sqrt(d^2 + 4 lambda h a))     a as unmasked,  d = Sum w_e;  d = 0 -> 0
+ *     masked NMFX_IS     h' = h sqrt(a / (d + lambda))                   a = Sum x_e / (q_e + 1e-9)^2 w_e,  d = Sum w_e / (q_e + 1e-9);  d + lambda = 0 -> 0
+ * in one launch, the iterate in registers: after step t, delta_t = max_j |h'_j - h_j| and xmax_t = max_j h'_j; the column stops
+ * after the first t with delta_t <= tol xmax_t (delta_t = 0 included), or after max_iter.  One step of a column of at most 256
+ * entries is the H half-step bit for bit.  Padded components are exact zeros, no atomics: two runs give the same bits.
+ * nmfx_sparse_foldin_run records obj[0] of the start and obj[1] of the result (nmfx_get_objectives), as nmfx_mur_run records the
+ * objective of that loss on this handle at lambda_w = 0; the stop rule of the outer loop never fires.  MUR family (NMFX_E_STATE when
+ * continuing another solver's run without nmfx_set_factors, and after nmfx_mur_run has iterated on the handle since the factors
+ * were set); the H-side statistics of an unmasked handle are current again on return.
+ * NMFX_E_ARG with a message, nothing launched: a dense handle (nmfx_foldin_run takes those, and keeps refusing sparse ones),
+ * NMFX_IS on an unmasked handle, NMFX_BETA or an unknown distance, a NaN or negative tol or tol >= 1, max_iter outside 1 .. 10000,
+ * a lambda_h that is not >= 0.
+ * nmfx_sparse_foldin_get_iters: out[n] = the steps each column took; NMFX_E_STATE unless nmfx_sparse_foldin_run has run since
+ * the factors were set (nmfx_hals_foldin_get_sweeps keeps a flag of its own: neither getter answers for the other's run). */
+int nmfx_sparse_foldin_run(nmfx_handle_t h, int distance, double lambda_h, double tol, int max_iter);
+int nmfx_sparse_foldin_get_iters(nmfx_handle_t h, int32_t* out /* n */);
+
 /* ---- stacked HALS (version 390)------------------------------------------------------------------------------------------
  * MANY least-squares factorizations of the same V in one pass over it: P problems sit side by side in the factor columns,
  * W = [W_0 | W_1 | ...], H = [H_0; H_1; ...].  The V-sized products V H^T and W^T V of the stacked factors are the P problems'

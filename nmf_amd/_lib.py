@@ -124,6 +124,8 @@ SIGNATURES = {
     "nmfx_hals_foldin_get_sweeps": (_i32, [_vp, _vp]),
     "nmfx_hals_foldin_dense_run": (_i32, [_vp, _dbl, _dbl, _i32]),
     "nmfx_hals_foldin_dense_get_sweeps": (_i32, [_vp, _vp]),
+    "nmfx_sparse_foldin_run": (_i32, [_vp, _i32, _dbl, _dbl, _i32]),
+    "nmfx_sparse_foldin_get_iters": (_i32, [_vp, _vp]),
     "nmfx_hals_stack_set":(_i32, [_vp, _i32, C.POINTER(_i32)]),
     "nmfx_hals_stack_terms": (_i32, [_vp, _vp]),
     "nmfx_hals_stack_run": (_i32, [_vp, _pd, _pd, _i32, _i64, _dbl, _dbl, _i64, _i64]),

@@ -1,4 +1,5 @@
-// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.  (HALS and its fold-in on the same handle: the last three sections.)
+// MUR on sparse V (nmfx_create_csr / nmfx_upload_csr): both losses, one GPU.  (HALS and its fold-in on the same handle, then the
+// MUR fold-in: the last four sections.)
 //
 // Layout.  Both factors are row-major along their long dimension: W [m][kp] (double buffered, E->W) and H^T [n][kp]
 // (nmfx_sparse::Ht), kp in {4, 8, 16, 32, 64, 128, 256}.  V is held twice: CSR (the W phase walks rows of V and gathers
@@ -72,6 +73,8 @@ struct nmfx_sparse {
     bool masked = false;      // the stored entries are the observed set (nmfx_set_masked)
     int32_t* foldin_sweeps = nullptr;      // HALS fold-in: [n] sweeps each column of H took (allocated at first use)
     bool foldin_done = false;              // ... of a solve that has run since nmfx_set_factors
+    int32_t* mur_foldin_iters = nullptr;   // MUR fold-in: [n] steps each column of H took (allocated at first use)
+    bool mur_foldin_done = false;          // ... of a run since nmfx_set_factors (a flag of its own: neither getter reads the other's counts)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -91,13 +94,14 @@ __device__ __forceinline__ float4 sp_sum_groups(float4 a) {
     return a;
 }
 
-// The update epilogue of one owned row (every lane of the wave takes part; group 0 writes).
+// The update epilogue of one owned row (every lane of the wave takes part; group 0 writes).  sp_epilogue_value returns the
+// new row, this lane's four components (every group holds the same bits); sp_epilogue writes it.
 //   Euclidean  out = w a / (w G + lam w + 1e-9)                         (nmf/mur.py:30, 45: (WH)H^T = W (H H^T))
 //   KL         out = 2 w a / (s + sqrt(s^2 + 4 lam w a)),  s = sums     (nmf/mur.py:25-27, 40-42)
 // Components c >= k (the zero padding) are written as 0.
 template <int KP, bool KL>
-__device__ __forceinline__ void sp_epilogue(float4 w4, float4 a4, const float* __restrict__ Gsrc, const float* __restrict__ S,
-                                            float lam, int k, float* __restrict__ out_row, int lig, int grp)
+__device__ __forceinline__ float4 sp_epilogue_value(float4 w4, float4 a4, const float* __restrict__ Gsrc, const float* __restrict__ S,
+                                                    float lam, int k, int lig, int grp)
 {
     constexpr int G = KP / 4, NG = 64 / G;
     float4 o;
@@ -132,6 +136,13 @@ __device__ __forceinline__ void sp_epilogue(float4 w4, float4 a4, const float* _
     if (c0 + 1 >= k) o.y = 0.f;
     if (c0 + 2 >= k) o.z = 0.f;
     if (c0 + 3 >= k) o.w = 0.f;
+    return o;
+}
+template <int KP, bool KL>
+__device__ __forceinline__ void sp_epilogue(float4 w4, float4 a4, const float* __restrict__ Gsrc, const float* __restrict__ S,
+                                            float lam, int k, float* __restrict__ out_row, int lig, int grp)
+{
+    const float4 o = sp_epilogue_value<KP, KL>(w4, a4, Gsrc, S, lam, k, lig, grp);
     if (grp == 0) *reinterpret_cast<float4*>(out_row + lig * 4) = o;
 }
 
@@ -139,8 +150,7 @@ __device__ __forceinline__ void sp_epilogue(float4 w4, float4 a4, const float* _
 //   Euclidean  out = w a / (d + lam w + 1e-9)
 //   KL         out = 2 w a / (d + sqrt(d^2 + 4 lam w a)), and 0 where d = 0 (no observed entry: 0 / 0 is defined as 0)
 template <bool KL, bool IS = false>
-__device__ __forceinline__ void sp_epilogue_masked(float4 w4, float4 a4, float4 d4, float lam, int k, float* __restrict__ out_row,
-                                                   int lig, int grp)
+__device__ __forceinline__ float4 sp_epilogue_masked_value(float4 w4, float4 a4, float4 d4, float lam, int k, int lig)
 {
     float4 o;
     if constexpr (IS) {
@@ -166,6 +176,13 @@ __device__ __forceinline__ void sp_epilogue_masked(float4 w4, float4 a4, float4 
     if (c0 + 1 >= k) o.y = 0.f;
     if (c0 + 2 >= k) o.z = 0.f;
     if (c0 + 3 >= k) o.w = 0.f;
+    return o;
+}
+template <bool KL, bool IS = false>
+__device__ __forceinline__ void sp_epilogue_masked(float4 w4, float4 a4, float4 d4, float lam, int k, float* __restrict__ out_row,
+                                                   int lig, int grp)
+{
+    const float4 o = sp_epilogue_masked_value<KL, IS>(w4, a4, d4, lam, k, lig);
     if (grp == 0) *reinterpret_cast<float4*>(out_row + lig * 4) = o;
 }
 
@@ -470,7 +487,7 @@ void nmfx_sparse_free(nmfx_engine* E) {
     nmfx_sparse* S = E->sp;
     if (!S) return;
     void* bufs[] = {S->Ht, S->g64[0], S->g64[1], S->gf[0], S->gf[1], S->cs64[0], S->cs64[1], S->csf[0], S->csf[1],
-                    S->stat_part, S->obj_part, S->hals_part, S->foldin_sweeps};
+                    S->stat_part, S->obj_part, S->hals_part, S->foldin_sweeps, S->mur_foldin_iters};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& sd : S->side) {
         void* sb[] = {sd.idx, sd.val, sd.units, sd.longs, sd.slab, sd.slab64};
@@ -693,6 +710,7 @@ static int sp_ready(nmfx_engine* E, int distance, int64_t first, int64_t count) 
 int nmfx_sparse_mur_run(nmfx_engine* E, int distance, double lw, double lh, int64_t min_iter, double tol1, double tol2,
                         int64_t first, int64_t count) {
     int rc = sp_ready(E, distance, first, count); if (rc) return rc;
+    if (E->sp->mur_foldin_done) { E->sp->mur_foldin_done = false; E->run.w_in_place = false; }      // (W ping-pongs again: a fold-in needs new factors)
     for (int64_t j = first; j < first + count && !rc; ++j) {
 #define SP_IT(KP) sp_iteration<KP>(E, distance, lw, lh, min_iter, tol1, tol2, j)
         switch (E->kp) { case 4: rc = SP_IT(4); break; case 8: rc = SP_IT(8); break; case 16: rc = SP_IT(16); break;
@@ -773,6 +791,7 @@ int nmfx_sparse_set_factors(nmfx_engine* E, const double* w, const double* hmat)
     E->derived.void_all_but(NMFX_D_NONE);
     E->run.reset();
     E->sp->foldin_done = false;
+    E->sp->mur_foldin_done = false;
     int rc;
     if (!E->sp->masked && (rc = stats_both(E))) return rc;
     NMFX_HIP(hipStreamSynchronize(E->stream));
@@ -1571,6 +1590,346 @@ extern "C" int nmfx_hals_foldin_get_sweeps(nmfx_handle_t E, int32_t* out) {
     if (!E->sp || !E->sp->foldin_done) { E->err = "nmfx_hals_foldin_get_sweeps: no nmfx_hals_foldin_run since the factors were set"; return NMFX_E_STATE; }
     NMFX_HIP(hipSetDevice(E->device));
     NMFX_HIP(hipMemcpyAsync(out, E->sp->foldin_sweeps, (size_t)E->n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    return NMFX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// MUR fold-in on a sparse handle (nmfx_sparse_foldin_run)
+// ---------------------------------------------------------------------------------------------------------------------
+// H for the handle's V against the W that was set, under the loss of sparse / masked MUR, W never touched.  With W fixed the
+// columns of H are independent: a column takes the H half-step of sp_phase_kernel over and over, its iterate in the wave's
+// registers (float4 per lane, the same bits in every group), until after step t
+//     delta_t = max_j |h'_j - h_j| <= tol * max_j h'_j        (both in f32; delta_t = 0 counts)
+// or max_iter.  What a step sums that does not depend on h is summed once, before the loop (FIXED):
+//     Euclidean  a = Sum x_e w_e        masked KL  d = Sum w_e        (unmasked: G = W^T W and s = colsum W of nmfx_set_factors)
+// and the loop sums the rest (STEP), q_e = <w_e, h> in f64 by the group butterfly:
+//     KL  a = Sum x_e / (q_e + 1e-9) w_e      masked Euclidean  d = Sum (float) q_e w_e      IS  a = Sum x_e / q^2 w_e, d = Sum 1 / q w_e
+// so on an unmasked handle a Euclidean step is k x k work against G (LDS for KP <= 128) and never touches the entries.  Lane
+// layout, summation order and epilogue are those of sp_phase_kernel: a step of a column of at most SP_CHUNK entries is the H
+// half-step bit for bit.  A column of more entries is one workgroup (sp_mur_foldin_long_kernel): the waves take its pieces
+// wave, wave + SP_WAVES, ..., leave their [a | d] in LDS regions that are added in wave order, wave 0 runs the epilogue and the
+// test and publishes h' and the decision through LDS.  No atomics; every loop bound and exit is wave- (block-) uniform.
+template <int LOSS, bool MASKED> struct SpFi {
+    static constexpr bool EU = LOSS == NMFX_EU, KL = LOSS == NMFX_KL, IS = LOSS == NMFX_IS;
+    static constexpr bool FIXED_A = EU, FIXED_D = KL && MASKED;      // summed once
+    static constexpr bool STEP_A = KL || IS, STEP_D = (EU && MASKED) || IS;   // summed per step
+    static constexpr bool WALKS = STEP_A || STEP_D;                  // (false: unmasked Euclidean)
+};
+
+// One walk over the entries [beg, beg + len) of a column whose iterate is h4: FIXED, the sums formed once; else those of a step.
+// acc / den are this lane's sums (before sp_sum_groups).
+template <int KP, int LOSS, bool MASKED, bool FIXED>
+__device__ __forceinline__ void sp_fi_walk(long long beg, int len, const int32_t* __restrict__ idx, const float* __restrict__ val,
+                                           const float* __restrict__ W, float4 h4, float4& acc, float4& den, int lig, int grp)
+{
+    constexpr int G = KP / 4, NG = 64 / G;
+    using F = SpFi<LOSS, MASKED>;
+    const long long end = beg + len;
+    for (long long e0 = beg + grp; e0 < end; e0 += 4 * NG) {
+        int c[4]; float x[4]; bool ok[4]; float4 w[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const long long e = e0 + (long long)t * NG;
+            ok[t] = e < end;
+            c[t] = ok[t] ? idx[e] : 0;
+            x[t] = ok[t] ? val[e] : 0.f;            // (a slot past the end gathers row 0 with weight 0)
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) w[t] = *reinterpret_cast<const float4*>(W + (int64_t)c[t] * KP + lig * 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            float qa = 0.f, qd = 0.f;
+            if constexpr (FIXED) {
+                qa = x[t]; qd = ok[t] ? 1.f : 0.f;
+            } else {
+                double wh = (double)h4.x * w[t].x + (double)h4.y * w[t].y + (double)h4.z * w[t].z + (double)h4.w * w[t].w;
+#pragma unroll
+                for (int off = 1; off < G; off <<= 1) wh += __shfl_xor(wh, off, 64);
+                if constexpr (F::IS) {
+                    const double iq = 1.0 / (wh + 1e-9);
+                    qa = (float)((double)x[t] * iq * iq); qd = ok[t] ? (float)iq : 0.f;
+                } else if constexpr (F::KL) {
+                    qa = (float)((double)x[t] / (wh + 1e-9));
+                } else {
+                    qd = ok[t] ? (float)wh : 0.f;
+                }
+            }
+            if constexpr (FIXED ? F::FIXED_A : F::STEP_A) {
+                acc.x = fmaf(qa, w[t].x, acc.x); acc.y = fmaf(qa, w[t].y, acc.y);
+                acc.z = fmaf(qa, w[t].z, acc.z); acc.w = fmaf(qa, w[t].w, acc.w);
+            }
+            if constexpr (FIXED ? F::FIXED_D : F::STEP_D) {
+                den.x = fmaf(qd, w[t].x, den.x); den.y = fmaf(qd, w[t].y, den.y);
+                den.z = fmaf(qd, w[t].z, den.z); den.w = fmaf(qd, w[t].w, den.w);
+            }
+        }
+    }
+}
+
+// One step from h4 with the summed a4 / d4: the epilogue of the H half-step in registers, then the stop test.  delta and xmax
+// over the components < k (the padding is 0 before and after) by one butterfly over the group's lanes, made uniform as
+// sp_hals_solve does.  Returns h'; *stop is wave-uniform.
+template <int KP, int LOSS, bool MASKED>
+__device__ __forceinline__ float4 sp_fi_step(float4 h4, float4 a4, float4 d4, const float* __restrict__ Gsrc, const float* __restrict__ S,
+                                             float lam, int k, float tol, int lig, int grp, bool* stop)
+{
+    constexpr int G = KP / 4;
+    using F = SpFi<LOSS, MASKED>;
+    float4 o;
+    if constexpr (MASKED) o = sp_epilogue_masked_value<F::KL, F::IS>(h4, a4, d4, lam, k, lig);
+    else o = sp_epilogue_value<KP, F::KL>(h4, a4, Gsrc, S, lam, k, lig, grp);
+    float delta = fmaxf(fmaxf(fabsf(o.x - h4.x), fabsf(o.y - h4.y)), fmaxf(fabsf(o.z - h4.z), fabsf(o.w - h4.w)));
+    float xmax = fmaxf(fmaxf(o.x, o.y), fmaxf(o.z, o.w));
+#pragma unroll
+    for (int off = 1; off < G; off <<= 1) {
+        delta = fmaxf(delta, __shfl_xor(delta, off, 64));
+        xmax = fmaxf(xmax, __shfl_xor(xmax, off, 64));
+    }
+    delta = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(delta)));
+    xmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xmax)));
+    *stop = delta <= tol * xmax;
+    return o;
+}
+
+// Columns of at most SP_CHUNK entries (the units of side 1 with slot < 0): one wave per column.
+//   W [m][KP]: gathered, never written; Ht [n][KP]: the iterate, read once and written once; Gf / S: W^T W and colsum W in f32
+//   (unmasked handles); iters[col]: the steps the column took.
+template <int KP, int LOSS, bool MASKED>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_mur_foldin_kernel(
+    const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
+    const float* __restrict__ W, float* __restrict__ Ht, const float* __restrict__ Gf, const float* __restrict__ S, float lam, int k,
+    float tol, int max_iter, int32_t* __restrict__ iters, const int* flag)
+{
+    if (*flag) return;
+    constexpr int G = KP / 4;
+    using F = SpFi<LOSS, MASKED>;
+    constexpr bool GLDS = F::EU && !MASKED && KP <= 128;
+    __shared__ __attribute__((aligned(16))) float gs[GLDS ? KP * KP : 4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
+    if constexpr (GLDS) {
+        for (int i = tid * 4; i < KP * KP; i += 64 * SP_WAVES * 4)
+            *reinterpret_cast<float4*>(gs + i) = *reinterpret_cast<const float4*>(Gf + i);
+        __syncthreads();
+    }
+    const float* Gsrc = GLDS ? gs : Gf;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t u = (int64_t)blockIdx.x * SP_WAVES + wave; u < nunits; u += (int64_t)gridDim.x * SP_WAVES) {      // (no block barrier in here)
+        const SpUnit U = units[u];
+        if (U.slot >= 0) continue;                      // a piece of a long column: sp_mur_foldin_long_kernel (wave-uniform)
+        float* row = Ht + (int64_t)U.row * KP;
+        float4 h4 = *reinterpret_cast<const float4*>(row + lig * 4);
+        float4 fa = zero, fd = zero;
+        if constexpr (F::FIXED_A || F::FIXED_D) {
+            sp_fi_walk<KP, LOSS, MASKED, true>(U.beg, U.len, idx, val, W, h4, fa, fd, lig, grp);
+            if constexpr (F::FIXED_A) fa = sp_sum_groups<G>(fa);
+            if constexpr (F::FIXED_D) fd = sp_sum_groups<G>(fd);
+        }
+        int t = 0;
+        for (;;) {                                      // (bounded by max_iter; the exit is wave-uniform)
+            float4 a4 = fa, d4 = fd;
+            if constexpr (F::WALKS) {
+                float4 sa = zero, sd = zero;
+                sp_fi_walk<KP, LOSS, MASKED, false>(U.beg, U.len, idx, val, W, h4, sa, sd, lig, grp);
+                if constexpr (F::STEP_A) a4 = sp_sum_groups<G>(sa);
+                if constexpr (F::STEP_D) d4 = sp_sum_groups<G>(sd);
+            }
+            bool stop;
+            h4 = sp_fi_step<KP, LOSS, MASKED>(h4, a4, d4, Gsrc, S, lam, k, tol, lig, grp, &stop);
+            ++t;
+            if (stop || t >= max_iter) break;
+        }
+        if (grp == 0) *reinterpret_cast<float4*>(row + lig * 4) = h4;
+        if (lane == 0) iters[U.row] = t;
+    }
+}
+
+// this wave's pieces of the long column L (wave, wave + SP_WAVES, ...) walked, and its [a | d] left in its LDS region
+template <int KP, int LOSS, bool MASKED, bool FIXED>
+__device__ __forceinline__ void sp_fi_deposit(const SpLong L, const SpUnit* __restrict__ units, const int32_t* __restrict__ idx,
+                                              const float* __restrict__ val, const float* __restrict__ W, float4 h4, float* part,
+                                              int wave, int lig, int grp)
+{
+    constexpr int G = KP / 4;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), d = a;
+    for (int p = wave; p < L.npieces; p += SP_WAVES) {
+        const SpUnit U = units[(int64_t)L.unit0 + p];
+        sp_fi_walk<KP, LOSS, MASKED, FIXED>(U.beg, U.len, idx, val, W, h4, a, d, lig, grp);
+    }
+    a = sp_sum_groups<G>(a);
+    d = sp_sum_groups<G>(d);
+    if (grp == 0) {
+        float* r = part + wave * (2 * KP) + lig * 4;
+        *reinterpret_cast<float4*>(r) = a;
+        *reinterpret_cast<float4*>(r + KP) = d;
+    }
+}
+
+// the waves' regions added in wave order (every group reads the same words: the same bits)
+template <int KP>
+__device__ __forceinline__ void sp_fi_regions(const float* part, int lig, float4& a, float4& d) {
+    a = make_float4(0.f, 0.f, 0.f, 0.f); d = a;
+#pragma unroll
+    for (int w = 0; w < SP_WAVES; ++w) {
+        const float* r = part + w * (2 * KP) + lig * 4;
+        a = sp_add4(a, *reinterpret_cast<const float4*>(r));
+        d = sp_add4(d, *reinterpret_cast<const float4*>(r + KP));
+    }
+}
+
+// Columns of more than SP_CHUNK entries: one workgroup per column (a blockIdx-strided loop: block-uniform, so every wave
+// reaches every barrier).  Unmasked Euclidean: the pieces are walked once for a, then wave 0 steps alone against G.
+template <int KP, int LOSS, bool MASKED>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_mur_foldin_long_kernel(
+    const SpLong* __restrict__ longs, int64_t nlong, const SpUnit* __restrict__ units, const int32_t* __restrict__ idx,
+    const float* __restrict__ val, const float* __restrict__ W, float* __restrict__ Ht, const float* __restrict__ Gf,
+    const float* __restrict__ S, float lam, int k, float tol, int max_iter, int32_t* __restrict__ iters, const int* flag)
+{
+    if (*flag) return;
+    constexpr int G = KP / 4;
+    using F = SpFi<LOSS, MASKED>;
+    constexpr bool GLDS = F::EU && !MASKED && KP <= 128;
+    __shared__ __attribute__((aligned(16))) float gs[GLDS ? KP * KP : 4];
+    __shared__ __attribute__((aligned(16))) float part[SP_WAVES * 2 * KP];      // region w: wave w's [a | d]
+    __shared__ __attribute__((aligned(16))) float hs[KP];                       // h' of the step
+    __shared__ int go;                                                          // 1: another step
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lig = lane % G, grp = lane / G;
+    if constexpr (GLDS) {
+        for (int i = tid * 4; i < KP * KP; i += 64 * SP_WAVES * 4)
+            *reinterpret_cast<float4*>(gs + i) = *reinterpret_cast<const float4*>(Gf + i);
+        __syncthreads();
+    }
+    const float* Gsrc = GLDS ? gs : Gf;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t l = blockIdx.x; l < nlong; l += gridDim.x) {
+        const SpLong L = longs[l];
+        float* row = Ht + (int64_t)L.row * KP;
+        float4 h4 = *reinterpret_cast<const float4*>(row + lig * 4);
+        float4 fa = zero, fd = zero;                    // (wave 0's)
+        if constexpr (F::FIXED_A || F::FIXED_D) {
+            sp_fi_deposit<KP, LOSS, MASKED, true>(L, units, idx, val, W, h4, part, wave, lig, grp);
+            __syncthreads();
+            if (wave == 0) sp_fi_regions<KP>(part, lig, fa, fd);
+            __syncthreads();                            // (the first step's deposits overwrite the regions)
+        }
+        int t = 0;
+        if constexpr (!F::WALKS) {
+            if (wave == 0) {
+                for (;;) {
+                    bool stop;
+                    h4 = sp_fi_step<KP, LOSS, MASKED>(h4, fa, fd, Gsrc, S, lam, k, tol, lig, grp, &stop);
+                    ++t;
+                    if (stop || t >= max_iter) break;
+                }
+            }
+        } else {
+            for (;;) {                                  // (bounded by max_iter; every wave leaves on the same step)
+                sp_fi_deposit<KP, LOSS, MASKED, false>(L, units, idx, val, W, h4, part, wave, lig, grp);
+                __syncthreads();
+                if (wave == 0) {
+                    float4 a4, d4;
+                    sp_fi_regions<KP>(part, lig, a4, d4);
+                    if constexpr (!F::STEP_A) a4 = fa;
+                    if constexpr (!F::STEP_D) d4 = fd;
+                    bool stop;
+                    const float4 o = sp_fi_step<KP, LOSS, MASKED>(h4, a4, d4, Gsrc, S, lam, k, tol, lig, grp, &stop);
+                    if (grp == 0) *reinterpret_cast<float4*>(hs + lig * 4) = o;
+                    if (lane == 0) go = (stop || t + 1 >= max_iter) ? 0 : 1;
+                }
+                __syncthreads();
+                ++t;
+                h4 = *reinterpret_cast<const float4*>(hs + lig * 4);
+                if (!go) break;
+            }
+        }
+        if (wave == 0) {
+            if (grp == 0) *reinterpret_cast<float4*>(row + lig * 4) = h4;
+            if (lane == 0) iters[L.row] = t;
+        }
+        __syncthreads();                                // (the next column's deposits and decision overwrite the LDS words)
+    }
+}
+
+template <int KP, int LOSS, bool MASKED>
+static int launch_mur_foldin(nmfx_engine* E, float lam, float tol, int max_iter) {
+    nmfx_sparse* S = E->sp;
+    SpSide& sd = S->side[1];
+    const int* flag = &E->state->flag;
+    const float* W = E->W[0];
+    hipLaunchKernelGGL((sp_mur_foldin_kernel<KP, LOSS, MASKED>), dim3(sd.nblk), dim3(64 * SP_WAVES), 0, E->stream, (const SpUnit*)sd.units,
+                       sd.nunits, (const int32_t*)sd.idx, (const float*)sd.val, W, S->Ht, (const float*)S->gf[0], (const float*)S->csf[0],
+                       lam, E->k, tol, max_iter, S->mur_foldin_iters, flag);
+    NMFX_HIP(hipGetLastError());
+    if (sd.nlong) {
+        const int nl = (int)std::min<int64_t>(4 * E->ncu, sd.nlong);
+        hipLaunchKernelGGL((sp_mur_foldin_long_kernel<KP, LOSS, MASKED>), dim3(nl), dim3(64 * SP_WAVES), 0, E->stream,
+                           (const SpLong*)sd.longs, sd.nlong, (const SpUnit*)sd.units, (const int32_t*)sd.idx, (const float*)sd.val, W,
+                           S->Ht, (const float*)S->gf[0], (const float*)S->csf[0], lam, E->k, tol, max_iter, S->mur_foldin_iters, flag);
+        NMFX_HIP(hipGetLastError());
+    }
+    return NMFX_OK;
+}
+
+// the solve, then on an unmasked handle the statistics of the new H (the objective reads them; they are current on return)
+template <int KP>
+static int sp_mur_foldin(nmfx_engine* E, int loss, float lam, float tol, int max_iter) {
+    int rc;
+    { ProfScope ps(E, "sp_mur_foldin");
+      if (E->sp->masked)
+          rc = loss == NMFX_IS ? launch_mur_foldin<KP, NMFX_IS, true>(E, lam, tol, max_iter)
+             : loss == NMFX_KL ? launch_mur_foldin<KP, NMFX_KL, true>(E, lam, tol, max_iter)
+                               : launch_mur_foldin<KP, NMFX_EU, true>(E, lam, tol, max_iter);
+      else
+          rc = loss == NMFX_KL ? launch_mur_foldin<KP, NMFX_KL, false>(E, lam, tol, max_iter)
+                               : launch_mur_foldin<KP, NMFX_EU, false>(E, lam, tol, max_iter);
+      if (rc) return rc; }
+    if (!E->sp->masked) {
+      ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<KP>(E, E->sp->Ht, E->n, 1, &E->state->flag))) return rc; }
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_sparse_foldin_run(nmfx_handle_t E, int distance, double lambda_h, double tol, int max_iter) {
+    const std::string who = "nmfx_sparse_foldin_run";
+    if (!E) return NMFX_E_ARG;
+    if (!E->sp) { E->err = who + ": needs a sparse handle (nmfx_create_csr), masked or not; a dense handle runs nmfx_foldin_run"; return NMFX_E_ARG; }
+    nmfx_sparse* S = E->sp;
+    nmfx_entry a = {NMFX_FAM_MUR, 0, 0, NMFX_D_NONE, NMFX_D_NONE};      // (derives nothing from (W, H) that outlives the call)
+    if (distance == NMFX_IS && !S->masked)
+        a.bad = who + ": the Itakura-Saito divergence (IS) is infinite at the zeros of an unmasked sparse V: make the handle masked (nmfx_set_masked)";
+    else if (distance != NMFX_EU && distance != NMFX_KL && distance != NMFX_IS)
+        a.bad = who + ": the distance must be NMFX_EU, NMFX_KL or (masked handles) NMFX_IS";
+    else if (!(tol >= 0.0 && tol < 1.0)) a.bad = who + ": tol must be at least 0 and below 1";
+    else if (max_iter < 1 || max_iter > 10000) a.bad = who + ": max_iter must be between 1 and 10000";
+    else if (!(lambda_h >= 0)) a.bad = who + ": bad lambda";
+    else if (E->run.started && !S->mur_foldin_done) {   // (MUR has ping-ponged W since: W[0] need not be the current one)
+        a.bad = who + ": nmfx_mur_run has iterated on this handle since nmfx_set_factors: set the factors again first";
+        a.bad_rc = NMFX_E_STATE;
+    }
+    int rc = nmfx_enter(E, a); if (rc) return rc;
+    E->run.mur_loss(distance);
+    E->run.in_place();                                 // (W[0], never written; H^T in place)
+    if ((rc = nmfx_lazy_alloc(E, &S->mur_foldin_iters, std::max<int64_t>(1, E->n)))) return rc;
+    const int* flag = &E->state->flag;
+    if ((rc = objective_pass(E, distance, E->W[0], flag))) return rc;
+    if ((rc = launch_objective(E, distance, E->xf64, true, 0, SP_FOLDIN_NEVER, 0.0, 0.0))) return rc;
+#define SP_MFI(KP) sp_mur_foldin<KP>(E, distance, (float)lambda_h, (float)tol, max_iter)
+    switch (E->kp) { case 4: rc = SP_MFI(4); break; case 8: rc = SP_MFI(8); break; case 16: rc = SP_MFI(16); break;
+                     case 32: rc = SP_MFI(32); break; case 64: rc = SP_MFI(64); break; case 128: rc = SP_MFI(128); break;
+                     default: rc = SP_MFI(256); break; }
+#undef SP_MFI
+    if (rc) return rc;
+    if ((rc = objective_pass(E, distance, E->W[0], flag))) return rc;
+    if ((rc = launch_objective(E, distance, E->xf64, true, 1, SP_FOLDIN_NEVER, 0.0, 0.0))) return rc;
+    S->mur_foldin_done = true;
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_sparse_foldin_get_iters(nmfx_handle_t E, int32_t* out) {
+    if (!E || !out) return NMFX_E_ARG;
+    if (!E->sp || !E->sp->mur_foldin_done) { E->err = "nmfx_sparse_foldin_get_iters: no nmfx_sparse_foldin_run since the factors were set"; return NMFX_E_STATE; }
+    NMFX_HIP(hipSetDevice(E->device));
+    NMFX_HIP(hipMemcpyAsync(out, E->sp->mur_foldin_iters, (size_t)E->n * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));
     return NMFX_OK;
 }

@@ -432,6 +432,18 @@ class Engine:
         self._ck(self.lib.nmfx_hals_foldin_dense_get_sweeps(self.h, _ptr(out)))
         return out
 
+    def sparse_foldin_run(self, dist, lam_h, tol, max_iter):
+        """H against the fixed W that was set, on a sparse handle (masked or not), under the loss `dist` of sparse / masked MUR:
+        every column repeats the H half-step in one launch until its own stop rule or `max_iter` (include/nmfx.h); records
+        obj[0] of the start and obj[1] of the result."""
+        self._ck(self.lib.nmfx_sparse_foldin_run(self.h, int(dist), float(lam_h), float(tol), int(max_iter)))
+
+    def sparse_foldin_iters(self):
+        """The steps each column took in the last sparse_foldin_run: int32, length n."""
+        out = np.empty(self.n, dtype=np.int32)
+        self._ck(self.lib.nmfx_sparse_foldin_get_iters(self.h, _ptr(out)))
+        return out
+
     def hals_stack_set(self, ks):
         """Problem p owns the components [sum(ks[:p]), sum(ks[:p + 1])); () clears the stack.  After set_factors, before the run."""
         ks = [int(k) for k in ks]

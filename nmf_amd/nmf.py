@@ -72,6 +72,19 @@ class NMF:
                 kw['beta'] = getattr(exp, 'beta', None)
         return transform(data, self.w, **kw)
 
+    def transform_sparse(self, data, mask=None, **kw):
+        """H for new sparse or masked `data` against the dictionary self.w of the last factorize, under the loss that
+        factorize used (nmf_amd.transform.transform_sparse): returns SparseTransformResults(h, iters, obj_history,
+        experiment).  distance_type defaults to the last factorize's when that was 'eu', 'kl' or 'is' (the function's own
+        default otherwise); every keyword of transform_sparse may be given.  `transform` keeps the routes it has."""
+        if self.results is None or self.w is None:
+            raise RuntimeError('NMF.transform needs a dictionary: call factorize first')
+        from .transform import transform_sparse
+        fitted = getattr(self.results.experiment, 'distance_type', None)
+        if 'distance_type' not in kw and isinstance(fitted, str) and fitted in ('eu', 'kl', 'is'):
+            kw['distance_type'] = fitted
+        return transform_sparse(data, self.w, mask, **kw)
+
     def save_factorization(self, save_dir='./results', save_name=None):
         """Write results to `save_dir`/`save_name`.npz; the default name follows
         the grammar of nmf/nmf.py:95-126, e.g. nmf_ao_admm_3_eu_0:nn_0.5:l1n_random."""
