@@ -310,7 +310,50 @@ int nmfx_mur_phase_b_rest(nmfx_handle_t h, int distance, int64_t c0, int64_t c1)
  *                   partial, least significant first; phase A writes the slots [0, world) -- its own digits, +0.0 elsewhere.
  * Phase A writes every element phase B reads, and so does nmfx_mur_finish_a for nmfx_mur_finish_b (f64 part [0]): neither buffer
  * needs to be zeroed by the caller, and what a phase does not write (f64 [1, 8) in MUR, tail slots from `world` on, the ranges of
- * other ranks after a reduce-scatter) is never read.  tests/test_gpu_shard_step.py fills all of it with NaN.            */
+ * other ranks after a reduce-scatter) is never read.  tests/test_gpu_shard_step.py fills all of it with NaN.
+ *
+ * The phases of the other solvers (declared further down), k <= 128 in either arithmetic mode and composed beyond 128 components.
+ * Layout of the f32 part behind every products phase of ADMM, AO-ADMM (both losses) and ANLS (mur_pack_kernel, pack_t_kernel, the
+ * generic products): P = [0, kp n_pad + kp kp): the product [factor][column], element f n_pad + c, then the Gram matrix [kp][kp]
+ * at kp n_pad; the padded rows and columns of both are exactly zero.  What lies behind P (the column-sum slot of composed MUR-KL,
+ * the tail) is neither written nor read by these phases, though the caller's all-reduce of the whole buffer carries it along.
+ * "reads" means: after the caller's all-reduce.  "keeps": what has to survive from an EARLIER phase when this one starts;
+ * everything else of both buffers may hold anything then (tests/test_gpu_shard_family_step.py makes it NaN before every phase
+ * that precedes a collective).
+ *   phase                              writes                              reads                               keeps
+ *   admm_phase_products(j)             P, f64 [0]                          -                                   composed, j > 0: f64 [0]
+ *   admm_phase_update                  composed: f64 [0] of the new pair   P, f64 [0]                          -
+ *   aoadmm_phase_h_products(j)         P, f64 [0]                          -                                   composed, j > 0: f64 [0]
+ *   aoadmm_phase_h_solve               -                                   P, f64 [0]                          -
+ *   aoadmm_phase_w_products            -                                   -                                   -
+ *   aoadmm_phase_w_round(r)            f64 [1, 5)                          r > 0: f64 [1, 5) of round r - 1    r > 0: f64 [1, 5)
+ *   aoadmm_phase_w_close               composed: f64 [0] of the new pair   f64 [1, 5) of the last round        -
+ *   aoadmm_phase_w_fused               f64 [8, 8 + 4 admm_iter)            -                                   -
+ *   aoadmm_phase_w_repair              -                                   f64 [8, 8 + 4 admm_iter)            -
+ *   aoadmm_kl_phase_h_products(j, r)   r = 0: P, f64 [0]; r > 0: the       -                                   composed, j > 0, r = 0:
+ *                                      product (k <= 128: all of P)                                            f64 [0]
+ *   aoadmm_kl_phase_h_round(r)         -                                   r = 0: P, f64 [0]; r > 0: the       -
+ *                                                                          product part of P
+ *   aoadmm_kl_phase_h_close            -                                   -                                   -
+ *   aoadmm_kl_phase_w_round(r)         as aoadmm_phase_w_round             as aoadmm_phase_w_round             r > 0: f64 [1, 5)
+ *   aoadmm_kl_phase_w_close            composed: f64 [0] of the new pair   f64 [1, 5) of the last round        -
+ *   anls_phase_objective               f64 [0]                             -                                   -
+ *   anls_phase_w                       P                                   f64 [0]                             f64 [0]
+ *   anls_phase_h                       -                                   P                                   -
+ *   nmfx_objective_partial             f64 [0]; composed ADMM / AO-ADMM:   -                                   composed ADMM / AO-ADMM:
+ *                                      nothing                                                                 f64 [0]
+ *   nmfx_mur_finish_b                  -                                   f64 [0]                             -
+ * The one value that lives from one outer iteration into the next inside an exchange buffer: beyond 128 components ADMM and
+ * AO-ADMM (both losses) close every iteration with the objective partial of the new pair in f64 [0] (phase_update, phase_w_close,
+ * and the run entry points alike); the next products phase and nmfx_objective_partial leave it where it is.  Up to 128 components
+ * the partials wait in the handle and the products phase / nmfx_objective_partial sum them into f64 [0].
+ * No phase reads f64 [5, 8), a table row from admm_iter on, or an element of P it is not listed with.  Behind the inner stop of a
+ * KL sub-problem the remaining rounds write and read nothing: their exchanges move whatever the buffers hold.  The W rounds after
+ * the stop of the W sub-problem likewise (the all-reduce then multiplies the kept sums by the world's size, which the two ratios
+ * of `terminate` do not see).
+ * The KL phase entry points are the exact-f32 ones in either arithmetic mode and keep v_aux / dual_v row-major; nmfx_admm_run and
+ * nmfx_aoadmm_run in split-bf16 mode keep them tile-major.  A handle changes from the run entry points to the KL phases (or back)
+ * only through nmfx_set_factors: otherwise the phases read auxiliaries the run never stored there.                      */
 int nmfx_exchange_sizes(nmfx_handle_t h, int64_t* n_f32, int64_t* n_f64);
 /* Stream-capture support for the caller-driven loop.  The phase calls only queue launches on the
  * handle's stream, so a caller may capture  phase_a(j=0) . all-reduce . phase_b(j=0) .

@@ -103,6 +103,7 @@ class HostShard(Shard):
             self.dual_w = np.zeros_like(self.w)
             self.dual_h = np.zeros_like(self.h)
             self.inner = {}
+            self.fired = {}                                 # (j, side) -> the inner stop test fired: bit 16 of the device's word
 
     def aoadmm_phase_h_products(self, j):
         self._ao_init()
@@ -131,7 +132,7 @@ class HostShard(Shard):
         g = x[k * n:k * n + k * k].reshape(k, k).copy()
         rho = np.trace(g) / k
         chol = sla.cholesky(g + rho * np.eye(k), lower=True)
-        ran = 0
+        ran, fired = 0, False
         for r in range(admm_iter):
             aux = sla.cho_solve((chol, True), b + rho * (self.h + self.dual_h))
             prev = self.h
@@ -139,8 +140,10 @@ class HostShard(Shard):
             self.dual_h = self.dual_h + self.h - aux
             ran = r + 1
             if R.inner_stop(self.h, prev, aux, self.dual_h):
+                fired = True
                 break
         self.inner[(j, 0)] = ran
+        self.fired[(j, 0)] = fired
 
     def aoadmm_phase_w_products(self, min_iter, tol1, tol2, j):
         import scipy.linalg as sla
@@ -175,9 +178,22 @@ class HostShard(Shard):
         self.w, self.dual_w = new.T.copy(), dual.T.copy()
         self._w_ran = rnd + 1
 
+    def _norms_say_stop(self):
+        """`terminate` (ao_admm.py:33-43) on the all-reduced sums of squares in x64[1:5]."""
+        n0, n1, n2, n3 = (float(t) for t in self.x64[1:5])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.sqrt(n0) / np.sqrt(n1)
+            s = np.sqrt(n2) / np.sqrt(n3)
+        return bool(r < 1e-2 and s < 1e-2)
+
+    def _w_closed(self, admm_iter, j):
+        self.inner[(j, 1)] = self._w_ran
+        # the last round's decision is nobody's input: it only sets the break bit of the recorded word
+        self.fired[(j, 1)] = self._w_stop or (self._w_ran == admm_iter and admm_iter > 0 and self._norms_say_stop())
+
     def aoadmm_phase_w_close(self, admm_iter, j):
         if not self.flag:
-            self.inner[(j, 1)] = self._w_ran
+            self._w_closed(admm_iter, j)
 
     # the W sub-problem with ONE exchange (nmfx_aoadmm_phase_w_fused / _repair): all rounds speculatively, the norm
     # sums of every round into x64[8 + 4 r + c]; after the all-reduce the stopping round is derived and the rows are
@@ -207,18 +223,19 @@ class HostShard(Shard):
         if self.flag:
             return
         table = self.x64[8:8 + 4 * admm_iter].numpy().reshape(admm_iter, 4)
-        rounds = admm_iter
+        rounds, fired = admm_iter, False
         for rnd in range(admm_iter):
             with np.errstate(divide="ignore", invalid="ignore"):
                 r = np.sqrt(table[rnd, 0]) / np.sqrt(table[rnd, 1])
                 s = np.sqrt(table[rnd, 2]) / np.sqrt(table[rnd, 3])
             if r < 1e-2 and s < 1e-2:
-                rounds = rnd + 1
+                rounds, fired = rnd + 1, True
                 break
         if rounds < admm_iter:
             wt, dt = self._w_rounds(prox_w, lam_w, rounds)
             self.w, self.dual_w = wt.T.copy(), dt.T.copy()
         self.inner[(j, 1)] = rounds
+        self.fired[(j, 1)] = fired
 
     # ---- AO-ADMM, KL loss (nmf/ao_admm.py:71-101, 277-283) in the sharded protocol: one exchange per inner round ----
     def _ao_kl_init(self):
@@ -272,6 +289,7 @@ class HostShard(Shard):
         if self.flag:
             return
         self.inner[(j, 0)] = self._h_ran
+        self.fired[(j, 0)] = self._h_stop
         g = self.h @ self.h.T
         self._rho_w = np.trace(g) / self.k
         self._chol_w = sla.cholesky(g + self._rho_w * np.eye(self.k), lower=True)
@@ -307,7 +325,7 @@ class HostShard(Shard):
 
     def aoadmm_kl_phase_w_close(self, admm_iter, j):
         if not self.flag:
-            self.inner[(j, 1)] = self._w_ran
+            self._w_closed(admm_iter, j)
 
     # ---- ADMM (nmf/admm.py:292-334) in the sharded protocol ----
     def set_l2n_operator(self, which, p):
@@ -404,6 +422,23 @@ class HostShard(Shard):
 
     def get_factors(self):
         return self.w, self.h
+
+    # ---- read-back under the Engine's names (tests/shard_step.py) ----
+    def get_matrix(self, name):
+        """'w_aux' | 'h_aux' | 'dual_w' | 'dual_h' of the ADMM / AO-ADMM state, as nmfx_get_matrix."""
+        if name not in ("w_aux", "h_aux", "dual_w", "dual_h"):
+            raise KeyError(name)
+        return np.array(getattr(self, name), dtype=np.float64)
+
+    def inner_counts(self, first, count):
+        """[count][2] words (H, W sub-problem) as nmfx_get_inner_counts: low 16 bits = rounds run, bit 16 = the stop fired."""
+        inner, fired = getattr(self, "inner", {}), getattr(self, "fired", {})
+        return np.array([[inner.get((j, s), 0) | (int(fired.get((j, s), False)) << 16) for s in (0, 1)]
+                         for j in range(first, first + count)], dtype=np.int32).reshape(count, 2)
+
+    def l2n_operator(self, which):
+        """What set_l2n_operator stored for side `which` (0: W, 1: H), or None."""
+        return getattr(self, "l2n", {}).get(which)
 
 
 class ChunkedHostShard(HostShard):
