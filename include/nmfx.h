@@ -55,7 +55,9 @@ enum { NMFX_PROX_NN = 0, NMFX_PROX_L1N = 1, NMFX_PROX_L2N = 2,      /* reg type 
  * GPU; a row shard when the caller shards rows over ranks).  k <= 4096 (nmf/nmf.py:32-35 accepts any `factors`): up to 128
  * every solver runs its tuned kernels; beyond that (padded to a multiple of 128) the MUR entry points and the whole-loop
  * entry points nmfx_aoadmm_run / nmfx_admm_run / nmfx_anls_run compose their iterations from a generic exact-f32 product
- * kernel (kernels_generic.hip); the row-sharded phase entry points of AO-ADMM / ADMM / ANLS stay at k <= 128. */
+ * kernel (kernels_generic.hip); the row-sharded phase entry points of AO-ADMM / ADMM / ANLS stay at k <= 128.  HALS runs
+ * up to 128 components through nmfx_hals_run and from 129 to 1024 through nmfx_hals_wide_run (version 396); its sparse, masked,
+ * stacked and fold-in forms stay at the ranks their sections name. */
 int nmfx_create(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k);
 int nmfx_destroy(nmfx_handle_t h);
 const char* nmfx_last_error(nmfx_handle_t h);        /* h may be NULL            */
@@ -566,6 +568,19 @@ int nmfx_anls_phase_h(nmfx_handle_t h, double lambda_h, int64_t j);
 int nmfx_hals_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
                   int64_t min_iter, double tol1, double tol2,
                   int64_t first, int64_t count);
+
+/* ---- HALS beyond 128 components (version 396) ------------------------------------------------------------------------------
+ * The iteration of nmfx_hals_run on a dense handle without weights and 128 < k <= 1024, on the products of nmfx_anls_run beyond
+ * 128 components: both Gram matrices in exact f32, the two V-sized products in the handle's arithmetic mode, then `sweeps`
+ * sweeps of the rule above per row of W / column of H by a kernel that streams G through LDS in row tiles.
+ * Update order, the exact-zero clamp, a component with G_jj = 0 keeping its value and the zero padding are those of
+ * nmfx_hals_run; no atomics, two runs give the same bits.  Records, stop rule, nmfx_anls_set_distance and the closing
+ * nmfx_aoadmm_finish as nmfx_hals_run; the family in the entry guard is HALS's, so nmfx_anls_run does not continue its run
+ * without nmfx_set_factors (NMFX_E_STATE).  NMFX_E_ARG, nothing launched: a sparse handle, a handle with weights, k <= 128
+ * (nmfx_hals_run serves those), k > 1024, and the argument rules of nmfx_hals_run.                                            */
+int nmfx_hals_wide_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
+                       int64_t min_iter, double tol1, double tol2,
+                       int64_t first, int64_t count);
 
 /* ---- HALS on sparse handles (version 391) ----------------------------------------------------------------------------------
  * The outer iteration of nmfx_hals_run on an unmasked nmfx_create_csr handle with k <= 128: the W half-step, then the H

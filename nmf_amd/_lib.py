@@ -116,6 +116,7 @@ SIGNATURES = {
     "nmfx_anls_set_distance": (_i32, [_vp, _i32]),
     "nmfx_anls_run": (_i32, [_vp, _dbl, _dbl, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_hals_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
+    "nmfx_hals_wide_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_hals_sparse_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_hals_sparse_finish": (_i32, [_vp, _i64, _dbl, _dbl, _i64]),
     "nmfx_hals_masked_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),

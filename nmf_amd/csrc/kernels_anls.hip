@@ -794,6 +794,21 @@ extern "C" int nmfx_hals_run(nmfx_handle_t E, double lambda_w, double lambda_h, 
     return NMFX_OK;
 }
 
+// HALS beyond 128 components (include/nmfx.h, version 396): the loop of nmfx_anls_run beyond 128 components with
+// the sweeps of hals_wide_sweep_kernel as its solve; the family and the argument rules of nmfx_hals_run
+extern "C" int nmfx_hals_wide_run(nmfx_handle_t E, double lambda_w, double lambda_h, int sweeps, int64_t min_iter, double tol1,
+                                  double tol2, int64_t first, int64_t count) {
+    const char* who = "nmfx_hals_wide_run";
+    if (!E) return NMFX_E_ARG;
+    if (E->sp) { E->err = std::string(who) + ": needs a dense handle (nmfx_create); a sparse handle runs nmfx_hals_sparse_run with k <= 128"; return NMFX_E_ARG; }
+    NMFX_DENSE_ONLY(E);
+    if (E->kp <= 128) { E->err = std::string(who) + ": serves more than 128 components; nmfx_hals_run runs k <= 128"; return NMFX_E_ARG; }
+    if (E->k > 1024) { E->err = std::string(who) + ": supports at most 1024 components (the sweep keeps k / 64 variables per lane in registers)"; return NMFX_E_ARG; }
+    const std::string bad = nmfx_hals_args_bad(who, sweeps, first, count, &lambda_w, &lambda_h);
+    int rc = anls_ready(E, first, count, !bad.empty(), true, NMFX_FAM_HALS, bad.c_str()); if (rc) return rc;
+    return nmfx_generic_anls_run(E, lambda_w, lambda_h, min_iter, tol1, tol2, first, count, sweeps);
+}
+
 // ---- dense HALS fold-in (include/nmfx.h, version 394) -----------------------------------------------------------
 // H for the handle's V against the W that was set, W never touched.  Every column shares G = W^T W + 2 lambda_h I and its
 // right-hand side is a column of W^T V: the products of the H half-step, formed once (ls_h_products, in the handle's arithmetic

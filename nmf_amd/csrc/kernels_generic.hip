@@ -2315,9 +2315,16 @@ int gx_nnls(nmfx_engine* E, const float* G, double diag_add, const float* R, flo
 }  // namespace
 
 // ANLS outer iterations (anls.py:111-126): rows of W from G = H H^T + 2 lw I, r = rows of V H^T; columns of H from G = W^T W + 2 lh I,
-// r = columns of W^T V; the objective (Euclidean or KL, E->anls_dist) of the new pair
-int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count) {
+// r = columns of W^T V; the objective (Euclidean or KL, E->anls_dist) of the new pair.
+// The least-squares iteration beyond 128 components, written once: `sweeps` = 0 solves every problem exactly (gx_nnls: ANLS),
+// 1 .. 16 makes that many projected Gauss-Seidel sweeps from the current solution instead (nmfx_hals_wide_sweep: HALS, with
+// (float)(2 lambda) on the diagonal as nmfx_hals_run forms it).  Everything around the solve is the same launches in the same order.
+int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count,
+                          int sweeps) {
     int rc;
+    auto solve = [&](const float* G, double lam, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob) {
+        return sweeps ? nmfx_hals_wide_sweep(E, G, (float)(2.0 * lam), R, X, sj, sc, nprob, sweeps) : gx_nnls(E, G, 2.0 * lam, R, X, sj, sc, nprob);
+    };
     if ((rc = gx_buffers(E, false))) return rc;
     const int64_t mp = E->mp, np = E->np, kp = E->kp;
     const bool kl = E->anls_dist == NMFX_KL;
@@ -2341,7 +2348,7 @@ int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t mi
           if (bf) rc = gxt_split_product(E, E->gxb_v[0], E->gxb_v[1], E->Hhi, E->Hlo, E->A_part, mp, kp, np, 4, 4);
           else rc = gx_split_product<true, true>(E, E->V, np, E->H, np, E->A_part, mp, kp, np, 1);
           if (rc) return rc; }
-        if ((rc = gx_nnls(E, E->HHt, 2.0 * lam_w, E->A_part, W, 1, kp, E->m))) return rc;
+        if ((rc = solve(E->HHt, lam_w, E->A_part, W, 1, kp, E->m))) return rc;
         if (bf) { ProfScope ps(E, "images");
                   if ((rc = gxb_images_w(E, W))) return rc; }
         { ProfScope ps(E, "gram_tn");
@@ -2350,7 +2357,7 @@ int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t mi
           if (bf) rc = gxt_split_product(E, E->WThi, E->WTlo, E->gxb_v[2], E->gxb_v[3], xB, kp, np, mp, 8, 4);
           else rc = gx_split_product<false, false>(E, W, kp, E->V, np, xB, kp, np, mp, 8);
           if (rc) return rc; }
-        if ((rc = gx_nnls(E, xG, 2.0 * lam_h, xB, E->H, np, 1, E->n))) return rc;
+        if ((rc = solve(xG, lam_h, xB, E->H, np, 1, E->n))) return rc;
         if (bf) { ProfScope ps(E, "images");
                   if ((rc = gxb_images_h(E, E->H))) return rc; }
         if ((rc = kl ? gx_kl_objective_partial(E) : gx_objective_partial(E, bf))) return rc;

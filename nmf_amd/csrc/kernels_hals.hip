@@ -181,6 +181,143 @@ int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float*
                           : hals_sweep_kp<true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, stack_side);
 }
 
+// ---- beyond 128 components: G streamed through LDS in row tiles (nmfx_hals_wide_run) ------------------------------
+// The sweep of hals_sweep_kernel at kp = 256, 384, .. 1024, where the kp x kp copy of G no longer fits in LDS (256 KiB at kp = 256).
+// One wavefront still owns one problem, variable i on lane i % 64, slot i / 64 (NV = kp / 64 per lane), with the kept residual, the
+// bound -x and 1 / G_jj (read once per launch from the diagonal in global memory) in registers; step j is the step above.  G
+// reaches the waves in tiles of T rows, T kp 4 B <= 64 KiB: the block stages rows j0 .. j0 + T - 1 (2 lambda on the diagonal as
+// it is staged) and each of its eight waves consumes them for its own problem -- once for the mat-vec, then once per sweep, the
+// rows in ascending order: the update order is the definition's, x_0 .. x_{j-1} are new when step j runs.  T divides 64, so a
+// tile's rows belong to one slot and the slot loop unrolls.
+// The tile hand-over needs two block barriers per tile, so every loop around them is BLOCK-UNIFORM: the trip count of the loop over
+// the problems is computed from nprob and the grid alone, every wave makes every trip, and a wave whose problem index is at or
+// beyond nprob works on zeros and skips only its global loads and stores.  The early return on st->flag is grid-uniform and
+// stands in front of the first barrier.  No atomics, a fixed order of every sum: two runs give the same bits.
+template <int KP>
+__global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_wide_sweep_kernel(
+    const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
+    int64_t sj, int64_t sc, int64_t nprob, int k, int sweeps, const DevState* __restrict__ st)
+{
+    if (st->flag) return;                               // (the stop rule has fired: the iterate stays; the same word for every block)
+    constexpr int NV = KP / 64;                         // variables per lane
+    constexpr int NW = NMFX_HALS_WAVES;
+    constexpr int T = KP <= 256 ? 64 : KP <= 512 ? 32 : 16;      // rows of a tile
+    static_assert(KP % 128 == 0 && KP >= 256 && KP <= 1024 && T * KP * 4 <= 65536 && (T * KP / 4) % (64 * NW) == 0, "tile");
+    extern __shared__ __attribute__((aligned(16))) float hals_tile[];   // rows j0 .. j0 + T - 1 of G + diag_add I, [T][KP]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool valid[NV], live[NV]; float inv[NV];
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+        const int idx = lane + 64 * t;                  // (< KP)
+        valid[t] = idx < k;
+        const float gd = G[(int64_t)idx * KP + idx] + diag_add;
+        live[t] = valid[t] && gd > 0.f;
+        inv[t] = live[t] ? 1.f / gd : 0.f;
+    }
+    const int64_t per_trip = (int64_t)gridDim.x * NW;
+    const int64_t trips = (nprob + per_trip - 1) / per_trip;            // (the same for every block)
+    for (int64_t trip = 0; trip < trips; ++trip) {
+        const int64_t c = trip * per_trip + (int64_t)blockIdx.x * NW + wave;
+        const bool mine = c < nprob;                    // (wave-uniform; decides loads and stores only)
+        float x[NV], g[NV], nx[NV];
+#pragma unroll
+        for (int t = 0; t < NV; ++t) {
+            const int64_t off = (int64_t)(lane + 64 * t) * sj + c * sc;
+            x[t] = (mine && valid[t]) ? X[off] : 0.f;
+            g[t] = (mine && valid[t]) ? R[off] : 0.f;
+            nx[t] = live[t] ? -x[t] : 0.f;              // the lower bound of a step, max(-x_j, .); 0 with inv = 0 where G_jj = 0: a step of 0
+        }
+        auto matvec = [&](int t2, int l, const float (&col)[NV]) {
+            const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t2]), l));
+#pragma unroll
+            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], xl, g[t]);
+        };
+        auto step = [&](int t2, int j, const float (&col)[NV]) {
+            const float cand = fmaxf(nx[t2], g[t2] * inv[t2]);
+            const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), j));
+            nx[t2] = (lane == j) ? nx[t2] - d : nx[t2];          // (d = -x_j: an exact zero)
+#pragma unroll
+            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], d, g[t]);
+        };
+        auto row = [&](int jj, float (&out)[NV]) {      // this lane's entries of row jj of the tile
+#pragma unroll
+            for (int t = 0; t < NV; ++t) out[t] = hals_tile[jj * KP + lane + 64 * t];
+        };
+        // one pass over the rows 0 .. k - 1 of G, tile by tile: op(slot, lane of the row's variable, the row)
+        auto pass = [&](auto&& op) {
+#pragma unroll
+            for (int t2 = 0; t2 < NV; ++t2) {
+                for (int j0 = 64 * t2; j0 < 64 * t2 + 64 && j0 < k; j0 += T) {       // (k: block-uniform)
+                    __syncthreads();                    // every wave has consumed the tile before
+                    for (int i4 = threadIdx.x; i4 < T * KP / 4; i4 += 64 * NW) {
+                        float4 v = *reinterpret_cast<const float4*>(G + (int64_t)j0 * KP + 4 * (int64_t)i4);     // (j0 + T <= KP)
+                        const int r = j0 + (4 * i4) / KP, col = (4 * i4) % KP;
+                        v.x += (col == r) ? diag_add : 0.f; v.y += (col + 1 == r) ? diag_add : 0.f;
+                        v.z += (col + 2 == r) ? diag_add : 0.f; v.w += (col + 3 == r) ? diag_add : 0.f;
+                        *reinterpret_cast<float4*>(hals_tile + 4 * i4) = v;
+                    }
+                    __syncthreads();
+                    const int lim = k - j0 < T ? k - j0 : T, l0 = j0 - 64 * t2;
+                    int j = 0;
+                    for (; j + 4 <= lim; j += 4) {       // four rows at a time: four LDS reads in flight together
+                        float c0[NV], c1[NV], c2[NV], c3[NV];
+                        row(j, c0); row(j + 1, c1); row(j + 2, c2); row(j + 3, c3);
+                        op(t2, l0 + j, c0); op(t2, l0 + j + 1, c1); op(t2, l0 + j + 2, c2); op(t2, l0 + j + 3, c3);
+                    }
+                    for (; j < lim; ++j) {
+                        float c0[NV];
+                        row(j, c0);
+                        op(t2, l0 + j, c0);
+                    }
+                }
+            }
+        };
+        pass(matvec);                                   // g = r - G x
+        for (int s = 0; s < sweeps; ++s) pass(step);
+        if (mine) {
+#pragma unroll
+            for (int t = 0; t < NV; ++t)
+                X[(int64_t)(lane + 64 * t) * sj + c * sc] = live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0; padded lanes hold x = 0)
+        }
+    }
+}
+
+template <int KP>
+static int launch_hals_wide_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                                  int64_t nprob, int sweeps) {
+    int rc;
+    const size_t shm = (size_t)(KP <= 256 ? 64 : KP <= 512 ? 32 : 16) * KP * sizeof(float);
+    auto kern = hals_wide_sweep_kernel<KP>;
+    if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm))) return rc;
+    const int64_t blocks_needed = (nprob + NMFX_HALS_WAVES - 1) / NMFX_HALS_WAVES;
+    const int64_t round = (int64_t)E->ncu * NMFX_HALS_BLOCKS_PER_CU;      // (a tile is at most 64 KiB: two blocks per CU)
+    const unsigned grid = (unsigned)(blocks_needed < round ? blocks_needed : round);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NMFX_HALS_WAVES), shm, E->stream, G, diag_add, R, X, sj, sc, nprob, E->k, sweeps,
+                       E->state);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+// Arguments and strides as nmfx_hals_sweep.  kp = 1024 is the last rank whose kept values fit the registers of a wave
+// (about 4 NV VGPRs, plus NV per row of G in flight): nothing beyond it is instantiated.
+int nmfx_hals_wide_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                         int64_t nprob, int sweeps) {
+    ProfScope ps(E, "hals_sweep");
+    ProfScope side(E, sc == 1 ? "hals_sweep_h" : "hals_sweep_w");
+    if (nprob <= 0) return NMFX_OK;
+    switch (E->kp) {
+        case 256: return launch_hals_wide_sweep<256>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 384: return launch_hals_wide_sweep<384>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 512: return launch_hals_wide_sweep<512>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 640: return launch_hals_wide_sweep<640>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 768: return launch_hals_wide_sweep<768>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 896: return launch_hals_wide_sweep<896>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 1024: return launch_hals_wide_sweep<1024>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+    }
+    E->err = "hals_wide_sweep: serves kp = 256, 384, .. 1024 (128 < k <= 1024 components)";
+    return NMFX_E_ARG;
+}
+
 // ---- the per-column solve of the dense fold-in (nmfx_hals_foldin_dense_run) ---------------------------------------
 // The layout, the staging and the step of hals_sweep_kernel -- a column that runs s <= 16 sweeps leaves the bits of the sweep kernel
 // with sweeps = s -- with the stop rule of sp_hals_solve (kernels_sparse.hip) per column: after sweep s, d_s is the running max |delta|

@@ -405,7 +405,9 @@ int nmfx_generic_aoadmm_kl_run(nmfx_engine* E, int prox_w, double lam_w, int pro
                                double tol1, double tol2, int64_t first, int64_t count);
 int nmfx_generic_admm_run(nmfx_engine* E, int distance, double rho, int prox_w, double lam_w, int prox_h, double lam_h, int64_t min_iter,
                           double tol1, double tol2, int64_t first, int64_t count);
-int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count);
+// sweeps = 0: the exact NNLS solves of ANLS; 1 .. 16: HALS, that many sweeps of nmfx_hals_wide_sweep in place of each solve (kp <= 1024)
+int nmfx_generic_anls_run(nmfx_engine* E, double lam_w, double lam_h, int64_t min_iter, double tol1, double tol2, int64_t first, int64_t count,
+                          int sweeps = 0);
 // row-sharded forms beyond 128 components (r4): ADMM phase 0 products / 1 update; ANLS phase 0 objective / 1 W half + products / 2 H half
 int nmfx_generic_admm_phase(nmfx_engine* E, int phase, int distance, double rho, int prox_w, double lam_w, int prox_h, double lam_h,
                             int64_t min_iter, double tol1, double tol2, int64_t j);
@@ -498,6 +500,8 @@ int nmfx_preload_hals();
 // component in place of diag_add (side 0: lambda_w, 1: lambda_h), the components of a stopped problem left as they are
 int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps,
                     int stack_side = -1);
+// ... beyond 128 components (kp = 256, 384, .. 1024): the same sweeps with G streamed through LDS in row tiles (hals_wide_sweep_kernel)
+int nmfx_hals_wide_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps);
 // the per-column solve of the dense fold-in: the sweeps of nmfx_hals_sweep until a sweep moves no component by more than tol times the
 // largest one, or max_sweeps; counts[nprob]: the sweeps each problem took
 int nmfx_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, float tol,

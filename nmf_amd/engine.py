@@ -390,6 +390,12 @@ class Engine:
         self._ck(self.lib.nmfx_hals_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
                                         float(tol2), int(first), int(count)))
 
+    def hals_wide_run(self, lam_w, lam_h, sweeps, min_iter, tol1, tol2, first, count):
+        """hals_run on an engine with 128 < k <= 1024: the same iteration on the products of anls_run beyond 128 components, the
+        sweeps by the kernel that streams G through LDS in row tiles (include/nmfx.h)."""
+        self._ck(self.lib.nmfx_hals_wide_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
+                                             float(tol2), int(first), int(count)))
+
     def hals_sparse_run(self, lam_w, lam_h, sweeps, min_iter, tol1, tol2, first, count):
         """`count` HALS iterations from iteration `first` on a sparse engine (for_sparse, unmasked, k <= 128): iteration j
         records obj[j + 1] and evaluates the stop rule for loop index j (include/nmfx.h)."""

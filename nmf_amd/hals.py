@@ -17,6 +17,8 @@ first W sweep clamp most of W to zero, and the run then needs many iterations to
 `hals_sparse` is the same iteration on scipy.sparse input: the right-hand sides are gathered from the non-zeros and swept in
 the same launch (csrc/kernels_sparse.hip); `hals` itself takes dense data only.
 
+`hals_wide` is `hals` for 129 <= k <= 1024 on dense data.
+
 `hals_stack` runs many Euclidean problems on the same data side by side in the factor columns of one engine: one pair of
 passes over V per iteration for all of them.
 
@@ -52,6 +54,7 @@ from .engine import Engine
 Experiment = namedtuple('Experiment', 'method components distance_type nndsvd_init max_iter tol1 tol2 lambda_w lambda_h sweeps')
 
 MAX_K = 128
+MAX_K_WIDE = 1024            # hals_wide: the sweep keeps k / 64 variables per lane in registers
 MAX_K_MASKED = 64            # hals_masked: a k x k Gram per row, formed in registers and swept from LDS
 MAX_SWEEPS = 16
 
@@ -229,22 +232,55 @@ def hals_stack(x, problems, *, sweeps=1, rescale_start=True, min_iter=10, max_it
     return out
 
 
-def hals(x, k, *, distance_type='eu', sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10,
-         max_iter=1000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
-         device=0, engine=None):
+def _run_dense(solver, run_of, x, k, dist, distance_type, sweeps, rescale_start, lambda_w, lambda_h, min_iter, max_iter, tol1,
+               tol2, nndsvd_init, device, engine):
+    """hals and hals_wide behind their refusals: the start, its scale, the run loop and the Results.  `run_of(eng)` is the
+    engine's run call; `solver` takes last_alpha and last_referee."""
     experiment = Experiment('hals', k, distance_type, nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
-    dist = check_hals(x, k, distance_type, sweeps, lambda_w, lambda_h)
     init = utils.initial_factors(x, k, nndsvd_init, uniform=True, defer_device=True)
     with Engine.for_data(x, k, device=device, engine=engine) as eng:
         w0, h0 = utils.device_initial_factors(eng, x, k, nndsvd_init, init)
         alpha = start_scale(eng, w0, h0) if rescale_start else None
-        hals.last_alpha = alpha
+        solver.last_alpha = alpha
         eng.set_factors(*scaled_start(alpha, w0, h0))
         eng.anls_set_distance(dist)
-        (i, history), _ = run_least_squares(hals, eng, eng.hals_run, (lambda_w, lambda_h, sweeps), distance_type,
+        (i, history), _ = run_least_squares(solver, eng, run_of(eng), (lambda_w, lambda_h, sweeps), distance_type,
                                             min_iter, max_iter, tol1, tol2)
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def hals(x, k, *, distance_type='eu', sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10,
+         max_iter=1000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
+         device=0, engine=None):
+    dist = check_hals(x, k, distance_type, sweeps, lambda_w, lambda_h)
+    return _run_dense(hals, lambda eng: eng.hals_run, x, k, dist, distance_type, sweeps, rescale_start, lambda_w, lambda_h,
+                      min_iter, max_iter, tol1, tol2, nndsvd_init, device, engine)
+
+
+def check_hals_wide(x, k, distance_type, sweeps, lambda_w, lambda_h):
+    """Every refusal of hals_wide, before any device work and before any RNG draw.  Returns the loss's library code."""
+    dist = loss_code('hals_wide', distance_type)
+    if sparse.is_sparse(x):
+        raise TypeError(f'hals_wide: takes dense data only; hals_sparse runs scipy.sparse input with k <= {MAX_K}')
+    if not (_is_count(k, MAX_K_WIDE) and k > MAX_K):
+        hint = f'; hals runs 1 <= k <= {MAX_K}' if _is_count(k, MAX_K) else ''
+        raise ValueError(f'hals_wide: supports {MAX_K + 1} <= k <= {MAX_K_WIDE} components (got k = {k!r}){hint}')
+    check_args('hals_wide', sweeps=sweeps, lambda_w=lambda_w, lambda_h=lambda_h, real_lambdas=False)
+    return dist
+
+
+def hals_wide(x, k, *, distance_type='eu', sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10,
+              max_iter=1000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
+              device=0, engine=None):
+    """`hals` with 129 <= k <= 1024 components on dense data: the same outer iteration -- start, RNG draws, `rescale_start`,
+    printed lines, stop rule with its float64 referee, history, Results and Experiment('hals', ...) are those of `hals` -- on the
+    products `anls` runs beyond 128 components, with the sweeps by a kernel that streams the k x k Gram matrix through LDS in
+    row tiles where `hals` keeps it there whole (csrc/kernels_hals.hip).  The update order within a sweep is
+    the definition above: component j sees the new x_0 .. x_{j-1}."""
+    dist = check_hals_wide(x, k, distance_type, sweeps, lambda_w, lambda_h)
+    return _run_dense(hals_wide, lambda eng: eng.hals_wide_run, x, k, dist, distance_type, sweeps, rescale_start, lambda_w,
+                      lambda_h, min_iter, max_iter, tol1, tol2, nndsvd_init, device, engine)
 
 
 def _check_sparse(x, k, sweeps, lambda_w, lambda_h):

@@ -9,6 +9,13 @@ from . import utils
 _METHODS = ('mur', 'anls', 'admm', 'ao_admm', 'hals')
 
 
+def _beyond_hals(factors):
+    """More components than nmf_amd.hals.hals takes: factorize('hals') then runs hals_wide (which words the refusal beyond 1024)."""
+    import numbers
+    from .hals import MAX_K
+    return isinstance(factors, numbers.Integral) and not isinstance(factors, bool) and factors > MAX_K
+
+
 class NMF:
     """Non-negative matrix factorisation of 2-D `data` into `factors`
     components by MUR, ANLS, ADMM or AO-ADMM.
@@ -40,6 +47,8 @@ class NMF:
             solver = lambda data, factors, mask, **kw: masked(data, factors, mask, **kw)
         elif method == 'hals' and sparse.is_sparse(self.data):     # (hals itself takes dense data only)
             solver = import_module('.hals', __package__).hals_sparse
+        elif method == 'hals' and _beyond_hals(self.factors):      # (dense, unmasked, more components than hals keeps in LDS)
+            solver = import_module('.hals', __package__).hals_wide
         self.results = solver(self.data, self.factors, **method_params)
         # README.md:22 promises nmf.w / nmf.h; the reference only sets .results
         self.w, self.h = self.results.w, self.results.h
