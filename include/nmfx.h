@@ -169,7 +169,7 @@ int nmfx_get_relevance(nmfx_handle_t h, double* lambda_out /* k */);
  * (and nmfx_reset_stream, nmfx_destroy, nmfx_last_error, nmfx_get_note; from version 391 nmfx_profile_enable,
  * nmfx_profile_get and nmfx_profile_reset, which count the sp_* scopes, and nmfx_hals_sparse_run / _finish on an unmasked
  * handle with k <= 128; from version 392 nmfx_hals_masked_run / _finish on a masked handle with k <= 64; from version 393 nmfx_hals_foldin_run and
- * nmfx_hals_foldin_get_sweeps on either).  The objective is recorded in f64 from the non-zeros plus k x k terms ("Sparse V").
+ * nmfx_hals_foldin_get_sweeps on either; from version 397 nmfx_hals_sparse_wide_run / _finish on an unmasked handle with 128 < k <= 256).  The objective is recorded in f64 from the non-zeros plus k x k terms ("Sparse V").
  * Every other entry point returns NMFX_E_ARG and launches nothing. */
 int nmfx_create_csr(nmfx_handle_t* out, int device, int64_t m, int64_t n, int k, int64_t nnz);
 int nmfx_upload_csr(nmfx_handle_t h, const int64_t* row_ptr, const int32_t* col_idx, const void* values, int dtype);
@@ -599,6 +599,22 @@ int nmfx_hals_sparse_run(nmfx_handle_t h, double lambda_w, double lambda_h, int 
                          int64_t min_iter, double tol1, double tol2,
                          int64_t first, int64_t count);
 int nmfx_hals_sparse_finish(nmfx_handle_t h, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
+
+/* ---- HALS on sparse handles with 129 .. 256 components (version 397) -------------------------------------------------------
+ * The outer iteration of nmfx_hals_sparse_run on an unmasked nmfx_create_csr handle with 128 < k <= 256 (kp = 256), where the
+ * Gram matrix no longer fits in LDS beside the gather: each half-step is a gather launch that leaves r of every row of W /
+ * column of H in a buffer (plus one launch for the rows longer than a piece) and then the tiled sweep of nmfx_hals_wide_run on
+ * G = the other factor's Gram + 2 lambda I.  The H half-step sums r in f64, keeps it in f64 and rounds it for
+ * the sweep only; a reduction sums <h_c, r_c> in f64 behind the sweep, so the objective costs no third pass over the non-zeros.
+ * Update order, the exact-zero clamp, a component with G_jj = 0 keeping its value and the zero padding are those of
+ * nmfx_hals_sparse_run; records, the stop flag, obj[0] when first == 0 and nmfx_hals_sparse_wide_finish as the
+ * nmfx_hals_sparse_* pair.  No atomics: two runs give the same bits.  HALS family (NMFX_E_STATE when nmfx_mur_run continues
+ * its run without nmfx_set_factors).  NMFX_E_ARG with a message, nothing launched: a dense handle, a masked handle, k <= 128
+ * (nmfx_hals_sparse_run serves those), sweeps outside 1 .. 16, a negative lambda or range.                                  */
+int nmfx_hals_sparse_wide_run(nmfx_handle_t h, double lambda_w, double lambda_h, int sweeps,
+                              int64_t min_iter, double tol1, double tol2,
+                              int64_t first, int64_t count);
+int nmfx_hals_sparse_wide_finish(nmfx_handle_t h, int64_t min_iter, double tol1, double tol2, int64_t iters_done);
 
 /* ---- HALS on masked handles (version 392) ----------------------------------------------------------------------------------
  * The same outer iteration on a masked handle (nmfx_set_masked) with k <= 64: only the stored entries are part of the fit,

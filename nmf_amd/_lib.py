@@ -119,6 +119,8 @@ SIGNATURES = {
     "nmfx_hals_wide_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_hals_sparse_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_hals_sparse_finish": (_i32, [_vp, _i64, _dbl, _dbl, _i64]),
+    "nmfx_hals_sparse_wide_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
+    "nmfx_hals_sparse_wide_finish": (_i32, [_vp, _i64, _dbl, _dbl, _i64]),
     "nmfx_hals_masked_run": (_i32, [_vp, _dbl, _dbl, _i32, _i64, _dbl, _dbl, _i64, _i64]),
     "nmfx_hals_masked_finish": (_i32, [_vp, _i64, _dbl, _dbl, _i64]),
     "nmfx_hals_foldin_run": (_i32, [_vp, _dbl, _dbl, _i32]),

@@ -153,7 +153,7 @@ int nmfx_enter(nmfx_engine* E, const nmfx_entry& a) {
 
 extern "C" {
 
-int nmfx_version(void) { return 396; }      // 396: HALS beyond 128 components (nmfx_hals_wide_run); 395: MUR fold-in on sparse and masked handles (nmfx_sparse_foldin_run, nmfx_sparse_foldin_get_iters); 394: dense HALS fold-in (nmfx_hals_foldin_dense_run, nmfx_hals_foldin_dense_get_sweeps); 393: HALS fold-in on sparse and masked handles (nmfx_hals_foldin_run, nmfx_hals_foldin_get_sweeps); 392: HALS on masked handles (nmfx_hals_masked_run, nmfx_hals_masked_finish); 391: HALS on sparse handles (nmfx_hals_sparse_run, nmfx_hals_sparse_finish); 390: stacked HALS (nmfx_hals_stack_*); 380: HALS (nmfx_hals_run); 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
+int nmfx_version(void) { return 397; }      // 397: HALS on sparse handles with 129 .. 256 components (nmfx_hals_sparse_wide_run, nmfx_hals_sparse_wide_finish); 396: HALS beyond 128 components (nmfx_hals_wide_run); 395: MUR fold-in on sparse and masked handles (nmfx_sparse_foldin_run, nmfx_sparse_foldin_get_iters); 394: dense HALS fold-in (nmfx_hals_foldin_dense_run, nmfx_hals_foldin_dense_get_sweeps); 393: HALS fold-in on sparse and masked handles (nmfx_hals_foldin_run, nmfx_hals_foldin_get_sweeps); 392: HALS on masked handles (nmfx_hals_masked_run, nmfx_hals_masked_finish); 391: HALS on sparse handles (nmfx_hals_sparse_run, nmfx_hals_sparse_finish); 390: stacked HALS (nmfx_hals_stack_*); 380: HALS (nmfx_hals_run); 370: fold-in, H for new data against a fixed W (nmfx_foldin_run, nmfx_foldin_finish); 360: automatic relevance determination on the beta path (nmfx_set_ard, nmfx_clear_ard, nmfx_get_relevance); 350: NMFX_BETA, nmfx_set_beta (the beta-divergence through nmfx_mur_run / nmfx_mur_finish); 340: per-entry weights (nmfx_upload_weights, nmfx_clear_weights); 330: NMFX_IS (nmfx_mur_run / nmfx_mur_finish); 320: masked sparse handles (nmfx_set_masked); 310: sparse handles (nmfx_create_csr, nmfx_upload_csr); 300: nmfx_set_exchange_buffers takes sizes; nmfx_comm_*; k <= 256
 
 int nmfx_device_count(void) {
     int n = 0;

@@ -70,6 +70,8 @@ struct nmfx_sparse {
     double* obj_part = nullptr;            // [blocks]
     int obj_cap = 0;
     double* hals_part = nullptr;           // sparse HALS: [blocks of the H phase | blocks of its fix-up] partials of Sum_nz x wh (allocated at first use)
+    float* hals_r32 = nullptr;             // sparse HALS at kp = 256: the right-hand sides the sweep reads, [max(m, n)][kp] (allocated at first use)
+    double* hals_r64 = nullptr;            // ... and the H phase's in f64, [n][kp]: the cross term reads them unrounded
     bool masked = false;      // the stored entries are the observed set (nmfx_set_masked)
     int32_t* foldin_sweeps = nullptr;      // HALS fold-in: [n] sweeps each column of H took (allocated at first use)
     bool foldin_done = false;              // ... of a solve that has run since nmfx_set_factors
@@ -487,7 +489,7 @@ void nmfx_sparse_free(nmfx_engine* E) {
     nmfx_sparse* S = E->sp;
     if (!S) return;
     void* bufs[] = {S->Ht, S->g64[0], S->g64[1], S->gf[0], S->gf[1], S->cs64[0], S->cs64[1], S->csf[0], S->csf[1],
-                    S->stat_part, S->obj_part, S->hals_part, S->foldin_sweeps, S->mur_foldin_iters};
+                    S->stat_part, S->obj_part, S->hals_part, S->hals_r32, S->hals_r64, S->foldin_sweeps, S->mur_foldin_iters};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& sd : S->side) {
         void* sb[] = {sd.idx, sd.val, sd.units, sd.longs, sd.slab, sd.slab64};
@@ -1020,6 +1022,46 @@ __device__ __forceinline__ void sp_hals_block_partial(double objacc, double* ob,
     }
 }
 
+// r of one unit, the non-zeros [beg, beg + len): acc += Sum_e v_e Other[idx_e, :], this lane's four components, in f64 where
+// CROSS.  Group grp of the wave takes the non-zeros grp, grp + NG, ..., four steps' gathers in flight; then the groups' sums are
+// added by a fixed butterfly, so every lane ends with the same bits.  (At KP = 256 a group is the whole wave: NG = 1, four
+// consecutive non-zeros in flight, no butterfly.)
+template <int KP, bool CROSS, typename R>
+__device__ __forceinline__ void sp_hals_gather(long long beg, int len, const int32_t* __restrict__ idx, const float* __restrict__ val,
+                                               const float* __restrict__ Other, int lig, int grp, R (&acc)[4])
+{
+    constexpr int G = KP / 4, NG = 64 / G;
+    const long long end = beg + len;
+    for (long long e0 = beg + grp; e0 < end; e0 += 4 * NG) {
+        int c[4]; float x[4]; float4 h[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const long long e = e0 + (long long)t * NG;
+            const bool ok = e < end;
+            c[t] = ok ? idx[e] : 0;
+            x[t] = ok ? val[e] : 0.f;               // (a slot past the unit's end gathers row 0 with weight 0)
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) h[t] = *reinterpret_cast<const float4*>(Other + (int64_t)c[t] * KP + lig * 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if constexpr (CROSS) {
+                const double xv = x[t];
+                acc[0] = fma(xv, (double)h[t].x, acc[0]); acc[1] = fma(xv, (double)h[t].y, acc[1]);
+                acc[2] = fma(xv, (double)h[t].z, acc[2]); acc[3] = fma(xv, (double)h[t].w, acc[3]);
+            } else {
+                acc[0] = fmaf(x[t], h[t].x, acc[0]); acc[1] = fmaf(x[t], h[t].y, acc[1]);
+                acc[2] = fmaf(x[t], h[t].z, acc[2]); acc[3] = fmaf(x[t], h[t].w, acc[3]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = G; off < 64; off <<= 1) {        // the groups' sums: every lane ends with the same bits
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] += __shfl_xor(acc[t], off, 64);
+    }
+}
+
 //   Own [rows][KP]: the factor being updated, in place (a row is owned by one wave; the gathers read the other factor only);
 //   Other [*][KP]: the factor gathered per non-zero; Gf: its Gram (KP x KP f32), diag_add = (float)(2 lambda);
 //   slab: the pieces' partial r, f32 (W phase) or f64 (CROSS); obj_part[blockIdx.x]: the block's Sum <x_new, r> (CROSS).
@@ -1033,7 +1075,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_phase_kernel(
     double* __restrict__ obj_part, int k, int sweeps, const int* flag, float tol = 0.f, int32_t* __restrict__ counts = nullptr)
 {
     if (*flag) return;
-    constexpr int G = KP / 4, NG = 64 / G;
+    constexpr int G = KP / 4;
     using R = typename std::conditional<CROSS, double, float>::type;
     __shared__ __attribute__((aligned(16))) float gs[KP * KP];
     __shared__ double ob[SP_WAVES];
@@ -1045,35 +1087,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_phase_kernel(
     for (int64_t u = (int64_t)blockIdx.x * SP_WAVES + wave; u < nunits; u += (int64_t)gridDim.x * SP_WAVES) {
         const SpUnit U = units[u];
         R acc[4] = {0, 0, 0, 0};
-        const long long end = U.beg + U.len;
-        for (long long e0 = U.beg + grp; e0 < end; e0 += 4 * NG) {
-            int c[4]; float x[4]; float4 h[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const long long e = e0 + (long long)t * NG;
-                const bool ok = e < end;
-                c[t] = ok ? idx[e] : 0;
-                x[t] = ok ? val[e] : 0.f;               // (a slot past the unit's end gathers row 0 with weight 0)
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) h[t] = *reinterpret_cast<const float4*>(Other + (int64_t)c[t] * KP + lig * 4);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if constexpr (CROSS) {
-                    const double xv = x[t];
-                    acc[0] = fma(xv, (double)h[t].x, acc[0]); acc[1] = fma(xv, (double)h[t].y, acc[1]);
-                    acc[2] = fma(xv, (double)h[t].z, acc[2]); acc[3] = fma(xv, (double)h[t].w, acc[3]);
-                } else {
-                    acc[0] = fmaf(x[t], h[t].x, acc[0]); acc[1] = fmaf(x[t], h[t].y, acc[1]);
-                    acc[2] = fmaf(x[t], h[t].z, acc[2]); acc[3] = fmaf(x[t], h[t].w, acc[3]);
-                }
-            }
-        }
-#pragma unroll
-        for (int off = G; off < 64; off <<= 1) {        // the groups' sums: every lane ends with the same bits
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] += __shfl_xor(acc[t], off, 64);
-        }
+        sp_hals_gather<KP, CROSS>(U.beg, U.len, idx, val, Other, lig, grp, acc);
         if (U.slot >= 0) {                              // (wave-uniform)
             if (grp == 0) {
                 R* p = static_cast<R*>(slab) + (int64_t)U.slot * KP + lig * 4;
@@ -1175,18 +1189,23 @@ static int sp_hals_iteration(nmfx_engine* E, double lw, double lh, int sweeps, i
 
 // what both entry points refuse, nothing launched; then the guard (family HALS: on a sparse handle neither MUR nor HALS
 // continues the other's run without nmfx_set_factors) and the buffers of first use
-static int sp_hals_ready(nmfx_engine* E, const char* who, int sweeps, double lw, double lh, int64_t first, int64_t count) {
+// wide: the kp = 256 pair (nmfx_hals_sparse_wide_*), which also needs the buffers of the right-hand sides
+static int sp_hals_ready(nmfx_engine* E, const char* who, int sweeps, double lw, double lh, int64_t first, int64_t count, bool wide = false) {
     if (!E) return NMFX_E_ARG;
     if (!E->sp) { E->err = std::string(who) + ": needs a sparse handle (nmfx_create_csr); a dense handle runs nmfx_hals_run"; return NMFX_E_ARG; }
     if (E->sp->masked) { E->err = std::string(who) + ": not available on a masked handle (nmfx_set_masked): masked handles run MUR only"; return NMFX_E_ARG; }
-    if (E->kp > 128) { E->err = nmfx_small_k_text(who); return NMFX_E_ARG; }
+    if (!wide && E->kp > 128) { E->err = nmfx_small_k_text(who); return NMFX_E_ARG; }
+    if (wide && E->kp != 256) { E->err = std::string(who) + ": serves 129 <= k <= 256 components (kp = 256); nmfx_hals_sparse_run serves k <= 128"; return NMFX_E_ARG; }
     nmfx_entry a = {NMFX_FAM_HALS, first, count, NMFX_D_NONE, NMFX_D_NONE};
     a.bad = nmfx_hals_args_bad(who, sweeps, first, count, &lw, &lh);
     int rc = nmfx_enter(E, a); if (rc) return rc;
     E->run.in_place();
     nmfx_sparse* S = E->sp;
     if ((rc = nmfx_lazy_alloc(E, &S->hals_part, (int64_t)8 * E->ncu + 64))) return rc;
-    return nmfx_lazy_alloc(E, &S->side[1].slab64, std::max<int64_t>(1, S->side[1].npieces * E->kp));
+    if ((rc = nmfx_lazy_alloc(E, &S->side[1].slab64, std::max<int64_t>(1, S->side[1].npieces * E->kp)))) return rc;
+    if (!wide) return NMFX_OK;
+    if ((rc = nmfx_lazy_alloc(E, &S->hals_r32, std::max<int64_t>(1, std::max(E->m, E->n) * E->kp)))) return rc;
+    return nmfx_lazy_alloc(E, &S->hals_r64, std::max<int64_t>(1, E->n * E->kp));
 }
 
 extern "C" int nmfx_hals_sparse_run(nmfx_handle_t E, double lambda_w, double lambda_h, int sweeps, int64_t min_iter, double tol1,
@@ -1209,6 +1228,170 @@ extern "C" int nmfx_hals_sparse_run(nmfx_handle_t E, double lambda_w, double lam
 // does not exist yet (no iteration has run).
 extern "C" int nmfx_hals_sparse_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
     int rc = sp_hals_ready(E, "nmfx_hals_sparse_finish", 1, 0.0, 0.0, iters_done, 0); if (rc) return rc;
+    DevState hs;
+    NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
+    NMFX_HIP(hipStreamSynchronize(E->stream));
+    if (hs.flag || hs.n_obj > iters_done) return NMFX_OK;
+    if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+    return launch_objective(E, NMFX_EU, E->xf64, true, iters_done, min_iter, tol1, tol2);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// HALS on sparse V with 129 .. 256 components (nmfx_hals_sparse_wide_run)
+// ---------------------------------------------------------------------------------------------------------------------
+// At kp = 256 the copy of G the sweep of sp_hals_phase_kernel reads is 256 KiB: it no longer fits in LDS.  The half-step is
+// composed instead: a gather launch leaves every owned row's r in a buffer, [rows][256], and nmfx_hals_wide_sweep (kernels_hals.hip)
+// sweeps the rows on G streamed through LDS in row tiles -- the owned factor is row-major along its long dimension, which is
+// the sweep's W layout on both sides (sj = 1, sc = 256).
+//
+// The gather is sp_hals_gather at KP = 256: a wave holds a 256-vector as one float4 per lane, so a group is the whole wave
+// (NG = 1) and each non-zero costs one coalesced 1 KiB row of the other factor, four of them in flight.  The wave index is made
+// uniform (v_readfirstlane), so the unit, and with it the index and the value of every non-zero, is read with scalar loads:
+// one request per non-zero where a vector load would issue 64 lanes for the same address.  Pieces of rows longer than SP_CHUNK
+// go to the slab and sp_hals_wide_fixup_kernel adds them in piece order, as sp_hals_fixup_kernel does.
+//
+// CROSS (the H phase): r is summed in f64, stored in f64 (r64) and rounded to f32 (r32) for the sweep only; after the sweep
+// sp_hals_wide_cross_kernel sums <h_new_c, r64_c> per block in a fixed order -- the cross term of the objective.
+template <bool CROSS>
+__device__ __forceinline__ void sp_hals_wide_store(const typename std::conditional<CROSS, double, float>::type (&acc)[4], int64_t row,
+                                                   float* __restrict__ r32, double* __restrict__ r64, int lane)
+{
+    *reinterpret_cast<float4*>(r32 + row * 256 + lane * 4) = make_float4((float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]);
+    if constexpr (CROSS) {
+        double* p = r64 + row * 256 + lane * 4;
+        *reinterpret_cast<double2*>(p) = make_double2(acc[0], acc[1]);
+        *reinterpret_cast<double2*>(p + 2) = make_double2(acc[2], acc[3]);
+    }
+}
+
+template <bool CROSS>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_wide_gather_kernel(
+    const SpUnit* __restrict__ units, int64_t nunits, const int32_t* __restrict__ idx, const float* __restrict__ val,
+    const float* __restrict__ Other, void* __restrict__ slab, float* __restrict__ r32, double* __restrict__ r64, const int* flag)
+{
+    if (*flag) return;
+    using R = typename std::conditional<CROSS, double, float>::type;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int64_t u = (int64_t)blockIdx.x * SP_WAVES + wave; u < nunits; u += (int64_t)gridDim.x * SP_WAVES) {
+        const SpUnit U = units[u];
+        R acc[4] = {0, 0, 0, 0};
+        sp_hals_gather<256, CROSS>(U.beg, U.len, idx, val, Other, lane, 0, acc);
+        if (U.slot >= 0) {
+            R* p = static_cast<R*>(slab) + (int64_t)U.slot * 256 + lane * 4;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) p[t] = acc[t];
+        } else {
+            sp_hals_wide_store<CROSS>(acc, U.row, r32, r64, lane);
+        }
+    }
+}
+
+template <bool CROSS>
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_wide_fixup_kernel(
+    const SpLong* __restrict__ longs, int64_t nlong, const void* __restrict__ slab, float* __restrict__ r32, double* __restrict__ r64,
+    const int* flag)
+{
+    if (*flag) return;
+    using R = typename std::conditional<CROSS, double, float>::type;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t l = (int64_t)blockIdx.x * SP_WAVES + wave; l < nlong; l += (int64_t)gridDim.x * SP_WAVES) {
+        const SpLong L = longs[l];
+        R acc[4] = {0, 0, 0, 0};
+        for (int p = 0; p < L.npieces; ++p) {
+            const R* s = static_cast<const R*>(slab) + (int64_t)(L.slot0 + p) * 256 + lane * 4;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] += s[t];
+        }
+        sp_hals_wide_store<CROSS>(acc, L.row, r32, r64, lane);
+    }
+}
+
+// Sum_c <x_c, r64_c> over the rows c of X [rows][256]: a wave per row (the row's sum as sp_hals_row forms it, then a fixed
+// butterfly), the waves' rows in a fixed stride, the block's partial into part[blockIdx.x].
+__global__ __launch_bounds__(64 * SP_WAVES) void sp_hals_wide_cross_kernel(const float* __restrict__ X, const double* __restrict__ r64,
+                                                                          int64_t rows, double* __restrict__ part, const int* flag)
+{
+    if (*flag) return;
+    __shared__ double ob[SP_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double objacc = 0.0;
+    for (int64_t c = (int64_t)blockIdx.x * SP_WAVES + wave; c < rows; c += (int64_t)gridDim.x * SP_WAVES) {
+        const float4 x = *reinterpret_cast<const float4*>(X + c * 256 + lane * 4);
+        const double2 ra = *reinterpret_cast<const double2*>(r64 + c * 256 + lane * 4);
+        const double2 rb = *reinterpret_cast<const double2*>(r64 + c * 256 + lane * 4 + 2);
+        double cross = fma((double)x.x, ra.x, fma((double)x.y, ra.y, fma((double)x.z, rb.x, (double)x.w * rb.y)));
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) cross += __shfl_xor(cross, off, 64);
+        if (lane == 0) objacc += cross;
+    }
+    sp_hals_block_partial(objacc, ob, part + blockIdx.x);
+}
+
+// the right-hand sides of one half-step into hals_r32 (CROSS: and hals_r64): side 0 gathers H^T over the CSR rows, side 1
+// (CROSS) the new W over the CSC columns
+template <bool CROSS>
+static int launch_hals_wide_gather(nmfx_engine* E, const float* Other) {
+    nmfx_sparse* S = E->sp;
+    SpSide& sd = S->side[CROSS ? 1 : 0];
+    const int* flag = &E->state->flag;
+    void* slab = CROSS ? (void*)sd.slab64 : (void*)sd.slab;
+    hipLaunchKernelGGL((sp_hals_wide_gather_kernel<CROSS>), dim3(sd.nblk), dim3(64 * SP_WAVES), 0, E->stream, (const SpUnit*)sd.units,
+                       sd.nunits, (const int32_t*)sd.idx, (const float*)sd.val, Other, slab, S->hals_r32, S->hals_r64, flag);
+    NMFX_HIP(hipGetLastError());
+    if (sd.nlong) {
+        const int nb = (int)std::min<int64_t>(4 * E->ncu, (sd.nlong + SP_WAVES - 1) / SP_WAVES);
+        hipLaunchKernelGGL((sp_hals_wide_fixup_kernel<CROSS>), dim3(nb), dim3(64 * SP_WAVES), 0, E->stream, (const SpLong*)sd.longs,
+                           sd.nlong, (const void*)slab, S->hals_r32, S->hals_r64, flag);
+        NMFX_HIP(hipGetLastError());
+    }
+    return NMFX_OK;
+}
+
+// Iteration j, the launches of sp_hals_iteration with each half-step in two: gather, then the tiled sweep.
+static int sp_hals_wide_iteration(nmfx_engine* E, double lw, double lh, int sweeps, int64_t min_iter, double tol1, double tol2, int64_t j) {
+    nmfx_sparse* S = E->sp;
+    const int* flag = &E->state->flag;
+    float* W = E->W[0];
+    int rc;
+    { ProfScope ps(E, "sp_hals_wide_wgather");
+      if ((rc = launch_hals_wide_gather<false>(E, S->Ht))) return rc; }
+    { ProfScope ps(E, "sp_hals_wide_wsweep");
+      if ((rc = nmfx_hals_wide_sweep(E, S->gf[1], (float)(2.0 * lw), S->hals_r32, W, 1, 256, E->m, sweeps))) return rc; }
+    { ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<256>(E, W, E->m, 0, flag))) return rc; }
+    { ProfScope ps(E, "sp_hals_wide_hgather");
+      if ((rc = launch_hals_wide_gather<true>(E, W))) return rc; }
+    { ProfScope ps(E, "sp_hals_wide_hsweep");
+      if ((rc = nmfx_hals_wide_sweep(E, S->gf[0], (float)(2.0 * lh), S->hals_r32, S->Ht, 1, 256, E->n, sweeps))) return rc; }
+    const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>(4 * E->ncu, (E->n + SP_WAVES - 1) / SP_WAVES));
+    { ProfScope ps(E, "sp_hals_wide_cross");
+      hipLaunchKernelGGL(sp_hals_wide_cross_kernel, dim3(nparts), dim3(64 * SP_WAVES), 0, E->stream, (const float*)S->Ht,
+                         (const double*)S->hals_r64, E->n, S->hals_part, flag);
+      NMFX_HIP(hipGetLastError()); }
+    { ProfScope ps(E, "sp_stats");
+      if ((rc = launch_stats<256>(E, S->Ht, E->n, 1, flag))) return rc; }
+    hipLaunchKernelGGL((sp_objective_kernel<false, false>), dim3(1), dim3(256), 0, E->stream, (const double*)S->hals_part, nparts,
+                       (const double*)S->g64[0], (const double*)S->g64[1], (const double*)S->cs64[0], (const double*)S->cs64[1],
+                       E->kp, S->x2, E->xf64, 1, (long long)(j + 1), (long long)min_iter, tol1, tol2, E->state, E->obj_hist);
+    NMFX_HIP(hipGetLastError());
+    return NMFX_OK;
+}
+
+extern "C" int nmfx_hals_sparse_wide_run(nmfx_handle_t E, double lambda_w, double lambda_h, int sweeps, int64_t min_iter, double tol1,
+                                         double tol2, int64_t first, int64_t count) {
+    int rc = sp_hals_ready(E, "nmfx_hals_sparse_wide_run", sweeps, lambda_w, lambda_h, first, count, true); if (rc) return rc;
+    if (first == 0 && count > 0) {                     // obj[0]: one objective-only pass over the start
+        if ((rc = objective_pass(E, NMFX_EU, E->W[0], &E->state->flag))) return rc;
+        if ((rc = launch_objective(E, NMFX_EU, E->xf64, true, 0, min_iter, tol1, tol2))) return rc;
+    }
+    for (int64_t j = first; j < first + count && !rc; ++j)
+        rc = sp_hals_wide_iteration(E, lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, j);
+    return rc;
+}
+
+// as nmfx_hals_sparse_finish
+extern "C" int nmfx_hals_sparse_wide_finish(nmfx_handle_t E, int64_t min_iter, double tol1, double tol2, int64_t iters_done) {
+    int rc = sp_hals_ready(E, "nmfx_hals_sparse_wide_finish", 1, 0.0, 0.0, iters_done, 0, true); if (rc) return rc;
     DevState hs;
     NMFX_HIP(hipMemcpyAsync(&hs, E->state, sizeof(DevState), hipMemcpyDeviceToHost, E->stream));
     NMFX_HIP(hipStreamSynchronize(E->stream));

@@ -405,6 +405,15 @@ class Engine:
     def hals_sparse_finish(self, min_iter, tol1, tol2, done):
         self._ck(self.lib.nmfx_hals_sparse_finish(self.h, int(min_iter), float(tol1), float(tol2), int(done)))
 
+    def hals_sparse_wide_run(self, lam_w, lam_h, sweeps, min_iter, tol1, tol2, first, count):
+        """hals_sparse_run on a sparse engine with 128 < k <= 256: each half-step is a gather of the right-hand sides and then
+        the sweep that streams G through LDS in row tiles; records and stop rule as hals_sparse_run (include/nmfx.h)."""
+        self._ck(self.lib.nmfx_hals_sparse_wide_run(self.h, float(lam_w), float(lam_h), int(sweeps), int(min_iter), float(tol1),
+                                                    float(tol2), int(first), int(count)))
+
+    def hals_sparse_wide_finish(self, min_iter, tol1, tol2, done):
+        self._ck(self.lib.nmfx_hals_sparse_wide_finish(self.h, int(min_iter), float(tol1), float(tol2), int(done)))
+
     def hals_masked_run(self, lam_w, lam_h, sweeps, min_iter, tol1, tol2, first, count):
         """`count` HALS iterations from iteration `first` on a masked engine (for_sparse(masked=True), k <= 64): every row of W /
         column of H is swept on the Gram matrix of its own observed entries; records and stop rule as hals_sparse_run."""

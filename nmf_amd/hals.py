@@ -19,6 +19,9 @@ the same launch (csrc/kernels_sparse.hip); `hals` itself takes d
 
 `hals_wide` is `hals` for 129 <= k <= 1024 on dense data.
 
+`hals_sparse_wide` is `hals_sparse` for 129 <= k <= 256: the right-hand sides are gathered into a buffer and
+swept by the kernel of `hals_wide`.
+
 `hals_stack` runs many Euclidean problems on the same data side by side in the factor columns of one engine: one pair of
 passes over V per iteration for all of them.
 
@@ -314,6 +317,47 @@ def hals_sparse(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, m
             eng,
             lambda first, count: eng.hals_sparse_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
             lambda done: eng.hals_sparse_finish(min_iter, tol1, tol2, done),
+            max_iter, tol1, tol2, referee=None)
+        w, h = eng.get_factors()
+    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
+def _check_sparse_wide(x, k, sweeps, lambda_w, lambda_h):
+    """Every refusal of hals_sparse_wide but the one of the stored values, before any device work and before any RNG draw."""
+    if not sparse.is_sparse(x):
+        raise TypeError(f'hals_sparse_wide: x must be a scipy.sparse matrix; hals_wide runs dense data with '
+                        f'{MAX_K + 1} <= k <= {MAX_K_WIDE}')
+    if not (_is_count(k, sparse.MAX_K) and k > MAX_K):
+        hint = f'; hals_sparse runs 1 <= k <= {MAX_K}' if _is_count(k, MAX_K) else ''
+        raise ValueError(f'hals_sparse_wide: supports {MAX_K + 1} <= k <= {sparse.MAX_K} components (got k = {k!r}){hint}')
+    check_args('hals_sparse_wide', sweeps=sweeps, lambda_w=lambda_w, lambda_h=lambda_h, real_lambdas=True)
+
+
+def hals_sparse_wide(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10, max_iter=1000, tol1=1e-3,
+                     tol2=1e-3, nndsvd_init=(True, 'zero'), device=0):
+    """`hals_sparse` with 129 <= k <= 256 components: the same outer iteration -- the W half-step, then the H half-step, each
+    `sweeps` projected Gauss-Seidel sweeps with an exact-zero clamp on G = F^T F + 2 lambda I and r = F^T b gathered from the
+    non-zeros; a component with G_jj = 0 keeps its value -- with r gathered into a buffer and the sweeps by the kernel of
+    `hals_wide`, which streams the k x k Gram matrix through LDS in row tiles (csrc/kernels_sparse.hip).  Input
+    rules (any scipy.sparse format, never densified, never modified), start, RNG draws, `rescale_start`
+    (`hals_sparse_wide.last_alpha`), printed lines, the stop rule on the float64 Euclidean objective with no referee, history,
+    Results and Experiment('hals', k, 'eu', ...) are those of `hals_sparse`.  Called by name: NMF.factorize('hals') routes sparse
+    data to `hals_sparse`, which refuses k > 128."""
+    experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
+    _check_sparse_wide(x, k, sweeps, lambda_w, lambda_h)
+    try:
+        xs = sparse.normalise(x, k)
+    except ValueError as e:
+        raise ValueError(f'hals_sparse_wide: {e}') from None
+    w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
+    with Engine.for_sparse(xs, k, device=device) as eng:
+        alpha = start_scale(eng, w0, h0) if rescale_start else None
+        hals_sparse_wide.last_alpha = alpha
+        eng.set_factors(*scaled_start(alpha, w0, h0))
+        i, history = drive(
+            eng,
+            lambda first, count: eng.hals_sparse_wide_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
+            lambda done: eng.hals_sparse_wide_finish(min_iter, tol1, tol2, done),
             max_iter, tol1, tol2, referee=None)
         w, h = eng.get_factors()
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)

@@ -5,6 +5,10 @@ reach the objective MUR has after --mur-iters iterations.
     python tools/sparse_hals_perf.py --m 16384 --n 8192 --density 0.01 --k 64 --powerlaw 1.0
     python tools/sparse_hals_perf.py --m 1048576 --n 131072 --density 0.0001 --k 32 --mur-iters 500
     python tools/sparse_hals_perf.py --table > profiles/sparse_hals_perf.txt       # the rows of DESIGN.md 4.2's table
+    python tools/sparse_hals_perf.py --wide-table > profiles/sparse_hals_wide_perf.txt      # k = 256: DESIGN.md 4.19
+
+With 129 <= k <= 256 HALS is nmfx_hals_sparse_wide_run and the split is by its scopes: the two gathers, the two tiled sweeps
+(sp_hals_wide_wsweep / _hsweep), the cross-term reduction and the two stats launches.
 
 Inputs are the seeded random CSR of tools/sparse_perf.py.  Both solvers start from the same seeded |randn| factors, HALS
 from their least-squares rescaling (hals.start_scale), each on a handle of its own in one process.  One JSON line per case:
@@ -30,6 +34,10 @@ NEVER = 10 ** 12
 TABLE = [["--m", "16384", "--n", "8192", "--k", "64", "--density", d] for d in ("0.001", "0.01", "0.05")]
 TABLE += [["--m", "16384", "--n", "8192", "--k", "64", "--density", "0.01", "--powerlaw", "1.0"],
           ["--m", "1048576", "--n", "131072", "--k", "32", "--density", "0.0001"]]
+WIDE_TABLE = [["--m", "16384", "--n", "8192", "--k", "256", "--density", d] for d in ("0.001", "0.01", "0.05")]
+WIDE_TABLE += [["--m", "16384", "--n", "8192", "--k", "256", "--density", "0.01", "--powerlaw", "1.0"]]
+SCOPES = ("sp_hals_wphase", "sp_stats", "sp_hals_hphase")
+WIDE_SCOPES = ("sp_hals_wide_wgather", "sp_hals_wide_wsweep", "sp_hals_wide_hgather", "sp_hals_wide_hsweep", "sp_hals_wide_cross", "sp_stats")
 
 
 def timed(run, first, count, torch):
@@ -55,9 +63,10 @@ def main():
     ap.add_argument("--hals-max", type=int, default=200)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--table", action="store_true", help="run the rows of DESIGN.md 4.2's table, one process each")
+    ap.add_argument("--wide-table", action="store_true", help="run the rows of DESIGN.md 4.19's table (k = 256), one process each")
     a = ap.parse_args()
-    if a.table:
-        for row in TABLE:
+    if a.table or a.wide_table:
+        for row in (WIDE_TABLE if a.wide_table else TABLE):
             subprocess.run([sys.executable, os.path.abspath(__file__), *row], check=True)
         return
 
@@ -76,8 +85,9 @@ def main():
         he.set_stream(stream)
         alpha = start_scale(he, w0, h0)
         ws, hs = w0 * np.sqrt(alpha), h0 * np.sqrt(alpha)
+        hals_run = he.hals_sparse_wide_run if a.k > 128 else he.hals_sparse_run
         run = {"mur": lambda first, count: me.mur_run(L.EU, 0.0, 0.0, NEVER, 1e-30, 1e-30, first, count),
-               "hals": lambda first, count: he.hals_sparse_run(0.0, 0.0, a.sweeps, NEVER, 1e-30, 1e-30, first, count)}
+               "hals": lambda first, count: hals_run(0.0, 0.0, a.sweeps, NEVER, 1e-30, 1e-30, first, count)}
 
         def restart():
             me.set_factors(w0, h0)
@@ -100,7 +110,7 @@ def main():
         run["hals"](done["hals"], a.iters)
         he.synchronize()
         split = {}
-        for scope in ("sp_hals_wphase", "sp_stats", "sp_hals_hphase"):
+        for scope in (WIDE_SCOPES if a.k > 128 else SCOPES):
             t, cnt = he.profile_get(scope)
             split[scope] = round(t / a.iters, 4)
         he.profile_enable(False)
