@@ -6,32 +6,220 @@
 //     for j = 0 .. k-1:  if G_jj > 0:  x_j <- max(0, x_j + (r_j - sum_l G_jl x_l) / G_jj)      (x_0 .. x_{j-1} already new)
 // A component with G_jj = 0 (dead, at lambda = 0) keeps its value.  The clamp is an exact zero.
 //
-// One wavefront owns one problem, variable i on lane i (at kp = 128: i and i + 64).  The wave keeps the residual
+// One wavefront owns one problem, variable i on lane i % 64, slot i / 64 (NV slots per lane).  The wave keeps the residual
 // g = r - G x in registers: one mat-vec per problem, and step j is
 //     delta = max(-x_j, g_j / G_jj) on lane j, broadcast (v_readlane);  x_j += delta;  g_i -= delta G_ij on every lane
 // (the lane keeps -x_j, the lower bound of its step, instead of x_j)
-// so that further sweeps need no new mat-vec.  G is symmetric, column j is row j: it is read from a copy of G in LDS that the
-// block stages once (2 lambda already on its diagonal), consecutive lanes on consecutive addresses, and the blocks loop over
-// the problems.  Every loop bound is wave-uniform (k, sweeps, the problem index); there are no atomics, and the order of every
-// sum is fixed: two runs give the same bits.  Rows, columns and lanes at or beyond k are never read into a sum; the padded
-// variables are written back as exact zeros.
+// so that further sweeps need no new mat-vec.  G is symmetric, column j is row j: it is read from a copy in LDS that the block
+// stages (2 lambda already on its diagonal), consecutive lanes on consecutive addresses.  Every loop bound is wave-uniform
+// (k, sweeps, the problem index); there are no atomics, and the order of every sum is fixed: two runs give the same bits.  Rows,
+// columns and lanes at or beyond k are never read into a sum; the padded variables are written back as exact zeros.
+//
+// Each piece of this is written once and the three kernels are shells over the pieces:
+//   hals_stage      rows [j0, j0 + T) of G into LDS with the diagonal added (STACK: masked to the problems' diagonal blocks)
+//   HalsLane        a lane's valid / live / 1 / G_jj, x, g and -x: set-up from the diagonal, load, matvec, step, value, store
+//   hals_rows       a run of rows, four LDS reads in flight, then the tail: op(row index, the lane's entries of the row)
+//   hals_problems   hals_sweep_kernel (kp <= 128, G whole in LDS; plain and STACK) and, with SOLVE, hals_solve_kernel: the same
+//                   body with the per-column stop rule of the dense fold-in
+//   hals_wide_sweep_kernel   kp = 256 .. 1024: G streamed through LDS in row tiles, two block barriers per tile
+//   hals_launch     the LDS allowance and the grid of all three
 #include "nmfx_internal.h"
 
 #define NMFX_HALS_WAVES 8                 // problems a block works on at a time
-#define NMFX_HALS_BLOCKS_PER_CU 2         // one round of the grid (kp = 128: the 64 KiB copy of G lets a CU hold two blocks)
+#define NMFX_HALS_BLOCKS_PER_CU 2         // one round of the grid (the copy of G, or a tile of it, is at most 64 KiB: a CU holds two blocks)
 
-// this lane's entries of row `j` of the LDS copy of G
+// Rows [j0, j0 + T) of G [KP][KP] -> lds [T][KP], diag_add on the diagonal (j0 + T <= KP; the whole block calls, no barrier inside).
+// STACK (nmfx_hals_stack_*): the k components are P problems side by side.  An entry whose row and column belong to different
+// problems, or to none, is stored as zero and the diagonal gets its own problem's 2 lambda_p (sk->diag[side], 0 for a component
+// of no problem) in place of diag_add: the sweep over the stacked components is then P independent sweeps -- a masked term is
+// fmaf(-0 d, ., g) = g, bit for bit.
+template <int KP, int T, bool STACK>
+__device__ __forceinline__ void hals_stage(float* lds, const float* __restrict__ G, float diag_add, int j0,
+                                           const HalsStackDev* __restrict__ sk = nullptr, int side = 0) {
+    for (int i4 = threadIdx.x; i4 < T * KP / 4; i4 += 64 * NMFX_HALS_WAVES) {
+        float4 v = *reinterpret_cast<const float4*>(G + (int64_t)j0 * KP + 4 * (int64_t)i4);
+        const int row = j0 + (4 * i4) / KP, col = (4 * i4) % KP;
+        float dg = diag_add;
+        if constexpr (STACK) {
+            const unsigned pr = sk->c2p[row];
+            const unsigned pc4 = *reinterpret_cast<const unsigned*>(sk->c2p + col);       // (col is a multiple of 4)
+            const bool own = pr != NMFX_STACK_NONE;
+            v.x = (own && (pc4 & 255u) == pr) ? v.x : 0.f;          v.y = (own && ((pc4 >> 8) & 255u) == pr) ? v.y : 0.f;
+            v.z = (own && ((pc4 >> 16) & 255u) == pr) ? v.z : 0.f;  v.w = (own && (pc4 >> 24) == pr) ? v.w : 0.f;
+            dg = sk->diag[side][row];
+        }
+        v.x += (col == row) ? dg : 0.f; v.y += (col + 1 == row) ? dg : 0.f;
+        v.z += (col + 2 == row) ? dg : 0.f; v.w += (col + 3 == row) ? dg : 0.f;
+        *reinterpret_cast<float4*>(lds + 4 * i4) = v;
+    }
+}
+
+// One lane's share of a wave's problem: variable at[t] = lane + 64 t in slot t.
+template <int KP, int NV>
+struct HalsLane {
+    int lane, at[NV];                     // (lanes at or beyond KP at kp = 16 / 32: an address inside the row; their values are unused, never stored)
+    bool valid[NV], live[NV];             // below k; and with G_jj > 0 (STACK: and owned by a problem that runs)
+    float inv[NV];                        // 1 / G_jj, 0 where not live: a step of 0
+    float x[NV], g[NV], nx[NV];           // x as loaded; the kept residual; -x, the lower bound of a step max(-x_j, .), 0 where not live
+
+    __device__ __forceinline__ void init(int k) {
+        lane = threadIdx.x & 63;
+#pragma unroll
+        for (int t = 0; t < NV; ++t) {
+            const int idx = lane + 64 * t;
+            valid[t] = idx < k;
+            at[t] = idx < KP ? idx : KP - 1;
+        }
+    }
+    // gd: the variable's diagonal entry of G + diag_add I
+    __device__ __forceinline__ void set_diag(int t, float gd, bool runs = true) {
+        live[t] = valid[t] && gd > 0.f && runs;
+        inv[t] = live[t] ? 1.f / gd : 0.f;
+    }
+    __device__ __forceinline__ int64_t off(int t, int64_t sj, int64_t sc, int64_t c) const { return (int64_t)at[t] * sj + c * sc; }
+    // `mine` (wave-uniform) guards the loads only: a wave without a problem works on zeros
+    __device__ __forceinline__ void load_rhs(const float* __restrict__ R, int64_t sj, int64_t sc, int64_t c, bool mine = true) {
+#pragma unroll
+        for (int t = 0; t < NV; ++t) g[t] = (mine && valid[t]) ? R[off(t, sj, sc, c)] : 0.f;
+    }
+    __device__ __forceinline__ void load(const float* __restrict__ X, const float* __restrict__ R, int64_t sj, int64_t sc, int64_t c,
+                                         bool mine = true) {
+#pragma unroll
+        for (int t = 0; t < NV; ++t) {
+            const int64_t o = off(t, sj, sc, c);        // (a single offset per slot, used by both loads, keeps the VGPR count these kernels had before the pieces were shared)
+            x[t] = (mine && valid[t]) ? X[o] : 0.f;
+            g[t] = (mine && valid[t]) ? R[o] : 0.f;
+            nx[t] = live[t] ? -x[t] : 0.f;
+        }
+    }
+    // g -= G[:, l] x_l for variable l of slot t2: column l of G (= row l) against x_l, broadcast from its lane
+    __device__ __forceinline__ void matvec(int t2, int l, const float (&row)[NV]) {
+        const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t2]), l));
+#pragma unroll
+        for (int t = 0; t < NV; ++t) g[t] = fmaf(-row[t], xl, g[t]);
+    }
+    // THE step, of variable j of slot t2: every lane forms its own candidate from its current g, lane j's is the step.  Returns
+    // delta (wave-uniform).
+    __device__ __forceinline__ float step(int t2, int j, const float (&row)[NV]) {
+        const float cand = fmaxf(nx[t2], g[t2] * inv[t2]);
+        const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), j));
+        nx[t2] = (lane == j) ? nx[t2] - d : nx[t2];              // (d = -x_j: an exact zero)
+#pragma unroll
+        for (int t = 0; t < NV; ++t) g[t] = fmaf(-row[t], d, g[t]);
+        return d;
+    }
+    // the current x: 0 - 0 is +0, a variable that is not live is as it was read (a padded one: 0)
+    __device__ __forceinline__ float value(int t) const { return live[t] ? 0.f - nx[t] : x[t]; }
+    __device__ __forceinline__ void store(float* __restrict__ X, int64_t sj, int64_t sc, int64_t c) const {
+#pragma unroll
+        for (int t = 0; t < NV; ++t)
+            if (lane + 64 * t < KP) X[off(t, sj, sc, c)] = value(t);
+    }
+};
+
+// this lane's entries of row `j` of a staged [.][KP] block of G, at the lane's (clamped) columns at[]
 template <int KP, int NV>
 __device__ __forceinline__ void hals_row(const float* gs, int j, const int (&at)[NV], float (&out)[NV]) {
 #pragma unroll
     for (int t = 0; t < NV; ++t) out[t] = gs[j * KP + at[t]];
 }
+// ... where no lane lies beyond KP (the wide kernel): column lane + 64 t, one base address and constant offsets
+template <int KP, int NV>
+__device__ __forceinline__ void hals_row(const float* gs, int j, int lane, float (&out)[NV]) {
+#pragma unroll
+    for (int t = 0; t < NV; ++t) out[t] = gs[j * KP + lane + 64 * t];
+}
 
-// STACK (nmfx_hals_stack_*): the k components are P problems side by side.  While G is staged, an entry whose row and column
-// belong to different problems, or to none, is stored as zero and the diagonal gets its own problem's 2 lambda_p (sk->diag[side]):
-// the sweep over the stacked components is then P independent sweeps -- a masked term is fmaf(-0 d, ., g) = g, bit for bit.  A
-// component of a stopped problem, or of none, is not live: its steps are exact zeros and its x is written back as it was read.
-// The stop state is read once per launch, before the loop over the problems.
+// op(l, row l) for l = 0 .. lim - 1, four rows at a time so that the four LDS reads are in flight together, then the tail
+// (written out: v_readlane is convergent and the trip count is not a constant).  l stays a scalar loop counter; no barrier.
+template <int NV, typename Read, typename Op>
+__device__ __forceinline__ void hals_rows(int lim, Read&& read, Op&& op) {
+    int l = 0;
+    for (; l + 4 <= lim; l += 4) {
+        float c0[NV], c1[NV], c2[NV], c3[NV];
+        read(l, c0); read(l + 1, c1); read(l + 2, c2); read(l + 3, c3);
+        op(l, c0); op(l + 1, c1); op(l + 2, c2); op(l + 3, c3);
+    }
+    for (; l < lim; ++l) {
+        float c0[NV];
+        read(l, c0);
+        op(l, c0);
+    }
+}
+
+// kp <= 128: the block stages G whole, once, and its waves loop over the problems at a static stride.  Behind the staging barrier
+// there is no block barrier (with SOLVE the trip counts differ per wave).
+// STACK: a component of a stopped problem, or of none, is not live: its steps are exact zeros and its x is written back as it was
+// read.  The stop state is read once per launch, before the loop over the problems.
+// SOLVE (the dense fold-in): `sweeps` is the cap, and a column stops after the first sweep s with d_s <= tol xmax_s,
+// d_s the running max |delta| of the sweep (delta comes from v_readlane and is wave-uniform) and xmax_s the largest component (a
+// dead component keeps its value and counts, padding does not; reduced over the wave, made uniform by v_readfirstlane).  Before the
+// sweeps 17, 33, ... the kept residual is formed anew: r is reloaded from R and the mat-vec redone.  Lane 0 writes the column's sweep
+// count.  Without SOLVE none of that is compiled, so a column that runs s <= 16 sweeps leaves the bits of the plain sweep.
+template <int KP, bool STACK, bool SOLVE>
+__device__ __forceinline__ void hals_problems(const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
+                                              int64_t sj, int64_t sc, int64_t nprob, int k, int sweeps, float tol, int32_t* __restrict__ counts,
+                                              const HalsStackDev* __restrict__ sk, int side)
+{
+    constexpr int NV = KP <= 64 ? 1 : KP / 64;          // variables per lane
+    constexpr int NW = NMFX_HALS_WAVES;
+    extern __shared__ __attribute__((aligned(16))) float hals_g[];      // G + diag_add I, [KP][KP]
+    hals_stage<KP, KP, STACK>(hals_g, G, diag_add, 0, sk, side);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6;
+    HalsLane<KP, NV> S;
+    S.init(k);
+#pragma unroll
+    for (int t = 0; t < NV; ++t) {
+        bool runs = true;
+        if constexpr (STACK) {
+            const unsigned p = sk->c2p[S.at[t]];
+            runs = p != NMFX_STACK_NONE && sk->pflag[p < NMFX_STACK_MAX ? p : 0] == 0;
+        }
+        S.set_diag(t, hals_g[S.at[t] * KP + S.at[t]], runs);
+    }
+    // one pass over the rows 0 .. k - 1 of G: op(slot, lane of the row's variable, the row)
+    auto pass = [&](auto&& op) {
+#pragma unroll
+        for (int t2 = 0; t2 < NV; ++t2)
+            hals_rows<NV>(k - 64 * t2 < 64 ? k - 64 * t2 : 64,
+                          [&](int l, float (&row)[NV]) { hals_row<KP, NV>(hals_g, 64 * t2 + l, S.at, row); },
+                          [&](int l, const float (&row)[NV]) { op(t2, l, row); });
+    };
+    auto matvec = [&](int t2, int l, const float (&row)[NV]) { S.matvec(t2, l, row); };
+    for (int64_t c = (int64_t)blockIdx.x * NW + wave; c < nprob; c += (int64_t)gridDim.x * NW) {      // (wave-uniform)
+        S.load(X, R, sj, sc, c);
+        pass(matvec);                                   // g = r - G x
+        int s = 0;
+        while (SOLVE || s < sweeps) {                   // (SOLVE: left by the break below, at s = sweeps at the latest)
+            [[maybe_unused]] float dmax = 0.f;
+            pass([&](int t2, int j, const float (&row)[NV]) {
+                [[maybe_unused]] const float d = S.step(t2, j, row);
+                if constexpr (SOLVE) dmax = fmaxf(dmax, fabsf(d));
+            });
+            ++s;
+            if constexpr (SOLVE) {
+                float xmax = 0.f;
+#pragma unroll
+                for (int t = 0; t < NV; ++t) xmax = fmaxf(xmax, S.value(t));
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) xmax = fmaxf(xmax, __shfl_xor(xmax, off, 64));
+                xmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xmax)));
+                const float dm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dmax)));
+                if (dm <= tol * xmax || s >= sweeps) break;
+                if ((s & 15) == 0) {                    // the kept residual anew: r from global memory, the mat-vec again
+#pragma unroll
+                    for (int t = 0; t < NV; ++t) S.x[t] = S.value(t);
+                    S.load_rhs(R, sj, sc, c);
+                    pass(matvec);
+                }
+            }
+        }
+        S.store(X, sj, sc, c);
+        if constexpr (SOLVE) { if (S.lane == 0) counts[c] = s; }
+    }
+}
+
 template <int KP, bool STACK = false>
 __global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_sweep_kernel(
     const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
@@ -39,156 +227,26 @@ __global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_sweep_kernel(
     const HalsStackDev* __restrict__ sk = nullptr, int side = 0)
 {
     if (st->flag) return;                               // (the stop rule has fired: the iterate stays)
-    constexpr int NV = KP <= 64 ? 1 : KP / 64;          // variables per lane
-    constexpr int NW = NMFX_HALS_WAVES;
-    extern __shared__ __attribute__((aligned(16))) float hals_g[];      // G + diag_add I, [KP][KP]
-    for (int i4 = threadIdx.x; i4 < KP * KP / 4; i4 += 64 * NW) {
-        float4 v = *reinterpret_cast<const float4*>(G + 4 * (int64_t)i4);
-        const int row = (4 * i4) / KP, col = (4 * i4) % KP;
-        v.x += (col == row) ? diag_add : 0.f; v.y += (col + 1 == row) ? diag_add : 0.f;
-        v.z += (col + 2 == row) ? diag_add : 0.f; v.w += (col + 3 == row) ? diag_add : 0.f;
-        if constexpr (STACK) {
-            v = *reinterpret_cast<const float4*>(G + 4 * (int64_t)i4);
-            const unsigned pr = sk->c2p[row];
-            const unsigned pc4 = *reinterpret_cast<const unsigned*>(sk->c2p + col);       // (col is a multiple of 4)
-            const float dg = sk->diag[side][row];                                          // (0 for a component of no problem)
-            const bool own = pr != NMFX_STACK_NONE;
-            v.x = (own && (pc4 & 255u) == pr) ? v.x : 0.f;          v.y = (own && ((pc4 >> 8) & 255u) == pr) ? v.y : 0.f;
-            v.z = (own && ((pc4 >> 16) & 255u) == pr) ? v.z : 0.f;  v.w = (own && (pc4 >> 24) == pr) ? v.w : 0.f;
-            v.x += (col == row) ? dg : 0.f; v.y += (col + 1 == row) ? dg : 0.f;
-            v.z += (col + 2 == row) ? dg : 0.f; v.w += (col + 3 == row) ? dg : 0.f;
-        }
-        *reinterpret_cast<float4*>(hals_g + 4 * i4) = v;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int at[NV]; bool valid[NV], live[NV]; float inv[NV];
-#pragma unroll
-    for (int t = 0; t < NV; ++t) {
-        const int idx = lane + 64 * t;
-        valid[t] = idx < k;
-        at[t] = idx < KP ? idx : KP - 1;                // (lanes beyond KP at kp = 16 / 32: any address inside the row; their values are unused)
-        const float gd = hals_g[at[t] * KP + at[t]];
-        live[t] = valid[t] && gd > 0.f;
-        if constexpr (STACK) {
-            const unsigned p = sk->c2p[at[t]];
-            live[t] = live[t] && p != NMFX_STACK_NONE && sk->pflag[p < NMFX_STACK_MAX ? p : 0] == 0;
-        }
-        inv[t] = live[t] ? 1.f / gd : 0.f;
-    }
-    for (int64_t c = (int64_t)blockIdx.x * NW + wave; c < nprob; c += (int64_t)gridDim.x * NW) {      // (wave-uniform)
-        float x[NV], g[NV], nx[NV];
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            const int64_t off = (int64_t)at[t] * sj + c * sc;
-            x[t] = valid[t] ? X[off] : 0.f;
-            g[t] = valid[t] ? R[off] : 0.f;
-            nx[t] = live[t] ? -x[t] : 0.f;              // the lower bound of a step, max(-x_j, .); 0 with inv = 0 where G_jj = 0: a step of 0
-        }
-        // g = r - G x: column l of G (= row l) against x_l, broadcast from its lane.  Both loops go four rows at a time, so that
-        // the four LDS reads are in flight together (written out: v_readlane is convergent and the trip count is not a constant).
-        auto matvec = [&](int t2, int l, const float (&col)[NV]) {
-            const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t2]), l));
-#pragma unroll
-            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], xl, g[t]);
-        };
-        // step j: every lane forms its own candidate from its current g; lane j's is the step of variable 64 t2 + j
-        auto step = [&](int t2, int j, const float (&col)[NV]) {
-            const float cand = fmaxf(nx[t2], g[t2] * inv[t2]);
-            const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), j));
-            nx[t2] = (lane == j) ? nx[t2] - d : nx[t2];          // (d = -x_j: an exact zero)
-#pragma unroll
-            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], d, g[t]);
-        };
-#pragma unroll
-        for (int t2 = 0; t2 < NV; ++t2) {
-            const int lim = k - 64 * t2 < 64 ? k - 64 * t2 : 64;
-            int l = 0;
-            for (; l + 4 <= lim; l += 4) {
-                float c0[NV], c1[NV], c2[NV], c3[NV];
-                hals_row<KP, NV>(hals_g, 64 * t2 + l, at, c0); hals_row<KP, NV>(hals_g, 64 * t2 + l + 1, at, c1);
-                hals_row<KP, NV>(hals_g, 64 * t2 + l + 2, at, c2); hals_row<KP, NV>(hals_g, 64 * t2 + l + 3, at, c3);
-                matvec(t2, l, c0); matvec(t2, l + 1, c1); matvec(t2, l + 2, c2); matvec(t2, l + 3, c3);
-            }
-            for (; l < lim; ++l) {
-                float c0[NV];
-                hals_row<KP, NV>(hals_g, 64 * t2 + l, at, c0);
-                matvec(t2, l, c0);
-            }
-        }
-        for (int s = 0; s < sweeps; ++s) {
-#pragma unroll
-            for (int t2 = 0; t2 < NV; ++t2) {
-                const int lim = k - 64 * t2 < 64 ? k - 64 * t2 : 64;
-                int j = 0;
-                for (; j + 4 <= lim; j += 4) {
-                    float c0[NV], c1[NV], c2[NV], c3[NV];
-                    hals_row<KP, NV>(hals_g, 64 * t2 + j, at, c0); hals_row<KP, NV>(hals_g, 64 * t2 + j + 1, at, c1);
-                    hals_row<KP, NV>(hals_g, 64 * t2 + j + 2, at, c2); hals_row<KP, NV>(hals_g, 64 * t2 + j + 3, at, c3);
-                    step(t2, j, c0); step(t2, j + 1, c1); step(t2, j + 2, c2); step(t2, j + 3, c3);
-                }
-                for (; j < lim; ++j) {
-                    float c0[NV];
-                    hals_row<KP, NV>(hals_g, 64 * t2 + j, at, c0);
-                    step(t2, j, c0);
-                }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NV; ++t)
-            if (lane + 64 * t < KP) X[(int64_t)at[t] * sj + c * sc] = live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0; invalid lanes hold x = 0)
-    }
+    hals_problems<KP, STACK, false>(G, diag_add, R, X, sj, sc, nprob, k, sweeps, 0.f, nullptr, sk, side);
 }
 
-template <int KP, bool STACK>
-static int launch_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                             int64_t nprob, int sweeps, int side) {
-    int rc;
-    const size_t shm = (size_t)KP * KP * sizeof(float);
-    auto kern = hals_sweep_kernel<KP, STACK>;
-    if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm))) return rc;
-    const int64_t blocks_needed = (nprob + NMFX_HALS_WAVES - 1) / NMFX_HALS_WAVES;
-    const int64_t round = (int64_t)E->ncu * NMFX_HALS_BLOCKS_PER_CU;
-    const unsigned grid = (unsigned)(blocks_needed < round ? blocks_needed : round);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NMFX_HALS_WAVES), shm, E->stream, G, diag_add, R, X, sj, sc, nprob, E->k,
-                       sweeps, E->state, STACK ? E->stack_dev : nullptr, side);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-
-// the one kp dispatch of the sweep, plain and stacked
-template <bool STACK>
-static int hals_sweep_kp(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                         int64_t nprob, int sweeps, int side) {
-    switch (E->kp) {
-        case 16: return launch_hals_sweep<16, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
-        case 32: return launch_hals_sweep<32, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
-        case 64: return launch_hals_sweep<64, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
-        case 128: return launch_hals_sweep<128, STACK>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, side);
-    }
-    E->err = nmfx_small_k_text(STACK ? "hals_stack_sweep" : "hals_sweep");
-    return NMFX_E_ARG;
-}
-
-// Same arguments and stride conventions as the NNLS launcher of kernels_anls.hip (W: sj = 1, sc = kp; H: sj = np, sc = 1).
-// stack_side >= 0: the stacked form (nmfx_internal.h); its diagonal comes from the stack's own lambdas, not from diag_add.
-int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                    int64_t nprob, int sweeps, int stack_side) {
-    ProfScope ps(E, "hals_sweep");
-    ProfScope side(E, sc == 1 ? "hals_sweep_h" : "hals_sweep_w");          // (the same launch under its side's name: tools/hals_transform_perf.py --dense)
-    if (nprob <= 0) return NMFX_OK;
-    return stack_side < 0 ? hals_sweep_kp<false>(E, G, diag_add, R, X, sj, sc, nprob, sweeps, 0)
-                          : hals_sweep_kp<true>(E, G, 0.f, R, X, sj, sc, nprob, sweeps, stack_side);
+// the per-column solve of the dense fold-in (nmfx_hals_foldin_dense_run)
+template <int KP>
+__global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_solve_kernel(
+    const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
+    int64_t sj, int64_t sc, int64_t nprob, int k, float tol, int max_sweeps, int32_t* __restrict__ counts,
+    const DevState* __restrict__ st)
+{
+    if (st->flag) return;                               // (as in hals_sweep_kernel)
+    hals_problems<KP, false, true>(G, diag_add, R, X, sj, sc, nprob, k, max_sweeps, tol, counts, nullptr, 0);
 }
 
 // ---- beyond 128 components: G streamed through LDS in row tiles (nmfx_hals_wide_run) ------------------------------
-// The sweep of hals_sweep_kernel at kp = 256, 384, .. 1024, where the kp x kp copy of G no longer fits in LDS (256 KiB at kp = 256).
-// One wavefront still owns one problem, variable i on lane i % 64, slot i / 64 (NV = kp / 64 per lane), with the kept residual, the
-// bound -x and 1 / G_jj (read once per launch from the diagonal in global memory) in registers; step j is the step above.  G
-// reaches the waves in tiles of T rows, T kp 4 B <= 64 KiB: the block stages rows j0 .. j0 + T - 1 (2 lambda on the diagonal as
-// it is staged) and each of its eight waves consumes them for its own problem -- once for the mat-vec, then once per sweep, the
-// rows in ascending order: the update order is the definition's, x_0 .. x_{j-1} are new when step j runs.  T divides 64, so a
-// tile's rows belong to one slot and the slot loop unrolls.
+// The sweep at kp = 256, 384, .. 1024, where the kp x kp copy of G no longer fits in LDS (256 KiB at kp = 256).  The lane state and
+// the step are HalsLane's, with 1 / G_jj read once per launch from the diagonal in global memory.  G reaches the waves in tiles of
+// T rows, T kp 4 B <= 64 KiB: the block stages rows j0 .. j0 + T - 1 and each of its eight waves consumes them for its own problem --
+// once for the mat-vec, then once per sweep, the rows in ascending order: the update order is the definition's, x_0 .. x_{j-1} are
+// new when step j runs.  T divides 64, so a tile's rows belong to one slot and the slot loop unrolls.
 // The tile hand-over needs two block barriers per tile, so every loop around them is BLOCK-UNIFORM: the trip count of the loop over
 // the problems is computed from nprob and the grid alone, every wave makes every trip, and a wave whose problem index is at or
 // beyond nprob works on zeros and skips only its global loads and stores.  The early return on st->flag is grid-uniform and
@@ -204,273 +262,122 @@ __global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_wide_sweep_kernel(
     constexpr int T = KP <= 256 ? 64 : KP <= 512 ? 32 : 16;      // rows of a tile
     static_assert(KP % 128 == 0 && KP >= 256 && KP <= 1024 && T * KP * 4 <= 65536 && (T * KP / 4) % (64 * NW) == 0, "tile");
     extern __shared__ __attribute__((aligned(16))) float hals_tile[];   // rows j0 .. j0 + T - 1 of G + diag_add I, [T][KP]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    bool valid[NV], live[NV]; float inv[NV];
+    const int wave = threadIdx.x >> 6;
+    HalsLane<KP, NV> S;
+    S.init(k);
 #pragma unroll
-    for (int t = 0; t < NV; ++t) {
-        const int idx = lane + 64 * t;                  // (< KP)
-        valid[t] = idx < k;
-        const float gd = G[(int64_t)idx * KP + idx] + diag_add;
-        live[t] = valid[t] && gd > 0.f;
-        inv[t] = live[t] ? 1.f / gd : 0.f;
-    }
+    for (int t = 0; t < NV; ++t) S.set_diag(t, G[(int64_t)S.at[t] * KP + S.at[t]] + diag_add);
     const int64_t per_trip = (int64_t)gridDim.x * NW;
     const int64_t trips = (nprob + per_trip - 1) / per_trip;            // (the same for every block)
     for (int64_t trip = 0; trip < trips; ++trip) {
         const int64_t c = trip * per_trip + (int64_t)blockIdx.x * NW + wave;
         const bool mine = c < nprob;                    // (wave-uniform; decides loads and stores only)
-        float x[NV], g[NV], nx[NV];
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            const int64_t off = (int64_t)(lane + 64 * t) * sj + c * sc;
-            x[t] = (mine && valid[t]) ? X[off] : 0.f;
-            g[t] = (mine && valid[t]) ? R[off] : 0.f;
-            nx[t] = live[t] ? -x[t] : 0.f;              // the lower bound of a step, max(-x_j, .); 0 with inv = 0 where G_jj = 0: a step of 0
-        }
-        auto matvec = [&](int t2, int l, const float (&col)[NV]) {
-            const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t2]), l));
-#pragma unroll
-            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], xl, g[t]);
-        };
-        auto step = [&](int t2, int j, const float (&col)[NV]) {
-            const float cand = fmaxf(nx[t2], g[t2] * inv[t2]);
-            const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), j));
-            nx[t2] = (lane == j) ? nx[t2] - d : nx[t2];          // (d = -x_j: an exact zero)
-#pragma unroll
-            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], d, g[t]);
-        };
-        auto row = [&](int jj, float (&out)[NV]) {      // this lane's entries of row jj of the tile
-#pragma unroll
-            for (int t = 0; t < NV; ++t) out[t] = hals_tile[jj * KP + lane + 64 * t];
-        };
+        S.load(X, R, sj, sc, c, mine);
         // one pass over the rows 0 .. k - 1 of G, tile by tile: op(slot, lane of the row's variable, the row)
         auto pass = [&](auto&& op) {
 #pragma unroll
             for (int t2 = 0; t2 < NV; ++t2) {
                 for (int j0 = 64 * t2; j0 < 64 * t2 + 64 && j0 < k; j0 += T) {       // (k: block-uniform)
                     __syncthreads();                    // every wave has consumed the tile before
-                    for (int i4 = threadIdx.x; i4 < T * KP / 4; i4 += 64 * NW) {
-                        float4 v = *reinterpret_cast<const float4*>(G + (int64_t)j0 * KP + 4 * (int64_t)i4);     // (j0 + T <= KP)
-                        const int r = j0 + (4 * i4) / KP, col = (4 * i4) % KP;
-                        v.x += (col == r) ? diag_add : 0.f; v.y += (col + 1 == r) ? diag_add : 0.f;
-                        v.z += (col + 2 == r) ? diag_add : 0.f; v.w += (col + 3 == r) ? diag_add : 0.f;
-                        *reinterpret_cast<float4*>(hals_tile + 4 * i4) = v;
-                    }
+                    hals_stage<KP, T, false>(hals_tile, G, diag_add, j0);
                     __syncthreads();
-                    const int lim = k - j0 < T ? k - j0 : T, l0 = j0 - 64 * t2;
-                    int j = 0;
-                    for (; j + 4 <= lim; j += 4) {       // four rows at a time: four LDS reads in flight together
-                        float c0[NV], c1[NV], c2[NV], c3[NV];
-                        row(j, c0); row(j + 1, c1); row(j + 2, c2); row(j + 3, c3);
-                        op(t2, l0 + j, c0); op(t2, l0 + j + 1, c1); op(t2, l0 + j + 2, c2); op(t2, l0 + j + 3, c3);
-                    }
-                    for (; j < lim; ++j) {
-                        float c0[NV];
-                        row(j, c0);
-                        op(t2, l0 + j, c0);
-                    }
+                    const int l0 = j0 - 64 * t2;
+                    hals_rows<NV>(k - j0 < T ? k - j0 : T,
+                                  [&](int j, float (&row)[NV]) { hals_row<KP, NV>(hals_tile, j, S.lane, row); },
+                                  [&](int j, const float (&row)[NV]) { op(t2, l0 + j, row); });
                 }
             }
         };
-        pass(matvec);                                   // g = r - G x
-        for (int s = 0; s < sweeps; ++s) pass(step);
-        if (mine) {
-#pragma unroll
-            for (int t = 0; t < NV; ++t)
-                X[(int64_t)(lane + 64 * t) * sj + c * sc] = live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0; padded lanes hold x = 0)
-        }
+        pass([&](int t2, int l, const float (&row)[NV]) { S.matvec(t2, l, row); });      // g = r - G x
+        for (int s = 0; s < sweeps; ++s) pass([&](int t2, int j, const float (&row)[NV]) { S.step(t2, j, row); });
+        if (mine) S.store(X, sj, sc, c);
     }
 }
 
-template <int KP>
-static int launch_hals_wide_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                                  int64_t nprob, int sweeps) {
+// ---- launches ------------------------------------------------------------------------------------------------------------------
+// One family of problems: the arguments every kernel above starts with.  Strides as the NNLS launcher of kernels_anls.hip
+// (W: sj = 1, sc = kp; H: sj = np, sc = 1).
+struct HalsSys { const float* G; float diag_add; const float* R; float* X; int64_t sj, sc, nprob; };
+
+// the LDS allowance and the grid of every kernel above; `rest`: the kernel's arguments behind k
+template <typename K, typename... A>
+static int hals_launch(nmfx_engine* E, K kern, size_t shm, const HalsSys& p, A... rest) {
     int rc;
-    const size_t shm = (size_t)(KP <= 256 ? 64 : KP <= 512 ? 32 : 16) * KP * sizeof(float);
-    auto kern = hals_wide_sweep_kernel<KP>;
     if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm))) return rc;
-    const int64_t blocks_needed = (nprob + NMFX_HALS_WAVES - 1) / NMFX_HALS_WAVES;
-    const int64_t round = (int64_t)E->ncu * NMFX_HALS_BLOCKS_PER_CU;      // (a tile is at most 64 KiB: two blocks per CU)
+    const int64_t blocks_needed = (p.nprob + NMFX_HALS_WAVES - 1) / NMFX_HALS_WAVES;
+    const int64_t round = (int64_t)E->ncu * NMFX_HALS_BLOCKS_PER_CU;
     const unsigned grid = (unsigned)(blocks_needed < round ? blocks_needed : round);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NMFX_HALS_WAVES), shm, E->stream, G, diag_add, R, X, sj, sc, nprob, E->k, sweeps,
-                       E->state);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NMFX_HALS_WAVES), shm, E->stream, p.G, p.diag_add, p.R, p.X, p.sj, p.sc, p.nprob, E->k,
+                       rest...);
     NMFX_HIP(hipGetLastError());
     return NMFX_OK;
 }
 
-// Arguments and strides as nmfx_hals_sweep.  kp = 1024 is the last rank whose kept values fit the registers of a wave
-// (about 4 NV VGPRs, plus NV per row of G in flight): nothing beyond it is instantiated.
+// the one kp dispatch of the kernels that hold G whole: launch(the constant KP, the bytes of LDS)
+template <typename F>
+static int hals_small_kp(nmfx_engine* E, const char* who, F&& launch) {
+    const size_t shm = (size_t)E->kp * E->kp * sizeof(float);
+    switch (E->kp) {
+        case 16: return launch(std::integral_constant<int, 16>(), shm);
+        case 32: return launch(std::integral_constant<int, 32>(), shm);
+        case 64: return launch(std::integral_constant<int, 64>(), shm);
+        case 128: return launch(std::integral_constant<int, 128>(), shm);
+    }
+    E->err = nmfx_small_k_text(who);
+    return NMFX_E_ARG;
+}
+
+// stack_side >= 0: the stacked form (nmfx_internal.h); its diagonal comes from the stack's own lambdas, not from diag_add.
+int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                    int64_t nprob, int sweeps, int stack_side) {
+    ProfScope ps(E, "hals_sweep");
+    ProfScope side(E, sc == 1 ? "hals_sweep_h" : "hals_sweep_w");          // (the same launch under its side's name: tools/hals_transform_perf.py --dense)
+    if (nprob <= 0) return NMFX_OK;
+    if (stack_side < 0)
+        return hals_small_kp(E, "hals_sweep", [&](auto kp, size_t shm) {
+            return hals_launch(E, hals_sweep_kernel<decltype(kp)::value, false>, shm, HalsSys{G, diag_add, R, X, sj, sc, nprob}, sweeps, E->state,
+                               (const HalsStackDev*)nullptr, 0);
+        });
+    return hals_small_kp(E, "hals_stack_sweep", [&](auto kp, size_t shm) {
+        return hals_launch(E, hals_sweep_kernel<decltype(kp)::value, true>, shm, HalsSys{G, 0.f, R, X, sj, sc, nprob}, sweeps, E->state,
+                           (const HalsStackDev*)E->stack_dev, stack_side);
+    });
+}
+
+// counts: [nprob]
+int nmfx_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
+                    int64_t nprob, float tol, int max_sweeps, int32_t* counts) {
+    ProfScope ps(E, "hals_solve");
+    if (nprob <= 0) return NMFX_OK;
+    return hals_small_kp(E, "hals_solve", [&](auto kp, size_t shm) {
+        return hals_launch(E, hals_solve_kernel<decltype(kp)::value>, shm, HalsSys{G, diag_add, R, X, sj, sc, nprob}, tol, max_sweeps, counts,
+                           E->state);
+    });
+}
+
+template <int KP>
+static int launch_hals_wide_sweep(nmfx_engine* E, const HalsSys& p, int sweeps) {
+    return hals_launch(E, hals_wide_sweep_kernel<KP>, (size_t)(KP <= 256 ? 64 : KP <= 512 ? 32 : 16) * KP * sizeof(float), p, sweeps, E->state);
+}
+
+// kp = 1024 is the last rank whose kept values fit the registers of a wave (about 4 NV VGPRs, plus NV per row of G in flight):
+// nothing beyond it is instantiated.
 int nmfx_hals_wide_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
                          int64_t nprob, int sweeps) {
     ProfScope ps(E, "hals_sweep");
     ProfScope side(E, sc == 1 ? "hals_sweep_h" : "hals_sweep_w");
     if (nprob <= 0) return NMFX_OK;
+    const HalsSys p{G, diag_add, R, X, sj, sc, nprob};
     switch (E->kp) {
-        case 256: return launch_hals_wide_sweep<256>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 384: return launch_hals_wide_sweep<384>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 512: return launch_hals_wide_sweep<512>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 640: return launch_hals_wide_sweep<640>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 768: return launch_hals_wide_sweep<768>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 896: return launch_hals_wide_sweep<896>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
-        case 1024: return launch_hals_wide_sweep<1024>(E, G, diag_add, R, X, sj, sc, nprob, sweeps);
+        case 256: return launch_hals_wide_sweep<256>(E, p, sweeps);
+        case 384: return launch_hals_wide_sweep<384>(E, p, sweeps);
+        case 512: return launch_hals_wide_sweep<512>(E, p, sweeps);
+        case 640: return launch_hals_wide_sweep<640>(E, p, sweeps);
+        case 768: return launch_hals_wide_sweep<768>(E, p, sweeps);
+        case 896: return launch_hals_wide_sweep<896>(E, p, sweeps);
+        case 1024: return launch_hals_wide_sweep<1024>(E, p, sweeps);
     }
     E->err = "hals_wide_sweep: serves kp = 256, 384, .. 1024 (128 < k <= 1024 components)";
-    return NMFX_E_ARG;
-}
-
-// ---- the per-column solve of the dense fold-in (nmfx_hals_foldin_dense_run) ---------------------------------------
-// The layout, the staging and the step of hals_sweep_kernel -- a column that runs s <= 16 sweeps leaves the bits of the sweep kernel
-// with sweeps = s -- with the stop rule of sp_hals_solve (kernels_sparse.hip) per column: after sweep s, d_s is the running max |delta|
-// of the sweep (delta comes from v_readlane and is wave-uniform) and xmax_s the largest component (a dead component keeps its value
-// and counts, padding does not; reduced over the wave, made uniform by v_readfirstlane); the column stops after the first s with
-// d_s <= tol xmax_s, or at max_sweeps.  Before the sweeps 17, 33, ... the kept residual is formed anew: r is reloaded from R and the
-// mat-vec redone.  Lane 0 writes the column's sweep count.  Behind the staging barrier there is no block barrier (the trip counts
-// differ per wave); every loop bound and every exit is wave-uniform and the sweep loop is bounded by max_sweeps; the waves take
-// the columns at a static stride: no atomics, two runs give the same bits.
-template <int KP>
-__global__ __launch_bounds__(64 * NMFX_HALS_WAVES) void hals_solve_kernel(
-    const float* __restrict__ G, float diag_add, const float* __restrict__ R, float* __restrict__ X,
-    int64_t sj, int64_t sc, int64_t nprob, int k, float tol, int max_sweeps, int32_t* __restrict__ counts,
-    const DevState* __restrict__ st)
-{
-    if (st->flag) return;                               // (the stop rule has fired: the iterate stays, as in hals_sweep_kernel)
-    constexpr int NV = KP <= 64 ? 1 : KP / 64;          // variables per lane
-    constexpr int NW = NMFX_HALS_WAVES;
-    extern __shared__ __attribute__((aligned(16))) float hals_g[];      // G + diag_add I, [KP][KP]
-    for (int i4 = threadIdx.x; i4 < KP * KP / 4; i4 += 64 * NW) {
-        float4 v = *reinterpret_cast<const float4*>(G + 4 * (int64_t)i4);
-        const int row = (4 * i4) / KP, col = (4 * i4) % KP;
-        v.x += (col == row) ? diag_add : 0.f; v.y += (col + 1 == row) ? diag_add : 0.f;
-        v.z += (col + 2 == row) ? diag_add : 0.f; v.w += (col + 3 == row) ? diag_add : 0.f;
-        *reinterpret_cast<float4*>(hals_g + 4 * i4) = v;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int at[NV]; bool valid[NV], live[NV]; float inv[NV];
-#pragma unroll
-    for (int t = 0; t < NV; ++t) {
-        const int idx = lane + 64 * t;
-        valid[t] = idx < k;
-        at[t] = idx < KP ? idx : KP - 1;                // (lanes beyond KP at kp = 16 / 32: any address inside the row; their values are unused)
-        const float gd = hals_g[at[t] * KP + at[t]];
-        live[t] = valid[t] && gd > 0.f;
-        inv[t] = live[t] ? 1.f / gd : 0.f;
-    }
-    for (int64_t c = (int64_t)blockIdx.x * NW + wave; c < nprob; c += (int64_t)gridDim.x * NW) {      // (wave-uniform)
-        float x[NV], g[NV], nx[NV];
-#pragma unroll
-        for (int t = 0; t < NV; ++t) {
-            const int64_t off = (int64_t)at[t] * sj + c * sc;
-            x[t] = valid[t] ? X[off] : 0.f;
-            g[t] = valid[t] ? R[off] : 0.f;
-            nx[t] = live[t] ? -x[t] : 0.f;
-        }
-        auto matvec = [&](int t2, int l, const float (&col)[NV]) {
-            const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t2]), l));
-#pragma unroll
-            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], xl, g[t]);
-        };
-        float dmax;                                     // the running max |delta| of the sweep (wave-uniform)
-        auto step = [&](int t2, int j, const float (&col)[NV]) {
-            const float cand = fmaxf(nx[t2], g[t2] * inv[t2]);
-            const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), j));
-            dmax = fmaxf(dmax, fabsf(d));
-            nx[t2] = (lane == j) ? nx[t2] - d : nx[t2];          // (d = -x_j: an exact zero)
-#pragma unroll
-            for (int t = 0; t < NV; ++t) g[t] = fmaf(-col[t], d, g[t]);
-        };
-        // g -= G x, four rows at a time as in hals_sweep_kernel
-        auto residual = [&]() {
-#pragma unroll
-            for (int t2 = 0; t2 < NV; ++t2) {
-                const int lim = k - 64 * t2 < 64 ? k - 64 * t2 : 64;
-                int l = 0;
-                for (; l + 4 <= lim; l += 4) {
-                    float c0[NV], c1[NV], c2[NV], c3[NV];
-                    hals_row<KP, NV>(hals_g, 64 * t2 + l, at, c0); hals_row<KP, NV>(hals_g, 64 * t2 + l + 1, at, c1);
-                    hals_row<KP, NV>(hals_g, 64 * t2 + l + 2, at, c2); hals_row<KP, NV>(hals_g, 64 * t2 + l + 3, at, c3);
-                    matvec(t2, l, c0); matvec(t2, l + 1, c1); matvec(t2, l + 2, c2); matvec(t2, l + 3, c3);
-                }
-                for (; l < lim; ++l) {
-                    float c0[NV];
-                    hals_row<KP, NV>(hals_g, 64 * t2 + l, at, c0);
-                    matvec(t2, l, c0);
-                }
-            }
-        };
-        residual();
-        int s = 0;
-        for (;;) {                                      // (bounded by max_sweeps)
-            dmax = 0.f;
-#pragma unroll
-            for (int t2 = 0; t2 < NV; ++t2) {
-                const int lim = k - 64 * t2 < 64 ? k - 64 * t2 : 64;
-                int j = 0;
-                for (; j + 4 <= lim; j += 4) {
-                    float c0[NV], c1[NV], c2[NV], c3[NV];
-                    hals_row<KP, NV>(hals_g, 64 * t2 + j, at, c0); hals_row<KP, NV>(hals_g, 64 * t2 + j + 1, at, c1);
-                    hals_row<KP, NV>(hals_g, 64 * t2 + j + 2, at, c2); hals_row<KP, NV>(hals_g, 64 * t2 + j + 3, at, c3);
-                    step(t2, j, c0); step(t2, j + 1, c1); step(t2, j + 2, c2); step(t2, j + 3, c3);
-                }
-                for (; j < lim; ++j) {
-                    float c0[NV];
-                    hals_row<KP, NV>(hals_g, 64 * t2 + j, at, c0);
-                    step(t2, j, c0);
-                }
-            }
-            ++s;
-            float xmax = 0.f;                           // (a dead component keeps its value and counts; padding holds x = 0)
-#pragma unroll
-            for (int t = 0; t < NV; ++t) xmax = fmaxf(xmax, live[t] ? 0.f - nx[t] : x[t]);
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) xmax = fmaxf(xmax, __shfl_xor(xmax, off, 64));
-            xmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xmax)));
-            const float dm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dmax)));
-            if (dm <= tol * xmax || s >= max_sweeps) break;
-            if ((s & 15) == 0) {                        // the kept residual anew: r from global memory, the mat-vec again
-#pragma unroll
-                for (int t = 0; t < NV; ++t) {
-                    x[t] = live[t] ? 0.f - nx[t] : x[t];
-                    g[t] = valid[t] ? R[(int64_t)at[t] * sj + c * sc] : 0.f;
-                }
-                residual();
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NV; ++t)
-            if (lane + 64 * t < KP) X[(int64_t)at[t] * sj + c * sc] = live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0; invalid lanes hold x = 0)
-        if (lane == 0) counts[c] = s;
-    }
-}
-
-template <int KP>
-static int launch_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                             int64_t nprob, float tol, int max_sweeps, int32_t* counts) {
-    int rc;
-    const size_t shm = (size_t)KP * KP * sizeof(float);
-    auto kern = hals_solve_kernel<KP>;
-    if ((rc = nmfx_allow_lds(E, reinterpret_cast<const void*>(kern), (int)shm))) return rc;
-    const int64_t blocks_needed = (nprob + NMFX_HALS_WAVES - 1) / NMFX_HALS_WAVES;
-    const int64_t round = (int64_t)E->ncu * NMFX_HALS_BLOCKS_PER_CU;
-    const unsigned grid = (unsigned)(blocks_needed < round ? blocks_needed : round);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NMFX_HALS_WAVES), shm, E->stream, G, diag_add, R, X, sj, sc, nprob, E->k, tol,
-                       max_sweeps, counts, E->state);
-    NMFX_HIP(hipGetLastError());
-    return NMFX_OK;
-}
-
-// the one kp dispatch of the solve; arguments and strides as nmfx_hals_sweep, counts: [nprob]
-int nmfx_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc,
-                    int64_t nprob, float tol, int max_sweeps, int32_t* counts) {
-    ProfScope ps(E, "hals_solve");
-    if (nprob <= 0) return NMFX_OK;
-    switch (E->kp) {
-        case 16: return launch_hals_solve<16>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
-        case 32: return launch_hals_solve<32>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
-        case 64: return launch_hals_solve<64>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
-        case 128: return launch_hals_solve<128>(E, G, diag_add, R, X, sj, sc, nprob, tol, max_sweeps, counts);
-    }
-    E->err = nmfx_small_k_text("hals_solve");
     return NMFX_E_ARG;
 }
 

@@ -834,7 +834,9 @@ int nmfx_sparse_get_factors(nmfx_engine* E, double* w, double* hmat) {
 // (the lane keeps -x_j, the lower bound of its step).  No wh, no butterfly per non-zero.  Loop bounds are wave-uniform
 // (ceil(k / 4) lanes, sweeps, the unit index); padded components are written as exact zeros; a component with G_jj = 0
 // keeps its value.  A piece of a long row stores its partial r in the slab; sp_hals_fixup_kernel adds the pieces in piece
-// order and runs the same sweep.
+// order and runs the same sweep.  The mat-vec and the step of this layout are written once, in sp_hals_sweeps<KP, SOLVE>:
+// sp_hals_row calls it for the sparse kernels here, for masked HALS and, with SOLVE, for the fold-in of either.  The dense
+// layout (one variable per lane and slot) has its own single copy in kernels_hals.hip; the two are not merged.
 //
 // CROSS (the H phase): r_c = W_new^T x_c is summed in f64 (products of f32 values are exact there) and rounded to f32 for
 // the sweep only; after the sweep the wave adds <h_new_c, r_c> in f64 to its block's partial.  Summed over the columns that
@@ -853,64 +855,25 @@ __device__ __forceinline__ void sp_hals_stage(float* gs, const float* __restrict
     __syncthreads();
 }
 
-// The sweeps of one owned row.  x: the row (this lane's four components), g: in r, out the kept residual; on return x is the
-// new row (padding 0, dead components as they were).
-template <int KP>
-__device__ __forceinline__ void sp_hals_sweep(const float* gs, const float (&inv)[4], const bool (&live)[4], float (&x)[4],
-                                              float (&g)[4], int k, int sweeps, int lig)
+// The sweeps of one owned row, written once for this layout.  x: the row (this lane's four components), g: in r, out the kept
+// residual; on return x is the new row (padding 0, dead components as they were).  Returns the number of sweeps run.
+// SOLVE (HALS fold-in): `sweeps` is the cap, and the row stops after the first sweep that moves no component by more
+// than tol times the largest component.  d comes from v_readlane and is wave-uniform: the sweep keeps a running max |d|; the largest
+// component is one butterfly over the group's lanes (every group holds the same bits; a dead component keeps its value and counts,
+// padding does not); the test and the exit are wave-uniform.  The kept residual is formed anew from r (reload: g <- r) before the
+// sweeps 17, 33, ...: the most a half-step ever carries it.  Without SOLVE none of that is compiled, so a count <= 16 leaves the
+// bits of the plain sweep with that count.
+template <int KP, bool SOLVE, typename RL>
+__device__ __forceinline__ int sp_hals_sweeps(const float* gs, const float (&inv)[4], const bool (&live)[4], float (&x)[4],
+                                              float (&g)[4], int k, int sweeps, float tol, int lig, RL reload)
 {
+    constexpr int G = KP / 4;
     const int nl = (k + 3) >> 2;                        // lanes of a group that hold a variable
     const float* grow = gs + lig * 4;
     float nx[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) nx[t] = live[t] ? -x[t] : 0.f;      // 0 with inv = 0 where G_jj = 0 or beyond k: a step of 0
-    for (int l4 = 0; l4 < nl; ++l4) {
-        float4 c[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) c[t] = *reinterpret_cast<const float4*>(grow + (4 * l4 + t) * KP);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float xl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x[t]), l4));
-            g[0] = fmaf(-c[t].x, xl, g[0]); g[1] = fmaf(-c[t].y, xl, g[1]);
-            g[2] = fmaf(-c[t].z, xl, g[2]); g[3] = fmaf(-c[t].w, xl, g[3]);
-        }
-    }
-    for (int s = 0; s < sweeps; ++s) {
-        for (int l4 = 0; l4 < nl; ++l4) {
-            float4 c[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) c[t] = *reinterpret_cast<const float4*>(grow + (4 * l4 + t) * KP);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float cand = fmaxf(nx[t], g[t] * inv[t]);
-                const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), l4));
-                nx[t] = (lig == l4) ? nx[t] - d : nx[t];           // (d = -x_j: an exact zero)
-                g[0] = fmaf(-c[t].x, d, g[0]); g[1] = fmaf(-c[t].y, d, g[1]);
-                g[2] = fmaf(-c[t].z, d, g[2]); g[3] = fmaf(-c[t].w, d, g[3]);
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) x[t] = lig * 4 + t >= k ? 0.f : live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0)
-}
-
-// The solve of one owned row (HALS fold-in): the sweeps of sp_hals_sweep -- the same layout and the same step,
-// so a count <= 16 leaves the bits of sp_hals_sweep with that count -- until a sweep moves no component by more than tol times
-// the largest component, or max_sweeps.  d comes from v_readlane and is wave-uniform: the sweep keeps a running max |d|; the
-// largest component is one butterfly over the group's lanes (every group holds the same bits); the test and the exit are
-// wave-uniform and the loop is bounded by max_sweeps.  The kept residual is formed anew from r (reload: g <- r) before the
-// sweeps 17, 33, ...: the most a half-step ever carries it.  Returns the number of sweeps run.
-template <int KP, typename RL>
-__device__ __forceinline__ int sp_hals_solve(const float* gs, const float (&inv)[4], const bool (&live)[4], float (&x)[4],
-                                             float (&g)[4], int k, float tol, int max_sweeps, int lig, RL reload)
-{
-    constexpr int G = KP / 4;
-    const int nl = (k + 3) >> 2;
-    const float* grow = gs + lig * 4;
-    float nx[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) nx[t] = live[t] ? -x[t] : 0.f;
-    auto residual = [&]() {                             // g -= G x
+    auto residual = [&]() {                             // g -= G x: the rows of a lane's four variables at a time
         for (int l4 = 0; l4 < nl; ++l4) {
             float4 c[4];
 #pragma unroll
@@ -925,8 +888,8 @@ __device__ __forceinline__ int sp_hals_solve(const float* gs, const float (&inv)
     };
     residual();
     int s = 0;
-    for (;;) {
-        float dmax = 0.f;
+    while (SOLVE || s < sweeps) {                       // (SOLVE: left by the break below, at s = sweeps at the latest)
+        [[maybe_unused]] float dmax = 0.f;
         for (int l4 = 0; l4 < nl; ++l4) {
             float4 c[4];
 #pragma unroll
@@ -935,29 +898,31 @@ __device__ __forceinline__ int sp_hals_solve(const float* gs, const float (&inv)
             for (int t = 0; t < 4; ++t) {
                 const float cand = fmaxf(nx[t], g[t] * inv[t]);
                 const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), l4));
-                dmax = fmaxf(dmax, fabsf(d));
-                nx[t] = (lig == l4) ? nx[t] - d : nx[t];
+                if constexpr (SOLVE) dmax = fmaxf(dmax, fabsf(d));
+                nx[t] = (lig == l4) ? nx[t] - d : nx[t];           // (d = -x_j: an exact zero)
                 g[0] = fmaf(-c[t].x, d, g[0]); g[1] = fmaf(-c[t].y, d, g[1]);
                 g[2] = fmaf(-c[t].z, d, g[2]); g[3] = fmaf(-c[t].w, d, g[3]);
             }
         }
         ++s;
-        float xmax = 0.f;                               // (a dead component keeps its value and counts; padding does not)
+        if constexpr (SOLVE) {
+            float xmax = 0.f;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) xmax = fmaxf(xmax, live[t] ? 0.f - nx[t] : lig * 4 + t < k ? x[t] : 0.f);
+            for (int t = 0; t < 4; ++t) xmax = fmaxf(xmax, live[t] ? 0.f - nx[t] : lig * 4 + t < k ? x[t] : 0.f);
 #pragma unroll
-        for (int off = 1; off < G; off <<= 1) xmax = fmaxf(xmax, __shfl_xor(xmax, off, 64));
-        xmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xmax)));
-        if (dmax <= tol * xmax || s >= max_sweeps) break;
-        if ((s & 15) == 0) {
+            for (int off = 1; off < G; off <<= 1) xmax = fmaxf(xmax, __shfl_xor(xmax, off, 64));
+            xmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xmax)));
+            if (dmax <= tol * xmax || s >= sweeps) break;
+            if ((s & 15) == 0) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) x[t] = live[t] ? 0.f - nx[t] : x[t];
-            reload(g);
-            residual();
+                for (int t = 0; t < 4; ++t) x[t] = live[t] ? 0.f - nx[t] : x[t];
+                reload(g);
+                residual();
+            }
         }
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t) x[t] = lig * 4 + t >= k ? 0.f : live[t] ? 0.f - nx[t] : x[t];
+    for (int t = 0; t < 4; ++t) x[t] = lig * 4 + t >= k ? 0.f : live[t] ? 0.f - nx[t] : x[t];      // (0 - 0: +0)
     return s;
 }
 
@@ -975,7 +940,7 @@ __device__ __forceinline__ void sp_hals_diag(const float* gs, int k, int lig, fl
 
 // One owned row with its summed right-hand side r (R = double on the CROSS side): the sweep, the row written by group 0, and
 // on the CROSS side the row's <x_new, r> in f64 (returned on every lane of group 0; added by lane 0).
-// SOLVE (fold-in): sp_hals_solve in place of the sweep, with `sweeps` its cap; lane 0 writes the row's sweep count to *count.
+// SOLVE (fold-in): the stop rule of sp_hals_sweeps<SOLVE>, with `sweeps` its cap; lane 0 writes the row's sweep count to *count.
 // rlds: where the row's r stays in LDS for the solve's refresh (masked HALS), or nullptr: r stays in this lane's registers.
 template <int KP, bool CROSS, typename R, bool SOLVE = false>
 __device__ __forceinline__ double sp_hals_row(const float* gs, const float (&inv)[4], const bool (&live)[4], const R (&r)[4],
@@ -986,20 +951,16 @@ __device__ __forceinline__ double sp_hals_row(const float* gs, const float (&inv
     const float4 x4 = *reinterpret_cast<const float4*>(row + lig * 4);
     float x[4] = {x4.x, x4.y, x4.z, x4.w};
     float g[4] = {(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
-    if constexpr (SOLVE) {
-        const int s = sp_hals_solve<KP>(gs, inv, live, x, g, k, tol, sweeps, lig, [&](float (&gg)[4]) {
-            if (rlds) {
-                const float4 r4 = *reinterpret_cast<const float4*>(rlds + lig * 4);
-                gg[0] = r4.x; gg[1] = r4.y; gg[2] = r4.z; gg[3] = r4.w;
-            } else {
+    [[maybe_unused]] const int s = sp_hals_sweeps<KP, SOLVE>(gs, inv, live, x, g, k, sweeps, tol, lig, [&](float (&gg)[4]) {
+        if (rlds) {
+            const float4 r4 = *reinterpret_cast<const float4*>(rlds + lig * 4);
+            gg[0] = r4.x; gg[1] = r4.y; gg[2] = r4.z; gg[3] = r4.w;
+        } else {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) gg[t] = (float)r[t];
-            }
-        });
-        if (grp == 0 && lig == 0) *count = s;
-    } else {
-        sp_hals_sweep<KP>(gs, inv, live, x, g, k, sweeps, lig);
-    }
+            for (int t = 0; t < 4; ++t) gg[t] = (float)r[t];
+        }
+    });
+    if constexpr (SOLVE) { if (grp == 0 && lig == 0) *count = s; }
     if (grp == 0) *reinterpret_cast<float4*>(row + lig * 4) = make_float4(x[0], x[1], x[2], x[3]);
     double cross = 0.0;
     if constexpr (CROSS) {
@@ -1065,7 +1026,7 @@ __device__ __forceinline__ void sp_hals_gather(long long beg, int len, const int
 //   Own [rows][KP]: the factor being updated, in place (a row is owned by one wave; the gathers read the other factor only);
 //   Other [*][KP]: the factor gathered per non-zero; Gf: its Gram (KP x KP f32), diag_add = (float)(2 lambda);
 //   slab: the pieces' partial r, f32 (W phase) or f64 (CROSS); obj_part[blockIdx.x]: the block's Sum <x_new, r> (CROSS).
-//   SOLVE (fold-in): every row is swept to the stop rule of sp_hals_solve (tol; `sweeps` is the cap) and leaves its count in
+//   SOLVE (fold-in): every row is swept to the stop rule of sp_hals_sweeps<SOLVE> (tol; `sweeps` is the cap) and leaves its count in
 //   counts[row].  The waves' trip counts then differ by more than the gather length: the only block barriers are the staging
 //   one before the unit loop and the partial reduction behind it.
 template <int KP, bool CROSS, bool SOLVE = false>
@@ -1706,7 +1667,7 @@ extern "C" int nmfx_hals_masked_finish(nmfx_handle_t E, int64_t min_iter, double
 // ---------------------------------------------------------------------------------------------------------------------
 // H for the handle's V against the W that was set, W never touched.  With W fixed a column's system depends on V and W only:
 // the H-side kernels of the two families above form it once (one gather; on a masked handle the column's own Gram) and
-// sp_hals_solve sweeps it in place until the column's stop rule or the cap.  obj[0] is the start's objective and obj[1] the
+// sp_hals_sweeps<SOLVE> sweeps it in place until the column's stop rule or the cap.  obj[0] is the start's objective and obj[1] the
 // result's, each as its family records it: an objective-only pass (both on a masked handle), and on an unmasked handle the
 // solve's own Sum <h_c, r_c> with the Gram of the new H for obj[1].  The stop rule of the outer loop never fires here.
 #define SP_FOLDIN_NEVER ((int64_t)1 << 40)
@@ -1852,7 +1813,7 @@ __device__ __forceinline__ void sp_fi_walk(long long beg, int len, const int32_t
 
 // One step from h4 with the summed a4 / d4: the epilogue of the H half-step in registers, then the stop test.  delta and xmax
 // over the components < k (the padding is 0 before and after) by one butterfly over the group's lanes, made uniform as
-// sp_hals_solve does.  Returns h'; *stop is wave-uniform.
+// sp_hals_sweeps<SOLVE> does.  Returns h'; *stop is wave-uniform.
 template <int KP, int LOSS, bool MASKED>
 __device__ __forceinline__ float4 sp_fi_step(float4 h4, float4 a4, float4 d4, const float* __restrict__ Gsrc, const float* __restrict__ S,
                                              float lam, int k, float tol, int lig, int grp, bool* stop)

@@ -495,15 +495,19 @@ int nmfx_preload_phase();
 int nmfx_preload_aoadmm();
 int nmfx_preload_anls();
 int nmfx_preload_hals();
-// kernels_hals.hip: `sweeps` projected Gauss-Seidel sweeps per problem on (G + diag_add I, R), X in place; strides as the NNLS launcher's
+// kernels_hals.hip: three launchers over one staging (hals_stage), one lane state with the one step (HalsLane), one row loop (hals_rows)
+// and one launch helper (hals_launch).  This one: `sweeps` projected Gauss-Seidel sweeps per problem on (G + diag_add I, R), X in place;
+// strides as the NNLS launcher's (hals_sweep_kernel = hals_problems<KP, STACK, SOLVE = false>).
 // stack_side >= 0 is the stacked form (nmfx_hals_stack_*): G masked to the problems' diagonal blocks while it is staged, 2 lambda_p per
 // component in place of diag_add (side 0: lambda_w, 1: lambda_h), the components of a stopped problem left as they are
 int nmfx_hals_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps,
                     int stack_side = -1);
-// ... beyond 128 components (kp = 256, 384, .. 1024): the same sweeps with G streamed through LDS in row tiles (hals_wide_sweep_kernel)
+// ... beyond 128 components (kp = 256, 384, .. 1024): the same lane state and step with G streamed through LDS in row tiles, staged
+// tile by tile by the same hals_stage (hals_wide_sweep_kernel)
 int nmfx_hals_wide_sweep(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, int sweeps);
-// the per-column solve of the dense fold-in: the sweeps of nmfx_hals_sweep until a sweep moves no component by more than tol times the
-// largest one, or max_sweeps; counts[nprob]: the sweeps each problem took
+// the per-column solve of the dense fold-in: the body of nmfx_hals_sweep's kernel compiled with SOLVE (hals_solve_kernel =
+// hals_problems<KP, false, true>), its sweeps until one moves no component by more than tol times the largest one, or max_sweeps;
+// counts[nprob]: the sweeps each problem took
 int nmfx_hals_solve(nmfx_engine* E, const float* G, float diag_add, const float* R, float* X, int64_t sj, int64_t sc, int64_t nprob, float tol,
                     int max_sweeps, int32_t* counts);
 // kernels_generic.hip: obj[j] = the f64 objective of nmfx_objective_f64 for the current pair, by its kernels, recorded without a stop rule

@@ -253,6 +253,34 @@ def _run_dense(solver, run_of, x, k, dist, distance_type, sweeps, rescale_start,
     return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
 
 
+def _run_sparse(solver, *, check, prepare, refusals, keep_class, masked_engine, scale_of, calls_of, k, sweeps, rescale_start, lambda_w,
+                lambda_h, min_iter, max_iter, tol1, tol2, nndsvd_init, device):
+    """hals_sparse, hals_sparse_wide and hals_masked: the argument check, the data, the start, its scale, the run loop and the
+    Results.  `check()` makes the front end's refusals; `prepare()` returns the canonical sparse data and refuses with one of
+    `refusals`, raised again under the solver's name as a ValueError, or with `keep_class` as the class it had;
+    `masked_engine` is Engine.for_sparse's masked=; `scale_of(eng, w0, h0)` is the start's scale; `calls_of(eng)` the engine's
+    run and finish calls; `solver` takes last_alpha."""
+    experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
+    check()
+    try:
+        xs = prepare()
+    except refusals as e:
+        raise (type(e) if keep_class else ValueError)(f'{solver.__name__}: {e}') from None
+    w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
+    with Engine.for_sparse(xs, k, device=device, masked=masked_engine) as eng:
+        alpha = scale_of(eng, w0, h0) if rescale_start else None
+        solver.last_alpha = alpha
+        eng.set_factors(*scaled_start(alpha, w0, h0))
+        run, finish = calls_of(eng)
+        i, history = drive(
+            eng,
+            lambda first, count: run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
+            lambda done: finish(min_iter, tol1, tol2, done),
+            max_iter, tol1, tol2, referee=None)
+        w, h = eng.get_factors()
+    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+
+
 def hals(x, k, *, distance_type='eu', sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, min_iter=10,
          max_iter=1000, tol1=1e-3, tol2=1e-3, nndsvd_init=(True, 'zero'), save_dir='./results/',
          device=0, engine=None):
@@ -302,24 +330,12 @@ def hals_sparse(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h=0, m
     draws, `rescale_start`, printed lines, stop rule and history are those of `hals`; the recorded objective is the Euclidean
     one, evaluated in float64 from the non-zeros plus k x k terms, so no float64 referee stands behind the stop rule.
     Returns Results with the Experiment of `hals` (distance_type 'eu')."""
-    experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
-    _check_sparse(x, k, sweeps, lambda_w, lambda_h)
-    try:
-        xs = sparse.normalise(x, k)
-    except ValueError as e:
-        raise ValueError(f'hals_sparse: {e}') from None
-    w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
-    with Engine.for_sparse(xs, k, device=device) as eng:
-        alpha = start_scale(eng, w0, h0) if rescale_start else None
-        hals_sparse.last_alpha = alpha
-        eng.set_factors(*scaled_start(alpha, w0, h0))
-        i, history = drive(
-            eng,
-            lambda first, count: eng.hals_sparse_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
-            lambda done: eng.hals_sparse_finish(min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
-        w, h = eng.get_factors()
-    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+    return _run_sparse(hals_sparse, check=lambda: _check_sparse(x, k, sweeps, lambda_w, lambda_h),
+                       prepare=lambda: sparse.normalise(x, k), refusals=ValueError, keep_class=False, masked_engine=False,
+                       scale_of=start_scale, calls_of=lambda eng: (eng.hals_sparse_run, eng.hals_sparse_finish),
+                       k=k, sweeps=sweeps, rescale_start=rescale_start,
+                       lambda_w=lambda_w, lambda_h=lambda_h, min_iter=min_iter, max_iter=max_iter, tol1=tol1, tol2=tol2,
+                       nndsvd_init=nndsvd_init, device=device)
 
 
 def _check_sparse_wide(x, k, sweeps, lambda_w, lambda_h):
@@ -343,24 +359,12 @@ def hals_sparse_wide(x, k, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_h
     (`hals_sparse_wide.last_alpha`), printed lines, the stop rule on the float64 Euclidean objective with no referee, history,
     Results and Experiment('hals', k, 'eu', ...) are those of `hals_sparse`.  Called by name: NMF.factorize('hals') routes sparse
     data to `hals_sparse`, which refuses k > 128."""
-    experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
-    _check_sparse_wide(x, k, sweeps, lambda_w, lambda_h)
-    try:
-        xs = sparse.normalise(x, k)
-    except ValueError as e:
-        raise ValueError(f'hals_sparse_wide: {e}') from None
-    w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
-    with Engine.for_sparse(xs, k, device=device) as eng:
-        alpha = start_scale(eng, w0, h0) if rescale_start else None
-        hals_sparse_wide.last_alpha = alpha
-        eng.set_factors(*scaled_start(alpha, w0, h0))
-        i, history = drive(
-            eng,
-            lambda first, count: eng.hals_sparse_wide_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
-            lambda done: eng.hals_sparse_wide_finish(min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
-        w, h = eng.get_factors()
-    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+    return _run_sparse(hals_sparse_wide, check=lambda: _check_sparse_wide(x, k, sweeps, lambda_w, lambda_h),
+                       prepare=lambda: sparse.normalise(x, k), refusals=ValueError, keep_class=False, masked_engine=False,
+                       scale_of=start_scale, calls_of=lambda eng: (eng.hals_sparse_wide_run, eng.hals_sparse_wide_finish),
+                       k=k, sweeps=sweeps, rescale_start=rescale_start,
+                       lambda_w=lambda_w, lambda_h=lambda_h, min_iter=min_iter, max_iter=max_iter, tol1=tol1, tol2=tol2,
+                       nndsvd_init=nndsvd_init, device=device)
 
 
 HalsTransformResults = namedtuple('HalsTransformResults', 'h sweeps obj_history experiment')
@@ -386,6 +390,16 @@ def _check_transform_factor(name, a, shape=None, who='hals_transform'):
     return a
 
 
+def _check_solve_args(who, tol, max_sweeps, lambda_h):
+    """The stop rule and the penalty of a fold-in (`who`: hals_transform or hals_transform_dense), in the order tol, max_sweeps,
+    lambda_h.  The factors w and h0 go through _check_transform_factor where each front end's order of refusals has them."""
+    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not 0 <= tol < 1:
+        raise ValueError(f'{who}: tol must be a real number with 0 <= tol < 1 (got tol = {tol!r})')
+    if not _is_count(max_sweeps, MAX_SOLVE_SWEEPS):
+        raise ValueError(f'{who}: max_sweeps must be an integer between 1 and {MAX_SOLVE_SWEEPS} (got max_sweeps = {max_sweeps!r})')
+    check_args(who, lambda_h=lambda_h, real_lambdas=True)
+
+
 def hals_transform(x_new, w, mask=None, *, h0=None, lambda_h=0, tol=1e-4, max_sweeps=200, device=0):
     """Least-squares fold-in: H for new data `x_new` (m x n) against the fixed dictionary `w` (m x k, real, finite, >= 0).
 
@@ -406,11 +420,7 @@ def hals_transform(x_new, w, mask=None, *, h0=None, lambda_h=0, tol=1e-4, max_sw
     most = MAX_K if mask is None else MAX_K_MASKED
     if not 1 <= k <= most:
         raise ValueError(f'hals_transform: supports 1 <= k <= {most} components{"" if mask is None else " with a mask"} (w has {k} columns)')
-    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not 0 <= tol < 1:
-        raise ValueError(f'hals_transform: tol must be a real number with 0 <= tol < 1 (got tol = {tol!r})')
-    if not _is_count(max_sweeps, MAX_SOLVE_SWEEPS):
-        raise ValueError(f'hals_transform: max_sweeps must be an integer between 1 and {MAX_SOLVE_SWEEPS} (got max_sweeps = {max_sweeps!r})')
-    check_args('hals_transform', lambda_h=lambda_h, real_lambdas=True)
+    _check_solve_args('hals_transform', tol, max_sweeps, lambda_h)
     try:
         xs = sparse.normalise(x_new, k) if mask is None else masked.observed(x_new, mask, k)
     except (ValueError, TypeError) as e:
@@ -458,11 +468,7 @@ def hals_transform_dense(x_new, w, *, h0=None, lambda_h=0, tol=1e-4, max_sweeps=
         raise ValueError(f'{who}: supports 1 <= k <= {MAX_K} components (w has {k} columns)')
     if m < 1 or n < 1:
         raise ValueError(f'{who}: x_new is empty')
-    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not 0 <= tol < 1:
-        raise ValueError(f'{who}: tol must be a real number with 0 <= tol < 1 (got tol = {tol!r})')
-    if not _is_count(max_sweeps, MAX_SOLVE_SWEEPS):
-        raise ValueError(f'{who}: max_sweeps must be an integer between 1 and {MAX_SOLVE_SWEEPS} (got max_sweeps = {max_sweeps!r})')
-    check_args(who, lambda_h=lambda_h, real_lambdas=True)
+    _check_solve_args(who, tol, max_sweeps, lambda_h)
     h64 = np.zeros((k, n)) if h0 is None else _check_transform_factor('h0', h0, (k, n), who=who)
     if not losses.is_real(xa):
         raise ValueError(f'{who}: x_new must be a real array')
@@ -506,21 +512,12 @@ def hals_masked(x, k, mask, *, sweeps=1, rescale_start=True, lambda_w=0, lambda_
     (`hals_masked.last_alpha`).  The recorded objective is 1/2 Sum_Omega (x - wh)^2 summed per entry in float64
     (nmf_amd.masked.objective), so no float64 referee stands behind the stop rule.  Returns Results with the Experiment of
     `hals` (distance_type 'eu')."""
-    experiment = Experiment('hals', k, 'eu', nndsvd_init, max_iter, tol1, tol2, lambda_w, lambda_h, sweeps)
-    check_args('hals_masked', k=k, sweeps=sweeps, lambda_w=lambda_w, lambda_h=lambda_h, real_lambdas=True, most=MAX_K_MASKED)
-    try:
-        xs = masked.observed(x, mask, k)
-    except (ValueError, TypeError) as e:
-        raise type(e)(f'hals_masked: {e}') from None
-    w0, h0 = utils.initial_factors(xs, k, nndsvd_init, uniform=True)
-    with Engine.for_sparse(xs, k, device=device, masked=True) as eng:
-        alpha = masked_start_scale(eng, w0, h0) if rescale_start else None
-        hals_masked.last_alpha = alpha
-        eng.set_factors(*scaled_start(alpha, w0, h0))
-        i, history = drive(
-            eng,
-            lambda first, count: eng.hals_masked_run(lambda_w, lambda_h, sweeps, min_iter, tol1, tol2, first, count),
-            lambda done: eng.hals_masked_finish(min_iter, tol1, tol2, done),
-            max_iter, tol1, tol2, referee=None)
-        w, h = eng.get_factors()
-    return Results(w=w, h=h, i=i, obj_history=history, experiment=experiment)
+    return _run_sparse(hals_masked,
+                       check=lambda: check_args('hals_masked', k=k, sweeps=sweeps, lambda_w=lambda_w, lambda_h=lambda_h,
+                                                real_lambdas=True, most=MAX_K_MASKED),
+                       prepare=lambda: masked.observed(x, mask, k), refusals=(ValueError, TypeError), keep_class=True,
+                       masked_engine=True, scale_of=masked_start_scale,
+                       calls_of=lambda eng: (eng.hals_masked_run, eng.hals_masked_finish),
+                       k=k, sweeps=sweeps, rescale_start=rescale_start,
+                       lambda_w=lambda_w, lambda_h=lambda_h, min_iter=min_iter, max_iter=max_iter, tol1=tol1, tol2=tol2,
+                       nndsvd_init=nndsvd_init, device=device)

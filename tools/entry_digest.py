@@ -21,7 +21,9 @@ the calls of a MUR-KL run and of an AO-ADMM run.  Last (hals_sections) the least
 sweeps 1 and 3 in both arithmetic modes with a change of the reported distance; stacked HALS at k = 40 and k = 100 (a stack that
 fills the handle and one of ranks 3, 5, 8 that leaves components unowned) through set, terms, runs with differing lambdas, finish
 and the per-problem getters; sparse HALS; and the hals entry points refused: without V, without a stack, behind another family,
-with j < 0, sweeps = 0, sweeps = 17, a negative lambda.
+with j < 0, sweeps = 0, sweeps = 17, a negative lambda.  Behind those (hals_variant_sections) hals_wide and hals_sparse_wide at
+k = 160, masked HALS at k = 40 and the HALS fold-in on sparse, masked and dense handles with its sweep counts, under caps of 3 and
+40 sweeps.
 
 Two builds that print the same lines keep and void the same things and refuse in the same order: the file is what a change of
 the host code between the ABI and the kernels that is meant to change nothing is checked against.  The script uses
@@ -687,6 +689,57 @@ def hals_refusals(s, lib, h, tag, names, accepted_ok=True):
     s.line(f"{tag} state", f"rule={st[0]} n_obj={st[2]}")
 
 
+def hals_variant_sections(k, v, w0, h0, mask):
+    """The HALS variants behind the stack: hals_wide and hals_sparse_wide at k = 160, masked HALS at k = 40, the fold-in on a sparse
+    handle (k = 40, 100), on a masked handle (k = 40) and on a dense one (k = 40, 100).  Every fold-in runs with tol = 0 under a cap of
+    3 sweeps and of 40 (the kept residual is formed anew before sweep 17 and before sweep 33), and its sweep counts are hashed.  The
+    sparse data and the mask hold one full row and one full column: longer than a piece, for the fix-up and long kernels."""
+    import scipy.sparse as sp
+    from nmf_amd import masked
+    from nmf_amd import sparse
+    from nmf_amd.engine import Engine
+    T = (NEVER, 1e-3, 1e-3)
+    wanted = lambda name: not (ONLY and ONLY not in name)
+
+    def runs(s, run, finish):
+        s.step("run 0..1", lambda: run(0.0, 0.01, 1, *T, 0, 2))
+        s.step("run 2..3", lambda: run(0.02, 0.0, 3, *T, 2, 2))
+        s.step("finish 4", lambda: finish(*T, 4))
+
+    def foldin(s, e, run, sweeps_of):
+        for cap in (3, 40):
+            s.step("set_factors", lambda: e.set_factors(w0, h0))
+            s.step(f"foldin cap {cap}", lambda: run(0.01, 0.0, cap))
+            s.line(f"  sweeps cap {cap}", f"{sha(sweeps_of())} max={int(sweeps_of().max())}")
+
+    xd = np.where(np.random.default_rng(9100 + k).random(v.shape) < 0.3, v, 0).astype(np.float64)
+    xd[:, 5], xd[7] = v[:, 5], v[7]
+    full = mask.copy()
+    full[:, 5], full[7] = True, True
+    if k > 128:
+        dense("hals_wide", k, v, w0, h0, lambda s, e: runs(s, e.hals_wide_run, e.aoadmm_finish))
+        if wanted("hals_sparse_wide"):
+            with Engine.for_sparse(sparse.normalise(sp.csr_matrix(xd), k), k) as e:
+                s = Section(f"hals_sparse_wide k={k}", e)
+                e.set_factors(w0, h0)
+                runs(s, e.hals_sparse_wide_run, e.hals_sparse_wide_finish)
+        return
+    if wanted("hals_foldin/sparse"):
+        with Engine.for_sparse(sparse.normalise(sp.csr_matrix(xd), k), k) as e:
+            foldin(Section(f"hals_foldin/sparse k={k}", e), e, e.hals_foldin_run, e.hals_foldin_sweeps)
+    dense("hals_foldin_dense", k, v, w0, h0, lambda s, e: foldin(s, e, e.hals_foldin_dense_run, e.hals_foldin_dense_sweeps))
+    if k > 64:
+        return
+    if wanted("hals_masked"):
+        with Engine.for_sparse(masked.observed(v.astype(np.float64), full, k), k, masked=True) as e:
+            s = Section(f"hals_masked k={k}", e)
+            e.set_factors(w0, h0)
+            runs(s, e.hals_masked_run, e.hals_masked_finish)
+    if wanted("hals_foldin/masked"):
+        with Engine.for_sparse(masked.observed(v.astype(np.float64), full, k), k, masked=True) as e:
+            foldin(Section(f"hals_foldin/masked k={k}", e), e, e.hals_foldin_run, e.hals_foldin_sweeps)
+
+
 def main():
     global LINES
     if "--fold" in sys.argv:
@@ -714,6 +767,10 @@ def main():
     for k in RANKS:
         v, w0, h0, om, mask = make_inputs(k, seed=5000 + k)
         hals_sections(k, v, w0, h0)
+    # (behind them) the HALS variants that came after the stack: wide, sparse wide, masked, the three fold-ins
+    for k in RANKS:
+        v, w0, h0, om, mask = make_inputs(k, seed=5000 + k)
+        hals_variant_sections(k, v, w0, h0, mask)
     if LINES is not None:
         fold(LINES)
 

@@ -13,7 +13,9 @@ differ; the NNDSVD starts run on the middle shape.  An exception is hashed as it
 least-squares part, on the same shapes with the same two stops: anls and hals with 'eu' and 'kl', hals with sweeps=2,
 rescale_start=False and lambdas, hals_sparse, hals_stack with three problems, factorize_grid(x, 'hals') on a 2 x 2 grid and
 NMF(x, k).factorize('hals') on dense and sparse x; there the hash also covers last_alpha, last_would_arm and the referee's
-walked / confirmed / final_rule.
+walked / confirmed / final_rule.  Behind those (variant_cases) hals_masked, hals_transform on sparse x and with mask=, and
+hals_transform_dense on the three shapes, hals_wide and hals_sparse_wide at 300 x 200, k = 160, and one refused call of each
+(imported from nmf_amd.hals inside variant_cases).
 
 Two commits that print the same lines hand the library the same inputs in the same order and return what it computed
 unchanged: the file is what a change of the Python in front of the kernels that is meant to change nothing is checked
@@ -141,6 +143,40 @@ def ls_cases(m, n, k, nndsvd):
     return out
 
 
+WIDE_SHAPE = (300, 200, 160)
+SOLVES = [("3sw", dict(tol=0, max_sweeps=3)), ("tol", {})]
+
+
+def variant_cases(m, n, k):
+    """The HALS variants behind hals_stack: (name, call, x, positional arguments, keywords, diagnostics, the two sets of stop
+    keywords).  hals_wide and hals_sparse_wide on WIDE_SHAPE; hals_masked, hals_transform (sparse and mask=) and
+    hals_transform_dense on SHAPES, the fold-ins under a cap of 3 sweeps at tol = 0 and with their defaults; and one refused
+    call of each."""
+    from nmf_amd.hals import hals_masked, hals_sparse_wide, hals_transform, hals_transform_dense, hals_wide
+    x, om, mask, w, h0 = make_inputs(m, n, k, seed=4000 + k)
+    xs = sp.csr_matrix(np.where(mask, x, 0.0))
+    rand = dict(nndsvd_init=(False, 'zero'))
+    alpha_of = lambda fn: lambda: getattr(fn, 'last_alpha', None)
+    if k > 128:
+        r = lambda: getattr(hals_wide, 'last_referee', None)
+        of_wide = lambda: (getattr(hals_wide, 'last_alpha', None), None if r() is None else (r().walked, r().confirmed, r().final_rule))
+        return [('hals_wide', hals_wide, x, (k,), dict(rand, lambda_w=0.05), of_wide, STOPS),
+                ('hals_wide sweeps=2', hals_wide, x, (k,), dict(rand, sweeps=2, rescale_start=False, distance_type='kl'), of_wide, STOPS),
+                ('hals_wide k=64', hals_wide, x, (64,), dict(rand), of_wide, STOPS[:1]),
+                ('hals_sparse_wide', hals_sparse_wide, xs, (k,), dict(rand, lambda_h=0.05), alpha_of(hals_sparse_wide), STOPS),
+                ('hals_sparse_wide dense x', hals_sparse_wide, x, (k,), dict(rand), alpha_of(hals_sparse_wide), STOPS[:1])]
+    return [('hals_masked', hals_masked, x, (k, mask), dict(rand, lambda_h=0.05), alpha_of(hals_masked), STOPS),
+            ('hals_masked sweeps=2', hals_masked, x, (k, mask), dict(rand, sweeps=2, rescale_start=False), alpha_of(hals_masked), STOPS),
+            ('hals_masked sweeps=17', hals_masked, x, (k, mask), dict(rand, sweeps=17), alpha_of(hals_masked), STOPS[:1]),
+            ('hals_transform', hals_transform, xs, (w,), dict(lambda_h=0.05), None, SOLVES),
+            ('hals_transform h0', hals_transform, xs, (w,), dict(h0=h0), None, SOLVES),
+            ('hals_transform mask', hals_transform, x, (w, mask), dict(lambda_h=0.05, h0=h0), None, SOLVES),
+            ('hals_transform tol=1', hals_transform, xs, (w,), dict(tol=1.0, max_sweeps=0, lambda_h=-1, h0=h0[:, :-1]), None, SOLVES[1:]),
+            ('hals_transform_dense', hals_transform_dense, x, (w,), dict(lambda_h=0.05), None, SOLVES),
+            ('hals_transform_dense h0', hals_transform_dense, x, (w,), dict(h0=h0), None, SOLVES),
+            ('hals_transform_dense cap=0', hals_transform_dense, x, (w,), dict(max_sweeps=0, lambda_h=-1, h0=h0[:, :-1]), None, SOLVES[1:])]
+
+
 def as_bytes(v):
     if sp.issparse(v):
         return v.data.tobytes() + v.indices.tobytes() + v.indptr.tobytes()
@@ -159,7 +195,9 @@ def digest(fn, x, args, kw, seed, diagnostics=None):
             res = fn(x, *args, **kw)
         results = res if isinstance(res, list) else [res]          # (mur_pair returns two)
         parts = [as_bytes(v) for r in results for v in r]
-        note = ' '.join(f'i={r.i} obj[-1]={r.obj_history[-1]!r}' for r in results)
+        # (a fold-in result has the columns' sweep counts where a run has i)
+        note = ' '.join((f'i={r.i}' if hasattr(r, 'i') else f'sweeps<={int(np.max(r.sweeps))}') + f' obj[-1]={r.obj_history[-1]!r}'
+                        for r in results)
     except Exception as e:  # noqa: BLE001  (a refusal is an outcome like any other)
         parts, note = [type(e).__name__.encode(), str(e).encode()], f'{type(e).__name__}: {e}'
     parts += [printed.getvalue().encode(), as_bytes(x), np.random.get_state()[1].tobytes()]
@@ -184,6 +222,11 @@ def main():
                 for s, (stop, stop_kw) in enumerate(STOPS):
                     sha, note = digest(fn, x, args, {**kw, **stop_kw}, seed=100 * c + s, diagnostics=diag)
                     print(f'{name:<22} {m}x{n} k={k} {stop:<4}  {sha}  {note}', flush=True)
+    for m, n, k in SHAPES + [WIDE_SHAPE]:                                        # (and behind those) the later HALS variants
+        for c, (name, fn, x, args, kw, diag, stops) in enumerate(variant_cases(m, n, k)):
+            for s, (stop, stop_kw) in enumerate(stops):
+                sha, note = digest(fn, x, args, {**kw, **stop_kw}, seed=100 * c + s, diagnostics=diag)
+                print(f'{name:<22} {m}x{n} k={k} {stop:<4}  {sha}  {note}', flush=True)
 
 
 if __name__ == '__main__':
